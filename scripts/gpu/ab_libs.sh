@@ -9,7 +9,7 @@ for lib in libgpullama_hip.so ${2:-libgpullama_hip_nopk.so}; do
   echo "=== $lib"
   for spec in "llama-3-8b q8_0" "llama-3-8b q4_0" "llama-3.2-1b f16" ${AB_EXTRA:-}; do
     set -- $spec
-    ( timeout 600 python bench.py --steps 2 --warmup 1 --model $1 --wtype $2 --no-cpu-baseline > $O/bench_${tag}_$1_$2.json 2> $O/bench_${tag}_$1_$2.err; echo "$1 $2 rc=$?" )
+    ( timeout 600 python bench.py --full --steps 2 --warmup 1 --model $1 --wtype $2 --no-cpu-baseline > $O/bench_${tag}_$1_$2.json 2> $O/bench_${tag}_$1_$2.err; echo "$1 $2 rc=$?" )
     python - <<PY
 import json
 try:

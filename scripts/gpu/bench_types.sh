@@ -5,7 +5,7 @@ O=gpurun_out/${1:-r3types}; mkdir -p $O
 export TMPDIR=/tmp
 for spec in "llama-3-8b q4_0" "llama-3-8b q8_0_f32act" "llama-3.2-1b f16"; do
   set -- $spec
-  ( timeout 900 python bench.py --steps 3 --warmup 1 --model $1 --wtype $2 --no-cpu-baseline > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err; echo "$1 $2 rc=$?" )
+  ( timeout 900 python bench.py --full --steps 3 --warmup 1 --model $1 --wtype $2 --no-cpu-baseline > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err; echo "$1 $2 rc=$?" )
   python - <<PY
 import json
 try:

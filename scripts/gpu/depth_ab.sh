@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 i=0
 for v in "$@"; do
   i=$((i+1))
-  ( env $v timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --depth $D > $O/depth_$i.json 2> $O/depth_$i.err; echo "[$v] rc=$?" )
+  ( env $v timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --depth $D > $O/depth_$i.json 2> $O/depth_$i.err; echo "[$v] rc=$?" )
   python3 - <<PY
 import json
 try:

@@ -15,7 +15,7 @@ tests)
     echo "== $f: $(tail -1 $O/pytest_$f.log)"
   done ;;
 bench)
-  ( timeout 600 python bench.py > $O/bench_8b.json 2> $O/bench_8b.err; echo "bench rc=$?" )
+  ( timeout 600 python bench.py --full > $O/bench_8b.json 2> $O/bench_8b.err; echo "bench rc=$?" )
   python - <<PY
 import json
 d = json.load(open("$O/bench_8b.json"))
@@ -24,8 +24,8 @@ print("8B: tg", d["value"], "pp", [(r["batch"], r.get("tok_s")) for r in d["pp_r
 PY
   ;;
 prof)
-  ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/trace -o k -- python $R/bench.py --steps 2 --no-cpu-baseline > $R/$O/bench_traced.json 2> $R/$O/bench_traced.err; echo trace rc=$? )
-  ( cd /tmp && timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/$O/pmc_fetch -o f -- python $R/bench.py --steps 1 --no-pp --no-cpu-baseline > $R/$O/bench_pmc.json 2> $R/$O/bench_pmc.err; echo pmc rc=$? )
+  ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/trace -o k -- python $R/bench.py --full --steps 2 --no-cpu-baseline > $R/$O/bench_traced.json 2> $R/$O/bench_traced.err; echo trace rc=$? )
+  ( cd /tmp && timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/$O/pmc_fetch -o f -- python $R/bench.py --full --steps 1 --no-pp --no-cpu-baseline > $R/$O/bench_pmc.json 2> $R/$O/bench_pmc.err; echo pmc rc=$? )
   ( cd /tmp && timeout 240 rocprofv3 --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $R/$O/pmc_pp_q8 -o p -- python $R/scripts/pp_only.py llama-3-8b 4 8 > $R/$O/pp_q8.log 2>&1; echo pp_q8 rc=$? )
   ( cd /tmp && timeout 240 rocprofv3 --pmc FETCH_SIZE GRBM_GUI_ACTIVE --output-format csv -d $R/$O/pmc_pp_q8_fetch -o p -- python $R/scripts/pp_only.py llama-3-8b 4 8 > $R/$O/pp_q8_fetch.log 2>&1; echo pp_q8_fetch rc=$? )
   ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/trace_bd -o bd -- python $R/scripts/bd_only.py qwen3-4b 32 16 > $R/$O/bd.log 2> $R/$O/bd.err; echo bd rc=$? )
@@ -34,7 +34,7 @@ prof)
 lines)
   for spec in "qwen3-4b q8_0" "llama-3.2-1b q8_0" "llama-3-8b q4_0" "llama-3.2-1b f16" "llama-3-8b q8_0_f32act"; do
     set -- $spec
-    ( timeout 500 python bench.py --steps 5 --warmup 1 --model $1 --wtype $2 --cpu-seconds 10 > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err; echo "$1 $2 rc=$?" )
+    ( timeout 500 python bench.py --full --steps 5 --warmup 1 --model $1 --wtype $2 --cpu-seconds 10 > $O/bench_$1_$2.json 2> $O/bench_$1_$2.err; echo "$1 $2 rc=$?" )
     python - <<PY
 import json
 try:
@@ -42,7 +42,7 @@ try:
 except Exception as e: print("no json", e)
 PY
   done
-  ( timeout 500 python bench.py --model qwen3-4b --decode-batch 32 --steps 5 --warmup 1 --cpu-seconds 10 > $O/bench_qwen3-4b_bd32.json 2> $O/bench_qwen3-4b_bd32.err; echo "bd32 rc=$?" )
+  ( timeout 500 python bench.py --full --model qwen3-4b --decode-batch 32 --steps 5 --warmup 1 --cpu-seconds 10 > $O/bench_qwen3-4b_bd32.json 2> $O/bench_qwen3-4b_bd32.err; echo "bd32 rc=$?" )
   python - <<PY
 import json
 try:

@@ -4,8 +4,10 @@ import sys
 # The in-process tensor-parallel test group runs up to 8 ranks as host threads of ONE process; every rank's gather kernel
 # polls for its peers on the device, so each rank's stream needs its own hardware queue (the HIP runtime's default is 4 queues
 # per process, onto which streams are multiplexed: a polling kernel would then block the peer queued behind it).  Must be set
-# before the HIP runtime initialises.  Production runs one process per GPU and does not need this.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
+# before the HIP runtime initialises.  Production runs one process per GPU and does not need this.  A value inherited from the
+# environment is overridden, not kept: with 4 queues (a common setting) the 8-rank groups' gathers time out.  The tests' child
+# processes (scripts/debug_tp_fold.py) inherit it.
+os.environ["GPU_MAX_HW_QUEUES"] = "32"
 
 import pytest
 

@@ -1159,9 +1159,7 @@ int32_t gl3_forward_prefill(gl3_ctx* ctx, const int32_t* tokens, int32_t n, int3
     return gl3_forward_prefill_seq(ctx, 0, tokens, n, start_pos);
 }
 
-int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
-                                 float* logits_out, int32_t* argmax_out) {
-    if (!ctx) return GL3_E_ARG;
+static int32_t check_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n) {
     if (!tokens || !seq_ids || !positions || n <= 0) GL3_FAIL(GL3_E_ARG, "bad batch arrays");
     if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
     if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, one rank in the Vector-API order)");
@@ -1172,7 +1170,69 @@ int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, const int3
         if (positions[i] < 0 || positions[i] >= ctx->d.ctx) GL3_FAIL(GL3_E_ARG, "position outside the KV cache (context length)");
         for (int j = 0; j < i; ++j) if (seq_ids[j] == seq_ids[i]) GL3_FAIL(GL3_E_ARG, "duplicate sequence id in one batched step");
     }
+    return GL3_OK;
+}
+
+int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
+                                 float* logits_out, int32_t* argmax_out) {
+    if (!ctx) return GL3_E_ARG;
+    const int32_t r = check_batch(ctx, tokens, seq_ids, positions, n);
+    if (r != GL3_OK) return r;
     return gl3_decode_batch_run(ctx, tokens, seq_ids, positions, n, logits_out, argmax_out);
+}
+
+// what the batched sampler does not cover yet is refused, not approximated
+static int32_t check_batch_sampler(gl3_ctx* ctx) {
+    if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
+    if (ctx->d.n_experts > 0) GL3_FAIL(GL3_E_UNSUPPORTED, "Qwen2-MoE plans have no static-batched decode, so no batched sampler");
+    if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "the batched sampler reads plain [n][vocab] logits: tensor-parallel plans (rank-chunked logits) are not supported yet");
+    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, one rank in the Vector-API order)");
+    return GL3_OK;
+}
+
+int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
+                                        const float* temperature, const float* topp, const float* coins, int32_t* tokens_out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!temperature || !topp || !coins) GL3_FAIL(GL3_E_ARG, "null temperature / topp / coins");
+    if (!tokens_out) GL3_FAIL(GL3_E_ARG, "null tokens_out");
+    int32_t r = check_batch_sampler(ctx);
+    if (r != GL3_OK) return r;
+    if ((r = check_batch(ctx, tokens, seq_ids, positions, n)) != GL3_OK) return r;
+    bool all_greedy = false;
+    if ((r = gl3_sample_batch_prepare(ctx, n, temperature, topp, coins, &all_greedy)) != GL3_OK) return r;
+    if (all_greedy) return gl3_decode_batch_run(ctx, tokens, seq_ids, positions, n, nullptr, tokens_out);      // Sampler.java:79-81 for every row
+    if ((r = gl3_decode_batch_run(ctx, tokens, seq_ids, positions, n, nullptr, nullptr, false)) != GL3_OK) return r;
+    const float* logits; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits, &greedy);
+    return gl3_sample_batch_finish(ctx, logits, greedy, n, tokens_out);
+}
+
+int32_t gl3_sample_rows(gl3_ctx* ctx, const float* logits, int32_t n, const float* temperature, const float* topp, const float* coins,
+                        int32_t* tokens_out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!logits || !temperature || !topp || !coins || n <= 0) GL3_FAIL(GL3_E_ARG, "bad logits / temperature / topp / coins arrays");
+    if (!tokens_out) GL3_FAIL(GL3_E_ARG, "null tokens_out");
+    int32_t r = check_batch_sampler(ctx);
+    if (r != GL3_OK) return r;
+    if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
+    bool all_greedy = false;
+    if ((r = gl3_sample_batch_prepare(ctx, n, temperature, topp, coins, &all_greedy)) != GL3_OK) return r;
+    if ((r = gl3_decode_batch_load_logits(ctx, logits, n)) != GL3_OK) return r;
+    const float* logits_dev; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits_dev, &greedy);
+    if (all_greedy) {
+        GL3_HIP(hipMemcpyAsync(tokens_out, greedy, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        GL3_HIP(hipStreamSynchronize(ctx->stream));
+        return GL3_OK;
+    }
+    return gl3_sample_batch_finish(ctx, logits_dev, greedy, n, tokens_out);
+}
+
+int32_t gl3_get_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!out) GL3_FAIL(GL3_E_ARG, "null out");
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    return gl3_sample_probs_row(ctx, row, out);
 }
 
 int32_t gl3_profile_decode(gl3_ctx* ctx, int32_t token, int32_t pos, gl3_kernel_times* out) {

@@ -173,6 +173,7 @@ struct gl3_ctx {
     int64_t topp_device = 0, topp_host = 0;       // top-p draws answered on the device / by the host heap (gl3_get_topp_counts)
     void* sm_sort = nullptr;                      // top-p on the device: (key, index) x 2, radix histogram, result words
     std::vector<int> topp_indices;
+    struct gl3_bsample_state* bs = nullptr;       // row-batched sampler (gl3_sample_batch.h)
     std::vector<std::pair<void*, size_t>> pinned;     // caller buffers registered with gl3_pin_host_buffer (logits land there directly)
     // upload staging
     uint8_t* staging = nullptr;
@@ -247,6 +248,11 @@ int32_t gl3_tp_check(gl3_ctx* ctx);      // after a stream sync: GL3_E_RCCL if a
 int32_t gl3_sample_run(gl3_ctx* ctx, const float* logits_dev, float temperature, float topp, float coin, int32_t* token_out);
 int32_t gl3_sample_probs(gl3_ctx* ctx, float* out);
 void gl3_sample_free(gl3_ctx* ctx);
+// row-batched form (gl3_sample_batch.h): prepare = check + stage the per-row settings (before the step is enqueued), finish = the
+// sampler's launches behind the step on the plan's stream, 8 * n bytes back, host heap for rows whose sampled rank is tied
+int32_t gl3_sample_batch_prepare(gl3_ctx* ctx, int32_t n, const float* temperature, const float* topp, const float* coins, bool* all_greedy);
+int32_t gl3_sample_batch_finish(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n, int32_t* tokens_out);
+int32_t gl3_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);
 
 // gl3_prefill.hip
 float* gl3_prefill_buf(gl3_ctx* ctx, int which);
@@ -255,4 +261,6 @@ void gl3_prefill_free(gl3_ctx* ctx);
 int32_t gl3_prefill_run(gl3_ctx* ctx, int32_t seq, const int32_t* tokens, int32_t n, int32_t start_pos);
 int32_t gl3_prefill_profile(gl3_ctx* ctx, int klass, int n, int iters, double* out_us, uint64_t* int8_ops);
 int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
-                             float* logits_out, int32_t* argmax_out);
+                             float* logits_out, int32_t* argmax_out, bool finish = true);      // finish = false: enqueue only
+void gl3_decode_batch_outputs(gl3_ctx* ctx, const float** logits, const int32_t** greedy);
+int32_t gl3_decode_batch_load_logits(gl3_ctx* ctx, const float* logits, int32_t n);

@@ -2755,11 +2755,9 @@ int32_t gl3_prefill_run(gl3_ctx* ctx, int32_t seq, const int32_t* tokens, int32_
 
 // One decode step of n independent sequences = the prefill machinery over (token, sequence, position) triples +
 // final RMSNorm + vocab projection for every row (the n matvecs become one GEMM over the shared weights).
-int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
-                             float* logits_out, int32_t* argmax_out) {
+static int32_t pf_grow_logits(gl3_ctx* ctx, int n) {
     gl3_prefill_state* p = ctx->pf;
     const gl3_model_desc& d = ctx->d;
-    GL3_HIP(hipSetDevice(d.device));
     if (p->logits_rows < n && p->in_arena) GL3_FAIL(GL3_E_UNSUPPORTED, "tensor-parallel static-batched decode is limited to 64 sequences per step");
     if (p->logits_rows < n) {
         for (auto& ge : p->step_graphs) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }      // captured steps point at the old buffer
@@ -2768,6 +2766,37 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
         GL3_HIP(hipMalloc((void**)&p->LOGITS, (size_t)n * d.vocab * 4));
         p->logits_rows = n;
     }
+    return GL3_OK;
+}
+
+// The batched sampler's view of a step (gl3_sample_batch.h): the logits rows and the greedy ids, both on the device.
+void gl3_decode_batch_outputs(gl3_ctx* ctx, const float** logits, const int32_t** greedy) {
+    *logits = ctx->pf->LOGITS; *greedy = ctx->pf->amax;
+}
+
+// Parity tap gl3_sample_rows: caller-supplied logits take the place of a step's (one rank: the plain [n][vocab] layout), followed by
+// the step's own greedy scan.  No forward pass, no KV change; nothing is waited for.
+int32_t gl3_decode_batch_load_logits(gl3_ctx* ctx, const float* logits, int32_t n) {
+    gl3_prefill_state* p = ctx->pf;
+    const gl3_model_desc& d = ctx->d;
+    GL3_HIP(hipSetDevice(d.device));
+    int32_t r = pf_grow_logits(ctx, n);
+    if (r != GL3_OK) return r;
+    hipStream_t s = ctx->stream;
+    GL3_HIP(hipMemcpyAsync(p->LOGITS, logits, (size_t)n * d.vocab * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(pf_argmax_part_kernel, dim3(AMX_SPLIT, n), dim3(256), 0, s, p->LOGITS, d.vocab, ctx->vocab_l, p->amx_v, p->amx_i);
+    hipLaunchKernelGGL(pf_argmax_fold_kernel, dim3(n), dim3(64), 0, s, p->amx_v, p->amx_i, p->amax);
+    GL3_HIP(hipGetLastError());
+    return GL3_OK;
+}
+
+int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
+                             float* logits_out, int32_t* argmax_out, bool finish) {
+    gl3_prefill_state* p = ctx->pf;
+    const gl3_model_desc& d = ctx->d;
+    GL3_HIP(hipSetDevice(d.device));
+    int32_t r0 = pf_grow_logits(ctx, n);
+    if (r0 != GL3_OK) return r0;
     int max_pos = 0;
     for (int i = 0; i < n; ++i) max_pos = positions[i] > max_pos ? positions[i] : max_pos;
     int32_t r = pf_stage_tokens(ctx, tokens, seq_ids, positions, n);
@@ -2817,6 +2846,7 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
                                      hipMemcpyDeviceToHost, s));
     }
     GL3_HIP(hipGetLastError());
+    if (!finish) return GL3_OK;          // the batched sampler's launches follow on the same stream (gl3_sample_batch_finish)
     GL3_HIP(hipStreamSynchronize(s));
     return gl3_tp_check(ctx);
 }

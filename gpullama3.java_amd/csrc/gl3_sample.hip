@@ -22,6 +22,8 @@
 // order reproduces.  The device path returns the token and a tie flag (8 bytes); on a tie at the sampled rank (~2 % of the draws on the
 // near-uniform distributions of random-weight test models, rarer on real ones) the probabilities are copied out and the reference's heap
 // runs on the host (same sift order, same choice).
+//
+// Static-batched decode (gl3_forward_decode_batch_sample) runs the same pipeline for all rows of a step at once: gl3_sample_batch.h.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -350,7 +352,10 @@ int32_t gl3_sample_alloc(gl3_ctx* ctx) {
     return r;
 }
 
+void gl3_sample_batch_free(gl3_ctx* ctx);      // gl3_sample_batch.h
+
 void gl3_sample_free(gl3_ctx* ctx) {
+    gl3_sample_batch_free(ctx);
     if (ctx->sm_probs) hipFree(ctx->sm_probs);
     if (ctx->sm_aux) hipFree(ctx->sm_aux);
     if (ctx->h_probs) hipHostFree(ctx->h_probs);
@@ -422,3 +427,6 @@ int32_t gl3_sample_probs(gl3_ctx* ctx, float* out) {       // parity tap: the pr
     GL3_HIP(hipMemcpy(out, ctx->sm_probs, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToHost));
     return GL3_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ every row of a batched step
+#include "gl3_sample_batch.h"

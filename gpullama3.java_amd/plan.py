@@ -182,6 +182,37 @@ class HipMasterPlan:
         hip.check(hip.lib().gl3_forward_decode_batch(self._ctx, _p(t), _p(s), _p(p), n, _p(logits) if want_logits else None, _p(ids)), self._ctx)
         return logits, ids
 
+    @staticmethod
+    def _per_row(v, n):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float32), (n,)))
+
+    def forward_decode_batch_sample(self, tokens, seq_ids, positions, temperature, topp, coins) -> np.ndarray:
+        """Static batched decode + the reference's sampler for every row on the device -> sampled ids [n].  temperature / topp /
+        coins: one entry per row (scalars broadcast); coins[i] = rng.nextFloat(1f) from row i's own generator (ignored for
+        temperature 0)."""
+        t = np.ascontiguousarray(tokens, np.int32); s = np.ascontiguousarray(seq_ids, np.int32); p = np.ascontiguousarray(positions, np.int32)
+        n = t.size
+        te, tp, co = self._per_row(temperature, n), self._per_row(topp, n), self._per_row(coins, n)
+        ids = np.empty(n, np.int32)
+        hip.check(hip.lib().gl3_forward_decode_batch_sample(self._ctx, _p(t), _p(s), _p(p), n, _p(te), _p(tp), _p(co), _p(ids)), self._ctx)
+        return ids
+
+    def sample_rows(self, logits, temperature, topp, coins) -> np.ndarray:
+        """The batched sampler alone on host logits [n][vocab] (no forward pass) -> sampled ids [n]."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2 and lg.shape[1] == self.cfg.vocab
+        n = lg.shape[0]
+        te, tp, co = self._per_row(temperature, n), self._per_row(topp, n), self._per_row(coins, n)
+        ids = np.empty(n, np.int32)
+        hip.check(hip.lib().gl3_sample_rows(self._ctx, _p(lg), n, _p(te), _p(tp), _p(co), _p(ids)), self._ctx)
+        return ids
+
+    def sample_probs_row(self, row: int) -> np.ndarray:
+        """The probabilities row `row` of the last batched sampled step was drawn from."""
+        out = np.empty(self.cfg.vocab, np.float32)
+        hip.check(hip.lib().gl3_get_sample_probs_row(self._ctx, row, _p(out)), self._ctx)
+        return out
+
     def kv_seq(self, seq: int, layer: int, pos: int):
         n = self.cfg.kv_dim // self.tp_size
         k, v = np.empty(n, np.float32), np.empty(n, np.float32)

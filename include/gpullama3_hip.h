@@ -263,6 +263,26 @@ GL3_API int32_t gl3_forward_prefill_seq(gl3_ctx* ctx, int32_t seq, const int32_t
 GL3_API int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
                                          int32_t n, float* logits_out, int32_t* argmax_out);
 
+/* One static-batched decode step + Sampler.selectSampler(vocab, temperature[i], topp[i], .).sampleToken(logits row i) for every
+ * row (gl3_forward_decode_sample, row by row).  temperature / topp / coins: f32[n], one entry per row (the requests of one batch
+ * have their own settings); temperature[i] == 0 -> the greedy first-max id of row i (its coin is not looked at); otherwise
+ * coins[i] = rng.nextFloat(1f) drawn by the CALLER from row i's own RandomGenerator, in [0, 1); 0 < topp[i] < 1 -> ToppSampler,
+ * else CategoricalSampler.  tokens_out: int32[n]; 8 * n bytes come back, and only a top-p row whose sampled rank is shared by
+ * equal probabilities has its probabilities copied out for the reference's heap (counted by gl3_get_topp_counts, one count per
+ * non-greedy top-p row).  The number of sampler launches does not depend on n (gl3_sample_batch.h).  Everything else as
+ * gl3_forward_decode_batch; with every temperature 0 the ids are its argmax_out.  GL3_E_UNSUPPORTED: tp_size > 1 (rank-chunked
+ * logits), Qwen2-MoE plans (no batched decode), max_batch <= 1. */
+GL3_API int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids,
+                                                const int32_t* positions, int32_t n, const float* temperature,
+                                                const float* topp, const float* coins, int32_t* tokens_out);
+/* Parity tap: the probabilities (f32[vocab]) row `row` of the last batched sampled step (or gl3_sample_rows call) was drawn from
+ * (GL3_E_STATE for a greedy row or before any such step). */
+GL3_API int32_t gl3_get_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);
+/* Parity tap: the batched sampler alone on caller-supplied logits (host f32[n][vocab]); no forward pass, no KV change.  Needs a
+ * plan with max_batch > 1; n <= max_batch.  The logits buffer of the batched step is overwritten. */
+GL3_API int32_t gl3_sample_rows(gl3_ctx* ctx, const float* logits, int32_t n, const float* temperature, const float* topp,
+                                const float* coins, int32_t* tokens_out);
+
 /* Parity taps. */
 GL3_API int32_t gl3_get_x(gl3_ctx* ctx, float* out /* f32[dim] */);
 GL3_API int32_t gl3_get_layer_x(gl3_ctx* ctx, int32_t layer, float* out /* f32[dim], needs GL3_FLAG_LAYER_TAPS */);

@@ -22,11 +22,7 @@
 
 using namespace gl3;
 #include "gl3_bd_gemm.h"      // GemmArgs, bdw_gemm_kernel (expects the gl3 names in scope)
-#include "gl3_bdk_gemm.h"     // r6: the same GEMM with K split over producer wavefronts + an ordered chain wavefront
-// gl3_prefill_gemm2.hip (own translation unit, -fno-slp-vectorize): the > 64-token GEMM with the scale products on the matrix pipe (r4)
-void gl3_gemm2_launch(int epi, const GemmArgs& a, int rows, int ntok, int mode, hipStream_t s);
-hipError_t gl3_gemm2_allow_lds();
-// r6: the same arithmetic behind a mid-stage barrier / partial-vmcnt operand ring, every GEMM class (gl3_prefill_gemm3.h)
+// gl3_prefill_gemm3.hip (own translation unit, -fno-slp-vectorize): the > 64-token GEMM, every class (gl3_prefill_gemm3.h / gl3_prefill_gemm3t.h)
 void gl3_gemm3_launch(int epi, const GemmArgs& a, int rows, int ntok, hipStream_t s);
 bool gl3_gemm3_swiglu_quantises(int rows, int ntok);
 hipError_t gl3_gemm3_allow_lds();
@@ -35,9 +31,12 @@ struct gl3_prefill_state {
     int max_batch = 0;
     int32_t* tokens = nullptr;          // [M]
     float* X = nullptr;                 // [M][dim] residual stream (rank-chunked [tp][n][dim/tp] under tensor parallelism)
-    uint8_t* XQ = nullptr;              // [M][maxk] int8 activations
-    float* XS = nullptr;                // [M][maxk/32] activation scales
-    uint8_t* XP = nullptr;              // [maxk/32 + 4][2 lane halves][xp_tok][16 B] the activation scales as bf16 MFMA operands (pf_gemm3_kernel)
+    // The next GEMM's activation operand, in one of two layouts chosen by the step's token count n (pf_chunk_major):
+    //   n <= 64 (bdw_gemm_kernel):  XQ / XS in the wave-owned layout of gl3_bd_gemm.h (bdq_offset / bds_offset, 32 or 64 token slots)
+    //   n >  64 (pf_gemm3*_kernel): XQ chunk-major + the scales in XP; XS is not used
+    uint8_t* XQ = nullptr;              // int8 activations; chunk-major: [maxk/16 + 8][xp_tok][16 B]
+    float* XS = nullptr;                // activation scales, one f32 per 32-element block (small-batch layout only)
+    uint8_t* XP = nullptr;              // chunk-major: [maxk/32 + 4][2 lane halves][xp_tok][16 B] the activation scales as bf16 MFMA operands
     int xp_tok = 0;                     //   token slots per block: max_batch rounded up to the GEMM's 128-token tile
     uint8_t* XQh = nullptr;             // second operand set of the > 64-token path: hb quantised by the gate + up GEMM's own epilogue (pf_gemm3t_kernel<.., QOUT>)
     uint8_t* XPh = nullptr;             //   while other workgroups still read XQ / XP
@@ -129,8 +128,6 @@ __global__ __launch_bounds__(256) void pf_norm_quant_kernel(const float* __restr
         ss += eps;
         scale = (float)(1.0 / sqrt((double)ss));
     }
-    uint8_t* xq = XQ + (size_t)b * maxk;
-    float* xs = XS + (size_t)b * (maxk >> 5);
     for (int qd = t + 256 * blockIdx.y; qd < nquads; qd += 256 * gridDim.y) {
         float4 v;
         if (NORM) {
@@ -141,31 +138,26 @@ __global__ __launch_bounds__(256) void pf_norm_quant_kernel(const float* __restr
             v = xquad(qd);
         }
         if (MODE == PQ_NORM_F32 || MODE == PQ_PLAIN_F32) { *reinterpret_cast<float4*>(XS + (size_t)b * k + 4 * qd) = v; continue; }
-        if (tslots == 0) {
+        if (tslots == 0) {                                 // chunk-major (pf_gemm3_kernel): int8 operand XQ[k / 16][xp_tok token slots][16 B], scales in XP
             float qs;
             const uint32_t packed = quantize_quad_pack(v, qs);
-            // XP set (pf_gemm3_kernel): chunk-major int8 operand XQ3[k / 16][xp_tok token slots][16 B]; otherwise the row layout XQ[token][k]
-            if (XP) *reinterpret_cast<uint32_t*>(XQ + ((size_t)(qd >> 2) * xp_tok + b) * 16 + 4 * (qd & 3)) = packed;
-            else *reinterpret_cast<uint32_t*>(xq + 4 * qd) = packed;
+            *reinterpret_cast<uint32_t*>(XQ + ((size_t)(qd >> 2) * xp_tok + b) * 16 + 4 * (qd & 3)) = packed;
             if ((qd & 7) == 0) {
-                xs[qd >> 3] = qs;
-                if (XP) {
-                    // the scale as the bf16 operands the s / -B s MFMAs read (gl3_prefill_gemm3.h): P = {a_hi, a_lo} (hi = top 8 significand bits, lo = the
-                    // rest: exact, qs is an f16 value), Q = P * -2^23 for the k slots of lane half 0, P * -2^22 for half 1 (their sum is -B = -3 * 2^22)
-                    const float ahi = __uint_as_float(__float_as_uint(qs) & 0xFFFF0000u), alo = qs - ahi;
-                    auto pk = [](float h, float l) { return (__float_as_uint(h) >> 16) | (__float_as_uint(l) & 0xFFFF0000u); };
-                    const uint32_t pr = pk(ahi, alo), q0 = pk(ahi * -8388608.f, alo * -8388608.f), q1 = pk(ahi * -4194304.f, alo * -4194304.f);
-                    const int blk = qd >> 3;
-                    uint4* xp = reinterpret_cast<uint4*>(XP);      // XP[block][half][xp_tok][16 B]
-                    xp[((size_t)blk * 2 + 0) * xp_tok + b] = make_uint4(pr, pr, q0, q0);
-                    xp[((size_t)blk * 2 + 1) * xp_tok + b] = make_uint4(0u, 0u, q1, q1);
-                    // ragged K: the padded blocks of the last tile group carry zero weights; give them zero activation operands too
-                    if (blk == (k >> 5) - 1)
-                        for (int pb = blk + 1; pb < ((blk + 4) & ~3); ++pb) {
-                            xp[((size_t)pb * 2 + 0) * xp_tok + b] = make_uint4(0u, 0u, 0u, 0u);
-                            xp[((size_t)pb * 2 + 1) * xp_tok + b] = make_uint4(0u, 0u, 0u, 0u);
-                        }
-                }
+                // the scale as the bf16 operands the s / -B s MFMAs read (gl3_prefill_gemm3.h): P = {a_hi, a_lo} (hi = top 8 significand bits, lo = the
+                // rest: exact, qs is an f16 value), Q = P * -2^23 for the k slots of lane half 0, P * -2^22 for half 1 (their sum is -B = -3 * 2^22)
+                const float ahi = __uint_as_float(__float_as_uint(qs) & 0xFFFF0000u), alo = qs - ahi;
+                auto pk = [](float h, float l) { return (__float_as_uint(h) >> 16) | (__float_as_uint(l) & 0xFFFF0000u); };
+                const uint32_t pr = pk(ahi, alo), q0 = pk(ahi * -8388608.f, alo * -8388608.f), q1 = pk(ahi * -4194304.f, alo * -4194304.f);
+                const int blk = qd >> 3;
+                uint4* xp = reinterpret_cast<uint4*>(XP);      // XP[block][half][xp_tok][16 B]
+                xp[((size_t)blk * 2 + 0) * xp_tok + b] = make_uint4(pr, pr, q0, q0);
+                xp[((size_t)blk * 2 + 1) * xp_tok + b] = make_uint4(0u, 0u, q1, q1);
+                // ragged K: the padded blocks of the last tile group carry zero weights; give them zero activation operands too
+                if (blk == (k >> 5) - 1)
+                    for (int pb = blk + 1; pb < ((blk + 4) & ~3); ++pb) {
+                        xp[((size_t)pb * 2 + 0) * xp_tok + b] = make_uint4(0u, 0u, 0u, 0u);
+                        xp[((size_t)pb * 2 + 1) * xp_tok + b] = make_uint4(0u, 0u, 0u, 0u);
+                    }
             }
         } else {                                           // the wave-owned small-batch GEMM's operand layout (gl3_bd_gemm.h)
             float qs;
@@ -176,309 +168,7 @@ __global__ __launch_bounds__(256) void pf_norm_quant_kernel(const float* __restr
     }
 }
 
-
-// LDS-tiled version: workgroup = 128 weight rows (64 gate + 64 up rows for the SwiGLU epilogue) x 128 tokens, 4
-// wavefronts in a 2 x 2 grid, each owning 64 rows x 64 tokens = four 32x32 int8 MFMA tiles.  K advances 4 blocks
-// (= one Q8T tile per 16-row strip) per stage; the next stage's operands travel HBM/L2 -> registers while the current
-// stage is consumed from LDS (double buffer).  LDS image per stage (36 KB):
-//   Aq[blk][half][128 rows][16 B] | As[blk][128 rows] f32 | Bq[blk][half][128 tokens][16 B] | Bs[blk][128 tokens] f32
-// so an MFMA fragment is one conflict-free ds_read_b128 and the 16 weight scales of a lane are four broadcast b128 reads.
-// RF = 32-row fragments per wavefront (2: 128-row workgroup tile for the wide matrices; 1: 64-row tile so that the
-// 4096-row wo / down projections still launch >= 256 workgroups at 512 tokens).  The SwiGLU epilogue always runs
-// RF = 1 over two matrices.
-constexpr int GM_TOK = 128, GM_KB = 4;
 typedef float v16f_t __attribute__((ext_vector_type(16)));
-__host__ __device__ constexpr int gm_stage_bytes(int arows, int toks = 128) {
-    return GM_KB * 2 * arows * 16 + GM_KB * arows * 4 + GM_KB * 2 * toks * 16 + GM_KB * toks * 4;
-}
-
-// NW = wavefronts per workgroup: 4 (2 x 2, two token fragments each) or 8 (2 x 4, one token fragment each; used for the
-// 4096-row matrices where only one workgroup fits a CU, so that every SIMD still interleaves two wavefronts).
-// TOK = tokens per workgroup: 128, or 32 for static-batched decode (few tokens: four wavefronts side by side along the
-// rows, one token fragment each, so that a batch of 32 does not pay for 128 padded columns).
-template <int EPI, int RF, int NW, int TOK = GM_TOK>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void pf_gemm_kernel(const GemmArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
-    static_assert(NM * RF <= 2, "accumulator budget");
-    static_assert(NW == 4 || (NW == 8 && NM * RF == 1), "8-wavefront layout is for the single-fragment variant");
-    static_assert(TOK == GM_TOK || (TOK == 32 && NW == 4 && RF == 1), "32-token tiles: 4 wavefronts x one fragment");
-    constexpr int NT = 64 * NW;                        // threads
-    constexpr int TF = TOK == 32 ? 1 : 8 / NW;         // 32-token fragments per wavefront
-    constexpr int WR = TOK == 32 ? 4 : 2;              // wavefronts along the rows
-    constexpr int AROWS = NM * RF * 32 * WR;           // weight rows staged per K stage (both matrices together)
-    constexpr int RPM = AROWS / NM;                    // output rows per matrix covered by this workgroup
-    constexpr int STAGE = gm_stage_bytes(AROWS, TOK);
-    constexpr int NAP = (AROWS * 4 + NT - 1) / NT;     // (strip, lane) pairs per thread
-    constexpr int NBP = (TOK * 8 + NT - 1) / NT;       // 16-byte activation pieces per thread
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int tl = lane & 31, hi = lane >> 5;
-    const int wr = TOK == 32 ? wave : NW == 4 ? wave >> 1 : wave >> 2;    // wavefront grid: row part wr,
-    const int wc = TOK == 32 ? 0 : NW == 4 ? wave & 1 : wave & 3;         // tokens wc * 32 * TF ..
-    // XCD-aware tile mapping: workgroups are dealt round-robin to the 8 XCDs (private L2 each), so the token tiles that
-    // share a weight row tile are given consecutive slots of ONE XCD — the weights cross the fabric once, not once per
-    // token tile (rocprofv3 FETCH_SIZE of the gate/up GEMM at 512 tokens: 517 MB -> see profiles/).
-    const int ntt_g = a.ntt, per_xcd = (a.ntt * a.nrt + 7) >> 3;
-    const int lin = blockIdx.x, J = (lin & 7) * per_xcd + (lin >> 3);
-    if (J >= ntt_g * a.nrt) return;
-    const int row0 = (J / ntt_g) * RPM;                // first output row (per matrix)
-    const int tok0 = (J % ntt_g) * TOK;
-    const size_t strip_bytes = (size_t)a.ng * TILE_BYTES;
-    const int nkb = a.ng;                              // K stages = tile groups per strip
-    const int nstrips = (a.rows + 15) >> 4;
-
-    // ---- global -> register staging of one K stage
-    // A: AROWS/16 strips x one tile (64 x f16 scales, 64 x 16 B lo, 64 x 16 B hi).  Thread t: lo/hi pieces
-    // t + 256 i of the (strip, lane-in-tile) pairs; scales: threads < AROWS/2 take 8 f16 = (strip t>>3, lanes 8*(t&7)..+7)
-    v4i_t ra_lo[NAP], ra_hi[NAP], ra_sc, rb[NBP];
-    float4 rb_s;
-    auto tile_of = [&](int sl, int kb) -> const uint8_t* {   // sl: local strip 0..AROWS/16-1
-        constexpr int SPM = RPM / 16;                      // strips per matrix in this workgroup
-        const int m = NM == 2 ? (sl / SPM) : 0;
-        const int strip = min(nstrips - 1, (row0 >> 4) + (NM == 2 ? (sl % SPM) : sl));
-        return (m == 0 ? a.w : a.w2) + (size_t)strip * strip_bytes + (size_t)kb * TILE_BYTES;
-    };
-    auto gload = [&](int kb) {
-#pragma unroll
-        for (int i = 0; i < NAP; ++i) {
-            const int pr = t + NT * i, lt = pr & 63;
-            if (pr < AROWS * 4) {
-                const uint8_t* tile = tile_of(pr >> 6, kb);
-                ra_lo[i] = *reinterpret_cast<const v4i_t*>(tile + 128 + 16 * lt);
-                ra_hi[i] = *reinterpret_cast<const v4i_t*>(tile + 1152 + 16 * lt);
-            }
-        }
-        if (t < AROWS / 2) ra_sc = *reinterpret_cast<const v4i_t*>(tile_of(t >> 3, kb) + 16 * (t & 7));
-        // B: 128 tokens x 128 B of int8 (4 blocks) -> 1024 16-byte pieces, 4 per thread: piece = t + 256*i ->
-        // token = piece >> 3, 16-byte chunk c = piece & 7 (block c>>1, half c&1)
-#pragma unroll
-        for (int i = 0; i < NBP; ++i) {
-            const int pc = t + NT * i, tk = min(a.ntok - 1, tok0 + (pc >> 3)), c = pc & 7;
-            if (pc < TOK * 8) rb[i] = *reinterpret_cast<const v4i_t*>(a.XQ + (size_t)tk * a.maxk + (size_t)kb * 128 + 16 * c);
-        }
-        if (t < TOK) {
-            const int tk = min(a.ntok - 1, tok0 + t);
-            rb_s = *reinterpret_cast<const float4*>(a.XS + (size_t)tk * (a.maxk >> 5) + kb * 4);
-        }
-    };
-    auto lstore = [&](int stage, int kbs) {        // kbs = K stage held in the staging registers
-        uint8_t* base = smem + (size_t)stage * STAGE;
-        uint8_t* Aq = base;
-        float* As = reinterpret_cast<float*>(base + GM_KB * 2 * AROWS * 16);
-        uint8_t* Bq = base + GM_KB * 2 * AROWS * 16 + GM_KB * AROWS * 4;
-        float* Bs = reinterpret_cast<float*>(Bq + GM_KB * 2 * TOK * 16);
-#pragma unroll
-        for (int i = 0; i < NAP; ++i) {
-            const int pr = t + NT * i, sl = pr >> 6, lt = pr & 63;
-            const int row = sl * 16 + (lt & 15), blk = lt >> 4;
-            if (pr < AROWS * 4) {
-                *reinterpret_cast<v4i_t*>(Aq + ((size_t)(blk * 2 + 0) * AROWS + row) * 16) = ra_lo[i];
-                *reinterpret_cast<v4i_t*>(Aq + ((size_t)(blk * 2 + 1) * AROWS + row) * 16) = ra_hi[i];
-            }
-        }
-        if (t < AROWS / 2) {
-            const int sl = t >> 3;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int lt = 8 * (t & 7) + j;
-                const uint32_t w = (uint32_t)ra_sc[j >> 1];
-                As[(lt >> 4) * AROWS + sl * 16 + (lt & 15)] = h2f((uint16_t)((j & 1) ? (w >> 16) : (w & 0xFFFF)));
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NBP; ++i) {
-            const int pc = t + NT * i, tk = pc >> 3, c = pc & 7;
-            if (pc < TOK * 8) *reinterpret_cast<v4i_t*>(Bq + ((size_t)c * TOK + (tk ^ c)) * 16) = rb[i]; // c = blk*2 + half; xor: bank spread
-        }
-        if (t < TOK) {
-            // ragged K (k % 128 != 0): the padded blocks carry zero weights; zero their activation scale too.  (Done
-            // here, not at load time, so that the global loads stay in flight across the compute phase.)
-            Bs[0 * TOK + t] = rb_s.x;
-            Bs[1 * TOK + t] = kbs * 4 + 1 < a.nb ? rb_s.y : 0.f;
-            Bs[2 * TOK + t] = kbs * 4 + 2 < a.nb ? rb_s.z : 0.f;
-            Bs[3 * TOK + t] = kbs * 4 + 3 < a.nb ? rb_s.w : 0.f;
-        }
-    };
-
-    // accumulators: [fragment f][token frag][8 x 2]; fragment f = matrix (SwiGLU) or row fragment
-    constexpr int NF = NM * RF;
-    v2f_t acc[NF][TF][8];
-#pragma unroll
-    for (int i = 0; i < NF; ++i)
-#pragma unroll
-        for (int j = 0; j < TF; ++j)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) acc[i][j][r] = v2f_t{0.f, 0.f};
-
-#ifdef GL3_GEMM_TIMING
-    const unsigned long long tk0 = __builtin_readcyclecounter(), rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    v16i_t cbias;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cbias[r] = 0x4B400000;
-    if constexpr (NM * RF == 1) asm volatile("" : "+v"(cbias));   // keep the splat in VGPRs (else 8 v_mov_b64 per MFMA pair)
-    gload(0);
-    lstore(0, 0);
-    __syncthreads();
-    for (int kb = 0; kb < nkb; ++kb) {
-        if (kb + 1 < nkb) gload(kb + 1);
-        const uint8_t* base = smem + (size_t)(kb & 1) * STAGE;
-        const uint8_t* Aq = base;
-        const float* As = reinterpret_cast<const float*>(base + GM_KB * 2 * AROWS * 16);
-        const uint8_t* Bq = base + GM_KB * 2 * AROWS * 16 + GM_KB * AROWS * 4;
-        const float* Bs = reinterpret_cast<const float*>(Bq + GM_KB * 2 * TOK * 16);
-        // operand fragments of one Q8_0 block for this wavefront
-        // MFMA_SCALES (single-fragment variants: wo / down at 512 tokens): the scale products wScale * aScale of the 32 x 32 tile
-        // come from the MATRIX pipe: one v_mfma_f32_32x32x2_f32 with A = wScale (k = 0 | 0), B = aScale (k = 0 | 0), C = 0 gives
-        // D[i][j] = fl(wScale_i * aScale_j) in the layout of the int8 tile — the f32 MFMA rounds once per step like fmaf
-        // (MI355X_MICROARCH.md), fma(0, 0, fl(w a)) = fl(w a), and both scales are >= +0 so no -0 arises.  The VALU keeps three
-        // operations per output and block (subtract, multiply, add) instead of four: down 145 -> 132 us, wo 46 -> 43 us at 512
-        // tokens.  With two or four fragments per wavefront the extra 64-cycle MFMAs sit in front of the dependent VALU work and
-        // the same change LOST time (gate/up 236 -> 275 us, qkv 73 -> 79 us), so those variants multiply on the VALU.
-        constexpr bool MFMA_SCALES = NF * TF == 1;
-        struct Frag { v4i_t bf[TF]; v2f_t xsc[TF]; v4i_t af[NF]; v2f_t wsf[NF][MFMA_SCALES ? 1 : 8]; };
-        auto fload_a = [&](Frag& fr, int blk, int f) {
-            const int lrow = NM == 2 ? f * RPM + wr * 32 : wr * (32 * RF) + f * 32;    // local row of this fragment
-            fr.af[f] = *reinterpret_cast<const v4i_t*>(Aq + ((size_t)(blk * 2 + hi) * AROWS + lrow + tl) * 16);
-            if constexpr (MFMA_SCALES) {
-                const float w = As[blk * AROWS + lrow + tl];
-                fr.wsf[f][0] = v2f_t{hi ? 0.f : w, 0.f};        // A operand: lane = row in k = 0, zeros in k = 1
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 w4 = *reinterpret_cast<const float4*>(As + blk * AROWS + lrow + 8 * q + 4 * hi);
-                    fr.wsf[f][2 * q] = v2f_t{w4.x, w4.y};
-                    fr.wsf[f][2 * q + 1] = v2f_t{w4.z, w4.w};
-                }
-            }
-        };
-        auto fload = [&](Frag& fr, int blk, bool with_a) {
-#pragma unroll
-            for (int tf = 0; tf < TF; ++tf) {
-                const int tk = wc * (32 * TF) + tf * 32 + tl;
-                fr.bf[tf] = *reinterpret_cast<const v4i_t*>(Bq + ((size_t)(blk * 2 + hi) * TOK + (tk ^ (blk * 2 + hi))) * 16);
-                const float x = Bs[blk * TOK + tk];
-                fr.xsc[tf] = MFMA_SCALES ? v2f_t{hi ? 0.f : x, 0.f} : v2f_t{x, x};
-            }
-            if (with_a) {
-#pragma unroll
-                for (int f = 0; f < NF; ++f) fload_a(fr, blk, f);
-            }
-        };
-        // The int32 block sums come out of the MFMA already biased by 0x4B400000: reinterpreted as f32 that is
-        // 12582912 + isum exactly (|isum| <= 32*127*127 < 2^22), so (float)isum = bits - 12582912.0f is one packed
-        // subtract per two values instead of two v_cvt_f32_i32.
-        auto fcompute = [&](Frag& fr, int blk, bool load_a) {
-#pragma unroll
-            for (int f = 0; f < NF; ++f) {
-                if (load_a) fload_a(fr, blk, f);
-                v16i_t c[TF];
-#pragma unroll
-                for (int tf = 0; tf < TF; ++tf) c[tf] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fr.af[f], fr.bf[tf], cbias, 0, 0, 0);
-#pragma unroll
-                for (int tf = 0; tf < TF; ++tf) {
-                    v2f_t cf[8], pr[8];
-#pragma unroll
-                    for (int r = 0; r < 8; ++r)
-                        cf[r] = v2f_t{__int_as_float(c[tf][2 * r]), __int_as_float(c[tf][2 * r + 1])} - v2f_t{12582912.f, 12582912.f};
-                    if constexpr (MFMA_SCALES) {
-                        const v16f_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                        const v16f_t p16 = __builtin_amdgcn_mfma_f32_32x32x2f32(fr.wsf[f][0][0], fr.xsc[tf][0], zero16, 0, 0, 0);
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) pr[r] = v2f_t{p16[2 * r], p16[2 * r + 1]};
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 8; ++r) pr[r] = fr.wsf[f][r] * fr.xsc[tf];
-                    }
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) cf[r] = cf[r] * pr[r];       // isum * (wScale * aScale)
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) acc[f][tf][r] = acc[f][tf][r] + cf[r];   // result +=, blocks ascending
-                }
-            }
-        };
-        if constexpr (NF == 1) {
-            // one wavefront per SIMD in the narrow-matrix launches: fetch block b+1's fragments while block b computes
-            Frag fa, fb;
-            fload(fa, 0, true);
-            if constexpr (TF == 1) {          // small fragments: static registers for the whole stage, no loop-carried copies
-#pragma unroll
-                for (int blk = 0; blk < GM_KB; blk += 2) {
-                    fload(fb, blk + 1, true);
-                    fcompute(fa, 0, false);
-                    if (blk + 2 < GM_KB) fload(fa, blk + 2, true);
-                    fcompute(fb, 0, false);
-                }
-            } else {
-#pragma unroll 1
-                for (int blk = 0; blk < GM_KB; blk += 2) {
-                    fload(fb, blk + 1, true);
-                    fcompute(fa, 0, false);
-                    if (blk + 2 < GM_KB) fload(fa, blk + 2, true);
-                    fcompute(fb, 0, false);
-                }
-            }
-        } else {
-#pragma unroll 1
-            for (int blk = 0; blk < GM_KB; ++blk) {
-                Frag fr;
-                fload(fr, blk, false);
-                fcompute(fr, blk, true);
-            }
-        }
-        if (kb + 1 < nkb) lstore((kb + 1) & 1, kb + 1);
-        __syncthreads();
-    }
-#ifdef GL3_GEMM_TIMING
-    if (t == 0 && (blockIdx.y % 97) == 0 && blockIdx.x == 0) {
-        const unsigned long long tk1 = __builtin_readcyclecounter(), rt1 = __builtin_amdgcn_s_memrealtime();
-        printf("gemm epi=%d wg=(%d,%d) nkb=%d ticks=%llu realtime=%llu start_rt=%llu\n", EPI, blockIdx.x, blockIdx.y, nkb, tk1 - tk0, rt1 - rt0, rt0);
-    }
-#endif
-    // ---- epilogue.  C layout: token = lane & 31 (column), weight row = (r & 3) + 8 * (r >> 2) + 4 * hi
-#pragma unroll
-    for (int tf = 0; tf < TF; ++tf) {
-        const int b = tok0 + wc * (32 * TF) + tf * 32 + tl;
-        if (b >= a.ntok) continue;
-        if (EPI == EPI_SWIGLU) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                if (row >= a.rows) continue;
-                float g = acc[0][tf][r >> 1][r & 1];
-                g = g / (float)(1.0 + exp(-(double)g));
-                a.out[(size_t)b * a.out_stride + row] = g * acc[NF - 1][tf][r >> 1][r & 1];
-            }
-        } else {
-#pragma unroll
-            for (int f = 0; f < NF; ++f) {
-                // rows (r & 3) + 8 * (r >> 2) + 4 * hi: four runs of four consecutive rows -> float4 accesses
-                float* o = a.out + (size_t)b * a.out_stride + row0 + wr * (32 * RF) + f * 32 + 4 * hi;
-                const int rbase = row0 + wr * (32 * RF) + f * 32 + 4 * hi;
-                float4 old[4];
-                if (EPI == EPI_RESID) {
-                    // unconditional loads (a guarded load into an array is followed by s_waitcnt vmcnt(0): four serialised round trips
-                    // per fragment); rows past the end read the buffer's first element instead and are not used
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        old[q] = *reinterpret_cast<const float4*>(rbase + 8 * q + 3 < a.rows ? o + 8 * q : a.out);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float4 v = {acc[f][tf][2 * q][0] * a.out_scale, acc[f][tf][2 * q][1] * a.out_scale, acc[f][tf][2 * q + 1][0] * a.out_scale, acc[f][tf][2 * q + 1][1] * a.out_scale};
-                    if (rbase + 8 * q + 3 < a.rows) {
-                        if (EPI == EPI_RESID) { v.x = old[q].x + v.x; v.y = old[q].y + v.y; v.z = old[q].z + v.z; v.w = old[q].w + v.w; }
-                        *reinterpret_cast<float4*>(o + 8 * q) = v;
-                    } else {
-                        const float vv[4] = {v.x, v.y, v.z, v.w};
-                        for (int i = 0; i < 4; ++i)
-                            if (rbase + 8 * q + i < a.rows) o[8 * q + i] = EPI == EPI_RESID ? o[8 * q + i] + vv[i] : vv[i];
-                    }
-                }
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------
 // RoPE on q and k of every token + KV-cache write (batchForwardJavaPrefill :106-121; Qwen3 adds the per-head
@@ -2243,23 +1933,27 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     }
     const size_t MQ = M < BD_TS_MAX ? BD_TS_MAX : M;      // the small-batch operand layout (bd_tslots) always spans its 32 / 64 token slots
     const size_t MQP = (MQ + 127) & ~(size_t)127;      // token slots of the chunk-major layouts (whole 128-token GEMM tiles)
-    GL3_HIP(hipMalloc((void**)&p->XQ, MQP * p->maxk + GL3_TAIL_PAD));
-    GL3_HIP(hipMalloc((void**)&p->XS, MQ * (p->maxk / 32) * 4 + GL3_TAIL_PAD));
+    // pf_gemm3_kernel's LDS-DMA reads whole K stages: both chunk-major operands carry four blocks (one stage) beyond maxk, zeroed once here
+    const size_t xq_bytes = MQP * (p->maxk + 4 * 32) + GL3_TAIL_PAD;
+    const size_t xp_bytes = MQP * (p->maxk / 32 + 4) * 32 + GL3_TAIL_PAD;
+    const size_t xs_bytes = MQ * (p->maxk / 32) * 4;
+    GL3_HIP(hipMalloc((void**)&p->XQ, xq_bytes));
+    GL3_HIP(hipMalloc((void**)&p->XS, xs_bytes + GL3_TAIL_PAD));
     p->xp_tok = (int)MQP;
-    GL3_HIP(hipMalloc((void**)&p->XP, (size_t)(p->maxk / 32 + 4) * p->xp_tok * 32 + GL3_TAIL_PAD));
-    GL3_HIP(hipMemsetAsync(p->XP, 0, (size_t)(p->maxk / 32 + 4) * p->xp_tok * 32 + GL3_TAIL_PAD, ctx->stream));
+    GL3_HIP(hipMalloc((void**)&p->XP, xp_bytes));
+    GL3_HIP(hipMemsetAsync(p->XP, 0, xp_bytes, ctx->stream));
     if (M > 64 && d.tp_size == 1) {
-        GL3_HIP(hipMalloc((void**)&p->XQh, MQP * p->maxk + GL3_TAIL_PAD));
-        GL3_HIP(hipMalloc((void**)&p->XPh, (size_t)(p->maxk / 32 + 4) * p->xp_tok * 32 + GL3_TAIL_PAD));
-        GL3_HIP(hipMemsetAsync(p->XQh, 0, MQP * p->maxk + GL3_TAIL_PAD, ctx->stream));
-        GL3_HIP(hipMemsetAsync(p->XPh, 0, (size_t)(p->maxk / 32 + 4) * p->xp_tok * 32 + GL3_TAIL_PAD, ctx->stream));
+        GL3_HIP(hipMalloc((void**)&p->XQh, xq_bytes));
+        GL3_HIP(hipMalloc((void**)&p->XPh, xp_bytes));
+        GL3_HIP(hipMemsetAsync(p->XQh, 0, xq_bytes, ctx->stream));
+        GL3_HIP(hipMemsetAsync(p->XPh, 0, xp_bytes, ctx->stream));
     }
     GL3_HIP(hipMalloc((void**)&p->XQb, (size_t)BD_TS_MAX * p->maxk + GL3_TAIL_PAD));
     GL3_HIP(hipMalloc((void**)&p->XSb, (size_t)BD_TS_MAX * (p->maxk / 32) * 4 + GL3_TAIL_PAD));
     GL3_HIP(hipMemsetAsync(p->XQb, 0, (size_t)BD_TS_MAX * p->maxk, ctx->stream));
     GL3_HIP(hipMemsetAsync(p->XSb, 0, (size_t)BD_TS_MAX * (p->maxk / 32) * 4, ctx->stream));
-    GL3_HIP(hipMemsetAsync(p->XQ, 0, MQP * p->maxk, ctx->stream));
-    GL3_HIP(hipMemsetAsync(p->XS, 0, MQ * (p->maxk / 32) * 4, ctx->stream));
+    GL3_HIP(hipMemsetAsync(p->XQ, 0, xq_bytes, ctx->stream));
+    GL3_HIP(hipMemsetAsync(p->XS, 0, xs_bytes, ctx->stream));
     GL3_HIP(hipMalloc((void**)&p->QKV, M * (ctx->q_dim + 2 * ctx->kv_dim) * 4));
     GL3_HIP(hipMalloc((void**)&p->ATT, M * d.n_heads * (size_t)d.ctx * 4));
     p->tmx_tiles = (d.ctx + 63) / 64;
@@ -2269,23 +1963,7 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     GL3_HIP(hipMalloc((void**)&p->amax, M * sizeof(int32_t)));
     GL3_HIP(hipMalloc((void**)&p->amx_v, M * AMX_SPLIT * sizeof(float)));
     GL3_HIP(hipMalloc((void**)&p->amx_i, M * AMX_SPLIT * sizeof(int)));
-#define GL3_GEMM_LDS(...) GL3_HIP(hipFuncSetAttribute((const void*)pf_gemm_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * gm_stage_bytes(128)))
-    GL3_GEMM_LDS(EPI_STORE, 1, 4); GL3_GEMM_LDS(EPI_STORE, 2, 4); GL3_GEMM_LDS(EPI_STORE, 1, 8);
-    GL3_GEMM_LDS(EPI_RESID, 1, 4); GL3_GEMM_LDS(EPI_RESID, 2, 4); GL3_GEMM_LDS(EPI_RESID, 1, 8);
-    GL3_GEMM_LDS(EPI_SWIGLU, 1, 4);
-    GL3_GEMM_LDS(EPI_STORE, 1, 4, 32); GL3_GEMM_LDS(EPI_RESID, 1, 4, 32); GL3_GEMM_LDS(EPI_SWIGLU, 1, 4, 32);
-#undef GL3_GEMM_LDS
-    GL3_HIP(gl3_gemm2_allow_lds());                      // pf_gemm2_kernel instantiations (own translation unit)
     GL3_HIP(gl3_gemm3_allow_lds());
-#define GL3_BDK_ATTR(EPI_, P_, DA_, Q_, TS_) GL3_HIP(hipFuncSetAttribute((const void*)bdk_gemm_kernel<EPI_, P_, DA_, Q_, TS_>, hipFuncAttributeMaxDynamicSharedMemorySize, bdk_lds_bytes<EPI_, P_, Q_>()))
-#define GL3_BDK_ATTRS(P_, TS_) GL3_BDK_ATTR(EPI_STORE, P_, 4, false, TS_); GL3_BDK_ATTR(EPI_RESID, P_, 4, false, TS_); GL3_BDK_ATTR(EPI_SWIGLU, P_, 4, false, TS_); GL3_BDK_ATTR(EPI_SWIGLU, (P_ > 2 ? 2 : P_), 4, true, TS_)
-    GL3_BDK_ATTRS(2, BD_TS); GL3_BDK_ATTRS(3, BD_TS); GL3_BDK_ATTRS(4, BD_TS); GL3_BDK_ATTRS(2, BD_TS_MAX); GL3_BDK_ATTRS(3, BD_TS_MAX); GL3_BDK_ATTRS(4, BD_TS_MAX);
-#undef GL3_BDK_ATTRS
-    // ring of 8 tiles per producer (GL3_BDK_DA=8): single-matrix classes only
-#define GL3_BDK_ATTRS8(P_, TS_) GL3_BDK_ATTR(EPI_STORE, P_, 8, false, TS_); GL3_BDK_ATTR(EPI_RESID, P_, 8, false, TS_)
-    GL3_BDK_ATTRS8(2, BD_TS); GL3_BDK_ATTRS8(3, BD_TS); GL3_BDK_ATTRS8(2, BD_TS_MAX); GL3_BDK_ATTRS8(3, BD_TS_MAX);
-#undef GL3_BDK_ATTRS8
-#undef GL3_BDK_ATTR
     GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     { const int32_t ar = pf_attention_attributes(ctx); if (ar != GL3_OK) return ar; }
@@ -2303,19 +1981,19 @@ void gl3_prefill_free(gl3_ctx* ctx) {
     ctx->pf = nullptr;
 }
 
-// > 64-token GEMMs on pf_gemm3_kernel (default) or on the r3 / r4 kernels (GL3_PF_GEMM3=0): the quantiser and the GEMM of a step must agree on the
-// activation layout, so both ask here
-static bool pf_use_gemm3() {
-    static const bool on = !(getenv("GL3_PF_GEMM3") && atoi(getenv("GL3_PF_GEMM3")) == 0);
-    return on;
-}
+// Token slots of the XQ / XS operand layout of gl3_bd_gemm.h when a step of n tokens runs on the wave-owned small-batch GEMM
+// (bdw_gemm_kernel: n <= 64), 0 for a larger step.
+static int bd_tslots(int n) { return n <= BD_TS ? BD_TS : n <= BD_TS_MAX ? BD_TS_MAX : 0; }
 
-// Token slots of the XQ2 / XS2 operand layout when a step of n tokens runs on the wave-owned small-batch GEMM
-// (bdw_gemm_kernel), 0 = row layout + the tiled GEMMs.  The quantiser and the GEMM of a step must agree, so both ask here.
-static int bd_tslots(int n) {
-    static const bool off = getenv("GL3_BD_GEMM") && atoi(getenv("GL3_BD_GEMM")) == 0;      // A/B switch: tiled GEMMs for small batches too
-    return off ? 0 : n <= BD_TS ? BD_TS : n <= BD_TS_MAX ? BD_TS_MAX : 0;
-}
+// The one fact that fixes a step's activation layout: more than 64 tokens run on pf_gemm3_kernel / pf_gemm3t_kernel, which read the
+// chunk-major int8 operand XQ[k / 16][token slot][16 B] and the scale operands XP.  Every producer of a GEMM operand (the quantiser,
+// the attention and gate + up epilogues that quantise their own output) and launch_gemm ask here, so they cannot disagree.
+static bool pf_chunk_major(int n) { return bd_tslots(n) == 0; }
+
+// A/B switches of the fused producers, read once: GL3_NO_FUSED_QUANT=1 keeps the separate quantise launches, GL3_NO_FUSED_BD_ATTN=1
+// the three-kernel attention of static-batched decode
+static bool pf_fused_quant_off() { static const bool off = getenv("GL3_NO_FUSED_QUANT") && atoi(getenv("GL3_NO_FUSED_QUANT")); return off; }
+static bool pf_fused_bd_attn_off() { static const bool off = getenv("GL3_NO_FUSED_BD_ATTN") && atoi(getenv("GL3_NO_FUSED_BD_ATTN")); return off; }
 
 template <int EPI>
 static void launch_gemm(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int ntok, float* out, int out_stride, float out_scale = 1.0f,
@@ -2327,89 +2005,26 @@ static void launch_gemm(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int ntok,
     a.maxk = p->maxk; a.ntok = ntok; a.out = out; a.out_stride = out_stride; a.out_scale = out_scale;
     a.XQo = p->XQb; a.XSo = p->XSb;
     a.XP = p->XP; a.xp_tok = p->xp_tok;
-    // 128-row tiles only when they still give >= 2 workgroups per CU; otherwise 64-row tiles, and 8 wavefronts per
-    // workgroup when even those leave a single workgroup per CU
-    if (const int ts = bd_tslots(ntok)) {      // static-batched decode / small chunks: one wavefront per (16-row strip, 16 tokens), all of K
-        a.tslots = ts;
-        const dim3 grid(bdw_grid((w.rows + 15) / 16, (ntok + 15) / 16));
-        const dim3 gridq(bdw_grid((w.rows + 31) / 32, (ntok + 15) / 16));      // quantised output: two strips per workgroup
-        // r6: K split over P producer wavefronts + one chain wavefront per (strip, token tile) (gl3_bdk_gemm.h); GL3_BDK=0: one wavefront per (strip, token tile)
-        // Measured slower than one wavefront per (strip, token tile) on every class (Qwen3-4B B = 32: 3.53 - 4.0 ms per step against 3.14;
-        // profiles/r06_bd32_kslice.md has the per-round stamps), so it is OFF by default and kept as the bit-exact record of that experiment.
-        static const int bdk = getenv("GL3_BDK") ? atoi(getenv("GL3_BDK")) : 0;
-        static const int bdk_p = getenv("GL3_BDK_P") ? atoi(getenv("GL3_BDK_P")) : 3;
-#define GL3_BDK_L(P_, TS_) \
-        do { \
-            if constexpr (EPI == EPI_SWIGLU) { \
-                if (quantised_out) hipLaunchKernelGGL((bdk_gemm_kernel<EPI, (P_ > 2 ? 2 : P_), 4, true, TS_>), gridq, dim3(128 * ((P_ > 2 ? 2 : P_) + 1)), (bdk_lds_bytes<EPI, (P_ > 2 ? 2 : P_), true>()), ctx->stream, a); \
-                else hipLaunchKernelGGL((bdk_gemm_kernel<EPI, P_, 4, false, TS_>), grid, dim3(64 * (P_ + 1)), (bdk_lds_bytes<EPI, P_, false>()), ctx->stream, a); \
-            } else hipLaunchKernelGGL((bdk_gemm_kernel<EPI, P_, 4, false, TS_>), grid, dim3(64 * (P_ + 1)), (bdk_lds_bytes<EPI, P_, false>()), ctx->stream, a); \
-        } while (0)
-#define GL3_BDK(TS_) do { if (bdk_p == 2) GL3_BDK_L(2, TS_); else if (bdk_p == 4) GL3_BDK_L(4, TS_); else GL3_BDK_L(3, TS_); } while (0)
-        static const int bdk_gu = getenv("GL3_BDK_GU") ? atoi(getenv("GL3_BDK_GU")) : 1;      // 0: the gate + up launch stays on bdw_gemm_kernel
-        static const int bdk_da = getenv("GL3_BDK_DA") ? atoi(getenv("GL3_BDK_DA")) : 4;      // tiles in flight per producer (8: single-matrix classes, P = 2 / 3)
-        if constexpr (EPI != EPI_SWIGLU) {
-            if (bdk && bdk_da == 8 && bdk_p <= 3) {
-#define GL3_BDK8(P_, TS_) hipLaunchKernelGGL((bdk_gemm_kernel<EPI, P_, 8, false, TS_>), grid, dim3(64 * (P_ + 1)), (bdk_lds_bytes<EPI, P_, false>()), ctx->stream, a)
-                if (ts == BD_TS) { if (bdk_p == 2) GL3_BDK8(2, BD_TS); else GL3_BDK8(3, BD_TS); }
-                else { if (bdk_p == 2) GL3_BDK8(2, BD_TS_MAX); else GL3_BDK8(3, BD_TS_MAX); }
-#undef GL3_BDK8
-                return;
-            }
-        }
-        if (bdk && (EPI != EPI_SWIGLU || bdk_gu)) { if (ts == BD_TS) GL3_BDK(BD_TS); else GL3_BDK(BD_TS_MAX); return; }
-#undef GL3_BDK
-#undef GL3_BDK_L
-#define GL3_BDW(TS_) \
-        do { \
-            if constexpr (EPI == EPI_SWIGLU) { \
-                if (quantised_out) hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, true, TS_>), gridq, dim3(128), 0, ctx->stream, a); \
-                else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, false, TS_>), grid, dim3(64), 0, ctx->stream, a); \
-            } else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 8, 2, false, TS_>), grid, dim3(64), 0, ctx->stream, a); \
-        } while (0)
-        if (ts == BD_TS) GL3_BDW(BD_TS); else GL3_BDW(BD_TS_MAX);
-#undef GL3_BDW
-        return;
-    }
-    if (ntok <= 64) {      // 32-token tiles, 128 rows (x2 matrices for SwiGLU) per workgroup
-        const int ntt = (ntok + 31) / 32, nrt = (w.rows + 127) / 128;
-        a.ntt = ntt; a.nrt = nrt;
-        constexpr int AR = EPI == EPI_SWIGLU ? 256 : 128;
-        hipLaunchKernelGGL((pf_gemm_kernel<EPI, 1, 4, 32>), dim3(8 * ((ntt * nrt + 7) / 8)), dim3(256), 2 * gm_stage_bytes(AR, 32), ctx->stream, a);
-        return;
-    }
-    const int ntt = (ntok + GM_TOK - 1) / GM_TOK;
-    a.ntt = ntt;
-    auto grid = [&](int nrt) { a.nrt = nrt; return dim3(8 * ((ntt * nrt + 7) / 8)); };
-    // r4: scale products on the matrix pipe (gl3_prefill_gemm2.h).  GL3_PF_GEMM2=0: the r3 kernel; 1: -B s on the VALU (A/B switches)
-    // Default: the gate/up GEMM (two matrices per workgroup, the dominant launch) on the r4 kernel — measured 246-250 us against 266-272
-    // for the r3 kernel at 512 tokens of the 8B layer; the other shapes stay on the r3 kernel (qkv 79 vs 80, wo 57 vs 45, down 222 vs 139:
-    // profiles/r04_gemm_experiments.md).  GL3_PF_GEMM2=0: r3 kernel everywhere; GL3_PF_GEMM2_ALL=1: r4 kernel for every shape;
-    // GL3_PF_GEMM2=1: A/B form (-B s on the VALU).
-    // r6: every class on pf_gemm3_kernel (mid-stage barrier, partial vmcnt, scale-operand side table, chunk-major activations);
-    // GL3_PF_GEMM3=0 restores the r5 choice below (the quantiser then writes the row layout those kernels read)
-    if (pf_use_gemm3()) {
+    if (pf_chunk_major(ntok)) {      // > 64 tokens: pf_gemm3_kernel / pf_gemm3t_kernel, tiling by matrix shape (gl3_prefill_gemm3.hip)
         if (quantised_out) { a.XQo = p->XQh; a.XPo = p->XPh; }          // gate + up: hb as the down projection's operand (tall tiling, one rank)
         if (second_operand) { a.XQ = p->XQh; a.XP = p->XPh; }            // down: reads it
         gl3_gemm3_launch(EPI, a, w.rows, ntok, ctx->stream);
         return;
     }
-    static const int g2 = getenv("GL3_PF_GEMM2") ? atoi(getenv("GL3_PF_GEMM2")) : 2;
-    static const bool g2_all = getenv("GL3_PF_GEMM2_ALL") && atoi(getenv("GL3_PF_GEMM2_ALL"));
-    if (g2 && (EPI == EPI_SWIGLU || g2_all)) { gl3_gemm2_launch(EPI, a, w.rows, ntok, g2, ctx->stream); return; }
-    if constexpr (EPI == EPI_SWIGLU) {
-        const dim3 g = grid((w.rows + 63) / 64);
-        hipLaunchKernelGGL((pf_gemm_kernel<EPI, 1, 4>), g, dim3(256), 2 * gm_stage_bytes(128), ctx->stream, a);
-    } else if ((size_t)ntt * ((w.rows + 127) / 128) >= 512) {
-        const dim3 g = grid((w.rows + 127) / 128);
-        hipLaunchKernelGGL((pf_gemm_kernel<EPI, 2, 4>), g, dim3(256), 2 * gm_stage_bytes(128), ctx->stream, a);
-    } else if ((size_t)ntt * ((w.rows + 63) / 64) > 256) {
-        const dim3 g = grid((w.rows + 63) / 64);
-        hipLaunchKernelGGL((pf_gemm_kernel<EPI, 1, 4>), g, dim3(256), 2 * gm_stage_bytes(64), ctx->stream, a);
-    } else {
-        const dim3 g = grid((w.rows + 63) / 64);
-        hipLaunchKernelGGL((pf_gemm_kernel<EPI, 1, 8>), g, dim3(512), 2 * gm_stage_bytes(64), ctx->stream, a);
-    }
+    // static-batched decode / small chunks: one wavefront per (16-row strip, 16 tokens), all of K
+    const int ts = bd_tslots(ntok);
+    a.tslots = ts;
+    const dim3 grid(bdw_grid((w.rows + 15) / 16, (ntok + 15) / 16));
+    const dim3 gridq(bdw_grid((w.rows + 31) / 32, (ntok + 15) / 16));      // quantised output: two strips per workgroup
+#define GL3_BDW(TS_) \
+    do { \
+        if constexpr (EPI == EPI_SWIGLU) { \
+            if (quantised_out) hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, true, TS_>), gridq, dim3(128), 0, ctx->stream, a); \
+            else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, false, TS_>), grid, dim3(64), 0, ctx->stream, a); \
+        } else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 8, 2, false, TS_>), grid, dim3(64), 0, ctx->stream, a); \
+    } while (0)
+    if (ts == BD_TS) GL3_BDW(BD_TS); else GL3_BDW(BD_TS_MAX);
+#undef GL3_BDW
 }
 
 // RoPE + KV write + attention of layer l for the n tokens whose raw q | k | v rows are in p->QKV -> AOr (this rank's chunk of the
@@ -2428,7 +2043,7 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
     const size_t kv_layer = (size_t)d.ctx * kvd;
     // one workgroup per (kv head, token) serves the kv head's whole group of query heads when its LDS image fits
     const int bd_group = (kvmul <= 8 && attn_head_smem(d.head_size, kvmul) <= 150 * 1024) ? kvmul : 1;
-    const bool fused_decode = ctx->fused_attn_ok && max_pos < AF_MAXN && !(getenv("GL3_NO_FUSED_BD_ATTN") && atoi(getenv("GL3_NO_FUSED_BD_ATTN")));
+    const bool fused_decode = ctx->fused_attn_ok && max_pos < AF_MAXN && !pf_fused_bd_attn_off();
     RopeArgs ra{};
     ra.QKV = p->QKV; ra.qkv_stride = qkv_dim; ra.kcache = ctx->kcache + l * kv_layer; ra.vcache = ctx->vcache + l * kv_layer;
     ra.cr = ctx->rope_cr; ra.ci = ctx->rope_ci; ra.qnorm = L.qnorm; ra.knorm = L.knorm; ra.bq = L.bq; ra.bk = L.bk; ra.bv = L.bv; ra.n_heads = H;
@@ -2468,7 +2083,7 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
         const float* vc1 = aa.vcache + (size_t)one_seq * ctx->kv_seq_stride;
         // r6: > 64 tokens on one rank with head size 128: the output is written quantised for the wo GEMM (pf_gemm3_kernel's operand layout)
         static const bool qao_off = getenv("GL3_PF_ATTN_QOUT") && atoi(getenv("GL3_PF_ATTN_QOUT")) == 0;
-        const bool qao = !qao_off && hs == 128 && n > 64 && d.tp_size == 1 && pf_use_gemm3() && p->XP && (getenv("GL3_NO_FUSED_QUANT") == nullptr || atoi(getenv("GL3_NO_FUSED_QUANT")) == 0);
+        const bool qao = !qao_off && hs == 128 && pf_chunk_major(n) && d.tp_size == 1 && p->XP && !pf_fused_quant_off();
         uint8_t* xqo = qao ? p->XQ : nullptr;
         uint4* xpo = qao ? reinterpret_cast<uint4*>(p->XP) : nullptr;
         // r6: packed-f32 scores + pinned weighted V sum (pf_attn_fused2_kernel) when its 16 KB of query rows still fit; GL3_PF_FUSED_V1=1: the r4 kernel
@@ -2664,10 +2279,10 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
     const int rank = d.tp_rank, qd = ctx->q_dim_l, kvd = ctx->kv_dim_l;
     const int hid = ctx->hidden_l, dml = ctx->dim_l;
     const int qkv_dim = qd + 2 * kvd;
-    const bool fused_decode = ctx->fused_attn_ok && max_pos < AF_MAXN && !(getenv("GL3_NO_FUSED_BD_ATTN") && atoi(getenv("GL3_NO_FUSED_BD_ATTN")));
+    const bool fused_decode = ctx->fused_attn_ok && max_pos < AF_MAXN && !pf_fused_bd_attn_off();
     // small batch on one rank: the attention output and hb leave their kernels already quantised for the next GEMM (no
     // separate quantise launches; under tensor parallelism the f32 vectors are gathered first, so the launches stay)
-    static const bool fuse_off = getenv("GL3_NO_FUSED_QUANT") && atoi(getenv("GL3_NO_FUSED_QUANT"));
+    const bool fuse_off = pf_fused_quant_off();
     const bool fuse_q = !fuse_off && bd_tslots(n) != 0 && d.tp_size == 1 && (d.hidden % 32) == 0 && (d.head_size % 32) == 0;
     float* Xr = p->X + (size_t)rank * n * dml;           // this rank's chunk of X / AO / HB
     float* AOr = p->AO + (size_t)rank * n * qd;
@@ -2679,13 +2294,13 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
         gl3_layer& L = ctx->layers[l];
         Gl3Range layer_range("layer", l);
         hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq_smem(d.dim), s, p->X, d.dim, dml, L.attn_norm, d.rms_eps,
-                           p->XQ, p->XS, p->maxk, bd_tslots(n), (pf_use_gemm3() && n > 64) ? (uint2*)p->XP : nullptr, p->xp_tok);
+                           p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
         launch_gemm<EPI_STORE>(ctx, L.wqkv, nullptr, n, p->QKV, qkv_dim);
         const bool quantised_ao = pf_attention(ctx, l, n, max_pos, one_seq, AOr, fuse_q && one_seq < 0 && fused_decode);
         if ((r = gl3_all_gather(ctx, GB_PF_AO, (size_t)n * qd)) != GL3_OK) return r;
         if (!quantised_ao)
             hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN>), dim3(n, (ctx->q_dim / 4 + 255) / 256), dim3(256), 0, s, p->AO, ctx->q_dim, qd, (const float*)nullptr,
-                               0.f, p->XQ, p->XS, p->maxk, bd_tslots(n), (pf_use_gemm3() && n > 64) ? (uint2*)p->XP : nullptr, p->xp_tok);
+                               0.f, p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
         if (ctx->wo_replicated) {
             // every rank holds all of Wo: one GEMM per rank chunk of the rank-chunked X (rows [c dml, (c + 1) dml) -> chunk c), no gather
             for (int c = 0; c < d.tp_size; ++c) {
@@ -2699,9 +2314,9 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
             if ((r = gl3_all_gather(ctx, GB_PF_X, (size_t)n * dml)) != GL3_OK) return r;
         }
         hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq_smem(d.dim), s, p->X, d.dim, dml, L.ffn_norm, d.rms_eps,
-                           p->XQ, p->XS, p->maxk, bd_tslots(n), (pf_use_gemm3() && n > 64) ? (uint2*)p->XP : nullptr, p->xp_tok);
+                           p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
         // > 64 tokens on one rank: the tall gate + up tiling writes hb quantised (no f32 round trip, no quantise launch)
-        const bool fuse_big = !fuse_off && n > 64 && d.tp_size == 1 && p->XQh && pf_use_gemm3() && gl3_gemm3_swiglu_quantises(L.w1.rows, n);
+        const bool fuse_big = !fuse_off && pf_chunk_major(n) && d.tp_size == 1 && p->XQh && gl3_gemm3_swiglu_quantises(L.w1.rows, n);
         if (fuse_q || fuse_big) {
             launch_gemm<EPI_SWIGLU>(ctx, L.w1, &L.w3, n, HBr, hid, 1.0f, false, true);
             launch_gemm<EPI_RESID>(ctx, L.w2, nullptr, n, Xr, dml, ctx->resid_scale, true);
@@ -2709,7 +2324,7 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
             launch_gemm<EPI_SWIGLU>(ctx, L.w1, &L.w3, n, HBr, hid);
             if ((r = gl3_all_gather(ctx, GB_PF_HB, (size_t)n * hid)) != GL3_OK) return r;
             hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN>), dim3(n, (d.hidden / 4 + 255) / 256), dim3(256), 0, s, p->HB, d.hidden, hid, (const float*)nullptr, 0.f,
-                               p->XQ, p->XS, p->maxk, bd_tslots(n), (pf_use_gemm3() && n > 64) ? (uint2*)p->XP : nullptr, p->xp_tok);
+                               p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
             launch_gemm<EPI_RESID>(ctx, L.w2, nullptr, n, Xr, dml, ctx->resid_scale);
         }
         if ((r = gl3_all_gather(ctx, GB_PF_X, (size_t)n * dml)) != GL3_OK) return r;
@@ -2812,7 +2427,7 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
             hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM_F32>), dim3(n), dim3(256), nq, s, p->X, d.dim, ctx->dim_l, ctx->out_norm, d.rms_eps, (uint8_t*)nullptr, p->XN, 0, 0);
             launch_gemm_vl<EPI_STORE>(ctx, ctx->wcls, n, p->XN, d.dim, p->LOGITS + (size_t)d.tp_rank * n * vl, vl, ctx->logit_scale);
         } else {
-        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq, s, p->X, d.dim, ctx->dim_l, ctx->out_norm, d.rms_eps, p->XQ, p->XS, p->maxk, bd_tslots(n), (pf_use_gemm3() && n > 64) ? (uint2*)p->XP : nullptr, p->xp_tok);
+        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq, s, p->X, d.dim, ctx->dim_l, ctx->out_norm, d.rms_eps, p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
         // vocab rows are split across ranks: this rank's logits are the chunk [n][vocab / tp] of the rank-chunked buffer
         launch_gemm<EPI_STORE>(ctx, ctx->wcls, nullptr, n, p->LOGITS + (size_t)d.tp_rank * n * vl, vl, ctx->logit_scale);
         }

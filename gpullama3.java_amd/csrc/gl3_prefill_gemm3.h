@@ -1,10 +1,27 @@
-// gl3_prefill_gemm3.h — batched-prefill Q8_0 GEMM (> 64 tokens), round 6.  Arithmetic of gl3_prefill_gemm2.h, unchanged and bit-exact:
+// gl3_prefill_gemm3.h — batched-prefill Q8_0 GEMM (> 64 tokens).  (Compiled in gl3_prefill_gemm3.hip.)  The per-block f32 arithmetic of the reference
 //     result += (float) isum * (wScale * aScale)                      (Q8_0FloatTensor.java:119, blocks ascending)
-// as   D = 0x4B400000 + isum (int8 MFMA),  s = wScale * aScale and -B s (two bf16 MFMAs, exact),  p = fma(D, s, -B s),  result += p.
-// What changed is how the operands reach the matrix pipe.  r4 / r5 stamps of pf_gemm2_kernel: arithmetic alone 123 cycles per (tile, block) and
-// SIMD, the whole kernel ~265 — the rest was the stage structure: a __syncthreads() per K stage that carries vmcnt(0) and so waits for the LDS-DMA
-// pieces the stage itself issued (issued -> landed is ~1-2 k cycles, about one stage), scale operands built by every thread inside the loop
-// (two VGPR-returning loads, ~25 VALU, three LDS stores), and a branchy piece issue.  Here:
+// as   D = 0x4B400000 + isum (int8 MFMA),  s = wScale * aScale and -B s (two bf16 MFMAs, exact),  p = fma(D, s, -B s),  result += p:
+// TWO VALU operations per output element and block.  Three exact identities put the other two on the matrix pipe (checked bit for bit incl.
+// f16 subnormals, zeros, the f16 maximum and negative block scales by scripts/probes/scale_mfma_probe.hip, profiles/r04_scale_mfma_probe.txt):
+//   (1) wScale and aScale are f16 values, so s = wScale * aScale is EXACT in f32 (11 + 11 significand bits <= 24);
+//   (2) the int8 MFMA's accumulator starts at the integer 0x4B400000, so its output read as f32 is D = B + isum exactly with
+//       B = 12582912 = 3 * 2^22, and B * s is exact too (2 + 22 bits), hence
+//           fl(float(isum) * s) = fl(D * s - B * s) = fma(D, s, -B s)          one rounding, the reference's;
+//   (3) an outer product of exactly representable 16-bit operands is what a 16-bit MFMA delivers exactly: with the bf16 splits
+//       w = w_hi + w_lo, a = a_hi + a_lo (hi = the top 8 significand bits, lo = the remaining <= 3),
+//           s    = sum over {w_hi, w_hi, w_lo, w_lo} x {a_hi, a_lo, a_hi, a_lo}                            (4 k-slots)
+//           -B s = the same four terms scaled by -2^23 (k-slots of lanes 0-31) plus by -2^22 (lanes 32-63)   (8 k-slots)
+//       every partial sum is a same-sign multiple of one ulp(w) ulp(a) below 2^24 of them, so the accumulation order and the
+//       internal precision of the MFMA cannot matter.  v_mfma_f32_32x32x8_bf16_1k carries 4 k-slots per lane half in two
+//       VGPRs: exactly these operands.
+// Per (tile, block): three 32-cycle MFMAs (int8 dot, s, -B s) and 16 v_fma_f32 + 16 v_add_f32 — SCALAR on purpose (this translation unit is
+// built with -fno-slp-vectorize): packed f32 instructions issued beside MFMAs cost ~13 extra cycles each (MI355X_MICROARCH.md, "price of one
+// filler beside MFMAs").
+// How the operands reach the matrix pipe.  The first kernel with this arithmetic (r4, removed; profiles/r04_gemm_experiments.md) measured 123
+// cycles per (tile, block) and SIMD for the arithmetic alone and ~265 for the whole kernel — the rest was its stage structure: a __syncthreads()
+// per K stage that carries vmcnt(0) and so waits for the LDS-DMA pieces the stage itself issued (issued -> landed is ~1-2 k cycles, about one
+// stage), scale operands built by every thread inside the loop (two VGPR-returning loads, ~25 VALU, three LDS stores), and a branchy piece
+// issue.  Here:
 //   * THE BARRIER SITS IN THE MIDDLE OF A STAGE.  The last LDS read of ring slot k is issued long before the slot's last arithmetic (operands
 //     are fetched one block ahead), so "slot k is free" and "slot k + 1 has landed" are both checked at the step whose operand refill first
 //     reaches into slot k + 1 — not at the stage's end.  The operand prefetch across the stage boundary (MFMAs of the next stage's first tile
@@ -29,7 +46,26 @@
 //     the qkv projection (6144 rows) 12 one-tile wavefronts on 96-row tiles = exactly one workgroup per CU.
 // Ring slot image: Aq[blk][half][AROWS][16 B] | At[blk][AROWS][8 B] | Bq[blk][half][TOK][16 B] | Bs[blk][half][TOK][16 B].
 #pragma once
-#include "gl3_prefill_gemm2.h"
+
+typedef short v4s_t __attribute__((ext_vector_type(4)));
+typedef int v2i_t __attribute__((ext_vector_type(2)));
+typedef float v16f2_t __attribute__((ext_vector_type(16)));
+
+template <int I, int N, class F>
+__device__ __forceinline__ void g3_static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        g3_static_for<I + 1, N>(f);
+    }
+}
+
+__device__ __forceinline__ uint32_t g3_bf16_dup(float x) {             // {bf16(x), bf16(x)} of an x with <= 8 significand bits
+    const uint32_t b = __float_as_uint(x);
+    return (b >> 16) | (b & 0xFFFF0000u);
+}
+__device__ __forceinline__ void g3_dma16(const uint8_t* src, uint8_t* lds_wave_base) {   // lane l's 16 bytes -> lds_wave_base + 16 l
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
 
 constexpr int G3_RING = 3;
 __host__ __device__ constexpr int g3_stage_bytes(int arows, int tok, int kb) { return kb * (2 * arows * 16 + arows * 8 + 2 * tok * 16 + 2 * tok * 16); }
@@ -75,7 +111,8 @@ __global__ __launch_bounds__(64 * WR * WC, (OCC * WR * WC + 3) / 4) void pf_gemm
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int tl = lane & 31, hi = lane >> 5;
     const int wr = wave / WC, wc = wave % WC;
-    // XCD-aware tile mapping (as pf_gemm_kernel): the token tiles that share a weight row tile sit on ONE XCD
+    // XCD-aware tile mapping: workgroups are dealt round-robin to the 8 XCDs (private L2 each), so the token tiles that share a weight row tile
+    // are given consecutive slots of ONE XCD — the weights cross the fabric once, not once per token tile
     const int ntt_g = a.ntt, per_xcd = (a.ntt * a.nrt + 7) >> 3;
     const int lin = blockIdx.x, J = (lin & 7) * per_xcd + (lin >> 3);
     if (J >= ntt_g * a.nrt) return;
@@ -122,7 +159,7 @@ __global__ __launch_bounds__(64 * WR * WC, (OCC * WR * WC + 3) / 4) void pf_gemm
     }
     auto dma_one = [&](int kf, int slot, int u) {      // piece u of K stage kf -> ring slot; branch-free scalar address arithmetic
         const uint32_t off = ((uint32_t)kf >> p_sh[u]) * p_mul[u] + ((uint32_t)kf & (uint32_t)p_sh[u]) * p_odd[u];
-        g2_dma16(p_base[u] + off + p_lane[u], smem + slot * STAGE + p_dst[u]);
+        g3_dma16(p_base[u] + off + p_lane[u], smem + slot * STAGE + p_dst[u]);
     };
     // ---- weight scale operands: thread t < NAT owns entry (row t % AROWS, block t / AROWS) of every stage
     const int s_row = t % AROWS, s_blk = (t / AROWS) % KB;
@@ -138,7 +175,7 @@ __global__ __launch_bounds__(64 * WR * WC, (OCC * WR * WC + 3) / 4) void pf_gemm
         if (t < NAT) {
             const float wf = h2f((uint16_t)r_ws);
             const float whi = __uint_as_float(__float_as_uint(wf) & 0xFFFF0000u), wlo = wf - whi;     // 8 + <= 3 significand bits
-            *reinterpret_cast<uint2*>(base + OFF_AT + ((size_t)s_blk * AROWS + s_row) * 8) = make_uint2(g2_bf16_dup(whi), g2_bf16_dup(wlo));
+            *reinterpret_cast<uint2*>(base + OFF_AT + ((size_t)s_blk * AROWS + s_row) * 8) = make_uint2(g3_bf16_dup(whi), g3_bf16_dup(wlo));
         }
     };
 
@@ -233,8 +270,9 @@ __global__ __launch_bounds__(64 * WR * WC, (OCC * WR * WC + 3) / 4) void pf_gemm
         const uint8_t* sb_nxt = smem + nxt * STAGE;    // past the last stage: a stale slot, results unused
         // step i finishes (tile, block) i of this stage and issues the MFMAs of step i + 1 (step 0 of the next stage at the end):
         //   [int8 MFMA i+1] [8 fma i] [s MFMA i+1] [8 fma i] [-B s MFMA i+1] (barrier) [operand refill] [LDS-DMA piece] [16 adds i]
-        // The schedule is pinned (sched_barrier + value pins), see gl3_prefill_gemm2.h.
-        g2_static_for<0, NTILE>([&](auto ic) {
+        // The schedule is pinned (sched_barrier + value pins): left alone, the compiler issues every MFMA of a stage first and
+        // spills the result tiles, and its IR-level sinking moves the arithmetic behind the stage's LDS stores.
+        g3_static_for<0, NTILE>([&](auto ic) {
             constexpr int i = decltype(ic)::value, f = (i % TPB) / TF, tf = i % TF;
             constexpr int in = (i + 1) % NTILE, fn = (in % TPB) / TF, tfn = in % TF;
             constexpr bool next_stage = i + 1 == NTILE;
@@ -270,7 +308,7 @@ __global__ __launch_bounds__(64 * WR * WC, (OCC * WR * WC + 3) / 4) void pf_gemm
 #if defined(G3_TIMING) && G3_TIMING >= 2
             G3_T0();
 #endif
-            g2_static_for<0, PPS>([&](auto pc) {       // window-relative step i' = i - BSTEP behind the barrier, i + NLATE in front of it
+            g3_static_for<0, PPS>([&](auto pc) {       // window-relative step i' = i - BSTEP behind the barrier, i + NLATE in front of it
                 constexpr int pi = decltype(pc)::value;
                 if constexpr (i >= BSTEP) {
                     if constexpr (PPS * (i - BSTEP) + pi < NDMA) dma_one(kf_late, cur, PPS * (i - BSTEP) + pi);

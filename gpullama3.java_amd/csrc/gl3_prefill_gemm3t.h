@@ -85,7 +85,7 @@ __global__ __launch_bounds__(512, 2) void pf_gemm3t_kernel(const GemmArgs a) {
     }
     auto dma_one = [&](int kf, int slot, int u) {
         const uint32_t off = ((uint32_t)kf >> p_sh[u]) * p_mul[u] + ((uint32_t)kf & ((1u << p_sh[u]) - 1)) * p_odd[u];
-        g2_dma16(p_base[u] + (p_lane[u] + off), smem + slot * STAGE + p_dst[u]);
+        g3_dma16(p_base[u] + (p_lane[u] + off), smem + slot * STAGE + p_dst[u]);
     };
     // ---- weight scale operands: thread t owns the entries t, t + NT (< KBT * AROWS) of every stage; entry = (block e / AROWS, row e % AROWS)
     const uint8_t* s_wp[NSC];
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(512, 2) void pf_gemm3t_kernel(const GemmArgs a) {
             if (e < KBT * AROWS) {
                 const float wf = h2f((uint16_t)r_ws[k]);
                 const float whi = __uint_as_float(__float_as_uint(wf) & 0xFFFF0000u), wlo = wf - whi;
-                *reinterpret_cast<uint2*>(base + OFF_AT + e * 8) = make_uint2(g2_bf16_dup(whi), g2_bf16_dup(wlo));      // At[blk][row]: e = blk * AROWS + row
+                *reinterpret_cast<uint2*>(base + OFF_AT + e * 8) = make_uint2(g3_bf16_dup(whi), g3_bf16_dup(wlo));      // At[blk][row]: e = blk * AROWS + row
             }
         }
     };
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(512, 2) void pf_gemm3t_kernel(const GemmArgs a) {
         const int kf_late = min(kb + RING, nkb - 1), kf_early = min(kb + RING - 1, nkb - 1);
         const uint8_t* sb_cur = smem + cur * STAGE;
         const uint8_t* sb_nxt = smem + nxt * STAGE;
-        g2_static_for<0, NSTEP>([&](auto ic) {
+        g3_static_for<0, NSTEP>([&](auto ic) {
             constexpr int i = decltype(ic)::value, q = PS * NSTEP + i, qb = q & 1, qn = (q + 1) & 1;      // q: tile count inside the body (register-set parity)
             constexpr int blk = i / NFR, f = i % NFR;
             constexpr int gb = PS * KBT + blk;                                     // block count inside the body: B register set gb & 1
@@ -327,8 +327,8 @@ __global__ __launch_bounds__(512, 2) void pf_gemm3t_kernel(const GemmArgs a) {
         }
     };
     // two straight-line branches (a shared loop with a run-time fragment index would move the accumulators to scratch)
-    if (wm == 0) g2_static_for<FH, NFR>(park); else g2_static_for<0, FH>(park);
+    if (wm == 0) g3_static_for<FH, NFR>(park); else g3_static_for<0, FH>(park);
     __syncthreads();
-    if (wm == 0) g2_static_for<0, FH>([&](auto fc) { finish(fc, std::true_type{}); });
-    else g2_static_for<FH, NFR>([&](auto fc) { finish(fc, std::false_type{}); });
+    if (wm == 0) g3_static_for<0, FH>([&](auto fc) { finish(fc, std::true_type{}); });
+    else g3_static_for<FH, NFR>([&](auto fc) { finish(fc, std::false_type{}); });
 }

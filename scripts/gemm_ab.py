@@ -1,5 +1,5 @@
 """Batched-prefill GEMM classes at 512 tokens on N layers of a named config: one HIP event pair per class (gl3_profile_prefill_kernel)
-+ the pp512 wall time.  A/B switches are environment variables read by the library (GL3_PF_GEMM2, GL3_PF_GEMM2_OCC, ...).
++ the pp512 wall time.  A/B switches are environment variables read by the library (GL3_PF_GEMM3_TALL, GL3_PF_GEMM3_SHAPE, ...).
     python scripts/gemm_ab.py llama-3-8b 4"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

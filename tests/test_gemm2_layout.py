@@ -1,4 +1,5 @@
-"""CPU mirror of the index arithmetic of the round-4 prefill GEMM (gpullama3.java_amd/csrc/gl3_prefill_gemm2.h): the LDS-DMA pieces of a K
+"""CPU mirror of the index arithmetic of the round-4 prefill GEMM, the first kernel with the LDS-DMA staging and the three-MFMA arithmetic that
+gpullama3.java_amd/csrc/gl3_prefill_gemm3.h documents (the r4 kernel itself was removed, HISTORY.md §10; its stage image is restated below): the LDS-DMA pieces of a K
 stage must cover every 16-byte piece of the staged weight / activation image exactly once, land where the MFMA operand fetch reads them
 (`la`, `lb` offsets), and the scale-operand identities the kernel rests on must hold in f32 / bf16 arithmetic — the three facts the GPU probe
 (scripts/probes/scale_mfma_probe.hip) checks on the matrix pipe are re-derived here with NumPy so that the construction is pinned without a GPU."""

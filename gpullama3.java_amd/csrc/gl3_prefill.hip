@@ -1995,6 +1995,11 @@ static bool pf_chunk_major(int n) { return bd_tslots(n) == 0; }
 static bool pf_fused_quant_off() { static const bool off = getenv("GL3_NO_FUSED_QUANT") && atoi(getenv("GL3_NO_FUSED_QUANT")); return off; }
 static bool pf_fused_bd_attn_off() { static const bool off = getenv("GL3_NO_FUSED_BD_ATTN") && atoi(getenv("GL3_NO_FUSED_BD_ATTN")); return off; }
 
+// A static-batched decode step whose deepest row is at max_pos runs the one-launch attention (attn_head_kernel).  Asked by the attention
+// dispatch, by the operand hand-over behind it and by the graph capture of the step (only such a step has nothing position-dependent
+// baked in: the three-kernel attention sizes its scores grid by the deepest row), so they cannot disagree.
+static bool pf_fused_decode(const gl3_ctx* ctx, int max_pos) { return ctx->fused_attn_ok && max_pos < AF_MAXN && !pf_fused_bd_attn_off(); }
+
 template <int EPI>
 static void launch_gemm(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int ntok, float* out, int out_stride, float out_scale = 1.0f,
                         bool second_operand = false, bool quantised_out = false) {
@@ -2043,7 +2048,7 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
     const size_t kv_layer = (size_t)d.ctx * kvd;
     // one workgroup per (kv head, token) serves the kv head's whole group of query heads when its LDS image fits
     const int bd_group = (kvmul <= 8 && attn_head_smem(d.head_size, kvmul) <= 150 * 1024) ? kvmul : 1;
-    const bool fused_decode = ctx->fused_attn_ok && max_pos < AF_MAXN && !pf_fused_bd_attn_off();
+    const bool fused_decode = pf_fused_decode(ctx, max_pos);
     RopeArgs ra{};
     ra.QKV = p->QKV; ra.qkv_stride = qkv_dim; ra.kcache = ctx->kcache + l * kv_layer; ra.vcache = ctx->vcache + l * kv_layer;
     ra.cr = ctx->rope_cr; ra.ci = ctx->rope_ci; ra.qnorm = L.qnorm; ra.knorm = L.knorm; ra.bq = L.bq; ra.bk = L.bk; ra.bv = L.bv; ra.n_heads = H;
@@ -2279,7 +2284,7 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
     const int rank = d.tp_rank, qd = ctx->q_dim_l, kvd = ctx->kv_dim_l;
     const int hid = ctx->hidden_l, dml = ctx->dim_l;
     const int qkv_dim = qd + 2 * kvd;
-    const bool fused_decode = ctx->fused_attn_ok && max_pos < AF_MAXN && !pf_fused_bd_attn_off();
+    const bool fused_decode = pf_fused_decode(ctx, max_pos);
     // small batch on one rank: the attention output and hb leave their kernels already quantised for the next GEMM (no
     // separate quantise launches; under tensor parallelism the f32 vectors are gathered first, so the launches stay)
     const bool fuse_off = pf_fused_quant_off();
@@ -2437,9 +2442,11 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
         return GL3_OK;
     };
     // ~400 launches per step: replay them as one hipGraph per batch size.  Nothing position-dependent is baked in when every
-    // position is below AF_MAXN (the one-launch attention reads sequence ids / positions from device memory).
+    // position is below AF_MAXN (the one-launch attention reads sequence ids / positions from device memory).  The three-kernel
+    // attention (GL3_NO_FUSED_BD_ATTN=1) sizes its scores grid by the deepest row: a step captured at position 0 would score the
+    // first 64 positions only, so those steps stay eager.
     static const bool graphs_off = getenv("GL3_NO_GRAPH") && atoi(getenv("GL3_NO_GRAPH"));
-    const bool graphable = !graphs_off && !gl3_roctx_on() && !(d.flags & GL3_FLAG_NO_GRAPH) && ctx->fused_attn_ok && max_pos < AF_MAXN && ctx->transport != GL3_TP_RCCL;
+    const bool graphable = !graphs_off && !gl3_roctx_on() && !(d.flags & GL3_FLAG_NO_GRAPH) && pf_fused_decode(ctx, max_pos) && ctx->transport != GL3_TP_RCCL;
     if (graphable) {
         if ((int)p->step_graphs.size() <= n) p->step_graphs.resize(n + 1, nullptr);
         if (!p->step_graphs[n]) {

@@ -31,11 +31,12 @@ def count_draws(plan):
     return dev, host
 
 
-def mixed_generation(pkg, orc, plan, oracles, m, nseq, steps):
-    """prefill nseq prompts of different lengths, then `steps` batched sampled steps; row order reversed on odd steps; row s at
-    step t uses SETTINGS[(s + t) % 8]; coins from one L32X64MixRandom(1234) in (step, sequence) order, non-greedy rows only."""
+def mixed_generation(pkg, orc, plan, oracles, m, nseq, steps, lens=None):
+    """prefill nseq prompts of different lengths (lens; default 3, 5, 7, ..), then `steps` batched sampled steps; row order reversed on odd
+    steps; row s at step t uses SETTINGS[(s + t) % 8]; coins from one L32X64MixRandom(1234) in (step, sequence) order, non-greedy rows only."""
     rng = np.random.default_rng(3)
-    lens = [3 + 2 * i for i in range(nseq)]
+    lens = list(lens) if lens is not None else [3 + 2 * i for i in range(nseq)]
+    assert len(lens) == nseq
     prompts = [rng.integers(0, m.cfg.vocab, n).tolist() for n in lens]
     for s in range(nseq):
         plan.prefill_seq(s, prompts[s], 0)

@@ -231,9 +231,10 @@ def test_two_launch_attention_between_128_and_767_positions(pkg, orc, planmod, c
 
 @pytest.mark.parametrize("cfg", ["mid-llama", "mid-qwen3", "mid-qwen2", "mha-llama", "mid-granite", "phi3-hs96"])   # head sizes 64 / 128 / 96, kvMul 4 / 6 / 1
 def test_fused_short_context_attention_and_the_handover_at_128(pkg, orc, planmod, cfg):
-    """Positions < 128 run attn_head_kernel (one launch per layer, one workgroup per query head), later ones the scores +
-    softmax/PV pair (positions < 768) or — `deep`, with GL3_ATTN_MID=0 right behind 128 — the four-launch long-context path (scores,
-    exp, exact parallel sum, chain-wavefront PV: r5); all must reproduce the oracle bit for bit, also across the handover."""
+    """Three plans on the same model walk positions 122 .. 133: `plan` (default) runs attn_head_kernel (one launch per layer, one workgroup per
+    query head) below 128 and the two-launch pair (attn_scores_kernel; attn_softmax_pv_kernel) from 128 on; `plain` (GL3_NO_FUSED_ATTN=1) runs the
+    two-launch pair from position 0; `deep` (GL3_ATTN_MID=0) runs attn_head_kernel below 128 and right behind it the four-launch long-context path
+    (scores, exp, exact parallel sum, chain-wavefront PV).  All must reproduce the oracle bit for bit, also across the handover."""
     plan_mod, hip = planmod
     base = pkg.synth.CONFIGS[cfg]
     m = pkg.synth.make_numpy(pkg.synth.ModelConfig(**{**base.__dict__, "ctx": 160}), seed=29)

@@ -5,7 +5,8 @@ parity tests (ragged small shapes to the 8B / 1B layers at 512 tokens) in its ow
    GL3_PF_GEMM3_TALL_KB=1      one block per K stage of the tall tiling (default: two)
    GL3_PF_GEMM3_SHAPE=1|2|3    128 x 128 / 96 x 128 / 64 x 128 workgroup tiles for every non-SwiGLU projection
 These tilings are what different matrix shapes take by default; the switches force each of them onto the test shapes.  The prefill attention has
-its own forms (test_prefill_attention_forms)."""
+its own forms (test_prefill_attention_forms), and so has the static-batched decode step (test_static_batched_decode_forms:
+GL3_NO_FUSED_BD_ATTN / GL3_NO_FUSED_QUANT)."""
 import os
 import subprocess
 import sys
@@ -53,3 +54,21 @@ def test_prefill_attention_forms(env, select):
     tail = out.stdout[-1500:] + out.stderr[-500:]
     assert out.returncode == 0, tail
     assert " passed" in out.stdout and "failed" not in out.stdout, tail
+
+
+@pytest.mark.parametrize("env", [{"GL3_NO_FUSED_BD_ATTN": "1"}, {"GL3_NO_FUSED_QUANT": "1"}, {"GL3_NO_FUSED_BD_ATTN": "1", "GL3_NO_FUSED_QUANT": "1"}],
+                         ids=["three-kernel-attention", "separate-quantise-launches", "both"])
+def test_static_batched_decode_forms(env):
+    """The A/B forms of the static-batched decode step stay bit-exact, each in its own process (switches are read once):
+       default                      attn_head_kernel below 128 positions, with the attention output and hb written as the next GEMM's int8 operand
+       GL3_NO_FUSED_BD_ATTN=1       pf_rope_kv_kernel -> pf_attn_scores_kernel -> pf_attn_softmax_pv_kernel from position 0: the only way the suite
+                                    runs them on shallow rows (and with every row of a step below 128)
+       GL3_NO_FUSED_QUANT=1         the separate quantise launches (pf_norm_quant_kernel<PQ_PLAIN>) behind attention and gate + up, at every batch size
+    Runs the depth / mixed-depth / tile-class / windowed / sampler tests of test_gpu_batch_decode_depth.py and the static-batched tests of test_gpu_decode.py."""
+    e = dict(os.environ, **env)
+    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_batch_decode_depth.py"), os.path.join(ROOT, "tests", "test_gpu_decode.py"),
+                          "-m", "gpu", "-x", "-q", "-k", "batch_decode_depth or static_batched", "-p", "no:cacheprovider"],
+                         capture_output=True, text=True, timeout=850, env=e, cwd=ROOT)
+    tail = out.stdout[-1500:] + out.stderr[-500:]
+    assert out.returncode == 0, tail
+    assert " passed" in out.stdout and "failed" not in out.stdout and "skipped" not in out.stdout, tail

@@ -209,6 +209,74 @@ def test_static_batched_decode_under_row_split(pkg, orc, planmod, wtype):
                 assert int(ids[s]) == orc.argmax(ref[s][i])
 
 
+def test_static_batched_decode_under_row_split_at_mixed_depths_across_128(pkg, orc, planmod):
+    """The same step on two row-split ranks with the rows at different depths on both sides of position 128 (sequences prefilled to 126, 4
+    and 129 positions, in chunks of 64): the three-kernel attention on this rank's heads reads every row's own sequence and position, the
+    attention output / hb go through the gathers and the separate quantise launches, every step is enqueued eagerly; sequence 0 walks
+    127 -> 128.  Logits and greedy ids of every row equal its own oracle's on both ranks, in changing row order, and so does each rank's
+    slice of the K / V rows the steps wrote in every sequence's cache."""
+    plan_mod, hip = planmod
+    tp, lens, steps = 2, [126, 4, 129], 4
+    nseq = len(lens)
+    m = pkg.synth.make_numpy(pkg.synth.CONFIGS["mid-llama"], wtype=8, seed=47)
+    assert m.cfg.ctx > max(lens) + steps
+    rng = np.random.default_rng(7)
+    prompts = [rng.integers(0, m.cfg.vocab, n).tolist() for n in lens]
+    first = [int(rng.integers(0, m.cfg.vocab)) for _ in lens]
+    orders = [[0, 1, 2], [2, 0, 1], [1, 2, 0], [2, 1, 0]]
+    ref, ref_kv = [], {}                                      # ref[s][i]: logits of sequence s at step i, greedy continuation
+    for s in range(nseq):
+        o = orc.COracle(m)
+        o.prefill(prompts[s], 0)
+        t, rows = first[s], []
+        for i in range(steps):
+            rows.append(o.forward(t, lens[s] + i))
+            t = orc.argmax(rows[-1])
+        ref.append(rows)
+        for l in range(m.cfg.n_layers):
+            for p in range(lens[s] - 1, lens[s] + steps + 1):
+                ref_kv[(s, l, p)] = o.kv(l, p)
+    assert lens[0] + 1 == 127 and lens[0] + steps - 1 >= 128 and max(lens) >= 128 > min(lens) + steps
+    grp = plan_mod.make_local_group(tp)
+    out, kvs, err = [None] * tp, [None] * tp, [None] * tp
+
+    def rank_main(r):
+        try:
+            plan = plan_mod.HipMasterPlan(m, prefill_batch_size=64, n_seqs=nseq, tp_rank=r, tp_size=tp, local_group=grp)
+            for s in range(nseq):
+                plan.prefill_seq(s, prompts[s], 0)
+            cur, res = list(first), []
+            for i in range(steps):
+                order = orders[i]
+                lg, ids = plan.forward_decode_batch([cur[s] for s in order], order, [lens[s] + i for s in order])
+                res.append((lg.copy(), ids.copy()))
+                for row, s in enumerate(order):
+                    cur[s] = int(ids[row])
+            out[r] = res
+            # this rank's slice of every K / V row the steps wrote, one before and one after (unwritten: zeros on both sides)
+            kvs[r] = {(s, l, p): plan.kv_seq(s, l, p) for s in range(nseq) for l in range(m.cfg.n_layers) for p in range(lens[s] - 1, lens[s] + steps + 1)}
+            plan.freeTornadoExecutionPlan()
+        except Exception as e:   # noqa: BLE001
+            err[r] = e
+
+    th = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(tp)]
+    [t.start() for t in th]
+    [t.join(timeout=900) for t in th]
+    assert all(e is None for e in err), err
+    assert not any(t.is_alive() for t in th)
+    hip.lib().gl3_local_group_destroy(grp)
+    for r in range(tp):
+        for i in range(steps):
+            lg, ids = out[r][i]
+            for row, s in enumerate(orders[i]):
+                assert np.array_equal(lg[row], ref[s][i]), (r, i, row, s)
+                assert int(ids[row]) == orc.argmax(ref[s][i]), (r, i, row, s)
+        kvl = m.cfg.kv_dim // tp
+        for key, (ko, vo) in ref_kv.items():
+            k, v = kvs[r][key]
+            assert np.array_equal(k, ko[r * kvl:(r + 1) * kvl]) and np.array_equal(v, vo[r * kvl:(r + 1) * kvl]), (r,) + key
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The production transport between PROCESSES: every rank exports the IPC handle of its arena, the handles travel over
 # torch.distributed (gloo), peers are mapped with hipIpcOpenMemHandle and the gather kernel stores into them.  On the

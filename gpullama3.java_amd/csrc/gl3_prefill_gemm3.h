@@ -63,6 +63,16 @@ __device__ __forceinline__ uint32_t g3_bf16_dup(float x) {             // {bf16(
     const uint32_t b = __float_as_uint(x);
     return (b >> 16) | (b & 0xFFFF0000u);
 }
+// One XP entry pair of an activation block whose scale is the f16 value qs (exact in f32): the bf16 operands the s / -B s MFMAs read.
+// P = {a_hi, a_lo} (hi = the top 8 significand bits, lo = the rest: exact), Q = P * -2^23 for the k slots of lane half 0, P * -2^22 for half 1
+// (their sum is -B = -3 * 2^22); half0 = {P, P, Q, Q}, half1 = {0, 0, Q, Q}.  Every producer of a chunk-major operand writes its XP entries from here.
+struct G3ScaleOperands { uint4 half0, half1; };
+__device__ __forceinline__ G3ScaleOperands g3_scale_operands(float qs) {
+    const float ahi = __uint_as_float(__float_as_uint(qs) & 0xFFFF0000u), alo = qs - ahi;
+    auto pk = [](float h, float l) { return (__float_as_uint(h) >> 16) | (__float_as_uint(l) & 0xFFFF0000u); };
+    const uint32_t pr = pk(ahi, alo), q0 = pk(ahi * -8388608.f, alo * -8388608.f), q1 = pk(ahi * -4194304.f, alo * -4194304.f);
+    return {make_uint4(pr, pr, q0, q0), make_uint4(0u, 0u, q1, q1)};
+}
 __device__ __forceinline__ void g3_dma16(const uint8_t* src, uint8_t* lds_wave_base) {   // lane l's 16 bytes -> lds_wave_base + 16 l
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }

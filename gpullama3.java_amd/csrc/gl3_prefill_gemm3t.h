@@ -310,13 +310,10 @@ __global__ __launch_bounds__(512, 2) void pf_gemm3t_kernel(const GemmArgs a) {
                     *reinterpret_cast<uint32_t*>(a.XQo + ((size_t)(2 * blk + (q4 >> 1)) * a.xp_tok + b) * 16 + ((8 * q4 + 4 * hi) & 15)) = packed;
                 }
                 if (hi == 0) {
-                    const float qf = (float)(_Float16)qs;                              // float16ToFloat(floatToFloat16(qs))
-                    const float ahi = __uint_as_float(__float_as_uint(qf) & 0xFFFF0000u), alo = qf - ahi;
-                    auto pk = [](float h, float l) { return (__float_as_uint(h) >> 16) | (__float_as_uint(l) & 0xFFFF0000u); };
-                    const uint32_t pr = pk(ahi, alo), q0 = pk(ahi * -8388608.f, alo * -8388608.f), q1 = pk(ahi * -4194304.f, alo * -4194304.f);
+                    const G3ScaleOperands so = g3_scale_operands((float)(_Float16)qs);    // float16ToFloat(floatToFloat16(qs))
                     uint4* xp = reinterpret_cast<uint4*>(a.XPo);
-                    xp[((size_t)blk * 2 + 0) * a.xp_tok + b] = make_uint4(pr, pr, q0, q0);
-                    xp[((size_t)blk * 2 + 1) * a.xp_tok + b] = make_uint4(0u, 0u, q1, q1);
+                    xp[((size_t)blk * 2 + 0) * a.xp_tok + b] = so.half0;
+                    xp[((size_t)blk * 2 + 1) * a.xp_tok + b] = so.half1;
                     if (blk == (a.rows >> 5) - 1)                                        // ragged K of the consumer: zero operands for the padded blocks
                         for (int pb = blk + 1; pb < ((blk + 4) & ~3); ++pb) {
                             xp[((size_t)pb * 2 + 0) * a.xp_tok + b] = make_uint4(0u, 0u, 0u, 0u);

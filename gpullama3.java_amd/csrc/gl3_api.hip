@@ -564,13 +564,17 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
         d.arch != GL3_ARCH_QWEN2MOE)
         return bail(GL3_E_UNSUPPORTED, "unsupported architecture");
     const bool moe = d.arch == GL3_ARCH_QWEN2MOE;
-    if (moe) {      // the reference's GPU plan for this family is Q8_0, single token (Qwen2MoEQ8_0PlanComponents); so is this one
+    if (moe) {      // the reference's GPU plan for this family is Q8_0 (Qwen2MoEQ8_0PlanComponents); so is this one
         if (d.weight_type != GL3_TYPE_Q8_0 || (d.flags & GL3_FLAG_F32_ACTIVATION))
             return bail(GL3_E_UNSUPPORTED, "qwen2moe: Q8_0 matrices with the int8 activation only");
         if (d.tp_size > 1 || (d.flags & GL3_FLAG_FORCE_RCCL)) return bail(GL3_E_UNSUPPORTED, "qwen2moe: tensor parallelism is not built");
-        // max_batch > 1 is accepted: a prefill chunk then runs token by token, as the reference prefills this family (and as the
-        // scalar-dot plans do); there are no batched buffers, so static-batched decode is refused
-        if (d.n_seqs > 1) return bail(GL3_E_UNSUPPORTED, "qwen2moe: static-batched decode is not built (n_seqs <= 1)");
+        // max_batch > 1: batched prefill and static-batched decode on the grouped expert GEMM (gl3_prefill.hip: pf_moe_ffn); without
+        // the batched buffers there is one sequence, prefilled token by token
+        if (d.n_seqs > 1 && d.max_batch <= 1) return bail(GL3_E_UNSUPPORTED, "qwen2moe: n_seqs > 1 (static-batched decode) needs max_batch > 1");
+        // the batched router and combine take the token as gridDim.y (<= 65535), and the one-workgroup grouping kernel walks all
+        // max_batch * n_experts_used assignments once per expert (moe_group_kernel, gl3_moe_kernels.h: built for chunks of a few thousand)
+        if (d.max_batch > 65535 || (d.max_batch > 1 && (int64_t)d.max_batch * d.n_experts_used > (1 << 16)))
+            return bail(GL3_E_ARG, "qwen2moe: need max_batch <= 65535 and max_batch * n_experts_used <= 65536");
         if (d.n_experts < 1 || d.n_experts > 4096 || d.n_experts_used < 1 || d.n_experts_used > d.n_experts || d.n_experts_used > 64)
             return bail(GL3_E_ARG, "qwen2moe: need 1 <= n_experts_used <= min(n_experts, 64), n_experts <= 4096");
         if (d.moe_hidden < 32 || d.moe_hidden % 32) return bail(GL3_E_ARG, "qwen2moe: moe_hidden must be a positive multiple of 32");
@@ -766,7 +770,7 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
         const bool int8_path = d.weight_type == GL3_TYPE_Q8_0 && !(d.flags & GL3_FLAG_F32_ACTIVATION);
         // (the 512-bit F16 species has decode kernels only: its prefill chunks run token by token, like the scalar order)
         const bool vl_path = !int8_path && !(d.flags & GL3_FLAG_SCALAR_DOT) && !(d.flags & GL3_FLAG_VECTOR_512);      // r4: tensor-parallel ranks too (rank-chunked activations)
-        if (d.max_batch > 1 && (int8_path || vl_path) && !moe) TRY(gl3_prefill_alloc(ctx));
+        if (d.max_batch > 1 && (int8_path || vl_path)) TRY(gl3_prefill_alloc(ctx));
     }
     if (getenv("GL3_DEBUG_ALLOC")) {
         fprintf(stderr, "[gl3 alloc] ctx %p emb %p (+%zu) kcache %p vcache %p (%zu floats) x %p qkv %p xb %p hb %p logits %p att %p xn %p\n", (void*)ctx, (void*)ctx->emb.w,
@@ -1174,7 +1178,6 @@ int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, const int3
 // what the batched sampler does not cover yet is refused, not approximated
 static int32_t check_batch_sampler(gl3_ctx* ctx) {
     if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
-    if (ctx->d.n_experts > 0) GL3_FAIL(GL3_E_UNSUPPORTED, "Qwen2-MoE plans have no static-batched decode, so no batched sampler");
     if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "the batched sampler reads plain [n][vocab] logits: tensor-parallel plans (rank-chunked logits) are not supported yet");
     if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, one rank in the Vector-API order)");
     return GL3_OK;
@@ -1477,6 +1480,8 @@ int32_t gl3_get_buffer(gl3_ctx* ctx, int32_t which, float* out, uint64_t n) {
         for (uint64_t i = 0; i < n; ++i) out[i] = (float)ids[i];
         return GL3_OK;
     }
+    case 9: case 10:                            // qwen2moe, last layer of the last batched step: weights [rows][topk + 1], expert ids as floats [rows][topk]
+        return gl3_prefill_moe_tap(ctx, which, out, n);
     default: GL3_FAIL(GL3_E_ARG, "unknown buffer id");
     }
     if (n > cap) GL3_FAIL(GL3_E_ARG, "buffer shorter than requested");

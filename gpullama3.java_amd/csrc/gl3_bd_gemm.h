@@ -28,6 +28,11 @@ struct GemmArgs {
     uint8_t* XQo; float* XSo;             // bdw_gemm_kernel<EPI_SWIGLU, .., QOUT>: hb leaves the kernel quantised (XQ2 / XS2 layout)
     uint8_t* XPo;                         // pf_gemm3t_kernel<.., QOUT>: the quantised hb's scale-operand table (XQo = its int8 chunks)
     const uint8_t* XP; int xp_tok;        // pf_gemm3_kernel: activation scale operands XP[block][half][xp_tok token slots][16 B] (gl3_prefill_gemm3.h)
+    // bdw_gemm_kernel<.., GRP>: the routed experts of a Qwen2-MoE step (tile table and sorted slots: moe_group_kernel, gl3_moe_kernels.h)
+    const int* gtab;                      // gtab[0] = entries; entry u = gtab[4 + 4u ..] = (expert, first sorted slot, valid slots <= 16)
+    const int* gtok;                      // token slot of the operand per sorted slot (gate + up); null = the sorted slot itself (down)
+    const int* gdst;                      // output row per sorted slot (down: token * (topk + 1) + choice); null = the sorted slot itself
+    int gspe;                             // strips per expert (rows = rows of ONE expert; w / w2 = the stacked tensors)
 };
 
 
@@ -61,6 +66,18 @@ struct GemmArgs {
 // matrix); token tiles of a strip in one workgroup; rings deeper than 8 tiles; non-temporal weight loads (the token tiles
 // re-read the lines from L2); gate and up as separate wavefronts with silu(g) * u in the next quantiser (2432 single-matrix
 // wavefronts fetch the activations twice: 21-22 us vs 18.3 fused).
+// GRP (Qwen2-MoE routed experts): the same wavefront over a (tile-table entry, strip of the entry's expert) instead of a (token tile,
+// strip).  The 16 tokens of an entry are 16 sorted (token, choice) slots of one expert; lane t's operand address is its own token's
+// (gtok[slot] * 64 + 16 g instead of (16 h + t) * 64 + 16 g: the gather is one index load per lane, no copy), the token-slot count of
+// XQ2 / XS2 is the run-time a.tslots (any chunk length; advancing stays a scalar add), lanes past the entry's valid count point at its
+// last valid slot and store nothing, and the result rows go to gdst[slot] (the scatter of the down projection).  Workgroups past the
+// table's entry count exit: the grid is sized for the bound moe_group_max_entries() from the step's token count alone.
+// Placement: workgroup id = entry * gspe + strip, so the entries of one expert that stream the same strip sit gspe ids apart.  With gspe a
+// multiple of 8 (88 and 128 strips at the A2.7B shape) they share id % 8, i.e. the XCD and its L2, as the token tiles of a dense strip
+// do (bdw_grid); for another gspe the rule is not kept and an expert with several entries re-reads its strips through several L2s
+// (not measured).  An odd number
+// of tiles per strip (K = 1408: 11, K = 384: 3, K = 128: 1) needs nothing special: the header load of the last, even-numbered tile
+// also fetches the header of the tile behind the strip (slack, or the next strip), whose scales are parked and never read.
 // Activation layout (written by pf_norm_quant_kernel when tslots != 0), tslots = 32 or 64 token slots (template parameter TS):
 //   XS2[k / 128][tslots][4] f32 = the 4 block scales of a tile;
 //   XQ2[k / 64][tslots][64] int8 = blocks 2j, 2j + 1 of a token, already in the lanes' operand order: bytes 16g .. 16g + 7 =
@@ -72,9 +89,10 @@ constexpr int BD_TS = 32, BD_TS_MAX = 64;            // token slots: 32 (<= 32 t
 // XCD (= id % 8), i.e. one L2, and dispatched together.
 __host__ __device__ inline int bdw_grid(int strips, int nt) { return ((strips + 7) / 8) * 8 * nt; }
 
-template <int EPI, int DA, int WPE, bool QOUT = false, int TS = BD_TS>
+template <int EPI, int DA, int WPE, bool QOUT = false, int TS = BD_TS, bool GRP = false>
 __global__ __launch_bounds__(QOUT ? 128 : 64, WPE) void bdw_gemm_kernel(const GemmArgs a) {
     static_assert(!QOUT || EPI == EPI_SWIGLU, "the quantising epilogue is the SwiGLU one");
+    static_assert(!GRP || !QOUT, "the grouped form writes f32");
     constexpr int NWV = QOUT ? 2 : 1;                  // QOUT: two wavefronts = the two strips of one 32-row activation block
     constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
     static_assert(DA % 2 == 0, "ring slots are static under the unroll");
@@ -90,10 +108,21 @@ __global__ __launch_bounds__(QOUT ? 128 : 64, WPE) void bdw_gemm_kernel(const Ge
     float* xsl = xsl_all[wv];
     const int NTG = (a.ntok + 15) >> 4;                                         // token tiles of this launch
     const int nstrips = (a.rows + 15) >> 4;
-    const int h = (blockIdx.x >> 3) % NTG;
-    const int unit = (blockIdx.x / (8 * NTG)) * 8 + (blockIdx.x & 7);           // strip (QOUT: strip pair)
-    if (unit * NWV >= nstrips) return;                                          // padding of the grid to a multiple of 8 units
-    const int strip = unit * NWV + wv;                                          // QOUT: rows % 32 == 0, so both strips exist
+    const int h = GRP ? 0 : (blockIdx.x >> 3) % NTG;
+    const int unit = GRP ? (int)(blockIdx.x % a.gspe) : (blockIdx.x / (8 * NTG)) * 8 + (blockIdx.x & 7);   // strip (QOUT: strip pair; GRP: of the entry's expert)
+    int strip = unit * NWV + wv;                                                // QOUT: rows % 32 == 0, so both strips exist
+    int gfirst = 0, gcnt = 16, gslot = 0;                                       // GRP: the entry's sorted slots, this lane's slot
+    uint32_t tokslot = 16 * h + t;                                              // this lane's token slot of XQ2 / XS2
+    if constexpr (GRP) {
+        const int u = blockIdx.x / a.gspe;
+        if (u >= a.gtab[0]) return;                                             // the grid is sized for the bound on the table
+        const int4 en = *reinterpret_cast<const int4*>(a.gtab + 4 + 4 * u);
+        strip += en.x * a.gspe;
+        gfirst = en.y; gcnt = en.z;
+        gslot = gfirst + min(t, gcnt - 1);                                      // lanes past the ragged end: the last valid slot
+        tokslot = a.gtok ? a.gtok[gslot] : gslot;
+    } else if (unit * NWV >= nstrips) return;                                   // padding of the grid to a multiple of 8 units
+    const int ts = GRP ? a.tslots : TS;                                         // token slots per block pair of XQ2 (GRP: run time)
     const int ntiles = a.ng;
     const size_t strip_bytes = (size_t)a.ng * TILE_BYTES;
     // uniform stream bases of the NEXT tile to fetch, advanced by scalar adds
@@ -104,8 +133,8 @@ __global__ __launch_bounds__(QOUT ? 128 : 64, WPE) void bdw_gemm_kernel(const Ge
     const float* px = a.XS;
     const uint32_t la = ((g & 1) ? 1152 : 128) + 16 * (t + 16 * (g >> 1));       // + 512 for the tile's second block pair
     const uint32_t lh = (lane >> 5) * TILE_BYTES + 4 * (lane & 31);              // headers of tiles i (lanes 0-31), i + 1 (32-63)
-    const uint32_t lb = (16 * h + t) * 64 + 16 * g;                              // + TS * 64 for the second pair
-    const uint32_t lx = ((16 * h + t) * 4 + g) * 4;
+    const uint32_t lb = tokslot * 64 + 16 * g;                                   // + ts * 64 for the second pair
+    const uint32_t lx = (tokslot * 4 + g) * 4;
     v4i_t Ar[NM][DA][2]; uint32_t Hr[NM][DA / 2]; v2l_t Br[DA][2]; float Xr[DA];
     auto fetch = [&](int u) {                            // the tile at the stream heads -> ring slot u; heads advance one tile
 #pragma unroll
@@ -116,10 +145,10 @@ __global__ __launch_bounds__(QOUT ? 128 : 64, WPE) void bdw_gemm_kernel(const Ge
             pa[m] += TILE_BYTES;
         }
 #pragma unroll
-        for (int jj = 0; jj < 2; ++jj) Br[u][jj] = *reinterpret_cast<const v2l_t*>(pb + lb + jj * (TS * 64));
+        for (int jj = 0; jj < 2; ++jj) Br[u][jj] = *reinterpret_cast<const v2l_t*>(pb + lb + jj * (ts * 64));
         Xr[u] = *reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(px) + lx);
-        pb += 2 * TS * 64;
-        px += TS * 4;
+        pb += 2 * ts * 64;
+        px += ts * 4;
     };
     auto park_h = [&](int u2, int i) {                   // f16 -> f32 weight scales of tiles i, i + 1 into their LDS slots
 #pragma unroll
@@ -265,9 +294,10 @@ __global__ __launch_bounds__(QOUT ? 128 : 64, WPE) void bdw_gemm_kernel(const Ge
         if (wv == 0 && g == 0) a.XSo[bds_offset(blk, b, TS)] = (float)(_Float16)qs;
         return;
     }
-    if (b >= a.ntok) return;
-    const int rbase = strip * 16 + 4 * g;
-    float* o = a.out + (size_t)b * a.out_stride + rbase;
+    if (GRP ? t >= gcnt : b >= a.ntok) return;
+    const int rbase = (GRP ? unit : strip) * 16 + 4 * g;                        // GRP: row of the expert's own output
+    const int orow = GRP ? (a.gdst ? a.gdst[gslot] : gslot) : b;
+    float* o = a.out + (size_t)orow * a.out_stride + rbase;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if (rbase + i >= a.rows) continue;

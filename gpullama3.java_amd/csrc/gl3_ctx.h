@@ -258,6 +258,7 @@ int32_t gl3_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);
 float* gl3_prefill_buf(gl3_ctx* ctx, int which);
 int32_t gl3_prefill_alloc(gl3_ctx* ctx);
 void gl3_prefill_free(gl3_ctx* ctx);
+int32_t gl3_prefill_moe_tap(gl3_ctx* ctx, int which, float* out, uint64_t n);      // gl3_get_buffer 9 / 10
 int32_t gl3_prefill_run(gl3_ctx* ctx, int32_t seq, const int32_t* tokens, int32_t n, int32_t start_pos);
 int32_t gl3_prefill_profile(gl3_ctx* ctx, int klass, int n, int iters, double* out_us, uint64_t* int8_ops);
 int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,

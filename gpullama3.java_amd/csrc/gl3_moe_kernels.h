@@ -1,4 +1,4 @@
-// gl3_moe_kernels.h — the routing side of the Qwen2-MoE feed-forward block (decode step).
+// gl3_moe_kernels.h — the routing side of the Qwen2-MoE feed-forward block (decode step and batched step).
 //
 // Replaces Qwen2MoEKernels.softmaxAndTopK and the router / shared-gate tasks of Qwen2MoEQ8_0FFNLayers
 // (J/tornadovm/kernels/Qwen2MoEKernels.java:37-100, J/tornadovm/layers/type/q8_0/Qwen2MoEQ8_0FFNLayers.java) with the ARITHMETIC
@@ -48,7 +48,9 @@ __host__ __device__ inline size_t moe_router_smem(int dim, int n_experts) {
 }
 __host__ __device__ inline int moe_router_wgs(int n_experts) { return (n_experts + 1 + MOE_RR - 1) / MOE_RR; }
 
-static __global__ __launch_bounds__(256) void moe_router_kernel(const MoeRouterArgs a) {
+// The router of ONE token (a: that token's x, logits, w_out, sel and ticket); blockIdx.x = the workgroup's rows.  The decode kernel and
+// the batched one below both run exactly this.
+static __device__ __forceinline__ void moe_router_token(const MoeRouterArgs& a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ int last;
     float* xf = reinterpret_cast<float*>(smem);
@@ -179,11 +181,88 @@ static __global__ __launch_bounds__(256) void moe_router_kernel(const MoeRouterA
     if (t == 0) __hip_atomic_store(a.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// x[i] = w[j] * y[j][i] + x[i] for j = 0 .. n_terms - 1 in order (the selected experts, then the shared expert)
+static __global__ __launch_bounds__(256) void moe_router_kernel(const MoeRouterArgs a) { moe_router_token(a); }
+
+// Batched step (prefill chunk, static-batched decode): the token is blockIdx.y.  x = X[n][dim], logits [n][n_experts], w_out [n][topk + 1],
+// sel [n][topk], ticket [n]: every token has its own arrival counter, so its last workgroup runs its softmax + top-k.
+static __global__ __launch_bounds__(256) void moe_router_batch_kernel(const MoeRouterArgs a0) {
+    MoeRouterArgs a = a0;
+    const size_t b = blockIdx.y;
+    a.x += b * a.dim; a.logits += b * a.n_experts; a.w_out += b * (a.topk + 1); a.sel += b * a.topk; a.ticket += b;
+    moe_router_token(a);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Grouping of a batched step's n * topk (token, choice) assignments by expert, in one launch of one workgroup, so that nothing the
+// host enqueues depends on the routing (the step stays one hipGraph per batch size):
+//   * counts per expert and their exclusive scan;
+//   * the assignments sorted by expert, stable in (token, choice): slot_tok[i] = token and slot_dst[i] = token * (topk + 1) + choice
+//     (the row of y) of sorted slot i;
+//   * the tile table of the grouped GEMMs (bdw_gemm_kernel<.., GRP>): tab[0] = number of entries, entry u = tab[4 + 4u ..] =
+//     (expert, first sorted slot, valid slots <= 16, 0); an expert with c assignments owns ceil(c / 16) consecutive entries.
+// Entries <= min(E, n topk) + n topk / 16: every non-empty expert has at most one ragged entry, and the full ones hold 16 slots each.
+// A wavefront owns an expert at a time and walks the assignments 64 per trip: a ballot of the matches counts them (first pass) and
+// ranks them (second pass), so the order needs no atomics.  tests/test_moe_grouping.py mirrors this kernel.
+// Cost: every wavefront rescans all S = n topk assignments for each expert it owns, twice — 2 * ceil(E / 16) * S / 64 ballot trips on
+// one CU.  Meant for E of a few hundred and S of a few thousand (E = 60, S = 2048: 256 trips per wavefront, a few microseconds);
+// gl3_create caps S at 65536 and E at 4096, where it is tens of milliseconds per layer — a wider plan wants a multi-workgroup sort.
+constexpr int MOE_GROUP_THREADS = 1024;
+__host__ __device__ inline int moe_group_max_entries(int n, int topk, int n_experts) {
+    const int s = n * topk;
+    return (n_experts < s ? n_experts : s) + s / 16;
+}
+__host__ __device__ inline size_t moe_group_smem(int n_experts) { return (size_t)3 * n_experts * sizeof(int); }
+
+static __global__ __launch_bounds__(MOE_GROUP_THREADS) void moe_group_kernel(const int* __restrict__ sel, int n, int topk, int n_experts,
+                                                                             int* __restrict__ slot_tok, int* __restrict__ slot_dst, int* __restrict__ tab) {
+    extern __shared__ __attribute__((aligned(16))) int gsm[];
+    int* cnt = gsm;                      // assignments per expert
+    int* start = cnt + n_experts;        // first sorted slot
+    int* tstart = start + n_experts;     // first tile-table entry
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = MOE_GROUP_THREADS / 64, S = n * topk;
+    for (int e = wave; e < n_experts; e += nw) {
+        int c = 0;
+        for (int i0 = 0; i0 < S; i0 += 64) {
+            const int i = i0 + lane;
+            c += __popcll(__ballot(i < S && sel[i] == e));
+        }
+        if (lane == 0) cnt[e] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0, u = 0;
+        for (int e = 0; e < n_experts; ++e) { start[e] = s; tstart[e] = u; s += cnt[e]; u += (cnt[e] + 15) >> 4; }
+        tab[0] = u;
+    }
+    __syncthreads();
+    for (int e = wave; e < n_experts; e += nw) {
+        const int c = cnt[e], first = start[e];
+        int at = first;
+        for (int i0 = 0; i0 < S; i0 += 64) {
+            const int i = i0 + lane;
+            const bool m = i < S && sel[i] == e;
+            const unsigned long long bal = __ballot(m);
+            if (m) {
+                const int pos = at + __popcll(bal & ((1ull << lane) - 1ull));
+                const int tok = i / topk;
+                slot_tok[pos] = tok;
+                slot_dst[pos] = tok * (topk + 1) + (i - tok * topk);
+            }
+            at += __popcll(bal);
+        }
+        for (int j = lane; 16 * j < c; j += 64)
+            *reinterpret_cast<int4*>(tab + 4 + 4 * (tstart[e] + j)) = make_int4(e, first + 16 * j, min(16, c - 16 * j), 0);
+    }
+}
+
+// x[i] = w[j] * y[j][i] + x[i] for j = 0 .. n_terms - 1 in order (the selected experts, then the shared expert); blockIdx.y = token
+// of a batched step (x [n][dim], y [n][n_terms][dim], w [n][n_terms]; the decode step launches one row)
 static __global__ __launch_bounds__(256) void moe_combine_kernel(float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ w,
                                                                  int dim, int n_terms) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= dim) return;
+    const size_t b = blockIdx.y;
+    x += b * dim; y += b * n_terms * dim; w += b * n_terms;
     float v = x[i];
     for (int j = 0; j < n_terms; ++j) {
         const float prod = w[j] * y[(size_t)j * dim + i];

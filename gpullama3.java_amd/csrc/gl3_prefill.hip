@@ -22,6 +22,7 @@
 
 using namespace gl3;
 #include "gl3_bd_gemm.h"      // GemmArgs, bdw_gemm_kernel (expects the gl3 names in scope)
+#include "gl3_moe_kernels.h"  // Qwen2-MoE: batched router, grouping, combine
 #include "gl3_prefill_gemm3.h"      // g3_scale_operands (the kernels of that header are instantiated in gl3_prefill_gemm3.hip only)
 // gl3_prefill_gemm3.hip (own translation unit, -fno-slp-vectorize): the > 64-token GEMM, every class (gl3_prefill_gemm3.h / gl3_prefill_gemm3t.h)
 void gl3_gemm3_launch(int epi, const GemmArgs& a, int rows, int ntok, hipStream_t s);
@@ -63,6 +64,23 @@ struct gl3_prefill_state {
     bool vl = false;
     float* XN = nullptr;                // [M][dim] RMS-normalised activations
     float* HB2 = nullptr;               // [M][hidden] up projection (hb = silu(HB) * HB2)
+    // Qwen2-MoE (pf_moe_ffn): the routing of every token of the step, its grouping by expert, and the routed experts' operands
+    struct {
+        float* logits = nullptr;        // [M][n_experts] router logits (scratch between the router's workgroups)
+        float* w = nullptr;             // [M][topk + 1] routing weights, last = the shared expert's sigmoid gate
+        int* sel = nullptr;             // [M][topk] expert ids
+        int* ticket = nullptr;          // [M] arrival counters of the router (0 between launches)
+        int* slot_tok = nullptr;        // [M topk] token of every sorted slot      } moe_group_kernel
+        int* slot_dst = nullptr;        // [M topk] row of y of every sorted slot   }
+        int* tab = nullptr;             // tile table: 4 ints header + 4 per entry  }
+        float* HB = nullptr;            // [M topk][moe_hidden] routed hb, sorted-slot order
+        float* Y = nullptr;             // [M][topk + 1][dim] down-projected outputs, last = the shared expert
+        uint8_t* XQx = nullptr;         // xb of a > 64-token step in the XQ2 / XS2 layout with ts_x token slots (the chunk-major
+        float* XSx = nullptr;           //   operand next to it serves the shared expert)
+        uint8_t* XQh = nullptr;         // routed hb quantised, XQ2 / XS2 layout with ts_h token slots (slot = sorted slot)
+        float* XSh = nullptr;
+        int ts_x = 0, ts_h = 0;
+    } moe;
 };
 
 
@@ -311,6 +329,35 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     { const int32_t ar = pf_attention_attributes(ctx); if (ar != GL3_OK) return ar; }
+    if (d.arch == GL3_ARCH_QWEN2MOE) {
+        auto& m = p->moe;
+        const size_t E = d.n_experts, K = d.n_experts_used, S = M * K;
+        GL3_HIP(hipMalloc((void**)&m.logits, M * E * 4));
+        GL3_HIP(hipMalloc((void**)&m.w, M * (K + 1) * 4));
+        GL3_HIP(hipMalloc((void**)&m.sel, S * sizeof(int)));
+        GL3_HIP(hipMalloc((void**)&m.ticket, M * sizeof(int)));
+        GL3_HIP(hipMemsetAsync(m.ticket, 0, M * sizeof(int), ctx->stream));
+        GL3_HIP(hipMalloc((void**)&m.slot_tok, S * sizeof(int)));
+        GL3_HIP(hipMalloc((void**)&m.slot_dst, S * sizeof(int)));
+        GL3_HIP(hipMalloc((void**)&m.tab, (size_t)(4 + 4 * moe_group_max_entries((int)M, (int)K, (int)E)) * sizeof(int)));
+        GL3_HIP(hipMalloc((void**)&m.HB, S * d.moe_hidden * 4));
+        GL3_HIP(hipMalloc((void**)&m.Y, M * (K + 1) * d.dim * 4));
+        // XQ2 / XS2 operands with a run-time slot count: [ceil(k / 128) tiles + the ring's read-ahead][ts slots] x (128 B | 4 floats).
+        // The rings of bdw_gemm_kernel read up to 8 tiles past the end unguarded, which here is more than GL3_TAIL_PAD: own slack.
+        auto operand = [&](uint8_t** xq, float** xs, int k, int ts) -> hipError_t {
+            const size_t tiles = (size_t)(k + 127) / 128 + 9;
+            hipError_t e = hipMalloc((void**)xq, tiles * ts * 128);
+            if (e == hipSuccess) e = hipMalloc((void**)xs, tiles * ts * 16);
+            if (e == hipSuccess) e = hipMemsetAsync(*xq, 0, tiles * ts * 128, ctx->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(*xs, 0, tiles * ts * 16, ctx->stream);
+            return e;
+        };
+        m.ts_x = (int)((M + 15) & ~(size_t)15);
+        m.ts_h = (int)((S + 15) & ~(size_t)15);
+        if (M > BD_TS_MAX) GL3_HIP(operand(&m.XQx, &m.XSx, d.dim, m.ts_x));
+        GL3_HIP(operand(&m.XQh, &m.XSh, d.moe_hidden, m.ts_h));
+        GL3_HIP(hipFuncSetAttribute((const void*)moe_router_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    }
     return GL3_OK;
 }
 
@@ -321,6 +368,8 @@ void gl3_prefill_free(gl3_ctx* ctx) {
     auto f = [](void* q) { if (q) hipFree(q); };
     f(p->tokens); f(p->XQ); f(p->XS); f(p->XP); f(p->XQh); f(p->XPh); f(p->XQb); f(p->XSb); f(p->QKV); f(p->ATT); f(p->TMX); f(p->SUMS); f(p->seqpos); f(p->amax); f(p->amx_v); f(p->amx_i); f(p->XN); f(p->HB2);
     if (!p->in_arena) { f(p->X); f(p->AO); f(p->HB); f(p->LOGITS); }
+    auto& m = p->moe;
+    f(m.logits); f(m.w); f(m.sel); f(m.ticket); f(m.slot_tok); f(m.slot_dst); f(m.tab); f(m.HB); f(m.Y); f(m.XQx); f(m.XSx); f(m.XQh); f(m.XSh);
     delete p;
     ctx->pf = nullptr;
 }
@@ -343,6 +392,9 @@ static bool pf_fused_bd_attn_off() { static const bool off = env_flag("GL3_NO_FU
 // dispatch, by the operand hand-over behind it and by the graph capture of the step (only such a step has nothing position-dependent
 // baked in: the three-kernel attention sizes its scores grid by the deepest row), so they cannot disagree.
 static bool pf_fused_decode(const gl3_ctx* ctx, int max_pos) { return ctx->fused_attn_ok && max_pos < AF_MAXN && !pf_fused_bd_attn_off(); }
+
+// dynamic LDS of pf_norm_quant_kernel<PQ_NORM> for rows of k elements: the row, the exact sum of squares' scratch, the result
+static size_t nq_smem(int k) { return (size_t)(k + 32) * 4 + ss_scratch_bytes(k) + 64; }
 
 template <int EPI>
 static void launch_gemm(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int ntok, float* out, int out_stride, float out_scale = 1.0f,
@@ -374,6 +426,22 @@ static void launch_gemm(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int ntok,
     } while (0)
     if (ts == BD_TS) GL3_BDW(BD_TS); else GL3_BDW(BD_TS_MAX);
 #undef GL3_BDW
+}
+
+// The routed experts of a Qwen2-MoE step: one launch over (tile-table entry, strip of the entry's expert) — bdw_gemm_kernel<.., GRP>.
+// w / w2 = the stacked expert tensors, rows = rows of one expert; XQ / XS = the operand in the XQ2 / XS2 layout with ts token slots;
+// gtok / gdst as in GemmArgs.  The grid covers the bound on the table's entries for n tokens; surplus workgroups exit.
+template <int EPI>
+static void launch_gemm_grouped(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int rows, int n, const uint8_t* XQ, const float* XS, int ts,
+                                const int* gtok, const int* gdst, float* out, int out_stride) {
+    gl3_prefill_state* p = ctx->pf;
+    GemmArgs a{};
+    a.w = w.w; a.w2 = w2 ? w2->w : nullptr; a.rows = rows; a.ng = w.ng; a.nb = w.k / 32;
+    a.XQ = XQ; a.XS = XS; a.tslots = ts; a.ntok = n; a.out = out; a.out_stride = out_stride; a.out_scale = 1.0f;
+    a.gtab = p->moe.tab; a.gtok = gtok; a.gdst = gdst; a.gspe = rows / 16;
+    const dim3 grid((unsigned)moe_group_max_entries(n, ctx->d.n_experts_used, ctx->d.n_experts) * a.gspe);
+    if constexpr (EPI == EPI_SWIGLU) hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, false, BD_TS, true>), grid, dim3(64), 0, ctx->stream, a);
+    else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 8, 2, false, BD_TS, true>), grid, dim3(64), 0, ctx->stream, a);
 }
 
 // A head size / kvMul that a prefill attention kernel takes as a template argument: f(std::integral_constant<int, ...>{}).  MIN_HS = 64: the kernels
@@ -578,7 +646,7 @@ static int32_t pf_layers_vl(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
     if (ctx->emb.fmt == GL3_TYPE_F16) hipLaunchKernelGGL((pf_embed_vl_kernel<WT_F16>), dim3(n), dim3(256), 0, s, ctx->emb.w, d.dim, p->tokens, p->X, ctx->emb_scale, dml);
     else if (ctx->emb.fmt == GL3_TYPE_Q4_0) hipLaunchKernelGGL((pf_embed_vl_kernel<WT_Q4_0>), dim3(n), dim3(256), 0, s, ctx->emb.w, d.dim, p->tokens, p->X, ctx->emb_scale, dml);
     else hipLaunchKernelGGL((pf_embed_vl_kernel<WT_Q8_0>), dim3(n), dim3(256), 0, s, ctx->emb.w, d.dim, p->tokens, p->X, ctx->emb_scale, dml);
-    const size_t nq = (size_t)(d.dim + 32) * 4 + ss_scratch_bytes(d.dim) + 64;
+    const size_t nq = nq_smem(d.dim);
     auto unchunk = [&](const float* src, int k, int cc) {          // rank-chunked [tp][n][cc] -> plain XN[n][k] (tp = 1: a copy the GEMM could skip, kept for one code path)
         hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN_F32>), dim3(n, (k / 4 + 255) / 256), dim3(256), 0, s, src, k, cc, (const float*)nullptr, 0.f, (uint8_t*)nullptr, p->XN, 0, 0);
     };
@@ -618,6 +686,73 @@ static int32_t pf_layers_vl(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
     return GL3_OK;
 }
 
+// The Qwen2-MoE feed-forward block of layer l for the n tokens of a step (one rank) — InferenceCore.forwardJavaQwen2MoE :363-415 per
+// token: xb = rmsnorm(x) quantised ONCE is the operand of the router's f32 rows (which normalise x themselves, as in the decode
+// step), of every selected expert and of the shared expert.  Router -> grouping by expert -> routed gate + up / down as grouped GEMMs
+// over the tile table -> shared expert on the dense GEMMs, its down projection stored into y[token][topk] -> combine.
+static void pf_moe_ffn(gl3_ctx* ctx, int l, int n) {
+    gl3_prefill_state* p = ctx->pf;
+    auto& m = p->moe;
+    const gl3_model_desc& d = ctx->d;
+    hipStream_t s = ctx->stream;
+    gl3_layer& L = ctx->layers[l];
+    const int E = d.n_experts, topk = d.n_experts_used, mh = d.moe_hidden, S = n * topk;
+    {   Gl3Range g("moe: rmsnorm + router + top-k");
+        MoeRouterArgs ra{};
+        ra.x = p->X; ra.norm_w = L.ffn_norm; ra.eps = d.rms_eps; ra.gate_inp = L.gate_inp; ra.gate_inp_shexp = L.gate_inp_shexp;
+        ra.dim = d.dim; ra.n_experts = E; ra.topk = topk; ra.logits = m.logits; ra.w_out = m.w; ra.sel = m.sel; ra.ticket = m.ticket;
+        hipLaunchKernelGGL(moe_router_batch_kernel, dim3(moe_router_wgs(E), n), dim3(256), moe_router_smem(d.dim, E), s, ra);
+        hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(MOE_GROUP_THREADS), moe_group_smem(E), s, m.sel, n, topk, E, m.slot_tok, m.slot_dst, m.tab); }
+    const size_t nq = nq_smem(d.dim);
+    hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq, s, p->X, d.dim, d.dim, L.ffn_norm, d.rms_eps,
+                       p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
+    const uint8_t* xq = p->XQ; const float* xs = p->XS; int ts = bd_tslots(n);
+    if (pf_chunk_major(n)) {      // the chunk-major operand serves the shared expert; the routed experts read the XQ2 / XS2 layout
+        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq, s, p->X, d.dim, d.dim, L.ffn_norm, d.rms_eps,
+                           m.XQx, m.XSx, p->maxk, m.ts_x, (uint2*)nullptr, 0);
+        xq = m.XQx; xs = m.XSx; ts = m.ts_x;
+    }
+    {   Gl3Range g("moe: routed experts");
+        launch_gemm_grouped<EPI_SWIGLU>(ctx, L.gate_exps, &L.up_exps, mh, n, xq, xs, ts, m.slot_tok, nullptr, m.HB, mh);
+        // hb per 32-block as matmulExpert quantises it (Q8_0FloatTensor.java:96-118); row = sorted slot, so a token tile is 16 consecutive rows
+        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN>), dim3(S, (mh / 4 + 255) / 256), dim3(256), 0, s, m.HB, mh, mh, (const float*)nullptr, 0.f,
+                           m.XQh, m.XSh, mh, m.ts_h, (uint2*)nullptr, 0);
+        launch_gemm_grouped<EPI_STORE>(ctx, L.down_exps, nullptr, d.dim, n, m.XQh, m.XSh, m.ts_h, nullptr, m.slot_dst, m.Y, d.dim); }
+    {   Gl3Range g("moe: shared expert");      // after the routed gate + up: the unfused hand-over below overwrites xb
+        float* ysh = m.Y + (size_t)topk * d.dim;
+        const int ystride = (topk + 1) * d.dim;
+        const bool fuse_off = pf_fused_quant_off();
+        const bool fuse_q = !fuse_off && bd_tslots(n) != 0 && (d.hidden % 32) == 0;
+        const bool fuse_big = !fuse_off && pf_chunk_major(n) && p->XQh && gl3_gemm3_swiglu_quantises(L.w1.rows, n);
+        if (fuse_q || fuse_big) {
+            launch_gemm<EPI_SWIGLU>(ctx, L.w1, &L.w3, n, p->HB, d.hidden, 1.0f, false, true);
+            launch_gemm<EPI_STORE>(ctx, L.w2, nullptr, n, ysh, ystride, 1.0f, true);
+        } else {
+            launch_gemm<EPI_SWIGLU>(ctx, L.w1, &L.w3, n, p->HB, d.hidden);
+            hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN>), dim3(n, (d.hidden / 4 + 255) / 256), dim3(256), 0, s, p->HB, d.hidden, d.hidden, (const float*)nullptr, 0.f,
+                               p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
+            launch_gemm<EPI_STORE>(ctx, L.w2, nullptr, n, ysh, ystride);
+        } }
+    {   Gl3Range g("moe: weighted accumulation into x");
+        hipLaunchKernelGGL(moe_combine_kernel, dim3((d.dim + 255) / 256, n), dim3(256), 0, s, p->X, m.Y, m.w, d.dim, topk + 1); }
+}
+
+// Parity taps gl3_get_buffer 9 / 10: the routing of the last layer of the last batched step, rows in step order — weights
+// [rows][topk + 1] (9), expert ids as floats [rows][topk] (10).
+int32_t gl3_prefill_moe_tap(gl3_ctx* ctx, int which, float* out, uint64_t n) {
+    gl3_prefill_state* p = ctx->pf;
+    if (!p || !p->moe.w) GL3_FAIL(GL3_E_STATE, "not a qwen2moe plan with batched buffers (max_batch > 1)");
+    const uint64_t per = which == 9 ? ctx->d.n_experts_used + 1 : ctx->d.n_experts_used;
+    if (n > (uint64_t)p->max_batch * per) GL3_FAIL(GL3_E_ARG, "buffer shorter than requested");
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
+    if (which == 9) { GL3_HIP(hipMemcpy(out, p->moe.w, n * sizeof(float), hipMemcpyDeviceToHost)); return GL3_OK; }
+    std::vector<int> ids(n);
+    GL3_HIP(hipMemcpy(ids.data(), p->moe.sel, n * sizeof(int), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; ++i) out[i] = (float)ids[i];
+    return GL3_OK;
+}
+
 // All layers for n tokens whose (token, sequence, position) are already on the device.  max_pos = largest position.
 // one_seq >= 0: all n tokens belong to that sequence at consecutive positions ending at max_pos (prefill).
 static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
@@ -640,7 +775,6 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
     float* HBr = p->HB + (size_t)rank * n * hid;
     int32_t r;
     hipLaunchKernelGGL(pf_embed_kernel, dim3(n), dim3(256), 0, s, ctx->emb.w, ctx->emb.ng, d.dim, p->tokens, p->X, dml, ctx->emb_scale);
-    auto nq_smem = [&](int k) { return (size_t)(k + 32) * 4 + ss_scratch_bytes(k) + 64; };
     for (int l = 0; l < d.n_layers; ++l) {
         gl3_layer& L = ctx->layers[l];
         Gl3Range layer_range("layer", l);
@@ -664,6 +798,7 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
             launch_gemm<EPI_RESID>(ctx, L.wo, nullptr, n, Xr, dml, ctx->resid_scale);
             if ((r = gl3_all_gather(ctx, GB_PF_X, (size_t)n * dml)) != GL3_OK) return r;
         }
+        if (d.arch == GL3_ARCH_QWEN2MOE) { pf_moe_ffn(ctx, l, n); continue; }
         hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq_smem(d.dim), s, p->X, d.dim, dml, L.ffn_norm, d.rms_eps,
                            p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
         // > 64 tokens on one rank: the tall gate + up tiling writes hb quantised (no f32 round trip, no quantise launch)
@@ -773,7 +908,7 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
     auto enqueue_step = [&](int mp) -> int32_t {
         int32_t rr = pf_layers(ctx, n, mp, -1);
         if (rr != GL3_OK) return rr;
-        const size_t nq = (size_t)(d.dim + 32) * 4 + ss_scratch_bytes(d.dim) + 64;
+        const size_t nq = nq_smem(d.dim);
         if (p->vl) {
             hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM_F32>), dim3(n), dim3(256), nq, s, p->X, d.dim, ctx->dim_l, ctx->out_norm, d.rms_eps, (uint8_t*)nullptr, p->XN, 0, 0);
             launch_gemm_vl<EPI_STORE>(ctx, ctx->wcls, n, p->XN, d.dim, p->LOGITS + (size_t)d.tp_rank * n * vl, vl, ctx->logit_scale);

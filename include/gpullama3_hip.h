@@ -66,7 +66,10 @@ enum { GL3_ARCH_LLAMA = 0, GL3_ARCH_QWEN3 = 1, GL3_ARCH_QWEN2 = 2,
        GL3_ARCH_QWEN2MOE = 5 /* InferenceCore.forwardJavaQwen2MoE :263-422 (Qwen1.5-MoE / Qwen2-MoE): the Qwen2 attention; the FFN is an F32
                               * router over n_experts (softmax over all, top n_experts_used by strict >, no renormalisation), the
                               * selected experts' SwiGLU FFNs accumulated into x in selection order, then the always-on shared
-                              * expert scaled by sigmoid(ffn_gate_inp_shexp . xb).  Q8_0 matrices, one rank, one sequence; a prefill chunk runs token by token. */ };
+                              * expert scaled by sigmoid(ffn_gate_inp_shexp . xb).  Q8_0 matrices with the int8 activation, one rank.  max_batch > 1:
+                              * batched prefill and static-batched decode (n_seqs > 1), the routed experts as one grouped GEMM over
+                              * the step's (token, choice) assignments sorted by expert; max_batch <= 1: one sequence, a prefill
+                              * chunk runs token by token. */ };
 
 /* ggml tensor types of the wire format (J/tensor/GGMLType.java:5-21) */
 enum { GL3_TYPE_F32 = 0, GL3_TYPE_F16 = 1, GL3_TYPE_Q4_0 = 2, GL3_TYPE_Q8_0 = 8,
@@ -271,7 +274,7 @@ GL3_API int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, co
  * equal probabilities has its probabilities copied out for the reference's heap (counted by gl3_get_topp_counts, one count per
  * non-greedy top-p row).  The number of sampler launches does not depend on n (gl3_sample_batch.h).  Everything else as
  * gl3_forward_decode_batch; with every temperature 0 the ids are its argmax_out.  GL3_E_UNSUPPORTED: tp_size > 1 (rank-chunked
- * logits), Qwen2-MoE plans (no batched decode), max_batch <= 1. */
+ * logits), max_batch <= 1. */
 GL3_API int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids,
                                                 const int32_t* positions, int32_t n, const float* temperature,
                                                 const float* topp, const float* coins, int32_t* tokens_out);
@@ -290,7 +293,9 @@ GL3_API int32_t gl3_get_kv(gl3_ctx* ctx, int32_t layer, int32_t position, float*
 GL3_API int32_t gl3_get_kv_seq(gl3_ctx* ctx, int32_t seq, int32_t layer, int32_t position, float* k_out, float* v_out);
 
 /* Debug/parity tap: copy a scratch buffer of the LAST executed layer to the host.
- * which: 0 = raw q|k|v of the qkv projection, 1 = attention output xb, 2 = hb (SwiGLU output), 3 = logits. */
+ * which: 0 = raw q|k|v of the qkv projection, 1 = attention output xb, 2 = hb (SwiGLU output), 3 = logits; 4 / 5 / 6 = X / AO / HB
+ * of the last batched step; Qwen2-MoE routing of the last layer: 7 = weights [topk + 1] and 8 = expert ids (as floats) [topk] of
+ * the last decode step, 9 = weights [rows][topk + 1] and 10 = expert ids [rows][topk] of the last batched step (rows in step order). */
 GL3_API int32_t gl3_get_buffer(gl3_ctx* ctx, int32_t which, float* out, uint64_t n_floats);
 
 /* Test hook: the strictly sequential f32 sum of squares of x[0..n) (InferenceCore.rmsnorm's reduce), evaluated

@@ -755,12 +755,12 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
         const char* mv = getenv("GL3_ATTN_MID");
         ctx->attn_mid = mv && *mv ? atoi(mv) : 768;
     }
-    TRY(dmalloc(ctx, &ctx->dyn, 4));
+    TRY(dmalloc(ctx, &ctx->dyn, GL3_DYN_INTS));
     ctx->dyn_cur = ctx->dyn;
     TRY(dmalloc(ctx, &ctx->argmax, 2 + 2 * AMX_WGS));          // result, ticket, (value, index) pairs of argmax_kernel
     TRYHIP(hipMemset(ctx->argmax, 0, (2 + 2 * AMX_WGS) * sizeof(int)));
     if (d.flags & GL3_FLAG_LAYER_TAPS) TRY(dmalloc(ctx, &ctx->taps, (size_t)d.n_layers * d.dim));
-    TRYHIP(hipHostMalloc((void**)&ctx->h_dyn, 4 * sizeof(int)));
+    TRYHIP(hipHostMalloc((void**)&ctx->h_dyn, GL3_DYN_INTS * sizeof(int)));
     TRYHIP(hipHostMalloc((void**)&ctx->h_logits, (size_t)d.vocab * 4));
     TRYHIP(hipHostMalloc((void**)&ctx->h_argmax, sizeof(int)));
     // batched prefill / static-batched decode: int8 MFMA GEMMs for Q8_0 (any tensor-parallel degree); f32-MFMA / VALU GEMMs in the
@@ -1033,13 +1033,15 @@ int32_t gl3_finalize(gl3_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-static int32_t set_dyn(gl3_ctx* ctx, int32_t token, int32_t pos) {
+// row: the sampler settings of a single-row sampled step, uploaded behind the pair in the same copy
+static int32_t set_dyn(gl3_ctx* ctx, int32_t token, int32_t pos, const SmpRow* row = nullptr) {
     if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
     if (token < 0 || token >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
     if (pos < 0 || pos >= ctx->d.ctx) GL3_FAIL(GL3_E_ARG, "position outside the KV cache (context length)");
     GL3_HIP(hipSetDevice(ctx->d.device));
     ctx->h_dyn[0] = token; ctx->h_dyn[1] = pos;
-    GL3_HIP(hipMemcpyAsync(ctx->dyn, ctx->h_dyn, 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (row) memcpy(ctx->h_dyn + GL3_DYN_ROW, row, sizeof(SmpRow));
+    GL3_HIP(hipMemcpyAsync(ctx->dyn, ctx->h_dyn, (row ? GL3_DYN_INTS : GL3_DYN_ROW) * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     return GL3_OK;
 }
 
@@ -1081,13 +1083,13 @@ int32_t gl3_forward_decode_sample(gl3_ctx* ctx, int32_t token, int32_t pos, floa
     if (!(temperature >= 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be >= 0");
     if (temperature == 0.f) return gl3_forward_decode(ctx, token, pos, nullptr, token_out);      // Sampler.java:79-81: greedy argmax
     if (!(coin >= 0.f && coin < 1.f)) GL3_FAIL(GL3_E_ARG, "coin must be rng.nextFloat(1f): in [0, 1)");
-    int32_t r = set_dyn(ctx, token, pos);
+    const SmpRow row = gl3_smp_row(temperature, topp, coin);
+    int32_t r = set_dyn(ctx, token, pos, &row);
     if (r != GL3_OK) return r;
     const int amode = attn_mode(ctx, pos);
     if (ctx->graph_exec) GL3_HIP(hipGraphLaunch(step_graph(ctx, amode), ctx->stream));
     else if ((r = enqueue_decode(ctx, true, nullptr, amode)) != GL3_OK) return r;
-    if ((r = gl3_sample_run(ctx, ctx->logits, temperature, topp, coin, token_out)) != GL3_OK) return r;
-    return gl3_tp_check(ctx);
+    return gl3_sample_run(ctx, ctx->logits, token_out);          // ends with the stream synchronisation and gl3_tp_check
 }
 
 int32_t gl3_tp_fold_mode(gl3_ctx* ctx, int32_t* mode, int32_t* consumer_mask) {

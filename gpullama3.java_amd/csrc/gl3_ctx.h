@@ -127,6 +127,37 @@ constexpr size_t GL3_ARENA_HDR = 1024, GL3_ARENA_SEQ = 64, GL3_ARENA_ARRIVE = 68
 // rank p has completed into this arena), u32 ticket[3] (finished producer wavefronts of the running launch), u32 step (decode steps)
 constexpr size_t GL3_ARENA_FOLD = 512, GL3_ARENA_FOLD_TICKET = 704, GL3_ARENA_STEP = 720;
 
+// Samplers (gl3_sample.hip).  A row's settings as the kernels read them from device memory.
+enum { SMP_GREEDY = 0, SMP_CATEGORICAL = 1, SMP_TOPP = 2 };
+struct SmpRow { float temperature, topp, coin; int mode; };
+constexpr int GL3_DYN_ROW = 2, GL3_DYN_INTS = GL3_DYN_ROW + (int)(sizeof(SmpRow) / sizeof(int));     // layout of gl3_ctx::dyn / h_dyn
+
+inline SmpRow gl3_smp_row(float temperature, float topp, float coin) {
+    const bool use_topp = topp > 0.f && topp < 1.f;                   // Sampler.java:88-98
+    return SmpRow{temperature, topp, temperature == 0.f ? 0.f : coin, temperature == 0.f ? SMP_GREEDY : use_topp ? SMP_TOPP : SMP_CATEGORICAL};
+}
+
+struct gl3_sample_state {
+    int blocks;                                // workgroups per row of the element-wise launches (<= 256)
+    bool graph;                                // replay the launches as one hipGraph per (rows, any top-p row) instead of launching eagerly
+    int rows = 0;                              // capacity of every buffer below
+    float* probs = nullptr;                    // [rows][vocab]
+    float* aux = nullptr;                      // [rows][aux_stride]: `blocks` block maxima, the total, nchunks chunk ends
+    int aux_stride = 0;
+    uint32_t* sort = nullptr;                  // [rows][4 vocab + 256 nb]: (keys, indices) x 2, radix histogram
+    size_t sort_stride = 0;
+    int* res = nullptr;                        // [rows][2] {token, tie}, then [rows] n0 (top-p candidates)
+    SmpRow* params = nullptr;                  // [rows] (the single-row entry's settings ride in gl3_ctx::dyn instead)
+    SmpRow* h_params = nullptr;                // pinned
+    int* h_res = nullptr;                      // pinned [rows][2]
+    float* h_probs = nullptr;                  // pinned [vocab]: one tied row at a time
+    std::vector<hipGraphExec_t> graphs;        // [2 n + (any top-p row)]
+    const float* graph_logits = nullptr;       // the pointers the captured launches hold
+    const int32_t* graph_greedy = nullptr;
+    int last_n = 0;                            // rows of the last sampled step (their modes: h_params); 0 = no sampled step yet
+    gl3_sample_state(int blocks_, bool graph_) : blocks(blocks_), graph(graph_) {}
+};
+
 struct gl3_ctx {
     gl3_model_desc d{};
     // derived (local = this tensor-parallel rank's share)
@@ -162,18 +193,18 @@ struct gl3_ctx {
     float *moe_logits = nullptr, *moe_w = nullptr, *moe_hb = nullptr, *moe_y = nullptr;
     int* moe_sel = nullptr;                       // [topk] expert ids, then the router kernel's arrival ticket
     void* moe_slots = nullptr;                    // MoeSlots[n_layers][3]: gate/up with the shared expert merged, gate/up alone, down
-    int *dyn = nullptr, *argmax = nullptr;        // dyn[0] = token, dyn[1] = position
-    int* h_dyn = nullptr;                         // pinned
+    int *dyn = nullptr, *argmax = nullptr;        // dyn[0] = token, dyn[1] = position, then the SmpRow of a single-row sampled step (GL3_DYN_ROW)
+    int* h_dyn = nullptr;                         // pinned, same layout
     const int* dyn_cur = nullptr;                 // (token, position) pair the next launches read: dyn, or an entry of dyn_seq
     int* dyn_seq = nullptr;                       // [2 * dyn_seq_cap] pairs of a sequential (token-by-token) prefill chunk
     int dyn_seq_cap = 0;
     float* h_logits = nullptr;                    // pinned f32[vocab]
     int* h_argmax = nullptr;
-    float *sm_probs = nullptr, *sm_aux = nullptr, *h_probs = nullptr;   // sampling (gl3_sample.hip): probabilities, scratch, pinned copy
     int64_t topp_device = 0, topp_host = 0;       // top-p draws answered on the device / by the host heap (gl3_get_topp_counts)
-    void* sm_sort = nullptr;                      // top-p on the device: (key, index) x 2, radix histogram, result words
     std::vector<int> topp_indices;
-    struct gl3_bsample_state* bs = nullptr;       // row-batched sampler (gl3_sample_batch.h)
+    // samplers (gl3_sample.hip): one set of kernels, one state per entry, so each entry's parity tap answers for its own last step
+    gl3_sample_state smp_one{256, false};         // gl3_forward_decode_sample: one row, eager launches
+    gl3_sample_state smp_rows{64, true};          // static-batched entries: grows with the batch, one hipGraph per (rows, any top-p row)
     std::vector<std::pair<void*, size_t>> pinned;     // caller buffers registered with gl3_pin_host_buffer (logits land there directly)
     // upload staging
     uint8_t* staging = nullptr;
@@ -245,10 +276,11 @@ int32_t gl3_tp_local_resolve(gl3_ctx* ctx);
 int32_t gl3_tp_check(gl3_ctx* ctx);      // after a stream sync: GL3_E_RCCL if a gather timed out
 
 // gl3_sample.hip
-int32_t gl3_sample_run(gl3_ctx* ctx, const float* logits_dev, float temperature, float topp, float coin, int32_t* token_out);
+// single row: the launches behind a decode step whose set_dyn uploaded the row's settings, 8 bytes back
+int32_t gl3_sample_run(gl3_ctx* ctx, const float* logits_dev, int32_t* token_out);
 int32_t gl3_sample_probs(gl3_ctx* ctx, float* out);
 void gl3_sample_free(gl3_ctx* ctx);
-// row-batched form (gl3_sample_batch.h): prepare = check + stage the per-row settings (before the step is enqueued), finish = the
+// row-batched entries: prepare = check + stage the per-row settings (before the step is enqueued), finish = the
 // sampler's launches behind the step on the plan's stream, 8 * n bytes back, host heap for rows whose sampled rank is tied
 int32_t gl3_sample_batch_prepare(gl3_ctx* ctx, int32_t n, const float* temperature, const float* topp, const float* coins, bool* all_greedy);
 int32_t gl3_sample_batch_finish(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n, int32_t* tokens_out);

@@ -870,7 +870,7 @@ static int32_t pf_grow_logits(gl3_ctx* ctx, int n) {
     return GL3_OK;
 }
 
-// The batched sampler's view of a step (gl3_sample_batch.h): the logits rows and the greedy ids, both on the device.
+// The batched sampler's view of a step (gl3_sample.hip): the logits rows and the greedy ids, both on the device.
 void gl3_decode_batch_outputs(gl3_ctx* ctx, const float** logits, const int32_t** greedy) {
     *logits = ctx->pf->LOGITS; *greedy = ctx->pf->amax;
 }

@@ -23,7 +23,20 @@
 // near-uniform distributions of random-weight test models, rarer on real ones) the probabilities are copied out and the reference's heap
 // runs on the host (same sift order, same choice).
 //
-// Static-batched decode (gl3_forward_decode_batch_sample) runs the same pipeline for all rows of a step at once: gl3_sample_batch.h.
+// One set of kernels serves both entries.  Rows are a grid dimension, and every per-row setting (temperature, topp, coin, mode) is read
+// from a small device array (SmpRow, gl3_ctx.h), so no kernel takes a per-step scalar and a step costs the same launches at every row
+// count:
+//     bsm_scale_max, bsm_exp, bsm_seqsum<false>, bsm_div, bsm_seqsum<true> (categorical pick),
+//     btp_keys, 4 x (btp_hist, btp_scan, btp_scatter), btp_pick                      (left out when no row of the step uses top-p)
+// A row whose mode does not need a stage returns at once in that stage: greedy rows take the id of the step's own greedy scan
+// (pf_argmax_*), categorical rows skip the sort.  The sequential sums keep one workgroup per row (n rows run side by side on n CUs); the
+// radix sort is segmented by row (histogram [row][digit][tile], one scan workgroup per row, stable scatter inside the row).  {token, tie}
+// of every row come back in one copy of 8 * n bytes; only rows whose tie flag is set have their probabilities copied out and run through
+// the host heap (topp_sample).  The logits are read, never written.
+//
+// The two entries are two instances of gl3_sample_state.  gl3_forward_decode_sample is the n = 1 case: 256 workgroups per element-wise
+// launch, launched eagerly, its SmpRow riding behind the (token, position) pair in ctx->dyn.  The static-batched entries
+// (gl3_forward_decode_batch_sample, gl3_sample_rows) use 64 workgroups per row and replay one hipGraph per (row count, any top-p row).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -34,27 +47,41 @@
 
 using namespace gl3;
 
-constexpr int SM_BLOCKS = 256, SM_CHUNK = 4096;
+constexpr int SM_CHUNK = 4096;               // elements per exact sequential-sum chunk
 
-__global__ __launch_bounds__(256) void smp_scale_max_kernel(const float* __restrict__ logits, int n, float temperature, float* __restrict__ p,
-                                                            float* __restrict__ blockmax) {
+// aux row layout: `blocks` block maxima, the total, nchunks chunk ends.  blocks = workgroups per row of the element-wise launches
+// (gl3_sample_state::blocks, at most 256: bsm_exp reads one maximum per thread); the maximum does not depend on how rows are split.
+__global__ __launch_bounds__(256) void bsm_scale_max_kernel(const float* __restrict__ logits, int n, const SmpRow* __restrict__ rows, const int32_t* __restrict__ greedy,
+                                                            float* __restrict__ probs, float* __restrict__ aux, int aux_stride, int* __restrict__ res, int* __restrict__ n0) {
     __shared__ float red[4];
+    const int row = blockIdx.y;
+    const SmpRow R = rows[row];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        n0[row] = 0;
+        if (R.mode == SMP_GREEDY) { res[2 * row] = greedy[row]; res[2 * row + 1] = 0; }
+    }
+    if (R.mode == SMP_GREEDY) return;
+    const float* lg = logits + (size_t)row * n;
+    float* p = probs + (size_t)row * n;
     float mx = -INFINITY;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float v = logits[i] / temperature;                       // divideInPlace(temperature)
+        const float v = lg[i] / R.temperature;                         // divideInPlace(temperature)
         p[i] = v;
         mx = fmaxf(mx, v);
     }
     mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
     __syncthreads();
-    if (threadIdx.x == 0) blockmax[blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (threadIdx.x == 0) aux[(size_t)row * aux_stride + blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
-__global__ __launch_bounds__(256) void smp_exp_kernel(float* __restrict__ p, int n, const float* __restrict__ blockmax, int nblocks) {
+__global__ __launch_bounds__(256) void bsm_exp_kernel(float* __restrict__ probs, int n, const SmpRow* __restrict__ rows, const float* __restrict__ aux, int aux_stride, int blocks) {
     __shared__ float red[4];
-    float mx = -INFINITY;
-    for (int i = threadIdx.x; i < nblocks; i += 256) mx = fmaxf(mx, blockmax[i]);
+    const int row = blockIdx.y;
+    if (rows[row].mode == SMP_GREEDY) return;
+    float* p = probs + (size_t)row * n;
+    const float* blockmax = aux + (size_t)row * aux_stride;
+    float mx = threadIdx.x < blocks ? blockmax[threadIdx.x] : -INFINITY;
     mx = wave_max(mx);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
     __syncthreads();
@@ -62,19 +89,28 @@ __global__ __launch_bounds__(256) void smp_exp_kernel(float* __restrict__ p, int
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) p[i] = (float)exp((double)(p[i] - mx));   // (float) Math.exp(f - maxVal)
 }
 
-// Strictly sequential f32 sum of p[0..n) (all >= 0), one workgroup: chunks of SM_CHUNK through LDS, exact parallel evaluation
-// per chunk (gl3_seqsum.h) continued from the exact running value.  chunk_end[c] = running sum after chunk c (the cdf at the
-// chunk boundaries).  With pick = true the kernel then samples: first index whose cdf exceeds coin (CategoricalSampler).
+// Strictly sequential f32 sum of a row's p[0..n) (all >= 0), one workgroup per row: chunks of SM_CHUNK through LDS, exact parallel
+// evaluation per chunk (gl3_seqsum.h) continued from the exact running value.  chunk_end[c] = running sum after chunk c (the cdf at
+// the chunk boundaries).  PICK = false: every non-greedy row, total and chunk ends of the numerators; PICK = true: categorical rows
+// only, res[row] = {first index whose cdf exceeds the row's coin (CategoricalSampler), 0}.
 template <bool PICK>
-__global__ __launch_bounds__(256) void smp_seqsum_kernel(const float* __restrict__ p, int n, float* __restrict__ total, float* __restrict__ chunk_end,
-                                                         float coin, int* __restrict__ picked) {
+__global__ __launch_bounds__(256) void bsm_seqsum_kernel(const float* __restrict__ probs, int n, const SmpRow* __restrict__ rows, float* __restrict__ aux, int aux_stride,
+                                                         int blocks, int* __restrict__ res) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     float* xf = reinterpret_cast<float*>(smem);                      // [SM_CHUNK + 32]
     uint8_t* scratch = smem + (size_t)(SM_CHUNK + 32) * 4;
     __shared__ float run_s;
     __shared__ int hit_s;
+    const int row = blockIdx.x;
+    const SmpRow R = rows[row];
+    if (PICK ? R.mode != SMP_CATEGORICAL : R.mode == SMP_GREEDY) return;
+    const float* p = probs + (size_t)row * n;
+    float* total = aux + (size_t)row * aux_stride + blocks;
+    float* chunk_end = total + 1;
+    const float coin = R.coin;
+    int* picked = res + 2 * row;
     const int t = threadIdx.x;
-    if (t == 0) { run_s = 0.f; hit_s = -1; }
+    if (t == 0) { run_s = 0.f; hit_s = -1; if (PICK) picked[1] = 0; }
     __syncthreads();
     const int nchunks = (n + SM_CHUNK - 1) / SM_CHUNK;
     for (int c = 0; c < nchunks; ++c) {
@@ -103,20 +139,23 @@ __global__ __launch_bounds__(256) void smp_seqsum_kernel(const float* __restrict
                 float cdf = c ? chunk_end[c - 1] : 0.f;
                 int idx = -1;
                 for (int i = 0; i < len; ++i) { cdf = cdf + xf[i]; if (coin < cdf) { idx = base + i; break; } }
-                *picked = idx >= 0 ? idx : base + len - 1;
+                picked[0] = idx >= 0 ? idx : base + len - 1;
             }
             break;
         }
     }
     __syncthreads();
     if (t == 0) {
-        if (total) *total = run_s;
-        if (PICK && hit_s < 0) *picked = n - 1;                       // "in case of rounding errors"
+        if (!PICK) *total = run_s;
+        if (PICK && hit_s < 0) picked[0] = n - 1;                     // "in case of rounding errors"
     }
 }
 
-__global__ __launch_bounds__(256) void smp_div_kernel(float* __restrict__ p, int n, const float* __restrict__ total) {
-    const float s = *total;
+__global__ __launch_bounds__(256) void bsm_div_kernel(float* __restrict__ probs, int n, const SmpRow* __restrict__ rows, const float* __restrict__ aux, int aux_stride, int blocks) {
+    const int row = blockIdx.y;
+    if (rows[row].mode == SMP_GREEDY) return;
+    float* p = probs + (size_t)row * n;
+    const float s = aux[(size_t)row * aux_stride + blocks];
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) p[i] = p[i] / s;     // divideInPlace(sum)
 }
 
@@ -166,31 +205,53 @@ static int topp_sample(const float* p, int n, float topp, float coin, std::vecto
 
 // ------------------------------------------------------------------------------------------------ top-p on the device
 // Keys: candidates (p >= cutoff, ToppSampler.java:74-81) get ~bits(p) (positive floats order like their bit patterns, so ascending keys
-// = descending probabilities), everything else the maximal key; a stable LSD radix sort (4 x 8 bits) of (key, index) pairs puts the n0
-// candidates first in descending order.
+// = descending probabilities), everything else the maximal key; a stable LSD radix sort (4 x 8 bits) of (key, index) pairs, segmented by
+// row, puts the n0 candidates first in descending order.  A row's segment of `sort`: ka[n] ia[n] kb[n] ib[n] hist[256 nb].
 constexpr int RS_THREADS = 256, RS_PER = 4, RS_TILE = RS_THREADS * RS_PER;
+struct BtpSeg {
+    uint32_t *ka, *kb;
+    int *ia, *ib, *hist;
+    __device__ BtpSeg(uint32_t* sort, size_t stride, int row, int n) {
+        ka = sort + (size_t)row * stride;
+        ia = reinterpret_cast<int*>(ka + n);
+        kb = reinterpret_cast<uint32_t*>(ia + n);
+        ib = reinterpret_cast<int*>(kb + n);
+        hist = ib + n;
+    }
+};
 
-__global__ __launch_bounds__(RS_THREADS) void topp_keys_kernel(const float* __restrict__ p, int n, float cutoff, uint32_t* __restrict__ keys, int* __restrict__ idx,
-                                                                int* __restrict__ n0) {
+__global__ __launch_bounds__(RS_THREADS) void btp_keys_kernel(const float* __restrict__ probs, int n, const SmpRow* __restrict__ rows, uint32_t* __restrict__ sort, size_t stride,
+                                                               int* __restrict__ n0) {
     __shared__ int cnt_s;
+    const int row = blockIdx.y;
+    const SmpRow R = rows[row];
+    if (R.mode != SMP_TOPP) return;
+    const float cutoff = (1.0f - R.topp) / (float)(n - 1);            // ToppSampler.java:73
+    const float* p = probs + (size_t)row * n;
+    const BtpSeg S(sort, stride, row, n);
     if (threadIdx.x == 0) cnt_s = 0;
     __syncthreads();
     int c = 0;
     for (int i = blockIdx.x * RS_THREADS + threadIdx.x; i < n; i += gridDim.x * RS_THREADS) {
         const float v = p[i];
         const bool cand = v >= cutoff;
-        keys[i] = cand ? ~__builtin_bit_cast(uint32_t, v) : 0xFFFFFFFFu;
-        idx[i] = i;
+        S.ka[i] = cand ? ~__builtin_bit_cast(uint32_t, v) : 0xFFFFFFFFu;
+        S.ia[i] = i;
         c += cand ? 1 : 0;
     }
     atomicAdd(&cnt_s, c);
     __syncthreads();
-    if (threadIdx.x == 0 && cnt_s) atomicAdd(n0, cnt_s);
+    if (threadIdx.x == 0 && cnt_s) atomicAdd(n0 + row, cnt_s);
 }
 
-// hist[d * nblocks + b] = elements of tile b whose digit is d
-__global__ __launch_bounds__(RS_THREADS) void radix_hist_kernel(const uint32_t* __restrict__ keys, int n, int shift, int* __restrict__ hist, int nblocks) {
+// hist[row][d * nblocks + b] = elements of tile b of the row whose digit is d.  pass = 0..3: odd passes read (kb, ib).
+__global__ __launch_bounds__(RS_THREADS) void btp_hist_kernel(const SmpRow* __restrict__ rows, uint32_t* __restrict__ sort, size_t stride, int n, int pass, int nblocks) {
     __shared__ int h[256];
+    const int row = blockIdx.y;
+    if (rows[row].mode != SMP_TOPP) return;
+    const BtpSeg S(sort, stride, row, n);
+    const uint32_t* keys = pass & 1 ? S.kb : S.ka;
+    const int shift = 8 * pass;
     h[threadIdx.x] = 0;
     __syncthreads();
 #pragma unroll
@@ -199,13 +260,16 @@ __global__ __launch_bounds__(RS_THREADS) void radix_hist_kernel(const uint32_t* 
         if (e < n) atomicAdd(&h[(keys[e] >> shift) & 255u], 1);
     }
     __syncthreads();
-    hist[threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
+    S.hist[threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
 }
 
-// exclusive prefix over hist in (digit, block) order, in place; one workgroup of 1024 threads
-__global__ __launch_bounds__(1024) void radix_scan_kernel(int* __restrict__ hist, int total) {
+// exclusive prefix over a row's histogram in (digit, tile) order, in place; one workgroup of 1024 threads per row
+__global__ __launch_bounds__(1024) void btp_scan_kernel(const SmpRow* __restrict__ rows, uint32_t* __restrict__ sort, size_t stride, int n, int total) {
     __shared__ int part[1024];
-    const int t = threadIdx.x, per = (total + 1023) / 1024, lo = t * per, hi = min(total, lo + per);
+    const int row = blockIdx.x;
+    if (rows[row].mode != SMP_TOPP) return;
+    int* hist = BtpSeg(sort, stride, row, n).hist;
+    const int t = threadIdx.x, per = (total + 1023) / 1024, lo = min(total, t * per), hi = min(total, lo + per);
     int s = 0;
     for (int i = lo; i < hi; ++i) s += hist[i];
     part[t] = s;
@@ -220,13 +284,20 @@ __global__ __launch_bounds__(1024) void radix_scan_kernel(int* __restrict__ hist
     for (int i = lo; i < hi; ++i) { const int v = hist[i]; hist[i] = run; run += v; }
 }
 
-// stable scatter of tile blockIdx.x: element order inside a tile is (round, wavefront, lane) = ascending index
-__global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const uint32_t* __restrict__ kin, const int* __restrict__ iin, uint32_t* __restrict__ kout,
-                                                                    int* __restrict__ iout, int n, int shift, const int* __restrict__ hist, int nblocks) {
+// stable scatter of tile blockIdx.x of row blockIdx.y: element order inside a tile is (round, wavefront, lane) = ascending index
+__global__ __launch_bounds__(RS_THREADS) void btp_scatter_kernel(const SmpRow* __restrict__ rows, uint32_t* __restrict__ sort, size_t stride, int n, int pass, int nblocks) {
     __shared__ int base[256];                  // next output slot of digit d for this tile
     __shared__ int wcnt[4][256];               // per wavefront: elements of digit d in the current round
+    const int row = blockIdx.y;
+    if (rows[row].mode != SMP_TOPP) return;
+    const BtpSeg S(sort, stride, row, n);
+    const uint32_t* kin = pass & 1 ? S.kb : S.ka;
+    const int* iin = pass & 1 ? S.ib : S.ia;
+    uint32_t* kout = pass & 1 ? S.ka : S.kb;
+    int* iout = pass & 1 ? S.ia : S.ib;
+    const int shift = 8 * pass;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    base[t] = hist[t * nblocks + blockIdx.x];
+    base[t] = S.hist[t * nblocks + blockIdx.x];
 #pragma unroll
     for (int r = 0; r < RS_PER; ++r) {
 #pragma unroll
@@ -250,8 +321,10 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const uint32_
         if (valid) {
             int off = base[d] + before;
             for (int w = 0; w < wave; ++w) off += wcnt[w][d];
-            kout[off] = key;
-            iout[off] = id;
+            if (off >= 0 && off < n) {         // a row-relative slot by construction; never write outside the row's segment
+                kout[off] = key;
+                iout[off] = id;
+            }
         }
         __syncthreads();
         base[t] += wcnt[0][t] + wcnt[1][t] + wcnt[2][t] + wcnt[3][t];
@@ -259,21 +332,30 @@ __global__ __launch_bounds__(RS_THREADS) void radix_scatter_kernel(const uint32_
     }
 }
 
-// ToppSampler.processTopP :118-160 on the sorted candidates sv[0 .. n0) (sv[r] = probability at rank r, descending):
+// ToppSampler.processTopP :118-160 on a row's sorted candidates sv[0 .. n0) (sv[r] = probability at rank r, descending), one workgroup
+// per row:
 //   cumulativeProb += value (f32, in order) until it EXCEEDS topp -> last rank (rank n0 - 1 if it never does);
 //   r = coin * cumulativeProb;  cdf += value from rank 0: the first rank with r < cdf, bounded by the last rank.
 // The two strictly sequential prefix scans run 4096 ranks at a time with the exact parallel sum (gl3_seqsum.h) and walk only the
-// chunk in which the threshold falls.  out[0] = index at the chosen rank, out[1] = 1 if another candidate has the same probability
-// (then the reference's heap order, not this sort order, names the token: the host re-runs it).
-__global__ __launch_bounds__(256) void topp_pick_kernel(const uint32_t* __restrict__ skeys, const int* __restrict__ sidx, const int* __restrict__ n0p, float topp, float coin,
-                                                        int* __restrict__ out) {
+// chunk in which the threshold falls.  res[row] = {index at the chosen rank, 1 if another candidate has the same probability (then the
+// reference's heap order, not this sort order, names the token: the host re-runs it)}.
+__global__ __launch_bounds__(256) void btp_pick_kernel(const SmpRow* __restrict__ rows, uint32_t* __restrict__ sort, size_t stride, int n, const int* __restrict__ n0p,
+                                                       int* __restrict__ res) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     float* xf = reinterpret_cast<float*>(smem);                      // [SM_CHUNK + 32]
     uint8_t* scratch = smem + (size_t)(SM_CHUNK + 32) * 4;
     __shared__ float run_s, thr_s, cum_s;
     __shared__ int rank_s, last_s;
+    const int row = blockIdx.x;
+    const SmpRow R = rows[row];
+    if (R.mode != SMP_TOPP) return;
+    const BtpSeg S(sort, stride, row, n);
+    const uint32_t* skeys = S.ka;                                    // 4 passes: the sorted pairs are back in (ka, ia)
+    const int* sidx = S.ia;
+    int* out = res + 2 * row;
+    const float topp = R.topp, coin = R.coin;
     const int t = threadIdx.x;
-    const int n0 = *n0p;
+    const int n0 = min(n0p[row], n);
     if (n0 <= 0) { if (t == 0) { out[0] = 0; out[1] = 1; } return; }      // no candidate (cannot happen for a normalised row): let the host decide
     if (t == 0) { thr_s = topp; last_s = n0 - 1; cum_s = 0.f; }
     for (int phase = 0; phase < 2; ++phase) {
@@ -327,106 +409,179 @@ __global__ __launch_bounds__(256) void topp_pick_kernel(const uint32_t* __restri
     }
 }
 
-static int32_t sample_alloc_all(gl3_ctx* ctx) {
-    const int nchunks = (ctx->d.vocab + SM_CHUNK - 1) / SM_CHUNK;
-    GL3_HIP(hipMalloc((void**)&ctx->sm_probs, (size_t)ctx->d.vocab * 4));
-    GL3_HIP(hipMalloc((void**)&ctx->sm_aux, (size_t)(SM_BLOCKS + nchunks + 8) * 4));
-    GL3_HIP(hipHostMalloc((void**)&ctx->h_probs, (size_t)ctx->d.vocab * 4));
-    {   // top-p on the device: two (key, index) buffers, the radix histogram, {n0, token, tie}
-        const int nb = (ctx->d.vocab + RS_TILE - 1) / RS_TILE;
-        GL3_HIP(hipMalloc((void**)&ctx->sm_sort, ((size_t)4 * ctx->d.vocab + (size_t)256 * nb + 8) * 4));
-    }
-    GL3_HIP(hipFuncSetAttribute((const void*)topp_pick_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    GL3_HIP(hipFuncSetAttribute((const void*)smp_seqsum_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-    GL3_HIP(hipFuncSetAttribute((const void*)smp_seqsum_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+// ------------------------------------------------------------------------------------------------ host side
+static void sample_drop_graphs(gl3_sample_state* b) {
+    for (auto& ge : b->graphs) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }
+}
+
+static void sample_free_buffers(gl3_sample_state* b) {
+    sample_drop_graphs(b);
+    if (b->probs) hipFree(b->probs);
+    if (b->aux) hipFree(b->aux);
+    if (b->sort) hipFree(b->sort);
+    if (b->res) hipFree(b->res);
+    if (b->params) hipFree(b->params);
+    if (b->h_params) hipHostFree(b->h_params);
+    if (b->h_res) hipHostFree(b->h_res);
+    if (b->h_probs) hipHostFree(b->h_probs);
+    b->probs = nullptr; b->aux = nullptr; b->sort = nullptr; b->res = nullptr; b->params = nullptr;
+    b->h_params = nullptr; b->h_res = nullptr; b->h_probs = nullptr;
+    b->rows = 0; b->last_n = 0;
+}
+
+void gl3_sample_free(gl3_ctx* ctx) {
+    sample_free_buffers(&ctx->smp_one);
+    sample_free_buffers(&ctx->smp_rows);
+}
+
+static int32_t sample_alloc_all(gl3_ctx* ctx, gl3_sample_state* b, int rows) {
+    const size_t vocab = (size_t)ctx->d.vocab;
+    const int nchunks = (ctx->d.vocab + SM_CHUNK - 1) / SM_CHUNK, nb = (ctx->d.vocab + RS_TILE - 1) / RS_TILE;
+    b->aux_stride = b->blocks + 1 + nchunks;
+    b->sort_stride = 4 * vocab + (size_t)256 * nb;
+    GL3_HIP(hipMalloc((void**)&b->probs, (size_t)rows * vocab * 4));
+    GL3_HIP(hipMalloc((void**)&b->aux, (size_t)rows * b->aux_stride * 4));
+    GL3_HIP(hipMalloc((void**)&b->sort, (size_t)rows * b->sort_stride * 4));
+    GL3_HIP(hipMalloc((void**)&b->res, (size_t)rows * 3 * sizeof(int)));
+    GL3_HIP(hipMalloc((void**)&b->params, (size_t)rows * sizeof(SmpRow)));
+    GL3_HIP(hipHostMalloc((void**)&b->h_params, (size_t)rows * sizeof(SmpRow)));
+    GL3_HIP(hipHostMalloc((void**)&b->h_res, (size_t)rows * 2 * sizeof(int)));
+    GL3_HIP(hipHostMalloc((void**)&b->h_probs, vocab * 4));
+    GL3_HIP(hipFuncSetAttribute((const void*)btp_pick_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    GL3_HIP(hipFuncSetAttribute((const void*)bsm_seqsum_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    GL3_HIP(hipFuncSetAttribute((const void*)bsm_seqsum_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
+    b->rows = rows;
     return GL3_OK;
 }
 
-// All three buffers or none: a partial allocation (out of memory half way) is released, so the next call starts over instead of
-// launching kernels on null pointers.
-int32_t gl3_sample_alloc(gl3_ctx* ctx) {
-    if (ctx->sm_probs && ctx->sm_aux && ctx->h_probs && ctx->sm_sort) return GL3_OK;
-    gl3_sample_free(ctx);
-    const int32_t r = sample_alloc_all(ctx);
-    if (r != GL3_OK) gl3_sample_free(ctx);
+// Every buffer sized for the largest n seen, all or none: a failed allocation (out of memory half way) releases what it got, so the
+// next call starts over instead of launching kernels on null pointers.
+static int32_t sample_alloc(gl3_ctx* ctx, gl3_sample_state* b, int n) {
+    if (b->rows >= n) return GL3_OK;
+    if (b->rows) GL3_HIP(hipStreamSynchronize(ctx->stream));      // an earlier step may still read the buffers about to be freed
+    sample_free_buffers(b);
+    const int32_t r = sample_alloc_all(ctx, b, n);
+    if (r != GL3_OK) sample_free_buffers(b);
     return r;
 }
 
-void gl3_sample_batch_free(gl3_ctx* ctx);      // gl3_sample_batch.h
-
-void gl3_sample_free(gl3_ctx* ctx) {
-    gl3_sample_batch_free(ctx);
-    if (ctx->sm_probs) hipFree(ctx->sm_probs);
-    if (ctx->sm_aux) hipFree(ctx->sm_aux);
-    if (ctx->h_probs) hipHostFree(ctx->h_probs);
-    if (ctx->sm_sort) hipFree(ctx->sm_sort);
-    ctx->sm_probs = nullptr; ctx->sm_aux = nullptr; ctx->h_probs = nullptr; ctx->sm_sort = nullptr;
-}
-
-// logits (device, f32[vocab], complete on this rank) -> sampled id.  temperature > 0.
-int32_t gl3_sample_run(gl3_ctx* ctx, const float* logits_dev, float temperature, float topp, float coin, int32_t* token_out) {
-    int32_t r = gl3_sample_alloc(ctx);
-    if (r != GL3_OK) return r;
-    const int n = ctx->d.vocab;
+static void sample_enqueue(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, const int32_t* greedy, const SmpRow* params, int n, bool any_topp) {
     hipStream_t s = ctx->stream;
-    float* blockmax = ctx->sm_aux;
-    float* total = ctx->sm_aux + SM_BLOCKS;
-    int* picked = reinterpret_cast<int*>(ctx->sm_aux + SM_BLOCKS + 1);
-    float* chunk_end = ctx->sm_aux + SM_BLOCKS + 8;
+    const int v = ctx->d.vocab, nb = (v + RS_TILE - 1) / RS_TILE;
     const size_t smem = (size_t)(SM_CHUNK + 32) * 4 + ss_scratch_bytes(SM_CHUNK);
-    hipLaunchKernelGGL(smp_scale_max_kernel, dim3(SM_BLOCKS), dim3(256), 0, s, logits_dev, n, temperature, ctx->sm_probs, blockmax);
-    hipLaunchKernelGGL(smp_exp_kernel, dim3(SM_BLOCKS), dim3(256), 0, s, ctx->sm_probs, n, blockmax, SM_BLOCKS);
-    hipLaunchKernelGGL(smp_seqsum_kernel<false>, dim3(1), dim3(256), smem, s, ctx->sm_probs, n, total, chunk_end, 0.f, picked);
-    hipLaunchKernelGGL(smp_div_kernel, dim3(SM_BLOCKS), dim3(256), 0, s, ctx->sm_probs, n, total);
-    GL3_HIP(hipGetLastError());
-    const bool use_topp = topp > 0.f && topp < 1.f;                  // Sampler.java:88-98
-    if (!use_topp) {
-        hipLaunchKernelGGL(smp_seqsum_kernel<true>, dim3(1), dim3(256), smem, s, ctx->sm_probs, n, (float*)nullptr, chunk_end, coin, picked);
-        GL3_HIP(hipGetLastError());
-        GL3_HIP(hipMemcpyAsync(ctx->h_argmax, picked, sizeof(int), hipMemcpyDeviceToHost, s));
-        GL3_HIP(hipStreamSynchronize(s));
-        *token_out = *ctx->h_argmax;
-        return GL3_OK;
+    int* n0 = b->res + 2 * b->rows;
+    const dim3 ge(b->blocks, n), gt(nb, n);
+    hipLaunchKernelGGL(bsm_scale_max_kernel, ge, dim3(256), 0, s, logits, v, params, greedy, b->probs, b->aux, b->aux_stride, b->res, n0);
+    hipLaunchKernelGGL(bsm_exp_kernel, ge, dim3(256), 0, s, b->probs, v, params, b->aux, b->aux_stride, b->blocks);
+    hipLaunchKernelGGL(bsm_seqsum_kernel<false>, dim3(n), dim3(256), smem, s, b->probs, v, params, b->aux, b->aux_stride, b->blocks, b->res);
+    hipLaunchKernelGGL(bsm_div_kernel, ge, dim3(256), 0, s, b->probs, v, params, b->aux, b->aux_stride, b->blocks);
+    hipLaunchKernelGGL(bsm_seqsum_kernel<true>, dim3(n), dim3(256), smem, s, b->probs, v, params, b->aux, b->aux_stride, b->blocks, b->res);
+    if (!any_topp) return;
+    hipLaunchKernelGGL(btp_keys_kernel, ge, dim3(RS_THREADS), 0, s, b->probs, v, params, b->sort, b->sort_stride, n0);
+    for (int pass = 0; pass < 4; ++pass) {
+        hipLaunchKernelGGL(btp_hist_kernel, gt, dim3(RS_THREADS), 0, s, params, b->sort, b->sort_stride, v, pass, nb);
+        hipLaunchKernelGGL(btp_scan_kernel, dim3(n), dim3(1024), 0, s, params, b->sort, b->sort_stride, v, 256 * nb);
+        hipLaunchKernelGGL(btp_scatter_kernel, gt, dim3(RS_THREADS), 0, s, params, b->sort, b->sort_stride, v, pass, nb);
     }
-    // ---- top-p on the device: candidates -> descending radix sort -> truncation, renormalised coin, rank (8 bytes come back)
-    static const bool host_topp = env_flag("GL3_TOPP_HOST", false);              // A/B switch: the r4 path (probabilities to the host)
-    if (!host_topp) {
-        const int nb = (n + RS_TILE - 1) / RS_TILE;
-        uint32_t* ka = reinterpret_cast<uint32_t*>(ctx->sm_sort);
-        int* ia = reinterpret_cast<int*>(ka + n);
-        uint32_t* kb = reinterpret_cast<uint32_t*>(ia + n);
-        int* ib = reinterpret_cast<int*>(kb + n);
-        int* hist = ib + n;
-        int* res = hist + (size_t)256 * nb;                               // [0] n0, [1] token, [2] tie
-        const float cutoff = (1.0f - topp) / (float)(n - 1);             // ToppSampler.java:73
-        GL3_HIP(hipMemsetAsync(res, 0, 3 * sizeof(int), s));
-        hipLaunchKernelGGL(topp_keys_kernel, dim3(SM_BLOCKS), dim3(RS_THREADS), 0, s, ctx->sm_probs, n, cutoff, ka, ia, res);
-        for (int pass = 0; pass < 4; ++pass) {
-            uint32_t* kin = pass & 1 ? kb : ka; int* iin = pass & 1 ? ib : ia;
-            uint32_t* kout = pass & 1 ? ka : kb; int* iout = pass & 1 ? ia : ib;
-            hipLaunchKernelGGL(radix_hist_kernel, dim3(nb), dim3(RS_THREADS), 0, s, kin, n, 8 * pass, hist, nb);
-            hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, s, hist, 256 * nb);
-            hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(RS_THREADS), 0, s, kin, iin, kout, iout, n, 8 * pass, hist, nb);
+    hipLaunchKernelGGL(btp_pick_kernel, dim3(n), dim3(256), smem, s, params, b->sort, b->sort_stride, v, n0, b->res);
+}
+
+// The sampler's launches for rows 0..n) of `logits` behind whatever produced them on the plan's stream (params / h_params: the rows'
+// settings on the device / the host), 8 * n bytes back, host heap for top-p rows whose sampled rank is tied.
+static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, const int32_t* greedy, const SmpRow* params, const SmpRow* h_params, int n,
+                             int32_t* tokens_out) {
+    hipStream_t s = ctx->stream;
+    const int v = ctx->d.vocab;
+    static const bool host_topp = env_flag("GL3_TOPP_HOST", false);              // A/B switch: no sort launches, every top-p row through the host heap
+    bool any_topp = false;
+    for (int i = 0; i < n; ++i) any_topp |= h_params[i].mode == SMP_TOPP && !host_topp;
+    static const bool graphs_off = getenv("GL3_NO_GRAPH") && atoi(getenv("GL3_NO_GRAPH"));
+    if (b->graph && !graphs_off && !gl3_roctx_on() && !(ctx->d.flags & GL3_FLAG_NO_GRAPH)) {
+        if (b->graph_logits != logits || b->graph_greedy != greedy) {      // the step's logits buffer has grown: captured launches point at the old one
+            sample_drop_graphs(b);
+            b->graph_logits = logits; b->graph_greedy = greedy;
         }
-        hipLaunchKernelGGL(topp_pick_kernel, dim3(1), dim3(256), smem, s, ka, ia, res, topp, coin, res + 1);       // 4 passes: the result is back in (ka, ia)
-        GL3_HIP(hipGetLastError());
-        GL3_HIP(hipMemcpyAsync(ctx->h_dyn + 2, res + 1, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        GL3_HIP(hipStreamSynchronize(s));
-        if (!ctx->h_dyn[3]) { *token_out = ctx->h_dyn[2]; ++ctx->topp_device; return GL3_OK; }
-        // a tie at the sampled rank: the reference's heap history decides between equal probabilities — run it
+        const size_t slot = (size_t)2 * n + (any_topp ? 1 : 0);
+        if (b->graphs.size() <= slot) b->graphs.resize(slot + 1, nullptr);
+        if (!b->graphs[slot]) {
+            hipGraph_t g = nullptr;
+            GL3_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+            sample_enqueue(ctx, b, logits, greedy, params, n, any_topp);
+            GL3_HIP(hipStreamEndCapture(s, &g));
+            GL3_HIP(hipGraphInstantiate(&b->graphs[slot], g, nullptr, nullptr, 0));
+            hipGraphDestroy(g);
+        }
+        GL3_HIP(hipGraphLaunch(b->graphs[slot], s));
+    } else {
+        sample_enqueue(ctx, b, logits, greedy, params, n, any_topp);
     }
-    GL3_HIP(hipMemcpyAsync(ctx->h_probs, ctx->sm_probs, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    GL3_HIP(hipGetLastError());
+    GL3_HIP(hipMemcpyAsync(b->h_res, b->res, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     GL3_HIP(hipStreamSynchronize(s));
-    *token_out = topp_sample(ctx->h_probs, n, topp, coin, ctx->topp_indices);
-    ++ctx->topp_host;
+    int32_t r = gl3_tp_check(ctx);
+    if (r != GL3_OK) return r;
+    b->last_n = n;
+    for (int i = 0; i < n; ++i) {
+        const SmpRow& R = h_params[i];
+        if (R.mode != SMP_TOPP || (!host_topp && !b->h_res[2 * i + 1])) {
+            tokens_out[i] = b->h_res[2 * i];
+            if (R.mode == SMP_TOPP) ++ctx->topp_device;
+            continue;
+        }
+        // a tie at the sampled rank of this row: the reference's heap history decides between equal probabilities — run it
+        GL3_HIP(hipMemcpyAsync(b->h_probs, b->probs + (size_t)i * v, (size_t)v * 4, hipMemcpyDeviceToHost, s));
+        GL3_HIP(hipStreamSynchronize(s));
+        tokens_out[i] = topp_sample(b->h_probs, v, R.topp, R.coin, ctx->topp_indices);
+        ++ctx->topp_host;
+    }
     return GL3_OK;
 }
 
-int32_t gl3_sample_probs(gl3_ctx* ctx, float* out) {       // parity tap: the probabilities of the last sampled step
-    if (!ctx->sm_probs) GL3_FAIL(GL3_E_STATE, "no sampled step yet");
-    GL3_HIP(hipMemcpy(out, ctx->sm_probs, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToHost));
+// ---- single-row entry: logits (device, f32[vocab], complete on this rank) -> sampled id.  The row's settings were uploaded behind the
+// (token, position) pair by the step's own copy (set_dyn, gl3_api.hip); never greedy (temperature > 0), so no greedy ids are passed.
+int32_t gl3_sample_run(gl3_ctx* ctx, const float* logits_dev, int32_t* token_out) {
+    const int32_t r = sample_alloc(ctx, &ctx->smp_one, 1);
+    if (r != GL3_OK) return r;
+    return sample_finish(ctx, &ctx->smp_one, logits_dev, nullptr, reinterpret_cast<const SmpRow*>(ctx->dyn + GL3_DYN_ROW), reinterpret_cast<const SmpRow*>(ctx->h_dyn + GL3_DYN_ROW), 1, token_out);
+}
+
+int32_t gl3_sample_probs(gl3_ctx* ctx, float* out) {       // parity tap: the probabilities of the last single-row sampled step
+    if (!ctx->smp_one.last_n) GL3_FAIL(GL3_E_STATE, "no sampled step yet");
+    GL3_HIP(hipMemcpy(out, ctx->smp_one.probs, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToHost));
     return GL3_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ every row of a batched step
-#include "gl3_sample_batch.h"
+// ---- batched entries: prepare = check + stage the per-row settings (before the step is enqueued), finish = the launches behind it
+int32_t gl3_sample_batch_prepare(gl3_ctx* ctx, int32_t n, const float* temperature, const float* topp, const float* coins, bool* all_greedy) {
+    gl3_sample_state* b = &ctx->smp_rows;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        if (!(temperature[i] >= 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be >= 0");
+        if (temperature[i] == 0.f) continue;                          // Sampler.java:79-81: greedy argmax; the row's coin is not looked at
+        if (!(coins[i] >= 0.f && coins[i] < 1.f)) GL3_FAIL(GL3_E_ARG, "coin must be rng.nextFloat(1f): in [0, 1)");
+        any = true;
+    }
+    *all_greedy = !any;
+    b->last_n = 0;
+    if (!any) return GL3_OK;                                          // the step's own greedy ids answer every row: nothing to stage
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    const int32_t r = sample_alloc(ctx, b, n);
+    if (r != GL3_OK) return r;
+    for (int i = 0; i < n; ++i) b->h_params[i] = gl3_smp_row(temperature[i], topp[i], coins[i]);
+    GL3_HIP(hipMemcpyAsync(b->params, b->h_params, (size_t)n * sizeof(SmpRow), hipMemcpyHostToDevice, ctx->stream));
+    return GL3_OK;
+}
+
+int32_t gl3_sample_batch_finish(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n, int32_t* tokens_out) {
+    gl3_sample_state* b = &ctx->smp_rows;
+    return sample_finish(ctx, b, logits_dev, greedy_dev, b->params, b->h_params, n, tokens_out);
+}
+
+int32_t gl3_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out) {      // parity tap: what row `row` of the last batched sampled step was drawn from
+    const gl3_sample_state* b = &ctx->smp_rows;
+    if (!b->last_n) GL3_FAIL(GL3_E_STATE, "no batched sampled step yet");
+    if (row < 0 || row >= b->last_n) GL3_FAIL(GL3_E_ARG, "row outside the last batched sampled step");
+    if (b->h_params[row].mode == SMP_GREEDY) GL3_FAIL(GL3_E_STATE, "the row was greedy: it has no probabilities");
+    GL3_HIP(hipMemcpy(out, b->probs + (size_t)row * ctx->d.vocab, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToHost));
+    return GL3_OK;
+}

@@ -272,7 +272,7 @@ GL3_API int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, co
  * coins[i] = rng.nextFloat(1f) drawn by the CALLER from row i's own RandomGenerator, in [0, 1); 0 < topp[i] < 1 -> ToppSampler,
  * else CategoricalSampler.  tokens_out: int32[n]; 8 * n bytes come back, and only a top-p row whose sampled rank is shared by
  * equal probabilities has its probabilities copied out for the reference's heap (counted by gl3_get_topp_counts, one count per
- * non-greedy top-p row).  The number of sampler launches does not depend on n (gl3_sample_batch.h).  Everything else as
+ * non-greedy top-p row).  The number of sampler launches does not depend on n (gl3_sample.hip).  Everything else as
  * gl3_forward_decode_batch; with every temperature 0 the ids are its argmax_out.  GL3_E_UNSUPPORTED: tp_size > 1 (rank-chunked
  * logits), max_batch <= 1. */
 GL3_API int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids,

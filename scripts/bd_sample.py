@@ -8,7 +8,11 @@ synchronisation) of
                                                     sampler, the copy only (no host softmax, no heap): a lower bound
   (c) forward_decode_batch_sample, every row (0.7, 0.95)    top-p
   (d) forward_decode_batch_sample, every row (1.0, 0)       categorical
-The four lines alternate inside every repetition, so they share whatever else the machine is doing.  `only` = a | b | c | d runs
+and, on the single-row entry of the same plan at positions 0 .. steps - 1, of
+  (e) forward_decode                                 greedy id
+  (f) forward_decode_sample (0.7, 0.95)              top-p
+  (g) forward_decode_sample (1.0, 0)                 categorical
+The seven lines alternate inside every repetition, so they share whatever else the machine is doing.  `only` = a | b | .. | g runs
 one line alone (for a kernel trace)."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,6 +43,9 @@ lines = {
     "b": ("all logits to the host", lambda i: plan.forward_decode_batch(toks[i], seqs, poss[i], want_logits=True)),
     "c": ("sampled on the device, top-p (0.7, 0.95)", lambda i: plan.forward_decode_batch_sample(toks[i], seqs, poss[i], temp_c, topp_c, coins[i])),
     "d": ("sampled on the device, categorical (1.0, 0)", lambda i: plan.forward_decode_batch_sample(toks[i], seqs, poss[i], temp_d, topp_d, coins[i])),
+    "e": ("single row, greedy id", lambda i: plan.forward_decode_argmax(int(toks[i, 0]), i)),
+    "f": ("single row, top-p (0.7, 0.95)", lambda i: plan.forward_decode_sample(int(toks[i, 0]), i, 0.7, 0.95, float(coins[i, 0]))),
+    "g": ("single row, categorical (1.0, 0)", lambda i: plan.forward_decode_sample(int(toks[i, 0]), i, 1.0, 0.0, float(coins[i, 0]))),
 }
 keys = [only] if only else list(lines)
 ms = {k: [] for k in keys}
@@ -65,5 +72,6 @@ for k in keys:
 if not only:
     med = {k: sorted(ms[k])[len(ms[k]) // 2] for k in keys}
     print("sampler cost per step: (c) - (a) = %.3f ms, (d) - (a) = %.3f ms; logits copy: (b) - (a) = %.3f ms" % (med["c"] - med["a"], med["d"] - med["a"], med["b"] - med["a"]))
+    print("single-row sampler cost per step: (f) - (e) = %.3f ms, (g) - (e) = %.3f ms" % (med["f"] - med["e"], med["g"] - med["e"]))
     dev, host = plan.topp_counts()
     print("top-p draws answered on the device / by the host heap: %d / %d" % (dev, host))

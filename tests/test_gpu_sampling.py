@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as ge
+from test_gpu_batch_sampling import SETTINGS          # (temperature, topp) per row: greedy, categorical and top-p entries
 
 pytestmark = pytest.mark.gpu
 
@@ -82,4 +83,56 @@ def test_top_p_runs_on_the_device_and_ties_fall_back_to_the_heap(pkg, orc, planm
                 n += 1
     dev, host = plan.topp_counts()
     assert dev + host == n and dev >= 0.8 * n, (dev, host)
+    plan.freeTornadoExecutionPlan()
+
+
+def test_single_row_and_batched_entries_share_kernels_but_not_state(pkg, orc, planmod):
+    """One sampler (gl3_sample.hip), two instances of its state: gl3_forward_decode_sample (one row, 256 workgroups per element-wise
+    launch, eager) and gl3_sample_rows (3 and 6 rows, 64 workgroups per row, one hipGraph per row count: captured in rounds 0 and 1,
+    replayed in rounds 2 and 3) alternate on one plan.  After every call the ids are the oracle's and BOTH parity taps still hold the
+    probabilities of their own entry's last step, bit for bit: a call on one entry leaves the other's buffers alone.  vocab 4096 = exactly
+    one exact chunk of the sequential sums."""
+    plan_mod, hip = planmod
+    m = pkg.synth.make_numpy(pkg.synth.CONFIGS["mid-llama"], seed=61)
+    assert m.cfg.vocab == 4096
+    plan = plan_mod.HipMasterPlan(m, prefill_batch_size=16, n_seqs=2)
+    o = orc.COracle(m)
+    rows_oracle = orc.COracle(m)
+    rows = np.stack([rows_oracle.forward(100 + 37 * i, 0) for i in range(6)])
+    rng = pkg.javarand.L32X64MixRandom(1234)
+    last_single, last_rows, n_topp = None, [], 0
+
+    def check_taps(where):
+        if last_single is not None:
+            assert np.array_equal(plan.sample_probs(), last_single), where
+        for i, probs in enumerate(last_rows):
+            if probs is not None:
+                assert np.array_equal(plan.sample_probs_row(i), probs), (where, i)
+
+    tok = 1
+    for rnd, (temperature, topp) in enumerate([(0.7, 0.95), (1.0, 0.0), (0.4, 0.5), (1.3, 1.0)]):
+        coin = rng.next_float()
+        want, last_single = orc.sample(o.forward(tok, rnd), temperature, topp, coin, want_probs=True)
+        got = plan.forward_decode_sample(tok, rnd, temperature, topp, coin)
+        n_topp += 0 < topp < 1
+        assert got == want, (rnd, temperature, topp, coin)
+        check_taps(("single", rnd))
+        tok = got
+
+        n = (3, 6, 3, 6)[rnd]
+        sets = [SETTINGS[(i + 2 - rnd) % 8] for i in range(n)]          # the greedy entry (index 2) is in every call
+        coins = [rng.next_float() if s[0] > 0 else 0.0 for s in sets]
+        ids = plan.sample_rows(rows[:n], [s[0] for s in sets], [s[1] for s in sets], coins)
+        last_rows = []
+        for i, (t, p) in enumerate(sets):
+            if t > 0:
+                want, probs = orc.sample(rows[i], t, p, coins[i], want_probs=True)
+                n_topp += 0 < p < 1
+            else:
+                want, probs = orc.argmax(rows[i]), None
+            last_rows.append(probs)
+            assert ids[i] == want, (rnd, i, t, p, coins[i])
+        assert any(p is None for p in last_rows) and any(p is not None for p in last_rows)
+        check_taps(("rows", rnd))
+    assert sum(plan.topp_counts()) == n_topp
     plan.freeTornadoExecutionPlan()

@@ -596,7 +596,7 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     if (d.weight_type != GL3_TYPE_Q8_0 && d.weight_type != GL3_TYPE_F16 && d.weight_type != GL3_TYPE_Q4_0)
         return bail(GL3_E_UNSUPPORTED, "matrix weight type must be Q8_0, F16 or Q4_0");
     const bool q8v = d.weight_type == GL3_TYPE_Q8_0 && (d.flags & GL3_FLAG_F32_ACTIVATION);
-    {   // the Vector-API species (-Dllama.VectorBitSize; include/gpullama3_hip.h): 256 by default, 512 for F16 decode, the rest refused
+    {   // the Vector-API species (-Dllama.VectorBitSize; include/gpullama3_hip.h): 256 by default, 512 for F16 on one rank (decode, batched prefill, batched decode), the rest refused
         const bool species_type = d.weight_type == GL3_TYPE_F16 || d.weight_type == GL3_TYPE_Q4_0 || q8v;
         if ((d.flags & GL3_FLAG_VECTOR_512) && (d.flags & GL3_FLAG_VECTOR_128)) return bail(GL3_E_ARG, "GL3_FLAG_VECTOR_512 and GL3_FLAG_VECTOR_128 exclude each other");
         if ((d.flags & (GL3_FLAG_VECTOR_512 | GL3_FLAG_VECTOR_128)) && (d.flags & GL3_FLAG_SCALAR_DOT))
@@ -768,8 +768,9 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     // (GL3_FLAG_SCALAR_DOT) prefills token by token.
     {
         const bool int8_path = d.weight_type == GL3_TYPE_Q8_0 && !(d.flags & GL3_FLAG_F32_ACTIVATION);
-        // (the 512-bit F16 species has decode kernels only: its prefill chunks run token by token, like the scalar order)
-        const bool vl_path = !int8_path && !(d.flags & GL3_FLAG_SCALAR_DOT) && !(d.flags & GL3_FLAG_VECTOR_512);      // r4: tensor-parallel ranks too (rank-chunked activations)
+        // (the 512-bit F16 species takes the same path: its GEMM is gemm_f16_mfma_v512_kernel, everything else does not depend on the
+        // species; one rank only, refused above otherwise)
+        const bool vl_path = !int8_path && !(d.flags & GL3_FLAG_SCALAR_DOT);      // r4: tensor-parallel ranks too (rank-chunked activations)
         if (d.max_batch > 1 && (int8_path || vl_path)) TRY(gl3_prefill_alloc(ctx));
     }
     if (getenv("GL3_DEBUG_ALLOC")) {
@@ -1158,7 +1159,7 @@ int32_t gl3_forward_prefill(gl3_ctx* ctx, const int32_t* tokens, int32_t n, int3
 static int32_t check_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n) {
     if (!tokens || !seq_ids || !positions || n <= 0) GL3_FAIL(GL3_E_ARG, "bad batch arrays");
     if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
-    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, one rank in the Vector-API order)");
+    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, a Vector-API order: 256 bits, or 512 bits for F16 on one rank)");
     if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
     for (int i = 0; i < n; ++i) {
         if (tokens[i] < 0 || tokens[i] >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
@@ -1181,7 +1182,7 @@ int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, const int3
 static int32_t check_batch_sampler(gl3_ctx* ctx) {
     if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
     if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "the batched sampler reads plain [n][vocab] logits: tensor-parallel plans (rank-chunked logits) are not supported yet");
-    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, one rank in the Vector-API order)");
+    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, a Vector-API order: 256 bits, or 512 bits for F16 on one rank)");
     return GL3_OK;
 }
 

@@ -266,6 +266,8 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
                     (void*)p->X, (void*)p->XN, (void*)p->AO, (void*)p->HB, (void*)p->HB2, (void*)p->QKV, (void*)p->ATT, (void*)p->seqpos, (void*)p->amax, d.dim, d.hidden, ctx->q_dim, d.ctx);
         GL3_HIP(hipFuncSetAttribute((const void*)gemm_f16_mfma_kernel<EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * F16G_STAGE));
         GL3_HIP(hipFuncSetAttribute((const void*)gemm_f16_mfma_kernel<EPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * F16G_STAGE));
+        GL3_HIP(hipFuncSetAttribute((const void*)gemm_f16_mfma_v512_kernel<EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * F16G_STAGE));
+        GL3_HIP(hipFuncSetAttribute((const void*)gemm_f16_mfma_v512_kernel<EPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * F16G_STAGE));
         GL3_HIP(hipFuncSetAttribute((const void*)gemm_vlq_kernel<WT_Q4_0, EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * vlq_stage_floats<WT_Q4_0>() * 4));
         GL3_HIP(hipFuncSetAttribute((const void*)gemm_vlq_kernel<WT_Q4_0, EPI_RESID>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * vlq_stage_floats<WT_Q4_0>() * 4));
         GL3_HIP(hipFuncSetAttribute((const void*)gemm_vlq_kernel<WT_Q8_0, EPI_STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * vlq_stage_floats<WT_Q8_0>() * 4));
@@ -602,7 +604,10 @@ static void launch_gemm_vl(gl3_ctx* ctx, const Q8Mat& w, int ntok, const float* 
     a.nrt = (w.rows + 63) / 64;
     if (w.fmt == GL3_TYPE_F16) {
         a.ntt = (ntok + F16G_TOK - 1) / F16G_TOK;
-        hipLaunchKernelGGL((gemm_f16_mfma_kernel<EPI>), dim3(8 * ((a.nrt * a.ntt + 7) / 8)), dim3(256), 2 * F16G_STAGE, ctx->stream, a);
+        const dim3 g(8 * ((a.nrt * a.ntt + 7) / 8));
+        if (ctx->d.flags & GL3_FLAG_VECTOR_512)          // 16 accumulator lanes: the same tiles, a wavefront pair per sub-tile
+            hipLaunchKernelGGL((gemm_f16_mfma_v512_kernel<EPI>), g, dim3(512), 2 * F16G_STAGE, ctx->stream, a);
+        else hipLaunchKernelGGL((gemm_f16_mfma_kernel<EPI>), g, dim3(256), 2 * F16G_STAGE, ctx->stream, a);
     } else if (ntok > VLQ_TOK && env_flag_cached_vlq_mfma() && a.nrt * ((ntok + VQM_TOK - 1) / VQM_TOK) >= 192) {
         // enough 64 x 64 tiles to fill the chip: products on the f32 matrix cores (gemm_vlq_mfma_kernel; 8B Q4_0 pp512 2.53 k -> 3.4 k
         // tok/s).  Fewer tiles (short chunks, the 4096-row projections at 128 tokens) keep the 16-token VALU kernel; GL3_VLQ_MFMA=0: always.

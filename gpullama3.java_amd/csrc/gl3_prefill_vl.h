@@ -151,6 +151,129 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_mfma_kernel(const VlGemmArgs 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// F16 in the order of a 512-bit species (GL3_FLAG_VECTOR_512): FP16FloatTensor.vectorDot keeps 16 accumulator lanes, lane j =
+// elements j, j + 16, ....  Over the same VL bytes (matvec_vl_kernel, SPECIES = 512): the halfs k = 0..7 of VL lane l with even k
+// belong to accumulator lane l, those with odd k to lane l + 8, each in ascending element order; reduceLanes adds lanes 0..15 in
+// order.  So sixteen accumulator tiles and the same MFMAs per chunk as the 256-bit form: tile l takes (k0, k1) = halfs
+// (4 s, 4 s + 2), tile l + 8 halfs (4 s + 1, 4 s + 3), s = 0, 1, with the operands x[64 c + 8 k + l] of the same k.  Halfs 4 s + 2 kk
+// and 4 s + 2 kk + 1 are the low and the high half of word 2 s + kk of the lane's 16 bytes: one select per (l, s), no shifts.
+//
+// Register budget.  Sixteen 32 x 32 f32 tiles are 256 accumulator registers per lane.  Form chosen: EIGHT wavefronts per
+// workgroup, the same 64 x 64 tile and the same LDS stages; wavefronts w and w + 4 share a 32 x 32 sub-tile, w runs accumulator
+// lanes 0..7 (the low halfs), w + 4 lanes 8..15 (the high halfs, the x operands 8 floats further).  Each wavefront so has the
+// register shape of the 256-bit kernel (8 x 16 accumulators, <= 256 registers, two wavefronts per SIMD), and the workgroup of 512
+// threads fills the CU as two of the 256-bit kernel's workgroups do.  reduceLanes is ONE ordered sum over the 16 lanes, so in the
+// epilogue w sums its eight tiles from 0 and hands the partial sum through LDS (the stages are free by then) to w + 4, which
+// CONTINUES it with lanes 8..15 and stores: 16 floats per lane and pair, once per tile.
+// Not chosen: all sixteen tiles in one wavefront (256 AGPRs + ~70 VGPRs) means one wavefront per SIMD, and this kernel has a
+// workgroup barrier and a dependent LDS read per chunk that only a second wavefront on the SIMD covers (the 256-bit form reaches
+// 50-68 % MFMA utilisation WITH two); a narrower sub-tile does not exist for v_mfma_f32_32x32x2_f32, and the 16 x 16 x 4 form
+// would halve the reuse of every LDS operand read.  Price of this form against the 256-bit one: every wavefront still reads the
+// whole 16-byte A slot but uses half of it (twice the A bytes from LDS per MFMA), and one barrier serves half as many MFMAs.
+// Measured (profiles/f16_v512_batched.md, Llama-3.2-1B shape, 512 tokens): this kernel / the 256-bit one = 0.829 over the GEMM
+// launches of a chunk.  With one tile per CU (wo, down: 256 tiles) the two take the same time, so the A reads and the hand-over
+// are covered; with more tiles than CUs (qkv, gate, up) it is 0.74: the 256-bit form's two workgroups per CU cover each other's
+// barriers, this form's single workgroup meets at one.
+template <int EPI>
+__global__ __launch_bounds__(512, 2) void gemm_f16_mfma_v512_kernel(const VlGemmArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), wr = (wave >> 1) & 1, wc = wave & 1, hf = wave >> 2;
+    int rt, tt;
+    if (!vl_tile_of(a, rt, tt)) return;
+    const int row0 = rt * F16G_ROWS, tok0 = tt * F16G_TOK;
+    const int nch = a.k >> 6, ngroups = (a.rows + 7) >> 3;
+    const size_t gbytes = (size_t)nch * 1024;
+    // ---- global -> registers of one K stage: A = 8 row groups x 64 lanes x 16 B (1 piece per thread), B = 64 tokens x 16
+    // float4 (2 pieces per thread); rows / tokens past the end re-read the last valid one (never stored)
+    int4 ra; float4 rb[2];
+    const uint8_t* pa; const float* pb[2];
+    pa = a.w + (size_t)min(ngroups - 1, (row0 >> 3) + (t >> 6)) * gbytes + 16 * (t & 63);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int p = t + 512 * j, tk = min(a.ntok - 1, tok0 + (p >> 4));
+        pb[j] = a.X + (size_t)tk * a.x_stride + 4 * (p & 15);
+    }
+#define F16G5_GLOAD(c_) do { \
+        ra = ld16<false>(pa + (size_t)(c_) * 1024); \
+        _Pragma("unroll") for (int j = 0; j < 2; ++j) rb[j] = *reinterpret_cast<const float4*>(pb[j] + 64 * (c_)); \
+    } while (0)
+#define F16G5_LSTORE(stage_) do { \
+        uint8_t* A_ = smem + (size_t)(stage_) * F16G_STAGE; \
+        float* B_ = reinterpret_cast<float*>(A_ + F16G_A_BYTES); \
+        *reinterpret_cast<int4*>(A_ + ((size_t)(t & 7) * 65 + (t >> 6) * 8 + ((t >> 3) & 7)) * 16) = ra; \
+        _Pragma("unroll") for (int j = 0; j < 2; ++j) { \
+            const int p = t + 512 * j; \
+            *reinterpret_cast<float4*>(B_ + (p >> 4) * F16G_B_PITCH + 4 * (p & 15)) = rb[j]; \
+        } \
+    } while (0)
+    v16f_vl acc[8];                                    // accumulator lanes 8 hf + l
+#pragma unroll
+    for (int l = 0; l < 8; ++l)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[l][r] = 0.f;
+    const int mi = lane & 31, kk = lane >> 5;          // MFMA operand slot: A[row mi][k kk], B[k kk][token mi]
+    const uint32_t hsh = 16 * hf;                      // low halfs (accumulator lanes 0..7) or high halfs (8..15): wavefront-uniform
+    set_f16_denorm_flush(true);                        // v_cvt_f32_f16 flushes subnormal weights: the reference's DAZ bit trick
+    F16G5_GLOAD(0);
+    F16G5_LSTORE(0);
+    __syncthreads();
+    for (int c = 0; c < nch; ++c) {
+        F16G5_GLOAD(min(c + 1, nch - 1));              // unconditional: the last trip re-reads its own chunk
+        const uint8_t* A = smem + (size_t)(c & 1) * F16G_STAGE;
+        // x[64 c + 8 k + l] with k = 4 s + 2 kk + hf: float 32 s + 16 kk + 8 hf + l of the token's chunk
+        const float* B = reinterpret_cast<const float*>(A + F16G_A_BYTES) + (wc * 32 + mi) * F16G_B_PITCH + 16 * kk + 8 * hf;
+        int4 aw[8];
+#pragma unroll
+        for (int l = 0; l < 8; ++l) aw[l] = *reinterpret_cast<const int4*>(A + ((size_t)l * 65 + wr * 32 + mi) * 16);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {                  // chain steps 2 s (k = 0) and 2 s + 1 (k = 1) of this wavefront's accumulator lanes
+            const float4 b0 = *reinterpret_cast<const float4*>(B + 32 * s), b1 = *reinterpret_cast<const float4*>(B + 32 * s + 4);
+            const float bx[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+            for (int l = 0; l < 8; ++l) {
+                const uint32_t wd = (uint32_t)(s == 0 ? (kk ? aw[l].y : aw[l].x) : (kk ? aw[l].w : aw[l].z));      // word 2 s + kk
+                const float af = cvt_lo(wd >> hsh);
+                acc[l] = __builtin_amdgcn_mfma_f32_32x32x2f32(af, bx[l], acc[l], 0, 0, 0);
+            }
+        }
+        F16G5_LSTORE((c + 1) & 1);
+        __syncthreads();
+    }
+#undef F16G5_GLOAD
+#undef F16G5_LSTORE
+    set_f16_denorm_flush(false);
+    // ---- reduceLanes(ADD) in lane order from 0 across the wavefront pair, then the epilogue.  The last barrier of the loop
+    // freed both stages: hand[(pair * 16 + r) * 64 + lane] carries ((0 + val[0]) + ...) + val[7] from wavefront w to w + 4.
+    // C layout: token = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 kk
+    float* hand = reinterpret_cast<float*>(smem) + (size_t)(wave & 3) * 16 * 64 + lane;
+    if (hf == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = 0.f;
+#pragma unroll
+            for (int l = 0; l < 8; ++l) v = v + acc[l][r];
+            hand[r * 64] = v;
+        }
+    }
+    __syncthreads();
+    if (hf == 0) return;
+    const int b = tok0 + wc * 32 + mi;
+    if (b >= a.ntok) return;
+    float* o = a.out + (size_t)b * a.out_stride;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = row0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+        if (row >= a.rows) continue;
+        float v = hand[r * 64];
+#pragma unroll
+        for (int l = 0; l < 8; ++l) v = v + acc[l][r];
+        if (EPI == EPI_RESID) o[row] = o[row] + v * a.out_scale;
+        else o[row] = v * a.out_scale;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Q4_0 / Q8_0 with f32 activation on the VALU.  Workgroup = 4 wavefronts = 64 rows (wavefront = two 8-row VL groups, lane =
 // (row, accumulator lane l)) x 16 tokens; K advances one VL chunk per stage (Q4_0: 8 blocks, Q8_0: 4 blocks).  x of the
 // token tile is staged in LDS in the decode kernel's transposed order (xT[32 b + 4 l + q] = x[32 b + 8 q + l]: a lane's four

@@ -10,8 +10,8 @@
 //     the logits copied to the host, at positions d ..; tokens / wall seconds;
 //   * token ids java.util.Random(42).nextInt(vocab), indexed by ABSOLUTE position (:188-193); context = max(depth + tokens) + 8 (:173);
 //   * mean and sample standard deviation over the repetitions (:205-212); the five output formats :309-372 column for column.
-// Not in the reference: --ids (greedy ids of the first timed tg repetition), --scalar-dot / --f32-activation (the reference's
-// -Dllama.VectorBitSize=0 / -Dllama.quantizeActivation=false arithmetic switches).
+// Not in the reference: --ids (greedy ids of the first timed tg repetition), --scalar-dot / --f32-activation / --vector-bits 256|512
+// (the reference's -Dllama.VectorBitSize=0 / -Dllama.quantizeActivation=false / -Dllama.VectorBitSize=N arithmetic switches).
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -219,10 +219,15 @@ int main(int argc, char** argv) {
         else if (a == "--ids") o.print_ids = true;
         else if (a == "--scalar-dot") o.flags |= GL3_FLAG_SCALAR_DOT;          // -Dllama.VectorBitSize=0 (F16 / Q4_0)
         else if (a == "--f32-activation") o.flags |= GL3_FLAG_F32_ACTIVATION;  // -Dllama.quantizeActivation=false (Q8_0)
+        else if (a == "--vector-bits") {                                       // -Dllama.VectorBitSize=256|512 (512: F16 only)
+            const std::string v = val();
+            if (v == "512") o.flags |= GL3_FLAG_VECTOR_512;
+            else if (v != "256") { fprintf(stderr, "gl3_bench: --vector-bits 256|512\n"); return 2; }
+        }
         else { fprintf(stderr, "gl3_bench: unknown option %s\n", a.c_str()); return 2; }
     }
     if (models.empty()) {
-        fprintf(stderr, "usage: gl3_bench -m model.gguf [-m model2.gguf] [-p 512] [-n 128] [-pg 512,128] [-b 1] [-d 0] [-r 5] [-o md|csv|json|jsonl|sql] [-oe fmt] [--delay s] [--no-warmup]\n");
+        fprintf(stderr, "usage: gl3_bench -m model.gguf [-m model2.gguf] [-p 512] [-n 128] [-pg 512,128] [-b 1] [-d 0] [-r 5] [-o md|csv|json|jsonl|sql] [-oe fmt] [--delay s] [--no-warmup] [--scalar-dot] [--f32-activation] [--vector-bits 256|512]\n");
         return 1;
     }
     if (o.batch < 1 || o.reps < 1) { fprintf(stderr, "gl3_bench: -b and -r must be >= 1\n"); return 2; }

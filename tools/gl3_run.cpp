@@ -23,6 +23,7 @@
 //
 //   gl3_run -m model.gguf --ids 1,2,3 [--protocol llama|qwen3] [--bos ID] [-n maxTokens] [-b prefillBatch] [--start-pos P]
 //           [--temperature T] [--top-p P] [--seed S] [--rng l32x64|lcg] [--stop id,id] [--scalar-dot] [--f32-activation]
+//           [--vector-bits 256|512]
 // prints "generated: id id ..." (stdout) and the reference's metric lines (stderr).
 #include <chrono>
 #include <cstdint>
@@ -114,6 +115,11 @@ int main(int argc, char** argv) {
         else if (a == "--stop") stop = parse_ids(val());
         else if (a == "--scalar-dot") flags |= GL3_FLAG_SCALAR_DOT;
         else if (a == "--f32-activation") flags |= GL3_FLAG_F32_ACTIVATION;
+        else if (a == "--vector-bits") {                   // -Dllama.VectorBitSize: 256 (default) or 512 (F16: 16 accumulator lanes)
+            const std::string v = val();
+            if (v == "512") flags |= GL3_FLAG_VECTOR_512;
+            else if (v != "256") { fprintf(stderr, "gl3_run: --vector-bits 256|512\n"); return 2; }
+        }
         else { fprintf(stderr, "gl3_run: unknown argument %s (see the header of tools/gl3_run.cpp)\n", a.c_str()); return 2; }
     }
     if (path.empty() || prompt.empty()) { fprintf(stderr, "gl3_run: -m model.gguf and --ids a,b,c are required\n"); return 2; }

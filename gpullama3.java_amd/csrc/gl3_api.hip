@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "gl3_ctx.h"
+#include "gl3_batch_plan.h"
 #include "gl3_decode_kernels.h"
 #include "gl3_rowlane_kernels.h"
 #include "gl3_veclane_kernels.h"
@@ -1201,6 +1202,71 @@ int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tokens, con
     const float* logits; const int32_t* greedy;
     gl3_decode_batch_outputs(ctx, &logits, &greedy);
     return gl3_sample_batch_finish(ctx, logits, greedy, n, tokens_out);
+}
+
+// The checks of a mixed step, all before anything is enqueued: the arrays, the plan's capabilities, then the run structure (gl3_batch_plan.h)
+static int32_t check_mixed(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits, int32_t n,
+                           BatchPlan& bp) {
+    if (!tokens || !seq_ids || !positions || n <= 0) GL3_FAIL(GL3_E_ARG, "bad batch arrays");
+    if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
+    if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "the mixed batched step is built for one rank (tp_size == 1)");
+    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, a Vector-API order: 256 bits, or 512 bits for F16 on one rank)");
+    if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
+    for (int i = 0; i < n; ++i)
+        if (tokens[i] < 0 || tokens[i] >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
+    const char* why = batch_plan_build(seq_ids, positions, want_logits, n, ctx->n_seqs, ctx->d.ctx, ctx->d.max_batch, bp);
+    if (why) GL3_FAIL(GL3_E_ARG, why);
+    return GL3_OK;
+}
+
+int32_t gl3_forward_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits, int32_t n,
+                          float* logits_out, int32_t* argmax_out) {
+    if (!ctx) return GL3_E_ARG;
+    BatchPlan bp;
+    const int32_t r = check_mixed(ctx, tokens, seq_ids, positions, want_logits, n, bp);
+    if (r != GL3_OK) return r;
+    // every run a single row and every row wanted: a static-batched decode step, captured graph and all
+    if (bp.single_rows && (int)bp.out_rows.size() == n) {
+        const int32_t rr = gl3_decode_batch_run(ctx, tokens, seq_ids, positions, n, logits_out, argmax_out);
+        return rr != GL3_OK ? rr : gl3_prefill_tap_x(ctx, n - 1, n);      // gl3_get_x answers for the last row, as after every mixed step
+    }
+    return gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, logits_out, argmax_out);
+}
+
+int32_t gl3_forward_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits,
+                                 int32_t n, const float* temperature, const float* topp, const float* coins, int32_t* tokens_out) {
+    if (!ctx) return GL3_E_ARG;
+    BatchPlan bp;
+    int32_t r = check_mixed(ctx, tokens, seq_ids, positions, want_logits, n, bp);
+    if (r != GL3_OK) return r;
+    const int n_out = (int)bp.out_rows.size();
+    if (n_out == 0) return gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, nullptr);      // nothing to sample: a pure prefill
+    if (!temperature || !topp || !coins) GL3_FAIL(GL3_E_ARG, "null temperature / topp / coins");
+    if (!tokens_out) GL3_FAIL(GL3_E_ARG, "null tokens_out");
+    bool all_greedy = false;
+    if ((r = gl3_sample_batch_prepare(ctx, n_out, temperature, topp, coins, &all_greedy)) != GL3_OK) return r;
+    if (all_greedy) return gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, tokens_out);      // Sampler.java:79-81 for every output row
+    if ((r = gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, nullptr, false)) != GL3_OK) return r;
+    const float* logits; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits, &greedy);
+    return gl3_sample_batch_finish(ctx, logits, greedy, n_out, tokens_out);
+}
+
+int32_t gl3_debug_batch_plan(const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits, int32_t n, int32_t n_seqs, int32_t ctx_len,
+                             int32_t capacity, int32_t* runs_out, int32_t* n_runs, int32_t* tiles_out, int32_t* n_tiles, int32_t* out_rows,
+                             int32_t* n_out) {
+    if (!runs_out || !n_runs || !tiles_out || !n_tiles || !out_rows || !n_out) return GL3_E_ARG;
+    BatchPlan bp;
+    if (batch_plan_build(seq_ids, positions, want_logits, n, n_seqs, ctx_len, capacity, bp)) return GL3_E_ARG;
+    auto put = [](const std::vector<BatchSpan>& v, int32_t* out, int32_t* cnt) {
+        for (size_t i = 0; i < v.size(); ++i) { out[4 * i] = v[i].row0; out[4 * i + 1] = v[i].rows; out[4 * i + 2] = v[i].seq; out[4 * i + 3] = v[i].pos0; }
+        *cnt = (int32_t)v.size();
+    };
+    put(bp.runs, runs_out, n_runs);
+    put(bp.tiles, tiles_out, n_tiles);
+    for (size_t i = 0; i < bp.out_rows.size(); ++i) out_rows[i] = bp.out_rows[i];
+    *n_out = (int32_t)bp.out_rows.size();
+    return GL3_OK;
 }
 
 int32_t gl3_sample_rows(gl3_ctx* ctx, const float* logits, int32_t n, const float* temperature, const float* topp, const float* coins,

@@ -295,5 +295,10 @@ int32_t gl3_prefill_run(gl3_ctx* ctx, int32_t seq, const int32_t* tokens, int32_
 int32_t gl3_prefill_profile(gl3_ctx* ctx, int klass, int n, int iters, double* out_us, uint64_t* int8_ops);
 int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
                              float* logits_out, int32_t* argmax_out, bool finish = true);      // finish = false: enqueue only
+namespace gl3 { struct BatchPlan; }      // gl3_batch_plan.h
+// one mixed step (gl3_forward_batch) whose plan the caller built and checked; outputs: the plan's out_rows, compact
+int32_t gl3_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const gl3::BatchPlan& bp,
+                      float* logits_out, int32_t* argmax_out, bool finish = true);
+int32_t gl3_prefill_tap_x(gl3_ctx* ctx, int row, int n);
 void gl3_decode_batch_outputs(gl3_ctx* ctx, const float** logits, const int32_t** greedy);
 int32_t gl3_decode_batch_load_logits(gl3_ctx* ctx, const float* logits, int32_t n);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "gl3_ctx.h"
+#include "gl3_batch_plan.h"
 #include <type_traits>
 #include "gl3_decode_kernels.h"
 
@@ -52,6 +53,11 @@ struct gl3_prefill_state {
     float* SUMS = nullptr;              // [M][n_heads] softmax denominators (pf_softmax_rows_kernel -> pf_pv_tiled_kernel)
     int tmx_tiles = 0;
     int32_t* seqpos = nullptr;          // [2][M]: sequence id, position of every token of the step
+    // mixed steps (gl3_forward_batch): the attention tile table and the output rows of the step, staged with the tokens
+    int4* tiles = nullptr;              // [M] BatchSpan records, deepest tile first (gl3_batch_plan.h)
+    int step_tiles = 0;                 //   entries of the step being enqueued; 0: no run of the step has more than one row
+    int32_t* out_rows = nullptr;        // [M] rows whose logits are wanted
+    float* XG = nullptr;                // [M][dim] those rows of X, compact (allocated by the first mixed step)
     float* LOGITS = nullptr;            // [rows][vocab], grown on demand (batched decode)
     int logits_rows = 0;
     std::vector<hipGraphExec_t> step_graphs;   // static-batched decode: one captured step per batch size (positions < AF_MAXN)
@@ -258,6 +264,8 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
         GL3_HIP(hipMalloc((void**)&p->TMX, M * d.n_heads * (size_t)p->tmx_tiles * 4));
         GL3_HIP(hipMalloc((void**)&p->SUMS, M * d.n_heads * 4));
         GL3_HIP(hipMalloc((void**)&p->seqpos, 2 * M * sizeof(int32_t)));
+        GL3_HIP(hipMalloc((void**)&p->tiles, M * sizeof(int4)));
+        GL3_HIP(hipMalloc((void**)&p->out_rows, M * sizeof(int32_t)));
         GL3_HIP(hipMalloc((void**)&p->amax, M * sizeof(int32_t)));
         GL3_HIP(hipMalloc((void**)&p->amx_v, M * AMX_SPLIT * sizeof(float)));
         GL3_HIP(hipMalloc((void**)&p->amx_i, M * AMX_SPLIT * sizeof(int)));
@@ -324,6 +332,8 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     GL3_HIP(hipMalloc((void**)&p->TMX, M * d.n_heads * (size_t)p->tmx_tiles * 4));
     GL3_HIP(hipMalloc((void**)&p->SUMS, M * d.n_heads * 4));
     GL3_HIP(hipMalloc((void**)&p->seqpos, 2 * M * sizeof(int32_t)));
+    GL3_HIP(hipMalloc((void**)&p->tiles, M * sizeof(int4)));
+    GL3_HIP(hipMalloc((void**)&p->out_rows, M * sizeof(int32_t)));
     GL3_HIP(hipMalloc((void**)&p->amax, M * sizeof(int32_t)));
     GL3_HIP(hipMalloc((void**)&p->amx_v, M * AMX_SPLIT * sizeof(float)));
     GL3_HIP(hipMalloc((void**)&p->amx_i, M * AMX_SPLIT * sizeof(int)));
@@ -368,7 +378,7 @@ void gl3_prefill_free(gl3_ctx* ctx) {
     if (!p) return;
     for (auto ge : p->step_graphs) if (ge) hipGraphExecDestroy(ge);
     auto f = [](void* q) { if (q) hipFree(q); };
-    f(p->tokens); f(p->XQ); f(p->XS); f(p->XP); f(p->XQh); f(p->XPh); f(p->XQb); f(p->XSb); f(p->QKV); f(p->ATT); f(p->TMX); f(p->SUMS); f(p->seqpos); f(p->amax); f(p->amx_v); f(p->amx_i); f(p->XN); f(p->HB2);
+    f(p->tokens); f(p->XQ); f(p->XS); f(p->XP); f(p->XQh); f(p->XPh); f(p->XQb); f(p->XSb); f(p->QKV); f(p->ATT); f(p->TMX); f(p->SUMS); f(p->seqpos); f(p->tiles); f(p->out_rows); f(p->XG); f(p->amax); f(p->amx_v); f(p->amx_i); f(p->XN); f(p->HB2);
     if (!p->in_arena) { f(p->X); f(p->AO); f(p->HB); f(p->LOGITS); }
     auto& m = p->moe;
     f(m.logits); f(m.w); f(m.sel); f(m.ticket); f(m.slot_tok); f(m.slot_dst); f(m.tab); f(m.HB); f(m.Y); f(m.XQx); f(m.XSx); f(m.XQh); f(m.XSh);
@@ -393,7 +403,11 @@ static bool pf_fused_bd_attn_off() { static const bool off = env_flag("GL3_NO_FU
 // A static-batched decode step whose deepest row is at max_pos runs the one-launch attention (attn_head_kernel).  Asked by the attention
 // dispatch, by the operand hand-over behind it and by the graph capture of the step (only such a step has nothing position-dependent
 // baked in: the three-kernel attention sizes its scores grid by the deepest row), so they cannot disagree.
-static bool pf_fused_decode(const gl3_ctx* ctx, int max_pos) { return ctx->fused_attn_ok && max_pos < AF_MAXN && !pf_fused_bd_attn_off(); }
+// A mixed step with a run of several rows (step_tiles > 0) never does: attn_head_kernel writes a row's K / V in the launch that reads it, and a
+// later row of the same run would race with that write.
+static bool pf_fused_decode(const gl3_ctx* ctx, int max_pos) {
+    return ctx->fused_attn_ok && max_pos < AF_MAXN && !pf_fused_bd_attn_off() && ctx->pf->step_tiles == 0;
+}
 
 // dynamic LDS of pf_norm_quant_kernel<PQ_NORM> for rows of k elements: the row, the exact sum of squares' scratch, the result
 static size_t nq_smem(int k) { return (size_t)(k + 32) * 4 + ss_scratch_bytes(k) + 64; }
@@ -464,6 +478,9 @@ static inline void pf_kvmul_dispatch(int kvmul, F&& f) {      // pf_scores_pk_ke
 // RoPE + KV write + attention of layer l for the n tokens whose raw q | k | v rows are in p->QKV -> AOr (this rank's chunk of the
 // attention output).  fuse_q: static-batched decode on one rank writes the output as the wo projection's int8 operand instead.
 // returns true when the attention output was written as the wo projection's int8 operand (no quantise launch needed)
+// A mixed step with runs of several rows (p->step_tiles > 0, one_seq < 0): after the one RoPE + KV launch every K / V row of the step is in the
+// caches, and the step takes the run-table form of the one-launch kernels — or, when the shape has none or the deepest row's score rows do
+// not fit LDS, the per-row pair for the whole step.
 static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, float* AOr, bool fuse_q) {
     gl3_prefill_state* p = ctx->pf;
     const gl3_model_desc& d = ctx->d;
@@ -506,9 +523,17 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
     // r6: pf_softmax_rows_kernel streams the score rows (no row-fits-LDS limit); GL3_PF_SOFTMAX_ROWS=0: the one-row-per-wavefront kernel
     static const bool rows_off = getenv("GL3_PF_SOFTMAX_ROWS") && atoi(getenv("GL3_PF_SOFTMAX_ROWS")) == 0;
     const bool rows_softmax = !rows_off && d.ctx % 4 == 0 && d.ctx >= 64 && p->TMX && p->SUMS;
-    const bool tiled = one_seq >= 0 && kvmul <= 4 && (hs == 32 || hs == 64 || hs == 128) && (rows_softmax || (size_t)(max_pos + 1) * 4 <= 60 * 1024);
+    const int ntab = one_seq < 0 ? p->step_tiles : 0;      // > 0: the run-table form
+    const bool tiled = (one_seq >= 0 || ntab > 0) && kvmul <= 4 && (hs == 32 || hs == 64 || hs == 128) && (rows_softmax || (size_t)(max_pos + 1) * 4 <= 60 * 1024);
     const bool mfma_shape = kvmul == 4 && (hs == 128 || hs == 64);      // the kernels with their products on the matrix pipe
-    if (!tiled) {      // several sequences, or a shape the tiled kernels do not have: the per-token pair
+    // r4: one launch for scores + softmax + weighted V sum when a tile's score rows fit LDS (GL3_PF_FUSED_ATTN=0: the three kernels)
+    static const bool fused_off = getenv("GL3_PF_FUSED_ATTN") && atoi(getenv("GL3_PF_FUSED_ATTN")) == 0;
+    static const bool v1_only = env_flag("GL3_PF_FUSED_V1", false);
+    const int fa_sstride = ((max_pos + 1 + 63) & ~63) + 4;      // sized by the deepest row of the step
+    const bool one_launch = !fused_off && 64 * (hs / 4) <= 8 * 64 * kvmul && fa_smem_bytes(hs, kvmul, fa_sstride) <= PF_ATTN_LDS_MAX;      // 8 float4 per thread stage a tile
+    // the table form exists for pf_attn_fused3_kernel / pf_attn_fused2_kernel only: with fused2's rows fitting, one of the two is what the dispatch below picks
+    const bool tab_ok = ntab > 0 && tiled && one_launch && !v1_only && fa2_smem_bytes(hs, kvmul, fa_sstride) <= PF_ATTN_LDS_MAX;
+    if (!tiled || (ntab > 0 && !tab_ok)) {      // several sequences, or a shape / depth the tiled kernels do not have: the per-token pair
         const size_t sm1 = ((size_t)kvmul * d.head_size + (size_t)ATT_TT * (d.head_size + 1)) * 4;
         hipLaunchKernelGGL(pf_attn_scores_kernel, dim3(nsplit, KVH, n), dim3(64 * kvmul), sm1, s, aa);
         aa.win = ctx->attn_win;
@@ -516,13 +541,10 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
         return false;
     }
     const int pos0 = max_pos + 1 - n;      // one sequence: token b of the chunk sits at position pos0 + b
-    const float* kc1 = aa.kcache + (size_t)one_seq * ctx->kv_seq_stride;
-    const float* vc1 = aa.vcache + (size_t)one_seq * ctx->kv_seq_stride;
-    // r4: one launch for scores + softmax + weighted V sum when a tile's score rows fit LDS (GL3_PF_FUSED_ATTN=0: the three kernels)
-    static const bool fused_off = getenv("GL3_PF_FUSED_ATTN") && atoi(getenv("GL3_PF_FUSED_ATTN")) == 0;
-    const int fa_sstride = ((max_pos + 1 + 63) & ~63) + 4;
-    if (!fused_off && 64 * (hs / 4) <= 8 * 64 * kvmul && fa_smem_bytes(hs, kvmul, fa_sstride) <= PF_ATTN_LDS_MAX) {      // 8 float4 per thread stage a tile
-        const dim3 grid(KVH * ((n + FA_TB - 1) / FA_TB));
+    const float* kc1 = aa.kcache + (size_t)(ntab ? 0 : one_seq) * ctx->kv_seq_stride;      // table form: the tile's record names its sequence
+    const float* vc1 = aa.vcache + (size_t)(ntab ? 0 : one_seq) * ctx->kv_seq_stride;
+    if (one_launch) {
+        const dim3 grid(KVH * (ntab ? ntab : (n + FA_TB - 1) / FA_TB));
         // r6: > 64 tokens on one rank with head size 128: the output is written quantised for the wo GEMM (pf_gemm3_kernel's operand layout)
         static const bool qao_off = getenv("GL3_PF_ATTN_QOUT") && atoi(getenv("GL3_PF_ATTN_QOUT")) == 0;
         const bool qao = !qao_off && hs == 128 && pf_chunk_major(n) && d.tp_size == 1 && p->XP && !pf_fused_quant_off();
@@ -530,17 +552,23 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
         uint4* xpo = qao ? reinterpret_cast<uint4*>(p->XP) : nullptr;
         // r6: products of both phases on the matrix pipe (pf_attn_fused3_kernel); GL3_PF_FUSED_MFMA=0: the VALU kernels.  Else packed-f32 scores + pinned
         // weighted V sum (pf_attn_fused2_kernel) while its 16 KB of query rows still fit; GL3_PF_FUSED_V1=1: the r4 kernel
-        static const bool v1_only = env_flag("GL3_PF_FUSED_V1", false);
         static const bool mfma_off = getenv("GL3_PF_FUSED_MFMA") && atoi(getenv("GL3_PF_FUSED_MFMA")) == 0;
         const size_t sms = fa_smem_bytes(hs, kvmul, fa_sstride), sms2 = fa2_smem_bytes(hs, kvmul, fa_sstride), sms3 = fa3_smem_bytes(hs, fa_sstride);
+        const size_t sst = ctx->kv_seq_stride;
         if (!mfma_off && !v1_only && mfma_shape && sms3 <= PF_ATTN_LDS_MAX)
             pf_head_dispatch<64>(hs, [&](auto hc) {
-                hipLaunchKernelGGL((pf_attn_fused3_kernel<decltype(hc)::value>), grid, dim3(512), sms3, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
-                                   KVH, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok); });
+                constexpr int HS_ = decltype(hc)::value;
+                if (ntab) hipLaunchKernelGGL((pf_attn_fused3_kernel<HS_, true>), grid, dim3(512), sms3, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
+                                             KVH, aa.kv_dim, 0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, p->tiles, sst);
+                else hipLaunchKernelGGL((pf_attn_fused3_kernel<HS_>), grid, dim3(512), sms3, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
+                                        KVH, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, (const int4*)nullptr, (size_t)0); });
         else if (!v1_only && sms2 <= PF_ATTN_LDS_MAX)
             pf_head_dispatch<32>(hs, [&](auto hc) {
-                hipLaunchKernelGGL((pf_attn_fused2_kernel<decltype(hc)::value>), grid, dim3(128 * kvmul), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
-                                   KVH, kvmul, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok); });
+                constexpr int HS_ = decltype(hc)::value;
+                if (ntab) hipLaunchKernelGGL((pf_attn_fused2_kernel<HS_, true>), grid, dim3(128 * kvmul), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
+                                             KVH, kvmul, aa.kv_dim, 0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, p->tiles, sst);
+                else hipLaunchKernelGGL((pf_attn_fused2_kernel<HS_>), grid, dim3(128 * kvmul), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
+                                        KVH, kvmul, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, (const int4*)nullptr, (size_t)0); });
         else
             pf_head_dispatch<32>(hs, [&](auto hc) {
                 hipLaunchKernelGGL((pf_attn_fused_kernel<decltype(hc)::value>), grid, dim3(128 * kvmul), sms, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
@@ -957,6 +985,72 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
     if (!finish) return GL3_OK;          // the batched sampler's launches follow on the same stream (gl3_sample_batch_finish)
     GL3_HIP(hipStreamSynchronize(s));
     return gl3_tp_check(ctx);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Mixed step (gl3_forward_batch): prompt chunks and decode rows of many sequences in one pass over the weights.  The layers are pf_layers
+// over (token, sequence, position) rows as in a static-batched step; the attention takes the run-table form (pf_attention); the logits stage
+// runs over the rows the caller flagged only.  Eager: the shape of a step differs from call to call.  One rank, plain row layouts.
+static_assert(BP_TILE_ROWS == FA_TB, "the step plan cuts runs into the attention kernels' token tiles");
+static_assert(sizeof(BatchSpan) == sizeof(int4), "a tile record is read as one int4");
+
+// rows[r] of X -> row r of out (float4 per thread; dim % 4 == 0)
+static __global__ __launch_bounds__(256) void pf_gather_rows_kernel(const float* __restrict__ X, const int32_t* __restrict__ rows, int dim, float* __restrict__ out) {
+    const float4* src = reinterpret_cast<const float4*>(X + (size_t)rows[blockIdx.x] * dim);
+    float4* dst = reinterpret_cast<float4*>(out + (size_t)blockIdx.x * dim);
+    for (int i = threadIdx.x; i < (dim >> 2); i += 256) dst[i] = src[i];
+}
+
+// x of row `row` of the n-row step the stream just ran -> the decode path's ctx->x (parity tap gl3_get_x), waited for
+int32_t gl3_prefill_tap_x(gl3_ctx* ctx, int row, int n) {
+    hipLaunchKernelGGL(pf_unchunk_row_kernel, dim3(4), dim3(256), 0, ctx->stream, ctx->pf->X, row, ctx->d.dim, ctx->dim_l, n, ctx->x);
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
+    return GL3_OK;
+}
+
+int32_t gl3_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const BatchPlan& bp,
+                      float* logits_out, int32_t* argmax_out, bool finish) {
+    gl3_prefill_state* p = ctx->pf;
+    const gl3_model_desc& d = ctx->d;
+    const int n_out = (int)bp.out_rows.size();
+    GL3_HIP(hipSetDevice(d.device));
+    if (n_out) {
+        const int32_t r0 = pf_grow_logits(ctx, n_out);
+        if (r0 != GL3_OK) return r0;
+        if (!p->XG) GL3_HIP(hipMalloc((void**)&p->XG, (size_t)p->max_batch * d.dim * 4));
+    }
+    hipStream_t s = ctx->stream;
+    int32_t r = pf_stage_tokens(ctx, tokens, seq_ids, positions, n);
+    if (r != GL3_OK) return r;
+    const int ntab = bp.single_rows ? 0 : (int)bp.tiles.size();
+    if (ntab) GL3_HIP(hipMemcpyAsync(p->tiles, bp.tiles.data(), (size_t)ntab * sizeof(BatchSpan), hipMemcpyHostToDevice, s));
+    if (n_out) GL3_HIP(hipMemcpyAsync(p->out_rows, bp.out_rows.data(), (size_t)n_out * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    p->step_tiles = ntab;
+    r = pf_layers(ctx, n, bp.max_pos, -1);
+    p->step_tiles = 0;
+    if (r != GL3_OK) return r;
+    // keep the decode path's x in step with the last row (parity tap gl3_get_x)
+    hipLaunchKernelGGL(pf_unchunk_row_kernel, dim3(4), dim3(256), 0, s, p->X, n - 1, d.dim, ctx->dim_l, n, ctx->x);
+    if (n_out) {      // output RMSNorm + vocabulary projection + greedy ids of the flagged rows, compact
+        hipLaunchKernelGGL(pf_gather_rows_kernel, dim3(n_out), dim3(256), 0, s, p->X, p->out_rows, d.dim, p->XG);
+        const size_t nq = nq_smem(d.dim);
+        if (p->vl) {
+            hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM_F32>), dim3(n_out), dim3(256), nq, s, p->XG, d.dim, d.dim, ctx->out_norm, d.rms_eps, (uint8_t*)nullptr, p->XN, 0, 0);
+            launch_gemm_vl<EPI_STORE>(ctx, ctx->wcls, n_out, p->XN, d.dim, p->LOGITS, d.vocab, ctx->logit_scale);
+        } else {
+            hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n_out), dim3(256), nq, s, p->XG, d.dim, d.dim, ctx->out_norm, d.rms_eps, p->XQ, p->XS, p->maxk,
+                               bd_tslots(n_out), (uint2*)p->XP, p->xp_tok);
+            launch_gemm<EPI_STORE>(ctx, ctx->wcls, nullptr, n_out, p->LOGITS, d.vocab, ctx->logit_scale);
+        }
+        hipLaunchKernelGGL(pf_argmax_part_kernel, dim3(AMX_SPLIT, n_out), dim3(256), 0, s, p->LOGITS, d.vocab, d.vocab, p->amx_v, p->amx_i);
+        hipLaunchKernelGGL(pf_argmax_fold_kernel, dim3(n_out), dim3(64), 0, s, p->amx_v, p->amx_i, p->amax);
+        if (argmax_out) GL3_HIP(hipMemcpyAsync(argmax_out, p->amax, (size_t)n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (logits_out) GL3_HIP(hipMemcpyAsync(logits_out, p->LOGITS, (size_t)n_out * d.vocab * 4, hipMemcpyDeviceToHost, s));
+    }
+    GL3_HIP(hipGetLastError());
+    if (!finish) return GL3_OK;          // the batched sampler's launches follow on the same stream (gl3_sample_batch_finish)
+    GL3_HIP(hipStreamSynchronize(s));
+    return GL3_OK;
 }
 
 

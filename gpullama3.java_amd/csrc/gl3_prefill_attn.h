@@ -670,6 +670,28 @@ constexpr int FA_TB = 8;
 __host__ __device__ constexpr size_t fa_smem_bytes(int hs, int kvmul, int sstride) {
     return ((size_t)kvmul * FA_TB * sstride + 2 * 64 * (hs + 4) + 64) * 4;
 }
+// The (kv head, token tile) of a workgroup of the one-launch kernels.  One sequence (TAB = false): tiles of FA_TB rows of the chunk, dealt
+// heaviest first from blockIdx and (pos0, ntok).  Run-table form (TAB = true, a mixed step of gl3_forward_batch): blockIdx / n_kv_heads picks a
+// record {first row, rows, sequence, position of the first row} of the step's tile table (gl3_batch_plan.h, already ordered deepest first);
+// the caches move to the record's sequence and pos0 becomes position - row, so that everything behind this prologue — "row b of the step sits
+// at position pos0 + b" — is the one-sequence code unchanged.  The record's address depends on blockIdx alone: it arrives by a scalar load
+// and the four values are wavefront-uniform (SGPRs), like the arithmetic on blockIdx they replace.
+struct FaTile { int kvh, b0, nb, pos0; size_t cache_off; };      // cache_off: floats from the caches' base to the tile's sequence
+template <bool TAB>
+__device__ __forceinline__ FaTile fa_tile(int n_kv_heads, int pos0, int ntok, const int4* __restrict__ tab, size_t seq_stride) {
+    FaTile r;
+    r.kvh = blockIdx.x % n_kv_heads;
+    if constexpr (TAB) {
+        const int4 rec = tab[blockIdx.x / n_kv_heads];
+        r.b0 = __builtin_amdgcn_readfirstlane(rec.x); r.nb = __builtin_amdgcn_readfirstlane(rec.y);
+        r.cache_off = (size_t)__builtin_amdgcn_readfirstlane(rec.z) * seq_stride;
+        r.pos0 = __builtin_amdgcn_readfirstlane(rec.w) - r.b0;
+    } else {
+        const int ntile = (ntok + FA_TB - 1) / FA_TB, tile = ntile - 1 - blockIdx.x / n_kv_heads;
+        r.b0 = tile * FA_TB; r.nb = min(FA_TB, ntok - r.b0); r.pos0 = pos0; r.cache_off = 0;
+    }
+    return r;
+}
 // ---- pieces the three one-launch kernels share
 // K / V tile staging: a 64-row tile travels global -> registers -> LDS, the next tile's loads in flight while the current one is consumed (clamped
 // rows: every address is inside the cache, the surplus rows are never read).  8 float4 per thread cover a tile (host check).  The registers are the
@@ -930,11 +952,12 @@ __global__ __launch_bounds__(512) void pf_attn_fused_kernel(const float* __restr
 // on packed f32, reads of the next 8 steps pinned under the current group) and pf_pv_ring_kernel (phase 3: masking by zero weights, the next
 // timestep group's LDS reads pinned under the current group's arithmetic).  Same arithmetic in the same order; 16 KB more LDS (query rows).
 __host__ __device__ constexpr size_t fa2_smem_bytes(int hs, int kvmul, int sstride) { return fa_smem_bytes(hs, kvmul, sstride) + (size_t)kvmul * FA_TB * hs * 4; }
-template <int HS>
+template <int HS, bool TAB = false>
 __global__ __launch_bounds__(512) void pf_attn_fused2_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc, const float* __restrict__ vc,
                                                             float* __restrict__ out, int out_stride, int n_kv_heads, int kvmul, int kv_dim,
                                                             int pos0, int ntok, float att_mul, int sstride,
-                                                            uint8_t* __restrict__ xq_out = nullptr, uint4* __restrict__ xp_out = nullptr, int xp_tok = 0) {
+                                                            uint8_t* __restrict__ xq_out = nullptr, uint4* __restrict__ xp_out = nullptr, int xp_tok = 0,
+                                                            const int4* __restrict__ tab = nullptr, size_t seq_stride = 0) {
     extern __shared__ __attribute__((aligned(16))) float fa_sm[];
     constexpr int PITCH = HS + 4, H4 = HS / 4, NCOL = HS > 64 ? 2 : 1;
     float* Ssc = fa_sm;                                             // [kvmul][FA_TB][sstride] score -> softmax rows
@@ -944,9 +967,10 @@ __global__ __launch_bounds__(512) void pf_attn_fused2_kernel(const float* __rest
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int nthr = blockDim.x, gthreads = 64 * kvmul;
     const int grp = wave / kvmul, hq = wave % kvmul, gt = t - grp * gthreads;
-    const int ntile = (ntok + FA_TB - 1) / FA_TB;
-    const int kvh = blockIdx.x % n_kv_heads, tile = ntile - 1 - blockIdx.x / n_kv_heads;
-    const int b0 = tile * FA_TB, nb = min(FA_TB, ntok - b0), tmax = pos0 + b0 + nb - 1;
+    const FaTile ft = fa_tile<TAB>(n_kv_heads, pos0, ntok, tab, seq_stride);
+    const int kvh = ft.kvh, b0 = ft.b0, nb = ft.nb;
+    pos0 = ft.pos0; kc += ft.cache_off; vc += ft.cache_off;      // of the tile's sequence from here on
+    const int tmax = pos0 + b0 + nb - 1;
     const int head = kvh * kvmul + hq;
     const float sqrt_hs = (float)sqrt((double)HS);
 
@@ -1044,7 +1068,7 @@ __global__ __launch_bounds__(512) void pf_attn_fused2_kernel(const float* __rest
     }
 #ifdef FA_TIMING
     fa_t3 = __builtin_readcyclecounter();
-    if (lane == 0 && kvh == 0 && (tile % 9) == 0) printf("fa tile %d wave %d: scores %llu softmax %llu pv %llu\n", tile, wave, fa_t1 - fa_t0, fa_t2 - fa_t1, fa_t3 - fa_t2);
+    if (lane == 0 && kvh == 0 && (b0 % 72) == 0) printf("fa tile %d wave %d: scores %llu softmax %llu pv %llu\n", b0 / FA_TB, wave, fa_t1 - fa_t0, fa_t2 - fa_t1, fa_t3 - fa_t2);
 #endif
     FA_STORE_ROWS4();
 }
@@ -1121,11 +1145,12 @@ __host__ __device__ constexpr size_t fa3_smem_bytes(int hs, int sstride) {
                 F3_LDV(g + 3, wb, vb8); __builtin_amdgcn_sched_barrier(0); \
             } \
             if (g < ngr_) F3_PV8(wa, va); } while (0)
-template <int HS>
+template <int HS, bool TAB = false>
 __global__ __launch_bounds__(512) void pf_attn_fused3_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc, const float* __restrict__ vc,
                                                              float* __restrict__ out, int out_stride, int n_kv_heads, int kv_dim,
                                                              int pos0, int ntok, float att_mul, int sstride,
-                                                             uint8_t* __restrict__ xq_out, uint4* __restrict__ xp_out, int xp_tok) {
+                                                             uint8_t* __restrict__ xq_out, uint4* __restrict__ xp_out, int xp_tok,
+                                                             const int4* __restrict__ tab = nullptr, size_t seq_stride = 0) {
     extern __shared__ __attribute__((aligned(16))) float fa_sm[];
     constexpr int KVM = 4, ROWS = KVM * FA_TB, PITCH = HS + 4, H4 = HS / 4, QP = HS + 2, NM = HS / 2, kvmul = KVM;
     static_assert(ROWS == 32 && NM % 16 == 0, "two row groups of 16; operand ring of 8 MFMAs");
@@ -1137,9 +1162,10 @@ __global__ __launch_bounds__(512) void pf_attn_fused3_kernel(const float* __rest
     constexpr int nthr = 512, gthreads = 256;
     const int grp = wave >> 2, wg = wave & 3, gt = t - grp * gthreads;
     const int lq = lane >> 4, li = lane & 15, par = lq >> 1;        // MFMA block of this lane's operands, index inside it, step parity of the block
-    const int ntile = (ntok + FA_TB - 1) / FA_TB;
-    const int kvh = blockIdx.x % n_kv_heads, tile = ntile - 1 - blockIdx.x / n_kv_heads;
-    const int b0 = tile * FA_TB, nb = min(FA_TB, ntok - b0), tmax = pos0 + b0 + nb - 1;
+    const FaTile ft = fa_tile<TAB>(n_kv_heads, pos0, ntok, tab, seq_stride);
+    const int kvh = ft.kvh, b0 = ft.b0, nb = ft.nb;
+    pos0 = ft.pos0; kc += ft.cache_off; vc += ft.cache_off;      // of the tile's sequence from here on
+    const int tmax = pos0 + b0 + nb - 1;
     const float sqrt_hs = (float)sqrt((double)HS);
     const v16f_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const int nkt = tmax / 64 + 1;
@@ -1222,7 +1248,7 @@ __global__ __launch_bounds__(512) void pf_attn_fused3_kernel(const float* __rest
     }
 #ifdef FA_TIMING
     fa_t3 = __builtin_readcyclecounter();
-    if (lane == 0 && kvh == 0 && (tile % 9) == 0) printf("fa tile %d wave %d: scores %llu softmax %llu pv %llu\n", tile, wave, fa_t1 - fa_t0, fa_t2 - fa_t1, fa_t3 - fa_t2);
+    if (lane == 0 && kvh == 0 && (b0 % 72) == 0) printf("fa tile %d wave %d: scores %llu softmax %llu pv %llu\n", b0 / FA_TB, wave, fa_t1 - fa_t0, fa_t2 - fa_t1, fa_t3 - fa_t2);
 #endif
     if (!pv_live) return;
     const float av[2][4] = {{ac[0], ac[1], ac[2], ac[3]}, {ac[4], ac[5], ac[6], ac[7]}};
@@ -1415,6 +1441,9 @@ static int32_t pf_attention_attributes(gl3_ctx* ctx) {
     GL3_ATTR150(pf_attn_fused_kernel<128>); GL3_ATTR150(pf_attn_fused_kernel<64>); GL3_ATTR150(pf_attn_fused_kernel<32>);
     GL3_ATTR150(pf_attn_fused2_kernel<128>); GL3_ATTR150(pf_attn_fused2_kernel<64>); GL3_ATTR150(pf_attn_fused2_kernel<32>);
     GL3_ATTR150(pf_attn_fused3_kernel<128>); GL3_ATTR150(pf_attn_fused3_kernel<64>);
+    // the run-table forms (mixed steps, gl3_forward_batch)
+    GL3_ATTR150((pf_attn_fused2_kernel<128, true>)); GL3_ATTR150((pf_attn_fused2_kernel<64, true>)); GL3_ATTR150((pf_attn_fused2_kernel<32, true>));
+    GL3_ATTR150((pf_attn_fused3_kernel<128, true>)); GL3_ATTR150((pf_attn_fused3_kernel<64, true>));
     GL3_ATTR150(pf_scores_mfma_kernel<128>); GL3_ATTR150(pf_scores_mfma_kernel<64>); GL3_ATTR150(pf_pv_mfma_kernel<128>); GL3_ATTR150(pf_pv_mfma_kernel<64>);
     GL3_ATTR150((pf_scores_pk_kernel<128, 4>)); GL3_ATTR150((pf_scores_pk_kernel<128, 2>)); GL3_ATTR150((pf_scores_pk_kernel<128, 1>));
     GL3_ATTR150((pf_scores_pk_kernel<64, 4>)); GL3_ATTR150((pf_scores_pk_kernel<64, 2>)); GL3_ATTR150((pf_scores_pk_kernel<64, 1>));

@@ -197,6 +197,39 @@ class HipMasterPlan:
         hip.check(hip.lib().gl3_forward_decode_batch_sample(self._ctx, _p(t), _p(s), _p(p), n, _p(te), _p(tp), _p(co), _p(ids)), self._ctx)
         return ids
 
+    def _mixed_args(self, tokens, seq_ids, positions, want_logits):
+        """The arrays of a mixed step and its number of output rows (want_logits None: the last row of every run)."""
+        t = np.ascontiguousarray(tokens, np.int32); s = np.ascontiguousarray(seq_ids, np.int32); p = np.ascontiguousarray(positions, np.int32)
+        assert t.size == s.size == p.size
+        if want_logits is None:
+            w, n_out = None, (int(np.count_nonzero(s[1:] != s[:-1])) + 1 if s.size else 0)
+        else:
+            w = np.ascontiguousarray(np.asarray(want_logits) != 0, np.int8)
+            assert w.size == t.size
+            n_out = int(np.count_nonzero(w))
+        return t, s, p, w, n_out
+
+    def forward_batch(self, tokens, seq_ids, positions, want_logits=None, logits: bool = True):
+        """Mixed batched step (gl3_forward_batch): rows = runs of consecutive rows of one sequence at consecutive positions, a run of one
+        row is a decode row, a longer one a prompt chunk -> (logits [n_out][vocab] or None, greedy ids [n_out]) of the rows flagged in
+        want_logits (None: the last row of every run).  logits=False skips the logits copy."""
+        t, s, p, w, n_out = self._mixed_args(tokens, seq_ids, positions, want_logits)
+        lg = np.empty((n_out, self.cfg.vocab), np.float32) if logits and n_out else None
+        ids = np.empty(n_out, np.int32)
+        hip.check(hip.lib().gl3_forward_batch(self._ctx, _p(t), _p(s), _p(p), _p(w) if w is not None else None, t.size,
+                                              _p(lg) if lg is not None else None, _p(ids) if n_out else None), self._ctx)
+        return lg, ids
+
+    def forward_batch_sample(self, tokens, seq_ids, positions, temperature, topp, coins, want_logits=None) -> np.ndarray:
+        """Mixed batched step + the reference's sampler for every OUTPUT row on the device -> sampled ids [n_out].  temperature / topp /
+        coins: one entry per output row (scalars broadcast), as in forward_decode_batch_sample."""
+        t, s, p, w, n_out = self._mixed_args(tokens, seq_ids, positions, want_logits)
+        te, tp, co = self._per_row(temperature, n_out), self._per_row(topp, n_out), self._per_row(coins, n_out)
+        ids = np.empty(n_out, np.int32)
+        hip.check(hip.lib().gl3_forward_batch_sample(self._ctx, _p(t), _p(s), _p(p), _p(w) if w is not None else None, t.size,
+                                                     _p(te), _p(tp), _p(co), _p(ids)), self._ctx)
+        return ids
+
     def sample_rows(self, logits, temperature, topp, coins) -> np.ndarray:
         """The batched sampler alone on host logits [n][vocab] (no forward pass) -> sampled ids [n]."""
         lg = np.ascontiguousarray(logits, np.float32)

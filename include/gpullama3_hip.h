@@ -279,6 +279,34 @@ GL3_API int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, co
 GL3_API int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids,
                                                 const int32_t* positions, int32_t n, const float* temperature,
                                                 const float* topp, const float* coins, int32_t* tokens_out);
+/* Mixed batched step: prompt chunks and decode rows of many sequences in one pass over the weights (continuous batching, speculative
+ * verification, perplexity).  The n rows are a list of RUNS: a run is a maximal stretch of consecutive rows with the same seq_ids[i], at
+ * consecutive ascending positions; a sequence id belongs to at most one run.  A run of one row is a decode row, a longer run a prompt
+ * chunk that may start at any position.  A row sees its sequence's KV rows below its position — as earlier calls left them or as earlier
+ * rows of its run write them in this step — plus its own, so its result is what gl3_forward_prefill_seq / gl3_forward_decode_batch give
+ * for that token and position.  Output rows: the rows with want_logits[i] != 0, in row order (want_logits == NULL: the last row of every
+ * run); logits_out: f32[n_out][vocab] or NULL, argmax_out: int32[n_out] or NULL.  n_out == 0 is a pure multi-sequence prefill (no output
+ * norm, vocabulary projection or argmax is launched).  Afterwards gl3_get_x returns x of the last row and gl3_get_buffer(4..6) hold all n
+ * rows in step order.  The step runs eagerly (its shape differs from call to call); a step whose runs are all single rows and whose rows
+ * all want logits is a gl3_forward_decode_batch step.  GL3_E_ARG, before anything is enqueued: null arrays, n <= 0, n > max_batch, a
+ * token / sequence / position out of range or a run ending past ctx, a sequence id in two runs, positions inside a run that are not
+ * consecutive ascending.  GL3_E_UNSUPPORTED: max_batch <= 1; tp_size > 1 — the mixed step is built for ONE rank. */
+GL3_API int32_t gl3_forward_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
+                                  const int8_t* want_logits, int32_t n, float* logits_out, int32_t* argmax_out);
+/* The same step + the sampler of gl3_forward_decode_batch_sample over the output rows: temperature / topp / coins / tokens_out have one
+ * entry per OUTPUT row (n_out > 0 with any of them NULL: GL3_E_ARG).  gl3_get_sample_probs_row (row = output row) and gl3_get_topp_counts
+ * answer for it. */
+GL3_API int32_t gl3_forward_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
+                                         const int8_t* want_logits, int32_t n, const float* temperature, const float* topp,
+                                         const float* coins, int32_t* tokens_out);
+/* Test hook, no plan and no device: the host-side plan of a mixed step (csrc/gl3_batch_plan.h) for a plan with n_seqs sequence slots,
+ * context length ctx and room for `capacity` rows.  runs_out / tiles_out: int32[.][4] = {first row, rows, sequence, position of the
+ * first row}, room for n records each (tiles: at most 8 rows, never across a run boundary, deepest last position first); out_rows:
+ * int32[n].  GL3_E_ARG for what gl3_forward_batch refuses about (seq_ids, positions, n). */
+GL3_API int32_t gl3_debug_batch_plan(const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits, int32_t n,
+                                     int32_t n_seqs, int32_t ctx, int32_t capacity, int32_t* runs_out, int32_t* n_runs,
+                                     int32_t* tiles_out, int32_t* n_tiles, int32_t* out_rows, int32_t* n_out);
+
 /* Parity tap: the probabilities (f32[vocab]) row `row` of the last batched sampled step (or gl3_sample_rows call) was drawn from
  * (GL3_E_STATE for a greedy row or before any such step). */
 GL3_API int32_t gl3_get_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);

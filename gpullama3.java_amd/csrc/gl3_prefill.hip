@@ -54,8 +54,7 @@ struct gl3_prefill_state {
     int tmx_tiles = 0;
     int32_t* seqpos = nullptr;          // [2][M]: sequence id, position of every token of the step
     // mixed steps (gl3_forward_batch): the attention tile table and the output rows of the step, staged with the tokens
-    int4* tiles = nullptr;              // [M] BatchSpan records, deepest tile first (gl3_batch_plan.h)
-    int step_tiles = 0;                 //   entries of the step being enqueued; 0: no run of the step has more than one row
+    int4* tiles = nullptr;              // [M] BatchSpan records, deepest tile first (gl3_batch_plan.h); PfStep::ntab of them belong to the step
     int32_t* out_rows = nullptr;        // [M] rows whose logits are wanted
     float* XG = nullptr;                // [M][dim] those rows of X, compact (allocated by the first mixed step)
     float* LOGITS = nullptr;            // [rows][vocab], grown on demand (batched decode)
@@ -242,33 +241,37 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     p->max_batch = d.max_batch;
     const size_t M = d.max_batch;
     p->vl = ctx->emb.vl;
-    if (p->vl) {       // f32-activation weight types: f32 buffers; the gathered ones (X, AO, HB, LOGITS) in the arena under tensor parallelism
-        GL3_HIP(hipMalloc((void**)&p->tokens, M * sizeof(int32_t)));
-        if (ctx->arena.base && ctx->arena.off[GB_PF_X]) {
-            uint8_t* b = ctx->arena.base;
-            p->X = (float*)(b + ctx->arena.off[GB_PF_X]); p->AO = (float*)(b + ctx->arena.off[GB_PF_AO]); p->HB = (float*)(b + ctx->arena.off[GB_PF_HB]);
-            p->LOGITS = (float*)(b + ctx->arena.off[GB_PF_LOGITS]); p->logits_rows = ctx->arena.pf_logits_rows;
-            p->in_arena = true;
-        } else {
-            GL3_HIP(hipMalloc((void**)&p->X, M * d.dim * 4));
-            GL3_HIP(hipMalloc((void**)&p->AO, M * ctx->q_dim * 4));
-            GL3_HIP(hipMalloc((void**)&p->HB, M * d.hidden * 4));
-        }
+    // every weight class: tokens, the f32 activations (the gathered ones in the arena the peers map under tensor parallelism), attention, greedy scan
+    GL3_HIP(hipMalloc((void**)&p->tokens, M * sizeof(int32_t)));
+    if (ctx->arena.base && ctx->arena.off[GB_PF_X]) {
+        uint8_t* b = ctx->arena.base;
+        p->X = (float*)(b + ctx->arena.off[GB_PF_X]); p->AO = (float*)(b + ctx->arena.off[GB_PF_AO]); p->HB = (float*)(b + ctx->arena.off[GB_PF_HB]);
+        p->LOGITS = (float*)(b + ctx->arena.off[GB_PF_LOGITS]); p->logits_rows = ctx->arena.pf_logits_rows;
+        p->in_arena = true;
+    } else {
+        GL3_HIP(hipMalloc((void**)&p->X, M * d.dim * 4));
+        GL3_HIP(hipMalloc((void**)&p->AO, M * ctx->q_dim * 4));
+        GL3_HIP(hipMalloc((void**)&p->HB, M * d.hidden * 4));
+    }
+    GL3_HIP(hipMalloc((void**)&p->QKV, M * (ctx->q_dim + 2 * ctx->kv_dim) * 4));
+    GL3_HIP(hipMalloc((void**)&p->ATT, M * d.n_heads * (size_t)d.ctx * 4));
+    p->tmx_tiles = (d.ctx + 63) / 64;
+    GL3_HIP(hipMalloc((void**)&p->TMX, M * d.n_heads * (size_t)p->tmx_tiles * 4));
+    GL3_HIP(hipMalloc((void**)&p->SUMS, M * d.n_heads * 4));
+    GL3_HIP(hipMalloc((void**)&p->seqpos, 2 * M * sizeof(int32_t)));
+    GL3_HIP(hipMalloc((void**)&p->tiles, M * sizeof(int4)));
+    GL3_HIP(hipMalloc((void**)&p->out_rows, M * sizeof(int32_t)));
+    GL3_HIP(hipMalloc((void**)&p->amax, M * sizeof(int32_t)));
+    GL3_HIP(hipMalloc((void**)&p->amx_v, M * AMX_SPLIT * sizeof(float)));
+    GL3_HIP(hipMalloc((void**)&p->amx_i, M * AMX_SPLIT * sizeof(int)));
+    GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    { const int32_t ar = pf_attention_attributes(ctx); if (ar != GL3_OK) return ar; }
+    if (p->vl) {       // f32-activation weight types: the GEMMs read f32 rows, no int8 operands
         // XN: normalised / un-chunked f32 operand of the next GEMM (K up to max(dim, q_dim, hidden)); HB2: this rank's up projection
         const size_t kmax = (size_t)(d.hidden > ctx->q_dim ? (d.hidden > d.dim ? d.hidden : d.dim) : (ctx->q_dim > d.dim ? ctx->q_dim : d.dim));
         GL3_HIP(hipMalloc((void**)&p->XN, M * kmax * 4));
         GL3_HIP(hipMalloc((void**)&p->HB2, M * ctx->hidden_l * 4));
-        GL3_HIP(hipMalloc((void**)&p->QKV, M * (ctx->q_dim + 2 * ctx->kv_dim) * 4));
-        GL3_HIP(hipMalloc((void**)&p->ATT, M * d.n_heads * (size_t)d.ctx * 4));
-        p->tmx_tiles = (d.ctx + 63) / 64;
-        GL3_HIP(hipMalloc((void**)&p->TMX, M * d.n_heads * (size_t)p->tmx_tiles * 4));
-        GL3_HIP(hipMalloc((void**)&p->SUMS, M * d.n_heads * 4));
-        GL3_HIP(hipMalloc((void**)&p->seqpos, 2 * M * sizeof(int32_t)));
-        GL3_HIP(hipMalloc((void**)&p->tiles, M * sizeof(int4)));
-        GL3_HIP(hipMalloc((void**)&p->out_rows, M * sizeof(int32_t)));
-        GL3_HIP(hipMalloc((void**)&p->amax, M * sizeof(int32_t)));
-        GL3_HIP(hipMalloc((void**)&p->amx_v, M * AMX_SPLIT * sizeof(float)));
-        GL3_HIP(hipMalloc((void**)&p->amx_i, M * AMX_SPLIT * sizeof(int)));
         if (getenv("GL3_DEBUG_ALLOC"))
             fprintf(stderr, "[gl3 alloc vl] M %zu tokens %p X %p XN %p AO %p HB %p HB2 %p QKV %p ATT %p seqpos %p amax %p (dim %d hidden %d qdim %d ctx %d)\n", M, (void*)p->tokens,
                     (void*)p->X, (void*)p->XN, (void*)p->AO, (void*)p->HB, (void*)p->HB2, (void*)p->QKV, (void*)p->ATT, (void*)p->seqpos, (void*)p->amax, d.dim, d.hidden, ctx->q_dim, d.ctx);
@@ -284,25 +287,11 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
         GL3_VQM_ATTR(WT_Q4_0, EPI_STORE, 2); GL3_VQM_ATTR(WT_Q4_0, EPI_RESID, 2); GL3_VQM_ATTR(WT_Q4_0, EPI_STORE, 4); GL3_VQM_ATTR(WT_Q4_0, EPI_RESID, 4);
         GL3_VQM_ATTR(WT_Q8_0, EPI_STORE, 2); GL3_VQM_ATTR(WT_Q8_0, EPI_RESID, 2); GL3_VQM_ATTR(WT_Q8_0, EPI_STORE, 4); GL3_VQM_ATTR(WT_Q8_0, EPI_RESID, 4);
 #undef GL3_VQM_ATTR
-        GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    { const int32_t ar = pf_attention_attributes(ctx); if (ar != GL3_OK) return ar; }
         return GL3_OK;
     }
     p->maxk = d.hidden > ctx->q_dim ? d.hidden : ctx->q_dim;
     if (d.dim > p->maxk) p->maxk = d.dim;
     p->maxk = (p->maxk + 127) & ~127;
-    GL3_HIP(hipMalloc((void**)&p->tokens, M * sizeof(int32_t)));
-    if (ctx->arena.base && ctx->arena.off[GB_PF_X]) {      // tensor parallel: the gathered activations live in the arena the peers map
-        uint8_t* b = ctx->arena.base;
-        p->X = (float*)(b + ctx->arena.off[GB_PF_X]); p->AO = (float*)(b + ctx->arena.off[GB_PF_AO]); p->HB = (float*)(b + ctx->arena.off[GB_PF_HB]);
-        p->LOGITS = (float*)(b + ctx->arena.off[GB_PF_LOGITS]); p->logits_rows = ctx->arena.pf_logits_rows;
-        p->in_arena = true;
-    } else {
-        GL3_HIP(hipMalloc((void**)&p->X, M * d.dim * 4));
-        GL3_HIP(hipMalloc((void**)&p->AO, M * ctx->q_dim * 4));
-        GL3_HIP(hipMalloc((void**)&p->HB, M * d.hidden * 4));
-    }
     const size_t MQ = M < BD_TS_MAX ? BD_TS_MAX : M;      // the small-batch operand layout (bd_tslots) always spans its 32 / 64 token slots
     const size_t MQP = (MQ + 127) & ~(size_t)127;      // token slots of the chunk-major layouts (whole 128-token GEMM tiles)
     // pf_gemm3_kernel's LDS-DMA reads whole K stages: both chunk-major operands carry four blocks (one stage) beyond maxk, zeroed once here
@@ -326,21 +315,7 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     GL3_HIP(hipMemsetAsync(p->XSb, 0, (size_t)BD_TS_MAX * (p->maxk / 32) * 4, ctx->stream));
     GL3_HIP(hipMemsetAsync(p->XQ, 0, xq_bytes, ctx->stream));
     GL3_HIP(hipMemsetAsync(p->XS, 0, xs_bytes, ctx->stream));
-    GL3_HIP(hipMalloc((void**)&p->QKV, M * (ctx->q_dim + 2 * ctx->kv_dim) * 4));
-    GL3_HIP(hipMalloc((void**)&p->ATT, M * d.n_heads * (size_t)d.ctx * 4));
-    p->tmx_tiles = (d.ctx + 63) / 64;
-    GL3_HIP(hipMalloc((void**)&p->TMX, M * d.n_heads * (size_t)p->tmx_tiles * 4));
-    GL3_HIP(hipMalloc((void**)&p->SUMS, M * d.n_heads * 4));
-    GL3_HIP(hipMalloc((void**)&p->seqpos, 2 * M * sizeof(int32_t)));
-    GL3_HIP(hipMalloc((void**)&p->tiles, M * sizeof(int4)));
-    GL3_HIP(hipMalloc((void**)&p->out_rows, M * sizeof(int32_t)));
-    GL3_HIP(hipMalloc((void**)&p->amax, M * sizeof(int32_t)));
-    GL3_HIP(hipMalloc((void**)&p->amx_v, M * AMX_SPLIT * sizeof(float)));
-    GL3_HIP(hipMalloc((void**)&p->amx_i, M * AMX_SPLIT * sizeof(int)));
     GL3_HIP(gl3_gemm3_allow_lds());
-    GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    { const int32_t ar = pf_attention_attributes(ctx); if (ar != GL3_OK) return ar; }
     if (d.arch == GL3_ARCH_QWEN2MOE) {
         auto& m = p->moe;
         const size_t E = d.n_experts, K = d.n_experts_used, S = M * K;
@@ -395,22 +370,47 @@ static int bd_tslots(int n) { return n <= BD_TS ? BD_TS : n <= BD_TS_MAX ? BD_TS
 // the attention and gate + up epilogues that quantise their own output) and launch_gemm ask here, so they cannot disagree.
 static bool pf_chunk_major(int n) { return bd_tslots(n) == 0; }
 
-// A/B switches of the fused producers, read once: GL3_NO_FUSED_QUANT=1 keeps the separate quantise launches, GL3_NO_FUSED_BD_ATTN=1
-// the three-kernel attention of static-batched decode
+// A/B switch of the fused producers, asked by the attention dispatch and both feed-forward blocks: GL3_NO_FUSED_QUANT=1 keeps the separate quantise launches
 static bool pf_fused_quant_off() { static const bool off = env_flag("GL3_NO_FUSED_QUANT", false); return off; }
-static bool pf_fused_bd_attn_off() { static const bool off = env_flag("GL3_NO_FUSED_BD_ATTN", false); return off; }
+
+// The shape of one batched step: built once by its entry point, read by the layers, the attention dispatch and pf_fused_decode.
+struct PfStep {
+    int n;              // rows (tokens) of the step
+    int max_pos;        // largest position of the step
+    int one_seq;        // >= 0: all n rows belong to that sequence at consecutive positions ending at max_pos (prefill); -1: rows of many sequences
+    int ntab;           // records of the attention tile table in p->tiles; 0 unless a mixed step has a run of several rows
+};
 
 // A static-batched decode step whose deepest row is at max_pos runs the one-launch attention (attn_head_kernel).  Asked by the attention
 // dispatch, by the operand hand-over behind it and by the graph capture of the step (only such a step has nothing position-dependent
 // baked in: the three-kernel attention sizes its scores grid by the deepest row), so they cannot disagree.
-// A mixed step with a run of several rows (step_tiles > 0) never does: attn_head_kernel writes a row's K / V in the launch that reads it, and a
+// A mixed step with a run of several rows (ntab > 0) never does: attn_head_kernel writes a row's K / V in the launch that reads it, and a
 // later row of the same run would race with that write.
-static bool pf_fused_decode(const gl3_ctx* ctx, int max_pos) {
-    return ctx->fused_attn_ok && max_pos < AF_MAXN && !pf_fused_bd_attn_off() && ctx->pf->step_tiles == 0;
+static bool pf_fused_decode(const gl3_ctx* ctx, const PfStep& st) {
+    static const bool bd_attn_off = env_flag("GL3_NO_FUSED_BD_ATTN", false);      // A/B switch: =1 the three-kernel attention of static-batched decode
+    return ctx->fused_attn_ok && st.max_pos < AF_MAXN && !bd_attn_off && st.ntab == 0;
 }
 
 // dynamic LDS of pf_norm_quant_kernel<PQ_NORM> for rows of k elements: the row, the exact sum of squares' scratch, the result
 static size_t nq_smem(int k) { return (size_t)(k + 32) * 4 + ss_scratch_bytes(k) + 64; }
+
+// Where a quantise launch writes: an int8 operand set in the layout its slot count names (tslots 0: chunk-major with the scales in XP), or,
+// for the f32 modes, plain f32 rows in XS.
+struct PfOperand {
+    uint8_t* XQ; float* XS;      // int8 blocks and their scales; f32 modes: XQ null, XS = the f32 destination rows (XN)
+    int maxk, tslots; uint8_t* XP; int xp_tok;      // 0 / null for the f32 modes
+};
+static PfOperand pf_operand(const gl3_prefill_state* p, int n) { return {p->XQ, p->XS, p->maxk, bd_tslots(n), p->XP, p->xp_tok}; }      // the next GEMM's, for a step of n tokens
+static PfOperand pf_operand_f32(const gl3_prefill_state* p) { return {nullptr, p->XN, 0, 0, nullptr, 0}; }
+
+// The one launch of pf_norm_quant_kernel: `rows` rows of k elements of src (rank-chunked, chunk width cc) -> dst.  The NORM modes take one
+// workgroup per row with the row in LDS, the PLAIN modes one per (row, 1024 elements) and no LDS; norm_w is null for the PLAIN modes.
+template <int MODE>
+static void pf_quant(gl3_ctx* ctx, const float* src, int k, int cc, const float* norm_w, int rows, const PfOperand& dst) {
+    constexpr bool NORM = MODE == PQ_NORM || MODE == PQ_NORM_F32;
+    hipLaunchKernelGGL((pf_norm_quant_kernel<MODE>), NORM ? dim3(rows) : dim3(rows, (k / 4 + 255) / 256), dim3(256), NORM ? nq_smem(k) : 0, ctx->stream,
+                       src, k, cc, norm_w, NORM ? ctx->d.rms_eps : 0.f, dst.XQ, dst.XS, dst.maxk, dst.tslots, (uint2*)dst.XP, dst.xp_tok);
+}
 
 template <int EPI>
 static void launch_gemm(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int ntok, float* out, int out_stride, float out_scale = 1.0f,
@@ -478,10 +478,24 @@ static inline void pf_kvmul_dispatch(int kvmul, F&& f) {      // pf_scores_pk_ke
 // RoPE + KV write + attention of layer l for the n tokens whose raw q | k | v rows are in p->QKV -> AOr (this rank's chunk of the
 // attention output).  fuse_q: static-batched decode on one rank writes the output as the wo projection's int8 operand instead.
 // returns true when the attention output was written as the wo projection's int8 operand (no quantise launch needed)
-// A mixed step with runs of several rows (p->step_tiles > 0, one_seq < 0): after the one RoPE + KV launch every K / V row of the step is in the
+// A mixed step with runs of several rows (st.ntab > 0, one_seq < 0): after the one RoPE + KV launch every K / V row of the step is in the
 // caches, and the step takes the run-table form of the one-launch kernels — or, when the shape has none or the deepest row's score rows do
 // not fit LDS, the per-row pair for the whole step.
-static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, float* AOr, bool fuse_q) {
+static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool fuse_q) {
+    // A/B switches, read once at the first call, whichever branch it takes (they are set for the life of the process; nothing sets one
+    // after the first step); each says what it turns off where it is used.  The default-on ones keep the getenv / atoi form: set to the
+    // empty string it turns the feature off, where env_flag(x, true) would leave it on
+    static const bool rows_off = getenv("GL3_PF_SOFTMAX_ROWS") && atoi(getenv("GL3_PF_SOFTMAX_ROWS")) == 0;
+    static const bool fused_off = getenv("GL3_PF_FUSED_ATTN") && atoi(getenv("GL3_PF_FUSED_ATTN")) == 0;
+    static const bool v1_only = env_flag("GL3_PF_FUSED_V1", false);
+    static const bool qao_off = getenv("GL3_PF_ATTN_QOUT") && atoi(getenv("GL3_PF_ATTN_QOUT")) == 0;
+    static const bool mfma_off = getenv("GL3_PF_FUSED_MFMA") && atoi(getenv("GL3_PF_FUSED_MFMA")) == 0;
+    static const bool pk_off = getenv("GL3_PF_SCORES_PK") && atoi(getenv("GL3_PF_SCORES_PK")) == 0;
+    static const bool scm_off = getenv("GL3_PF_SCORES_MFMA") && atoi(getenv("GL3_PF_SCORES_MFMA")) == 0;
+    static const int scm_split = getenv("GL3_SCM_SPLIT") ? atoi(getenv("GL3_SCM_SPLIT")) : SCM_SPLIT;      // workgroups that share a (kv head, token tile)'s K tiles
+    static const bool ring_off = getenv("GL3_PF_PV_RING") && atoi(getenv("GL3_PF_PV_RING")) == 0;
+    static const bool pvm_off = getenv("GL3_PF_PV_MFMA") && atoi(getenv("GL3_PF_PV_MFMA")) == 0;
+    const int n = st.n, max_pos = st.max_pos, one_seq = st.one_seq, ntab = st.ntab;      // ntab > 0: the run-table form
     gl3_prefill_state* p = ctx->pf;
     const gl3_model_desc& d = ctx->d;
     hipStream_t s = ctx->stream;
@@ -494,7 +508,7 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
     const size_t kv_layer = (size_t)d.ctx * kvd;
     // one workgroup per (kv head, token) serves the kv head's whole group of query heads when its LDS image fits
     const int bd_group = (kvmul <= 8 && attn_head_smem(d.head_size, kvmul) <= PF_ATTN_LDS_MAX) ? kvmul : 1;
-    const bool fused_decode = pf_fused_decode(ctx, max_pos);
+    const bool fused_decode = pf_fused_decode(ctx, st);
     RopeArgs ra{};
     ra.QKV = p->QKV; ra.qkv_stride = qkv_dim; ra.kcache = ctx->kcache + l * kv_layer; ra.vcache = ctx->vcache + l * kv_layer;
     ra.cr = ctx->rope_cr; ra.ci = ctx->rope_ci; ra.qnorm = L.qnorm; ra.knorm = L.knorm; ra.bq = L.bq; ra.bk = L.bk; ra.bv = L.bv; ra.n_heads = H;
@@ -521,14 +535,10 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
     }
     hipLaunchKernelGGL(pf_rope_kv_kernel, dim3(H + KVH, n), dim3(64), 0, s, ra);
     // r6: pf_softmax_rows_kernel streams the score rows (no row-fits-LDS limit); GL3_PF_SOFTMAX_ROWS=0: the one-row-per-wavefront kernel
-    static const bool rows_off = getenv("GL3_PF_SOFTMAX_ROWS") && atoi(getenv("GL3_PF_SOFTMAX_ROWS")) == 0;
     const bool rows_softmax = !rows_off && d.ctx % 4 == 0 && d.ctx >= 64 && p->TMX && p->SUMS;
-    const int ntab = one_seq < 0 ? p->step_tiles : 0;      // > 0: the run-table form
     const bool tiled = (one_seq >= 0 || ntab > 0) && kvmul <= 4 && (hs == 32 || hs == 64 || hs == 128) && (rows_softmax || (size_t)(max_pos + 1) * 4 <= 60 * 1024);
     const bool mfma_shape = kvmul == 4 && (hs == 128 || hs == 64);      // the kernels with their products on the matrix pipe
     // r4: one launch for scores + softmax + weighted V sum when a tile's score rows fit LDS (GL3_PF_FUSED_ATTN=0: the three kernels)
-    static const bool fused_off = getenv("GL3_PF_FUSED_ATTN") && atoi(getenv("GL3_PF_FUSED_ATTN")) == 0;
-    static const bool v1_only = env_flag("GL3_PF_FUSED_V1", false);
     const int fa_sstride = ((max_pos + 1 + 63) & ~63) + 4;      // sized by the deepest row of the step
     const bool one_launch = !fused_off && 64 * (hs / 4) <= 8 * 64 * kvmul && fa_smem_bytes(hs, kvmul, fa_sstride) <= PF_ATTN_LDS_MAX;      // 8 float4 per thread stage a tile
     // the table form exists for pf_attn_fused3_kernel / pf_attn_fused2_kernel only: with fused2's rows fitting, one of the two is what the dispatch below picks
@@ -546,13 +556,11 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
     if (one_launch) {
         const dim3 grid(KVH * (ntab ? ntab : (n + FA_TB - 1) / FA_TB));
         // r6: > 64 tokens on one rank with head size 128: the output is written quantised for the wo GEMM (pf_gemm3_kernel's operand layout)
-        static const bool qao_off = getenv("GL3_PF_ATTN_QOUT") && atoi(getenv("GL3_PF_ATTN_QOUT")) == 0;
         const bool qao = !qao_off && hs == 128 && pf_chunk_major(n) && d.tp_size == 1 && p->XP && !pf_fused_quant_off();
         uint8_t* xqo = qao ? p->XQ : nullptr;
         uint4* xpo = qao ? reinterpret_cast<uint4*>(p->XP) : nullptr;
         // r6: products of both phases on the matrix pipe (pf_attn_fused3_kernel); GL3_PF_FUSED_MFMA=0: the VALU kernels.  Else packed-f32 scores + pinned
         // weighted V sum (pf_attn_fused2_kernel) while its 16 KB of query rows still fit; GL3_PF_FUSED_V1=1: the r4 kernel
-        static const bool mfma_off = getenv("GL3_PF_FUSED_MFMA") && atoi(getenv("GL3_PF_FUSED_MFMA")) == 0;
         const size_t sms = fa_smem_bytes(hs, kvmul, fa_sstride), sms2 = fa2_smem_bytes(hs, kvmul, fa_sstride), sms3 = fa3_smem_bytes(hs, fa_sstride);
         const size_t sst = ctx->kv_seq_stride;
         if (!mfma_off && !v1_only && mfma_shape && sms3 <= PF_ATTN_LDS_MAX)
@@ -578,11 +586,8 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
     const int ntt = (n + PA_TB - 1) / PA_TB;
     const dim3 g1(nsplit, KVH, ntt), b1(64 * kvmul);
     float* tmx = rows_softmax ? p->TMX : nullptr;
-    static const bool pk_off = getenv("GL3_PF_SCORES_PK") && atoi(getenv("GL3_PF_SCORES_PK")) == 0;
     const bool pk = !pk_off && scores_pk_smem_bytes(hs, kvmul) <= PF_ATTN_LDS_MAX && (kvmul == 4 || kvmul == 2 || kvmul == 1);
-    static const bool scm_off = getenv("GL3_PF_SCORES_MFMA") && atoi(getenv("GL3_PF_SCORES_MFMA")) == 0;
     if (rows_softmax && !scm_off && mfma_shape) {      // r6: products on the matrix pipe, query rows resident, K tiles prefetched
-        static const int scm_split = getenv("GL3_SCM_SPLIT") ? atoi(getenv("GL3_SCM_SPLIT")) : SCM_SPLIT;      // workgroups that share a (kv head, token tile)'s K tiles
         const dim3 g(nsplit < scm_split ? nsplit : scm_split, KVH, (n + SCM_TB - 1) / SCM_TB);
         pf_head_dispatch<64>(hs, [&](auto hc) {
             hipLaunchKernelGGL((pf_scores_mfma_kernel<decltype(hc)::value>), g, dim3(512), scores_mfma_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att, aa.n_heads,
@@ -609,8 +614,6 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
         wpw = wpw > 4 ? 4 : wpw;
         hipLaunchKernelGGL(pf_softmax_kernel, dim3((n * H + wpw - 1) / wpw), dim3(256), (size_t)wpw * npad * 4, s, aa, n, wpw, npad);
     }
-    static const bool ring_off = getenv("GL3_PF_PV_RING") && atoi(getenv("GL3_PF_PV_RING")) == 0;
-    static const bool pvm_off = getenv("GL3_PF_PV_MFMA") && atoi(getenv("GL3_PF_PV_MFMA")) == 0;
     if (sums && !pvm_off && mfma_shape)                 // r6: products on the matrix pipe (no uniform-address LDS reads)
         pf_head_dispatch<64>(hs, [&](auto hc) {
             hipLaunchKernelGGL((pf_pv_mfma_kernel<decltype(hc)::value>), dim3(KVH, (n + PVM_TB - 1) / PVM_TB), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });
@@ -622,11 +625,10 @@ static bool pf_attention(gl3_ctx* ctx, int l, int n, int max_pos, int one_seq, f
     return false;
 }
 
-static bool env_flag_cached_vlq_mfma() { static const bool on = env_flag("GL3_VLQ_MFMA", true); return on; }
-
 // Batched matmul of the f32-activation weight types (gl3_prefill_vl.h): out[b][row] (+)= dot(W[row], act[b]) in the Vector-API order
 template <int EPI>
 static void launch_gemm_vl(gl3_ctx* ctx, const Q8Mat& w, int ntok, const float* act, int act_stride, float* out, int out_stride, float out_scale = 1.0f) {
+    static const bool vlq_mfma = env_flag("GL3_VLQ_MFMA", true);
     VlGemmArgs a{};
     a.w = w.w; a.rows = w.rows; a.k = w.k; a.X = act; a.x_stride = act_stride; a.ntok = ntok; a.out = out; a.out_stride = out_stride; a.out_scale = out_scale;
     a.nrt = (w.rows + 63) / 64;
@@ -636,7 +638,7 @@ static void launch_gemm_vl(gl3_ctx* ctx, const Q8Mat& w, int ntok, const float* 
         if (ctx->d.flags & GL3_FLAG_VECTOR_512)          // 16 accumulator lanes: the same tiles, a wavefront pair per sub-tile
             hipLaunchKernelGGL((gemm_f16_mfma_v512_kernel<EPI>), g, dim3(512), 2 * F16G_STAGE, ctx->stream, a);
         else hipLaunchKernelGGL((gemm_f16_mfma_kernel<EPI>), g, dim3(256), 2 * F16G_STAGE, ctx->stream, a);
-    } else if (ntok > VLQ_TOK && env_flag_cached_vlq_mfma() && a.nrt * ((ntok + VQM_TOK - 1) / VQM_TOK) >= 192) {
+    } else if (ntok > VLQ_TOK && vlq_mfma && a.nrt * ((ntok + VQM_TOK - 1) / VQM_TOK) >= 192) {
         // enough 64 x 64 tiles to fill the chip: products on the f32 matrix cores (gemm_vlq_mfma_kernel; 8B Q4_0 pp512 2.53 k -> 3.4 k
         // tok/s).  Fewer tiles (short chunks, the 4096-row projections at 128 tokens) keep the 16-token VALU kernel; GL3_VLQ_MFMA=0: always.
         a.ntt = (ntok + VQM_TOK - 1) / VQM_TOK;
@@ -664,7 +666,8 @@ static void launch_gemm_vl(gl3_ctx* ctx, const Q8Mat& w, int ntok, const float* 
 // activations, gate and up as two GEMMs + an element-wise SwiGLU.  Tensor parallel (r4): the row-split matrices write this rank's
 // chunk of the rank-chunked X / AO / HB (as the int8 path does), the gathers are in place, and the next GEMM's operand is the
 // gathered activation un-chunked (or normalised) into XN.
-static int32_t pf_layers_vl(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
+static int32_t pf_layers_vl(gl3_ctx* ctx, const PfStep& st) {
+    const int n = st.n;
     Gl3Range chunk_range("gl3 batched step, tokens", n);
     gl3_prefill_state* p = ctx->pf;
     const gl3_model_desc& d = ctx->d;
@@ -679,19 +682,16 @@ static int32_t pf_layers_vl(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
     if (ctx->emb.fmt == GL3_TYPE_F16) hipLaunchKernelGGL((pf_embed_vl_kernel<WT_F16>), dim3(n), dim3(256), 0, s, ctx->emb.w, d.dim, p->tokens, p->X, ctx->emb_scale, dml);
     else if (ctx->emb.fmt == GL3_TYPE_Q4_0) hipLaunchKernelGGL((pf_embed_vl_kernel<WT_Q4_0>), dim3(n), dim3(256), 0, s, ctx->emb.w, d.dim, p->tokens, p->X, ctx->emb_scale, dml);
     else hipLaunchKernelGGL((pf_embed_vl_kernel<WT_Q8_0>), dim3(n), dim3(256), 0, s, ctx->emb.w, d.dim, p->tokens, p->X, ctx->emb_scale, dml);
-    const size_t nq = nq_smem(d.dim);
-    auto unchunk = [&](const float* src, int k, int cc) {          // rank-chunked [tp][n][cc] -> plain XN[n][k] (tp = 1: a copy the GEMM could skip, kept for one code path)
-        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN_F32>), dim3(n, (k / 4 + 255) / 256), dim3(256), 0, s, src, k, cc, (const float*)nullptr, 0.f, (uint8_t*)nullptr, p->XN, 0, 0);
-    };
+    const PfOperand xn = pf_operand_f32(p);
     for (int l = 0; l < d.n_layers; ++l) {
         gl3_layer& L = ctx->layers[l];
         Gl3Range layer_range("layer", l);
-        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM_F32>), dim3(n), dim3(256), nq, s, p->X, d.dim, dml, L.attn_norm, d.rms_eps, (uint8_t*)nullptr, p->XN, 0, 0);
+        pf_quant<PQ_NORM_F32>(ctx, p->X, d.dim, dml, L.attn_norm, n, xn);
         launch_gemm_vl<EPI_STORE>(ctx, L.wqkv, n, p->XN, d.dim, p->QKV, qkv_dim);
-        pf_attention(ctx, l, n, max_pos, one_seq, AOr, false);
+        pf_attention(ctx, l, st, AOr, false);
         if ((r = gl3_all_gather(ctx, GB_PF_AO, (size_t)n * qd)) != GL3_OK) return r;
         const float* ao = p->AO;
-        if (tp > 1) { unchunk(p->AO, ctx->q_dim, qd); ao = p->XN; }
+        if (tp > 1) { pf_quant<PQ_PLAIN_F32>(ctx, p->AO, ctx->q_dim, qd, nullptr, n, xn); ao = p->XN; }      // rank-chunked [tp][n][qd] -> plain XN[n][q_dim]
         if (ctx->wo_replicated) {
             // every rank holds all of Wo: one GEMM per rank chunk of the rank-chunked X (rows [c dml, (c + 1) dml) -> chunk c), no gather
             for (int c = 0; c < tp; ++c) {
@@ -704,14 +704,14 @@ static int32_t pf_layers_vl(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
             launch_gemm_vl<EPI_RESID>(ctx, L.wo, n, ao, ctx->q_dim, Xr, dml, ctx->resid_scale);
             if ((r = gl3_all_gather(ctx, GB_PF_X, (size_t)n * dml)) != GL3_OK) return r;
         }
-        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM_F32>), dim3(n), dim3(256), nq, s, p->X, d.dim, dml, L.ffn_norm, d.rms_eps, (uint8_t*)nullptr, p->XN, 0, 0);
+        pf_quant<PQ_NORM_F32>(ctx, p->X, d.dim, dml, L.ffn_norm, n, xn);
         launch_gemm_vl<EPI_STORE>(ctx, L.w1, n, p->XN, d.dim, HBr, hid);
         launch_gemm_vl<EPI_STORE>(ctx, L.w3, n, p->XN, d.dim, p->HB2, hid);
         const size_t ne = (size_t)n * hid;
         hipLaunchKernelGGL(pf_swiglu_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, HBr, p->HB2, ne);
         if ((r = gl3_all_gather(ctx, GB_PF_HB, (size_t)n * hid)) != GL3_OK) return r;
         const float* hb = p->HB;
-        if (tp > 1) { unchunk(p->HB, d.hidden, hid); hb = p->XN; }
+        if (tp > 1) { pf_quant<PQ_PLAIN_F32>(ctx, p->HB, d.hidden, hid, nullptr, n, xn); hb = p->XN; }
         launch_gemm_vl<EPI_RESID>(ctx, L.w2, n, hb, d.hidden, Xr, dml, ctx->resid_scale);
         if ((r = gl3_all_gather(ctx, GB_PF_X, (size_t)n * dml)) != GL3_OK) return r;
     }
@@ -736,20 +736,16 @@ static void pf_moe_ffn(gl3_ctx* ctx, int l, int n) {
         ra.dim = d.dim; ra.n_experts = E; ra.topk = topk; ra.logits = m.logits; ra.w_out = m.w; ra.sel = m.sel; ra.ticket = m.ticket;
         hipLaunchKernelGGL(moe_router_batch_kernel, dim3(moe_router_wgs(E), n), dim3(256), moe_router_smem(d.dim, E), s, ra);
         hipLaunchKernelGGL(moe_group_kernel, dim3(1), dim3(MOE_GROUP_THREADS), moe_group_smem(E), s, m.sel, n, topk, E, m.slot_tok, m.slot_dst, m.tab); }
-    const size_t nq = nq_smem(d.dim);
-    hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq, s, p->X, d.dim, d.dim, L.ffn_norm, d.rms_eps,
-                       p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
-    const uint8_t* xq = p->XQ; const float* xs = p->XS; int ts = bd_tslots(n);
+    PfOperand xb = pf_operand(p, n);
+    pf_quant<PQ_NORM>(ctx, p->X, d.dim, d.dim, L.ffn_norm, n, xb);
     if (pf_chunk_major(n)) {      // the chunk-major operand serves the shared expert; the routed experts read the XQ2 / XS2 layout
-        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq, s, p->X, d.dim, d.dim, L.ffn_norm, d.rms_eps,
-                           m.XQx, m.XSx, p->maxk, m.ts_x, (uint2*)nullptr, 0);
-        xq = m.XQx; xs = m.XSx; ts = m.ts_x;
+        xb = {m.XQx, m.XSx, p->maxk, m.ts_x, nullptr, 0};
+        pf_quant<PQ_NORM>(ctx, p->X, d.dim, d.dim, L.ffn_norm, n, xb);
     }
     {   Gl3Range g("moe: routed experts");
-        launch_gemm_grouped<EPI_SWIGLU>(ctx, L.gate_exps, &L.up_exps, mh, n, xq, xs, ts, m.slot_tok, nullptr, m.HB, mh);
+        launch_gemm_grouped<EPI_SWIGLU>(ctx, L.gate_exps, &L.up_exps, mh, n, xb.XQ, xb.XS, xb.tslots, m.slot_tok, nullptr, m.HB, mh);
         // hb per 32-block as matmulExpert quantises it (Q8_0FloatTensor.java:96-118); row = sorted slot, so a token tile is 16 consecutive rows
-        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN>), dim3(S, (mh / 4 + 255) / 256), dim3(256), 0, s, m.HB, mh, mh, (const float*)nullptr, 0.f,
-                           m.XQh, m.XSh, mh, m.ts_h, (uint2*)nullptr, 0);
+        pf_quant<PQ_PLAIN>(ctx, m.HB, mh, mh, nullptr, S, {m.XQh, m.XSh, mh, m.ts_h, nullptr, 0});
         launch_gemm_grouped<EPI_STORE>(ctx, L.down_exps, nullptr, d.dim, n, m.XQh, m.XSh, m.ts_h, nullptr, m.slot_dst, m.Y, d.dim); }
     {   Gl3Range g("moe: shared expert");      // after the routed gate + up: the unfused hand-over below overwrites xb
         float* ysh = m.Y + (size_t)topk * d.dim;
@@ -762,8 +758,7 @@ static void pf_moe_ffn(gl3_ctx* ctx, int l, int n) {
             launch_gemm<EPI_STORE>(ctx, L.w2, nullptr, n, ysh, ystride, 1.0f, true);
         } else {
             launch_gemm<EPI_SWIGLU>(ctx, L.w1, &L.w3, n, p->HB, d.hidden);
-            hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN>), dim3(n, (d.hidden / 4 + 255) / 256), dim3(256), 0, s, p->HB, d.hidden, d.hidden, (const float*)nullptr, 0.f,
-                               p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
+            pf_quant<PQ_PLAIN>(ctx, p->HB, d.hidden, d.hidden, nullptr, n, pf_operand(p, n));
             launch_gemm<EPI_STORE>(ctx, L.w2, nullptr, n, ysh, ystride);
         } }
     {   Gl3Range g("moe: weighted accumulation into x");
@@ -786,19 +781,19 @@ int32_t gl3_prefill_moe_tap(gl3_ctx* ctx, int which, float* out, uint64_t n) {
     return GL3_OK;
 }
 
-// All layers for n tokens whose (token, sequence, position) are already on the device.  max_pos = largest position.
-// one_seq >= 0: all n tokens belong to that sequence at consecutive positions ending at max_pos (prefill).
-static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
+// All layers for the st.n tokens of a step whose (token, sequence, position) — and, for st.ntab > 0, tile table — are already on the device.
+static int32_t pf_layers(gl3_ctx* ctx, const PfStep& st) {
+    const int n = st.n;
     Gl3Range chunk_range("gl3 batched step, tokens", n);
     gl3_prefill_state* p = ctx->pf;
-    if (p->vl) return pf_layers_vl(ctx, n, max_pos, one_seq);
+    if (p->vl) return pf_layers_vl(ctx, st);
     const gl3_model_desc& d = ctx->d;
     hipStream_t s = ctx->stream;
     // tensor parallel: this rank's heads / hidden units / dim rows; activations that are gathered use the rank-chunked layout
     const int rank = d.tp_rank, qd = ctx->q_dim_l, kvd = ctx->kv_dim_l;
     const int hid = ctx->hidden_l, dml = ctx->dim_l;
     const int qkv_dim = qd + 2 * kvd;
-    const bool fused_decode = pf_fused_decode(ctx, max_pos);
+    const bool fused_decode = pf_fused_decode(ctx, st);
     // small batch on one rank: the attention output and hb leave their kernels already quantised for the next GEMM (no
     // separate quantise launches; under tensor parallelism the f32 vectors are gathered first, so the launches stay)
     const bool fuse_off = pf_fused_quant_off();
@@ -806,19 +801,17 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
     float* Xr = p->X + (size_t)rank * n * dml;           // this rank's chunk of X / AO / HB
     float* AOr = p->AO + (size_t)rank * n * qd;
     float* HBr = p->HB + (size_t)rank * n * hid;
+    const PfOperand xq = pf_operand(p, n);
     int32_t r;
     hipLaunchKernelGGL(pf_embed_kernel, dim3(n), dim3(256), 0, s, ctx->emb.w, ctx->emb.ng, d.dim, p->tokens, p->X, dml, ctx->emb_scale);
     for (int l = 0; l < d.n_layers; ++l) {
         gl3_layer& L = ctx->layers[l];
         Gl3Range layer_range("layer", l);
-        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq_smem(d.dim), s, p->X, d.dim, dml, L.attn_norm, d.rms_eps,
-                           p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
+        pf_quant<PQ_NORM>(ctx, p->X, d.dim, dml, L.attn_norm, n, xq);
         launch_gemm<EPI_STORE>(ctx, L.wqkv, nullptr, n, p->QKV, qkv_dim);
-        const bool quantised_ao = pf_attention(ctx, l, n, max_pos, one_seq, AOr, fuse_q && one_seq < 0 && fused_decode);
+        const bool quantised_ao = pf_attention(ctx, l, st, AOr, fuse_q && st.one_seq < 0 && fused_decode);
         if ((r = gl3_all_gather(ctx, GB_PF_AO, (size_t)n * qd)) != GL3_OK) return r;
-        if (!quantised_ao)
-            hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN>), dim3(n, (ctx->q_dim / 4 + 255) / 256), dim3(256), 0, s, p->AO, ctx->q_dim, qd, (const float*)nullptr,
-                               0.f, p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
+        if (!quantised_ao) pf_quant<PQ_PLAIN>(ctx, p->AO, ctx->q_dim, qd, nullptr, n, xq);
         if (ctx->wo_replicated) {
             // every rank holds all of Wo: one GEMM per rank chunk of the rank-chunked X (rows [c dml, (c + 1) dml) -> chunk c), no gather
             for (int c = 0; c < d.tp_size; ++c) {
@@ -832,8 +825,7 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
             if ((r = gl3_all_gather(ctx, GB_PF_X, (size_t)n * dml)) != GL3_OK) return r;
         }
         if (d.arch == GL3_ARCH_QWEN2MOE) { pf_moe_ffn(ctx, l, n); continue; }
-        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq_smem(d.dim), s, p->X, d.dim, dml, L.ffn_norm, d.rms_eps,
-                           p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
+        pf_quant<PQ_NORM>(ctx, p->X, d.dim, dml, L.ffn_norm, n, xq);
         // > 64 tokens on one rank: the tall gate + up tiling writes hb quantised (no f32 round trip, no quantise launch)
         const bool fuse_big = !fuse_off && pf_chunk_major(n) && d.tp_size == 1 && p->XQh && gl3_gemm3_swiglu_quantises(L.w1.rows, n);
         if (fuse_q || fuse_big) {
@@ -842,8 +834,7 @@ static int32_t pf_layers(gl3_ctx* ctx, int n, int max_pos, int one_seq) {
         } else {
             launch_gemm<EPI_SWIGLU>(ctx, L.w1, &L.w3, n, HBr, hid);
             if ((r = gl3_all_gather(ctx, GB_PF_HB, (size_t)n * hid)) != GL3_OK) return r;
-            hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_PLAIN>), dim3(n, (d.hidden / 4 + 255) / 256), dim3(256), 0, s, p->HB, d.hidden, hid, (const float*)nullptr, 0.f,
-                               p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
+            pf_quant<PQ_PLAIN>(ctx, p->HB, d.hidden, hid, nullptr, n, xq);
             launch_gemm<EPI_RESID>(ctx, L.w2, nullptr, n, Xr, dml, ctx->resid_scale);
         }
         if ((r = gl3_all_gather(ctx, GB_PF_X, (size_t)n * dml)) != GL3_OK) return r;
@@ -880,11 +871,32 @@ int32_t gl3_prefill_run(gl3_ctx* ctx, int32_t seq, const int32_t* tokens, int32_
     for (int i = 0; i < n; ++i) poss[i] = start_pos + i;
     int32_t r = pf_stage_tokens(ctx, tokens, seqs.data(), poss.data(), n);
     if (r != GL3_OK) return r;
-    if ((r = pf_layers(ctx, n, start_pos + n - 1, seq)) != GL3_OK) return r;
+    if ((r = pf_layers(ctx, PfStep{n, start_pos + n - 1, seq, 0})) != GL3_OK) return r;
     // keep the decode path's x in step with the last prefilled token (parity tap gl3_get_x)
     hipLaunchKernelGGL(pf_unchunk_row_kernel, dim3(4), dim3(256), 0, ctx->stream, p->X, n - 1, d.dim, ctx->dim_l, n, ctx->x);
     GL3_HIP(hipStreamSynchronize(ctx->stream));
     return gl3_tp_check(ctx);
+}
+
+// The logits stage of a step: output RMSNorm + vocabulary projection of `rows` rows of src (rank-chunked, chunk width src_cc) -> rows of
+// dst_stride floats at dst_chunk.  Vocabulary rows are split across ranks: dst_chunk is this rank's chunk of the rank-chunked logits.
+static void pf_logits_stage(gl3_ctx* ctx, const float* src, int src_cc, int rows, float* dst_chunk, int dst_stride) {
+    gl3_prefill_state* p = ctx->pf;
+    const int dim = ctx->d.dim;
+    if (p->vl) {
+        pf_quant<PQ_NORM_F32>(ctx, src, dim, src_cc, ctx->out_norm, rows, pf_operand_f32(p));
+        launch_gemm_vl<EPI_STORE>(ctx, ctx->wcls, rows, p->XN, dim, dst_chunk, dst_stride, ctx->logit_scale);
+    } else {
+        pf_quant<PQ_NORM>(ctx, src, dim, src_cc, ctx->out_norm, rows, pf_operand(p, rows));
+        launch_gemm<EPI_STORE>(ctx, ctx->wcls, nullptr, rows, dst_chunk, dst_stride, ctx->logit_scale);
+    }
+}
+
+// Greedy ids of the first `rows` rows of p->LOGITS (rank-chunked, chunk width cc) -> p->amax
+static void pf_greedy(gl3_ctx* ctx, int rows, int cc) {
+    gl3_prefill_state* p = ctx->pf;
+    hipLaunchKernelGGL(pf_argmax_part_kernel, dim3(AMX_SPLIT, rows), dim3(256), 0, ctx->stream, p->LOGITS, ctx->d.vocab, cc, p->amx_v, p->amx_i);
+    hipLaunchKernelGGL(pf_argmax_fold_kernel, dim3(rows), dim3(64), 0, ctx->stream, p->amx_v, p->amx_i, p->amax);
 }
 
 // One decode step of n independent sequences = the prefill machinery over (token, sequence, position) triples +
@@ -916,10 +928,8 @@ int32_t gl3_decode_batch_load_logits(gl3_ctx* ctx, const float* logits, int32_t 
     GL3_HIP(hipSetDevice(d.device));
     int32_t r = pf_grow_logits(ctx, n);
     if (r != GL3_OK) return r;
-    hipStream_t s = ctx->stream;
-    GL3_HIP(hipMemcpyAsync(p->LOGITS, logits, (size_t)n * d.vocab * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(pf_argmax_part_kernel, dim3(AMX_SPLIT, n), dim3(256), 0, s, p->LOGITS, d.vocab, ctx->vocab_l, p->amx_v, p->amx_i);
-    hipLaunchKernelGGL(pf_argmax_fold_kernel, dim3(n), dim3(64), 0, s, p->amx_v, p->amx_i, p->amax);
+    GL3_HIP(hipMemcpyAsync(p->LOGITS, logits, (size_t)n * d.vocab * 4, hipMemcpyHostToDevice, ctx->stream));
+    pf_greedy(ctx, n, ctx->vocab_l);
     GL3_HIP(hipGetLastError());
     return GL3_OK;
 }
@@ -938,35 +948,28 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
     hipStream_t s = ctx->stream;
     const int vl = ctx->vocab_l;
     // the whole step: layers, final RMSNorm + vocabulary projection of every row, greedy ids
-    auto enqueue_step = [&](int mp) -> int32_t {
-        int32_t rr = pf_layers(ctx, n, mp, -1);
+    auto enqueue_step = [&](const PfStep& st) -> int32_t {
+        int32_t rr = pf_layers(ctx, st);
         if (rr != GL3_OK) return rr;
-        const size_t nq = nq_smem(d.dim);
-        if (p->vl) {
-            hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM_F32>), dim3(n), dim3(256), nq, s, p->X, d.dim, ctx->dim_l, ctx->out_norm, d.rms_eps, (uint8_t*)nullptr, p->XN, 0, 0);
-            launch_gemm_vl<EPI_STORE>(ctx, ctx->wcls, n, p->XN, d.dim, p->LOGITS + (size_t)d.tp_rank * n * vl, vl, ctx->logit_scale);
-        } else {
-        hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n), dim3(256), nq, s, p->X, d.dim, ctx->dim_l, ctx->out_norm, d.rms_eps, p->XQ, p->XS, p->maxk, bd_tslots(n), (uint2*)p->XP, p->xp_tok);
-        // vocab rows are split across ranks: this rank's logits are the chunk [n][vocab / tp] of the rank-chunked buffer
-        launch_gemm<EPI_STORE>(ctx, ctx->wcls, nullptr, n, p->LOGITS + (size_t)d.tp_rank * n * vl, vl, ctx->logit_scale);
-        }
+        // this rank's logits are the chunk [n][vocab / tp] of the rank-chunked buffer
+        pf_logits_stage(ctx, p->X, ctx->dim_l, n, p->LOGITS + (size_t)d.tp_rank * n * vl, vl);
         if ((rr = gl3_all_gather(ctx, GB_PF_LOGITS, (size_t)n * vl)) != GL3_OK) return rr;
-        hipLaunchKernelGGL(pf_argmax_part_kernel, dim3(AMX_SPLIT, n), dim3(256), 0, s, p->LOGITS, d.vocab, vl, p->amx_v, p->amx_i);
-        hipLaunchKernelGGL(pf_argmax_fold_kernel, dim3(n), dim3(64), 0, s, p->amx_v, p->amx_i, p->amax);
+        pf_greedy(ctx, n, vl);
         return GL3_OK;
     };
     // ~400 launches per step: replay them as one hipGraph per batch size.  Nothing position-dependent is baked in when every
     // position is below AF_MAXN (the one-launch attention reads sequence ids / positions from device memory).  The three-kernel
     // attention (GL3_NO_FUSED_BD_ATTN=1) sizes its scores grid by the deepest row: a step captured at position 0 would score the
     // first 64 positions only, so those steps stay eager.
-    static const bool graphs_off = getenv("GL3_NO_GRAPH") && atoi(getenv("GL3_NO_GRAPH"));
-    const bool graphable = !graphs_off && !gl3_roctx_on() && !(d.flags & GL3_FLAG_NO_GRAPH) && pf_fused_decode(ctx, max_pos) && ctx->transport != GL3_TP_RCCL;
+    static const bool graphs_off = env_flag("GL3_NO_GRAPH", false);
+    const PfStep st{n, max_pos, -1, 0};
+    const bool graphable = !graphs_off && !gl3_roctx_on() && !(d.flags & GL3_FLAG_NO_GRAPH) && pf_fused_decode(ctx, st) && ctx->transport != GL3_TP_RCCL;
     if (graphable) {
         if ((int)p->step_graphs.size() <= n) p->step_graphs.resize(n + 1, nullptr);
         if (!p->step_graphs[n]) {
             hipGraph_t g = nullptr;
             GL3_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            r = enqueue_step(0);
+            r = enqueue_step(PfStep{n, 0, -1, 0});      // any depth below AF_MAXN enqueues the same launches: the capture names position 0
             const hipError_t e = hipStreamEndCapture(s, &g);
             if (r != GL3_OK) return r;
             GL3_HIP(e);
@@ -974,7 +977,7 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
             hipGraphDestroy(g);
         }
         GL3_HIP(hipGraphLaunch(p->step_graphs[n], s));
-    } else if ((r = enqueue_step(max_pos)) != GL3_OK) return r;
+    } else if ((r = enqueue_step(st)) != GL3_OK) return r;
     if (argmax_out) GL3_HIP(hipMemcpyAsync(argmax_out, p->amax, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (logits_out) {      // un-chunk on the way out: [tp][n][vl] -> [n][vocab]
         for (int c = 0; c < d.tp_size; ++c)
@@ -1025,25 +1028,13 @@ int32_t gl3_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_id
     const int ntab = bp.single_rows ? 0 : (int)bp.tiles.size();
     if (ntab) GL3_HIP(hipMemcpyAsync(p->tiles, bp.tiles.data(), (size_t)ntab * sizeof(BatchSpan), hipMemcpyHostToDevice, s));
     if (n_out) GL3_HIP(hipMemcpyAsync(p->out_rows, bp.out_rows.data(), (size_t)n_out * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    p->step_tiles = ntab;
-    r = pf_layers(ctx, n, bp.max_pos, -1);
-    p->step_tiles = 0;
-    if (r != GL3_OK) return r;
+    if ((r = pf_layers(ctx, PfStep{n, bp.max_pos, -1, ntab})) != GL3_OK) return r;
     // keep the decode path's x in step with the last row (parity tap gl3_get_x)
     hipLaunchKernelGGL(pf_unchunk_row_kernel, dim3(4), dim3(256), 0, s, p->X, n - 1, d.dim, ctx->dim_l, n, ctx->x);
     if (n_out) {      // output RMSNorm + vocabulary projection + greedy ids of the flagged rows, compact
         hipLaunchKernelGGL(pf_gather_rows_kernel, dim3(n_out), dim3(256), 0, s, p->X, p->out_rows, d.dim, p->XG);
-        const size_t nq = nq_smem(d.dim);
-        if (p->vl) {
-            hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM_F32>), dim3(n_out), dim3(256), nq, s, p->XG, d.dim, d.dim, ctx->out_norm, d.rms_eps, (uint8_t*)nullptr, p->XN, 0, 0);
-            launch_gemm_vl<EPI_STORE>(ctx, ctx->wcls, n_out, p->XN, d.dim, p->LOGITS, d.vocab, ctx->logit_scale);
-        } else {
-            hipLaunchKernelGGL((pf_norm_quant_kernel<PQ_NORM>), dim3(n_out), dim3(256), nq, s, p->XG, d.dim, d.dim, ctx->out_norm, d.rms_eps, p->XQ, p->XS, p->maxk,
-                               bd_tslots(n_out), (uint2*)p->XP, p->xp_tok);
-            launch_gemm<EPI_STORE>(ctx, ctx->wcls, nullptr, n_out, p->LOGITS, d.vocab, ctx->logit_scale);
-        }
-        hipLaunchKernelGGL(pf_argmax_part_kernel, dim3(AMX_SPLIT, n_out), dim3(256), 0, s, p->LOGITS, d.vocab, d.vocab, p->amx_v, p->amx_i);
-        hipLaunchKernelGGL(pf_argmax_fold_kernel, dim3(n_out), dim3(64), 0, s, p->amx_v, p->amx_i, p->amax);
+        pf_logits_stage(ctx, p->XG, d.dim, n_out, p->LOGITS, d.vocab);
+        pf_greedy(ctx, n_out, d.vocab);
         if (argmax_out) GL3_HIP(hipMemcpyAsync(argmax_out, p->amax, (size_t)n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         if (logits_out) GL3_HIP(hipMemcpyAsync(logits_out, p->LOGITS, (size_t)n_out * d.vocab * 4, hipMemcpyDeviceToHost, s));
     }

@@ -237,6 +237,31 @@ def test_no_output_rows(pkg, orc, planmod):
     plan.freeTornadoExecutionPlan()
 
 
+def test_table_steps_around_graph_replayed_decode_steps(pkg, orc, planmod):
+    """On one plan: runs of 5 and 3 rows (the run-table attention), a static-batched decode step of both sequences below position 128 (captured
+    as a graph behind the first table step, replayed behind the second), and a third table step behind the replay.  A step's shape travels
+    with the step: the decode steps take the one-launch attention and the graph although a table step ran before them, and the table steps
+    take the table although a replayed graph ran before them.  The test guards results only (every row bit for bit against the oracle): the
+    API does not say which attention kernel ran or whether a graph was replayed, and a step that kept another step's shape shows here as
+    wrong logits, not as a wrong path."""
+    plan_mod, _ = planmod
+    m = variant(pkg, "tiny-llama", seed=73)
+    plan = plan_mod.HipMasterPlan(m, prefill_batch_size=16, n_seqs=2)
+    oracles = [orc.COracle(m) for _ in range(2)]
+    b = Mixed(orc, plan, oracles, m, seed=23)
+    for _ in range(2):
+        b.step([(0, b.tokens(5)), (1, b.tokens(3))])
+        toks = [b.next_id[0], b.next_id[1]]
+        logits, ids = plan.forward_decode_batch(toks, [0, 1], list(b.pos))
+        for s in range(2):
+            ref = oracles[s].forward(toks[s], b.pos[s])
+            assert np.array_equal(logits[s], ref) and ids[s] == orc.argmax(ref), (s, b.pos[s])
+            b.pos[s] += 1
+    b.step([(0, b.tokens(5)), (1, b.tokens(3))])
+    assert b.pos == [17, 11]
+    plan.freeTornadoExecutionPlan()
+
+
 def test_sampled(pkg, orc, planmod):
     """One forward_batch_sample with four output rows — top-p, categorical, greedy, top-p (SETTINGS[0..3]) — the first and the last the ends
     of multi-row runs; ids and the probabilities they were drawn from equal the oracle's sampler on the oracle's logits."""

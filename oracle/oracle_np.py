@@ -23,9 +23,10 @@ BLOCK = {GGML_F32: (1, 4), GGML_F16: (1, 2), GGML_Q4_0: (32, 18), GGML_Q8_0: (32
 
 
 def seq_sum(a: np.ndarray, axis: int = -1) -> np.ndarray:
-    """Strict left-to-right float32 sum along ``axis`` starting from 0f (0+a0 == a0 exactly)."""
+    """Strict left-to-right float32 sum along ``axis`` starting from 0f (0+a0 == a0 exactly, except that 0f + -0f is +0f: the final
+    + 0f gives a sum whose terms are all -0 the sign the reference's accumulator has)."""
     a = np.asarray(a, dtype=F32)
-    return np.take(np.add.accumulate(a, axis=axis, dtype=F32), -1, axis=axis)
+    return np.take(np.add.accumulate(a, axis=axis, dtype=F32), -1, axis=axis) + F32(0.0)
 
 
 def dequant(raw: np.ndarray, ggml_type: int, n: int) -> np.ndarray:
@@ -241,9 +242,14 @@ class NpOracle:
         self.kv_dim = c["n_kv_heads"] * c["head_size"]
         self.kc = np.zeros((c["n_layers"], c["ctx"], self.kv_dim), F32)
         self.vc = np.zeros((c["n_layers"], c["ctx"], self.kv_dim), F32)
+        # taps for tests (recording only, no arithmetic): set mm_taps / attn_taps / moe_taps to a list and forward() appends
+        # (tensor name, first row, matmul input), (layer, head, pos, scores) and (layer prefix, expert ids, their weights) to them
+        self.mm_taps = self.attn_taps = self.moe_taps = None
 
     def _mm(self, name, x, d0, d1):
         raw, ty = self.t[name]
+        if self.mm_taps is not None:
+            self.mm_taps.append((name, 0, np.array(x, F32)))
         if self.vector_bits and (ty in (GGML_F16, GGML_Q4_0) or (ty == GGML_Q8_0 and self.f32_activation)):
             return matmul_vec(raw, ty, x, d0, d1, self.vector_bits)
         return matmul(raw, ty, x, d0, d1)
@@ -255,6 +261,8 @@ class NpOracle:
     def _mm_rows(self, name, row0, x, d0, d1):
         """InferenceCore.matmulExpert :430-432: rows [row0, row0 + d0) of a stacked [E x d0 x d1] tensor, the same per-row dot."""
         raw, ty = self.t[name]
+        if self.mm_taps is not None:
+            self.mm_taps.append((name, row0, np.array(x, F32)))
         bs, ts = BLOCK[ty]
         rb = d1 // bs * ts
         sub = raw.view(np.uint8).reshape(-1)[row0 * rb:(row0 + d0) * rb]
@@ -273,6 +281,8 @@ class NpOracle:
             sel.append(idx)
             wts.append(F32(probs[idx]))
             probs[idx] = -np.inf
+        if self.moe_taps is not None:
+            self.moe_taps.append((p, list(sel), list(wts)))
         silu = lambda h: (h / (1.0 + np.exp(-h.astype(np.float64))).astype(F32)).astype(F32)
         for e, w in zip(sel, wts):                                                # :392-402
             hb = self._mm_rows(p + "ffn_gate_exps.weight", e * mh, xb, mh, dim)
@@ -346,6 +356,8 @@ class NpOracle:
                 score = seq_sum(kk * qh[None, :], axis=1)
                 score = (score * F32(c["attention_scale"])).astype(F32) if granite else score / sqrt_hs
                 a = softmax(score)
+                if self.attn_taps is not None:
+                    self.attn_taps.append((l, h, pos, score.copy()))
                 vv = self.vc[l, :pos + 1, (h // kvmul) * hs:(h // kvmul + 1) * hs]
                 xb[h * hs:(h + 1) * hs] = seq_sum(a[:, None] * vv, axis=0)
             ao = self._mm(p + "attn_output.weight", xb, dim, qd)

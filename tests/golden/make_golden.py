@@ -32,13 +32,21 @@ CASES = [  # (fixture, config, ggml type, seed, prompt tokens, greedy steps, vec
     ("tiny_llama_tied_q4_0_v256", "tiny-llama-tied", 2, 11, 4, 8, 256),
     # Q8_0 weights with vector bits 256 = -Dllama.quantizeActivation=false: Q8_0FloatTensor.vectorDot on the f32 activation
     ("tiny_llama_q8_0_f32act_v256", "tiny-llama", 8, 7, 4, 8, 256),
+    # the "all" edit of tests/edge_models.py (edge-value weights and norm gains); prompt = edge_models.edge_tokens (zero / flat tokens inside)
+    ("tiny_llama_q8_0_edges", "tiny-llama", 8, 7, 8, 8, 0, "all"),
 ]
 
 
-def run_case(pkg, cfg_name, wtype, seed, n_prompt, n_greedy, vbits=0):
-    m = pkg.synth.make_numpy(pkg.synth.CONFIGS[cfg_name], wtype=wtype, seed=seed)
+def run_case(pkg, cfg_name, wtype, seed, n_prompt, n_greedy, vbits=0, edits=None):
+    if edits:
+        if os.path.join(ROOT, "tests") not in sys.path:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import edge_models
+        m = edge_models.make_edge_model(cfg_name, wtype, seed, edits)
+    else:
+        m = pkg.synth.make_numpy(pkg.synth.CONFIGS[cfg_name], wtype=wtype, seed=seed)
     o = oracle_np.NpOracle(m.oracle_cfg(), m.oracle_tensors(), m.rope, vector_bits=vbits, f32_activation=(wtype == 8 and vbits == 256))
-    prompt = pkg.javarand.bench_tokens(m.cfg.vocab, n_prompt)
+    prompt = edge_models.edge_tokens(pkg, m, n_prompt) if edits else pkg.javarand.bench_tokens(m.cfg.vocab, n_prompt)
     logits, lx = [], []
     tok_stream = list(prompt)
     for pos in range(n_prompt + n_greedy - 1):
@@ -55,9 +63,9 @@ def run_case(pkg, cfg_name, wtype, seed, n_prompt, n_greedy, vbits=0):
 if __name__ == "__main__":
     pkg = ge.load_package()
     only = sys.argv[1:]
-    for fx, cfg_name, wt, seed, npmt, ng, vbits in CASES:
+    for fx, cfg_name, wt, seed, npmt, ng, vbits, *edits in CASES:
         if only and fx not in only:
             continue
-        out = run_case(pkg, cfg_name, wt, seed, npmt, ng, vbits)
+        out = run_case(pkg, cfg_name, wt, seed, npmt, ng, vbits, *edits)
         np.savez_compressed(os.path.join(os.path.dirname(__file__), fx + ".npz"), **out)
         print(fx, out["tokens"].tolist())

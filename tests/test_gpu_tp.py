@@ -61,6 +61,39 @@ def test_row_split_ranks_are_bit_identical_to_the_oracle(pkg, orc, planmod, cfg,
             assert np.array_equal(out[r][p], ref[p]), (r, p)
 
 
+def test_row_split_ranks_on_edge_values(pkg, orc, planmod):
+    """tp = 2 on the "all" model of tests/edge_models.py (tiny-llama-tied, Q8_0): the row-split upload slicing and the folded gathers see
+    -128 quants, zero / subnormal / negative / 2^15 block scales and zero, subnormal-scaled and outlier activation blocks; every rank's
+    logits equal the oracle's bit for bit."""
+    import edge_models as em
+    plan_mod, hip = planmod
+    m = em.make_edge_model("tiny-llama-tied", 8, 7, "all")
+    o = orc.COracle(m)
+    toks = em.edge_tokens(pkg, m, 8)
+    ref = [o.forward(t, p) for p, t in enumerate(toks)]
+    assert all(np.all(np.isfinite(r)) for r in ref)
+    grp = plan_mod.make_local_group(2)
+    out, err = [None] * 2, [None] * 2
+
+    def rank_main(r):
+        try:
+            plan = plan_mod.HipMasterPlan(m, tp_rank=r, tp_size=2, local_group=grp)
+            out[r] = [plan.forward_decode(t, p) for p, t in enumerate(toks)]
+            plan.freeTornadoExecutionPlan()
+        except Exception as e:   # noqa: BLE001
+            err[r] = e
+
+    th = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(2)]
+    [t.start() for t in th]
+    [t.join(timeout=900) for t in th]
+    assert all(e is None for e in err), err
+    assert not any(t.is_alive() for t in th)
+    hip.lib().gl3_local_group_destroy(grp)
+    for r in range(2):
+        for p in range(len(toks)):
+            assert np.array_equal(out[r][p], ref[p]), (r, p)
+
+
 def test_q8_decode_gathers_are_folded_into_the_producers(pkg, orc, planmod):
     """The default hand-over of the decode step: the attention / gate-up / down kernels write their results into the peers' arenas (mode 1) — the
     Q8_0 int8 path and, since r6, the vector-order F16 / Q4_0 plans (BASELINE configs[3] is Q4_0 TP = 8); the scalar-order kernels

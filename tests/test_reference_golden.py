@@ -79,7 +79,7 @@ def load_case(pkg, stem, wt, seed):
     if not os.path.exists(path):
         pytest.skip("parity unpinned: no reference dump %s (INTEGRATION.md §6: make_pin_ggufs.py + GoldenDump.java need a JDK)" % os.path.relpath(path, os.path.dirname(HERE)))
     d = parse_dump(path)
-    m = pkg.synth.make_numpy(pin.pin_config(pkg), wtype=wt, seed=seed)
+    m = pin.pin_model(pkg, wt, seed, pin.PIN_EDITS.get(stem))
     assert d["vocab"] == m.cfg.vocab
     return d, m
 

@@ -33,7 +33,21 @@ PIN_CASES = [
     ("pin_llama_f16_v512", 1, 7, 4, 4, "-Dllama.VectorBitSize=512"),
     ("pin_llama_f16_v128", 1, 7, 4, 4, "-Dllama.VectorBitSize=128"),
     ("pin_llama_q8_0_f32act_v128", 8, 7, 4, 4, "-Dllama.VectorBitSize=128 -Dllama.quantizeActivation=false"),
+    # PIN_EDITS: the same weights with the edge-value block scales, quants and norm gains of tests/edge_models.py
+    ("pin_llama_q8_0_edges", 8, 7, 4, 4, ""),
 ]
+PIN_EDITS = {"pin_llama_q8_0_edges": "all"}      # file stem -> edits of tests/edge_models.py (the tuples above keep their six fields)
+
+
+def pin_model(pkg, wt, seed, edits=None):
+    """The model of a pin case: the Philox weights of pin_config, with the named edits of tests/edge_models.py applied if any."""
+    cfg = pin_config(pkg)
+    if not edits:
+        return pkg.synth.make_numpy(cfg, wtype=wt, seed=seed)
+    if os.path.join(ROOT, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import edge_models
+    return edge_models.make_edge_model("tiny-llama", wt, seed, edits, name=cfg.name, vocab=cfg.vocab, ctx=cfg.ctx)
 
 
 def tokenizer_metadata(vocab):
@@ -48,9 +62,10 @@ def main(out_dir):
     cfg = pin_config(pkg)
     done = {}
     for stem, wt, seed, n_prompt, n_greedy, flags in PIN_CASES:
-        gguf_name = "pin_llama_%s.gguf" % {8: "q8_0", 1: "f16"}[wt]
+        edits = PIN_EDITS.get(stem)
+        gguf_name = "pin_llama_%s%s.gguf" % ({8: "q8_0", 1: "f16"}[wt], "_edges" if edits else "")
         if gguf_name not in done:
-            m = pkg.synth.make_numpy(cfg, wtype=wt, seed=seed)
+            m = pin_model(pkg, wt, seed, edits)
             md = m.metadata()
             md.update(tokenizer_metadata(cfg.vocab))
             ts = []

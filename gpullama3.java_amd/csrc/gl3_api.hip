@@ -1269,6 +1269,32 @@ int32_t gl3_debug_batch_plan(const int32_t* seq_ids, const int32_t* positions, c
     return GL3_OK;
 }
 
+int32_t gl3_debug_batch_plan_split(const int32_t* seq_ids, const int32_t* positions, int32_t n, int32_t n_seqs, int32_t ctx_len, int32_t capacity,
+                                   int32_t fused_max_pos, int32_t* shallow_out, int32_t* n_shallow, int32_t* deep_out, int32_t* n_deep,
+                                   int32_t* deep_rows, int32_t* n_deep_rows) {
+    if (!shallow_out || !n_shallow || !deep_out || !n_deep || !deep_rows || !n_deep_rows) return GL3_E_ARG;
+    BatchPlan bp;
+    if (batch_plan_build(seq_ids, positions, nullptr, n, n_seqs, ctx_len, capacity, bp)) return GL3_E_ARG;
+    BatchSplit sp;
+    batch_plan_split(bp, fused_max_pos, sp);
+    auto put = [](const std::vector<BatchSpan>& v, int32_t* out, int32_t* cnt) {
+        for (size_t i = 0; i < v.size(); ++i) { out[4 * i] = v[i].row0; out[4 * i + 1] = v[i].rows; out[4 * i + 2] = v[i].seq; out[4 * i + 3] = v[i].pos0; }
+        *cnt = (int32_t)v.size();
+    };
+    put(sp.shallow, shallow_out, n_shallow);
+    put(sp.deep, deep_out, n_deep);
+    for (size_t i = 0; i < sp.deep_rows.size(); ++i) deep_rows[i] = sp.deep_rows[i];
+    *n_deep_rows = (int32_t)sp.deep_rows.size();
+    return GL3_OK;
+}
+
+int32_t gl3_get_attn_rows(gl3_ctx* ctx, int32_t out[4]) {
+    if (!ctx) return GL3_E_ARG;
+    if (!out) GL3_FAIL(GL3_E_ARG, "null out");
+    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched steps need max_batch > 1");
+    return gl3_prefill_attn_rows(ctx, out);
+}
+
 int32_t gl3_sample_rows(gl3_ctx* ctx, const float* logits, int32_t n, const float* temperature, const float* topp, const float* coins,
                         int32_t* tokens_out) {
     if (!ctx) return GL3_E_ARG;

@@ -300,5 +300,6 @@ namespace gl3 { struct BatchPlan; }      // gl3_batch_plan.h
 int32_t gl3_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const gl3::BatchPlan& bp,
                       float* logits_out, int32_t* argmax_out, bool finish = true);
 int32_t gl3_prefill_tap_x(gl3_ctx* ctx, int row, int n);
+int32_t gl3_prefill_attn_rows(gl3_ctx* ctx, int32_t out[4]);      // gl3_get_attn_rows
 void gl3_decode_batch_outputs(gl3_ctx* ctx, const float** logits, const int32_t** greedy);
 int32_t gl3_decode_batch_load_logits(gl3_ctx* ctx, const float* logits, int32_t n);

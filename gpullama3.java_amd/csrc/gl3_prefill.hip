@@ -55,6 +55,11 @@ struct gl3_prefill_state {
     int32_t* seqpos = nullptr;          // [2][M]: sequence id, position of every token of the step
     // mixed steps (gl3_forward_batch): the attention tile table and the output rows of the step, staged with the tokens
     int4* tiles = nullptr;              // [M] BatchSpan records, deepest tile first (gl3_batch_plan.h); PfStep::ntab of them belong to the step
+    int4* deep = nullptr;               // [M] the deep records of the step (batch_plan_split), deepest first; PfStep::ndeep of them
+    int32_t* deep_rows = nullptr;       // [M] the step rows of the deep records, ascending; PfStep::deep_rows of them
+    int tab_max_pos = 0;                // last position a tile may have in the one-launch table form (pf_tab_max_pos; INT_MAX: steps are not split)
+    int32_t attn_rows[4] = {0, 0, 0, 0};      // rows of the last batched step by attention form (gl3_get_attn_rows), from the last layer's pf_attention
+    bool attn_rows_set = false;
     int32_t* out_rows = nullptr;        // [M] rows whose logits are wanted
     float* XG = nullptr;                // [M][dim] those rows of X, compact (allocated by the first mixed step)
     float* LOGITS = nullptr;            // [rows][vocab], grown on demand (batched decode)
@@ -234,6 +239,7 @@ __global__ __launch_bounds__(64) void pf_argmax_fold_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+static int pf_tab_max_pos(const gl3_ctx* ctx);      // next to pf_attention, whose conditions it shares
 int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     const gl3_model_desc& d = ctx->d;
     gl3_prefill_state* p = new gl3_prefill_state();
@@ -260,6 +266,8 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     GL3_HIP(hipMalloc((void**)&p->SUMS, M * d.n_heads * 4));
     GL3_HIP(hipMalloc((void**)&p->seqpos, 2 * M * sizeof(int32_t)));
     GL3_HIP(hipMalloc((void**)&p->tiles, M * sizeof(int4)));
+    GL3_HIP(hipMalloc((void**)&p->deep, M * sizeof(int4)));
+    GL3_HIP(hipMalloc((void**)&p->deep_rows, M * sizeof(int32_t)));
     GL3_HIP(hipMalloc((void**)&p->out_rows, M * sizeof(int32_t)));
     GL3_HIP(hipMalloc((void**)&p->amax, M * sizeof(int32_t)));
     GL3_HIP(hipMalloc((void**)&p->amx_v, M * AMX_SPLIT * sizeof(float)));
@@ -267,6 +275,7 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     { const int32_t ar = pf_attention_attributes(ctx); if (ar != GL3_OK) return ar; }
+    p->tab_max_pos = pf_tab_max_pos(ctx);
     if (p->vl) {       // f32-activation weight types: the GEMMs read f32 rows, no int8 operands
         // XN: normalised / un-chunked f32 operand of the next GEMM (K up to max(dim, q_dim, hidden)); HB2: this rank's up projection
         const size_t kmax = (size_t)(d.hidden > ctx->q_dim ? (d.hidden > d.dim ? d.hidden : d.dim) : (ctx->q_dim > d.dim ? ctx->q_dim : d.dim));
@@ -353,7 +362,7 @@ void gl3_prefill_free(gl3_ctx* ctx) {
     if (!p) return;
     for (auto ge : p->step_graphs) if (ge) hipGraphExecDestroy(ge);
     auto f = [](void* q) { if (q) hipFree(q); };
-    f(p->tokens); f(p->XQ); f(p->XS); f(p->XP); f(p->XQh); f(p->XPh); f(p->XQb); f(p->XSb); f(p->QKV); f(p->ATT); f(p->TMX); f(p->SUMS); f(p->seqpos); f(p->tiles); f(p->out_rows); f(p->XG); f(p->amax); f(p->amx_v); f(p->amx_i); f(p->XN); f(p->HB2);
+    f(p->tokens); f(p->XQ); f(p->XS); f(p->XP); f(p->XQh); f(p->XPh); f(p->XQb); f(p->XSb); f(p->QKV); f(p->ATT); f(p->TMX); f(p->SUMS); f(p->seqpos); f(p->tiles); f(p->deep); f(p->deep_rows); f(p->out_rows); f(p->XG); f(p->amax); f(p->amx_v); f(p->amx_i); f(p->XN); f(p->HB2);
     if (!p->in_arena) { f(p->X); f(p->AO); f(p->HB); f(p->LOGITS); }
     auto& m = p->moe;
     f(m.logits); f(m.w); f(m.sel); f(m.ticket); f(m.slot_tok); f(m.slot_dst); f(m.tab); f(m.HB); f(m.Y); f(m.XQx); f(m.XSx); f(m.XQh); f(m.XSh);
@@ -378,17 +387,21 @@ struct PfStep {
     int n;              // rows (tokens) of the step
     int max_pos;        // largest position of the step
     int one_seq;        // >= 0: all n rows belong to that sequence at consecutive positions ending at max_pos (prefill); -1: rows of many sequences
-    int ntab;           // records of the attention tile table in p->tiles; 0 unless a mixed step has a run of several rows
+    int ntab;           // records of the attention tile table in p->tiles (the shallow tiles); 0 unless a mixed step has a run of several rows
+    int ndeep;          // records of the deep table in p->deep: rows past the one-launch table form's depth, on the long-context trio
+    int deep_rows;      // step rows of the deep records (p->deep_rows)
+    int tab_max_pos;    // last position of the deepest shallow tile (ndeep > 0 only: sizes the one-launch kernels' score rows)
+    bool runs() const { return ntab + ndeep > 0; }      // a mixed step with a run of several rows
 };
 
 // A static-batched decode step whose deepest row is at max_pos runs the one-launch attention (attn_head_kernel).  Asked by the attention
 // dispatch, by the operand hand-over behind it and by the graph capture of the step (only such a step has nothing position-dependent
 // baked in: the three-kernel attention sizes its scores grid by the deepest row), so they cannot disagree.
-// A mixed step with a run of several rows (ntab > 0) never does: attn_head_kernel writes a row's K / V in the launch that reads it, and a
+// A mixed step with a run of several rows (st.runs()) never does: attn_head_kernel writes a row's K / V in the launch that reads it, and a
 // later row of the same run would race with that write.
 static bool pf_fused_decode(const gl3_ctx* ctx, const PfStep& st) {
     static const bool bd_attn_off = env_flag("GL3_NO_FUSED_BD_ATTN", false);      // A/B switch: =1 the three-kernel attention of static-batched decode
-    return ctx->fused_attn_ok && st.max_pos < AF_MAXN && !bd_attn_off && st.ntab == 0;
+    return ctx->fused_attn_ok && st.max_pos < AF_MAXN && !bd_attn_off && !st.runs();
 }
 
 // dynamic LDS of pf_norm_quant_kernel<PQ_NORM> for rows of k elements: the row, the exact sum of squares' scratch, the result
@@ -475,19 +488,53 @@ static inline void pf_kvmul_dispatch(int kvmul, F&& f) {      // pf_scores_pk_ke
     else f(std::integral_constant<int, 1>{});
 }
 
+// The conditions that pf_attention and the split limit of a plan's mixed steps (pf_tab_max_pos) both ask, so they cannot disagree.  The
+// switches are read once per process.
+static bool pf_sw_rows_off() { static const bool v = getenv("GL3_PF_SOFTMAX_ROWS") && atoi(getenv("GL3_PF_SOFTMAX_ROWS")) == 0; return v; }
+static bool pf_sw_fused_off() { static const bool v = getenv("GL3_PF_FUSED_ATTN") && atoi(getenv("GL3_PF_FUSED_ATTN")) == 0; return v; }
+static bool pf_sw_v1_only() { static const bool v = env_flag("GL3_PF_FUSED_V1", false); return v; }
+// r6: pf_softmax_rows_kernel streams the score rows (no row-fits-LDS limit); GL3_PF_SOFTMAX_ROWS=0: the one-row-per-wavefront kernel
+static bool pf_rows_softmax(const gl3_ctx* ctx) {
+    return !pf_sw_rows_off() && ctx->d.ctx % 4 == 0 && ctx->d.ctx >= 64 && ctx->pf->TMX && ctx->pf->SUMS;
+}
+static bool pf_tiled_shape(int hs, int kvmul) { return kvmul <= 4 && (hs == 32 || hs == 64 || hs == 128); }      // shapes the tiled kernels exist for
+static int pf_fa_sstride(int max_pos) { return ((max_pos + 1 + 63) & ~63) + 4; }      // floats of a score row of the one-launch kernels whose deepest row is at max_pos
+// r4: one launch for scores + softmax + weighted V sum when a tile's score rows fit LDS (GL3_PF_FUSED_ATTN=0: the three kernels)
+static bool pf_one_launch_fits(int hs, int kvmul, int sstride) {
+    return !pf_sw_fused_off() && 64 * (hs / 4) <= 8 * 64 * kvmul && fa_smem_bytes(hs, kvmul, sstride) <= PF_ATTN_LDS_MAX;      // 8 float4 per thread stage a tile
+}
+// the table form exists for pf_attn_fused3_kernel / pf_attn_fused2_kernel only: with fused2's rows fitting, one of the two is what the dispatch picks
+static bool pf_tab_fits(int hs, int kvmul, int sstride) {
+    return pf_one_launch_fits(hs, kvmul, sstride) && !pf_sw_v1_only() && fa2_smem_bytes(hs, kvmul, sstride) <= PF_ATTN_LDS_MAX;
+}
+// fused_max_pos of a plan's mixed steps (batch_plan_split): the largest last position a tile may have in the one-launch table form, -1 for
+// a tiled shape without one.  INT_MAX — no split, the dispatch of a step is by its deepest row as before — where the long-context trio
+// cannot take the deep rows: shapes without tiled kernels, plans without pf_softmax_rows_kernel.
+// GL3_PF_TAB_MAXPOS=<p> (diagnostic) lowers the limit to min(own, p), so that a short-context model exercises the split.
+static int pf_tab_max_pos(const gl3_ctx* ctx) {
+    static const char* env = getenv("GL3_PF_TAB_MAXPOS");
+    const int hs = ctx->d.head_size, kvmul = ctx->d.n_heads / ctx->d.n_kv_heads;
+    if (!pf_rows_softmax(ctx) || !pf_tiled_shape(hs, kvmul)) return INT_MAX;
+    int fm = -1;
+    for (int k = 1; 64 * (k - 1) < ctx->d.ctx && pf_tab_fits(hs, kvmul, pf_fa_sstride(64 * k - 1)); ++k) fm = 64 * k - 1;      // score rows grow by 64 positions
+    if (env && *env) fm = std::min(fm, atoi(env));
+    return fm;
+}
+
 // RoPE + KV write + attention of layer l for the n tokens whose raw q | k | v rows are in p->QKV -> AOr (this rank's chunk of the
 // attention output).  fuse_q: static-batched decode on one rank writes the output as the wo projection's int8 operand instead.
 // returns true when the attention output was written as the wo projection's int8 operand (no quantise launch needed)
-// A mixed step with runs of several rows (st.ntab > 0, one_seq < 0): after the one RoPE + KV launch every K / V row of the step is in the
-// caches, and the step takes the run-table form of the one-launch kernels — or, when the shape has none or the deepest row's score rows do
-// not fit LDS, the per-row pair for the whole step.
+// A mixed step with runs of several rows (st.runs(), one_seq < 0): after the one RoPE + KV launch every K / V row of the step is in the
+// caches.  Its shallow tiles (st.ntab records in p->tiles) take the run-table form of the one-launch kernels, its deep rows (st.ndeep records
+// in p->deep, rows past the depth at which a tile's score rows fit LDS) the run-table form of the long-context trio; a step with both writes
+// its output as f32 and the caller's quantise launch serves all rows.  Shapes without tiled kernels and plans without pf_softmax_rows_kernel
+// are not split (pf_tab_max_pos): there the whole step takes the one-launch table form or, failing that, the per-row pair.
+// Every return notes the step's rows by the form that served them (gl3_get_attn_rows).
 static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool fuse_q) {
     // A/B switches, read once at the first call, whichever branch it takes (they are set for the life of the process; nothing sets one
     // after the first step); each says what it turns off where it is used.  The default-on ones keep the getenv / atoi form: set to the
     // empty string it turns the feature off, where env_flag(x, true) would leave it on
-    static const bool rows_off = getenv("GL3_PF_SOFTMAX_ROWS") && atoi(getenv("GL3_PF_SOFTMAX_ROWS")) == 0;
-    static const bool fused_off = getenv("GL3_PF_FUSED_ATTN") && atoi(getenv("GL3_PF_FUSED_ATTN")) == 0;
-    static const bool v1_only = env_flag("GL3_PF_FUSED_V1", false);
+    static const bool v1_only = pf_sw_v1_only();      // (GL3_PF_SOFTMAX_ROWS, GL3_PF_FUSED_ATTN, GL3_PF_FUSED_V1: above, shared with pf_tab_max_pos)
     static const bool qao_off = getenv("GL3_PF_ATTN_QOUT") && atoi(getenv("GL3_PF_ATTN_QOUT")) == 0;
     static const bool mfma_off = getenv("GL3_PF_FUSED_MFMA") && atoi(getenv("GL3_PF_FUSED_MFMA")) == 0;
     static const bool pk_off = getenv("GL3_PF_SCORES_PK") && atoi(getenv("GL3_PF_SCORES_PK")) == 0;
@@ -495,8 +542,10 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     static const int scm_split = getenv("GL3_SCM_SPLIT") ? atoi(getenv("GL3_SCM_SPLIT")) : SCM_SPLIT;      // workgroups that share a (kv head, token tile)'s K tiles
     static const bool ring_off = getenv("GL3_PF_PV_RING") && atoi(getenv("GL3_PF_PV_RING")) == 0;
     static const bool pvm_off = getenv("GL3_PF_PV_MFMA") && atoi(getenv("GL3_PF_PV_MFMA")) == 0;
-    const int n = st.n, max_pos = st.max_pos, one_seq = st.one_seq, ntab = st.ntab;      // ntab > 0: the run-table form
+    const int n = st.n, max_pos = st.max_pos, one_seq = st.one_seq, ntab = st.ntab, ndeep = st.ndeep;
+    const bool runs = st.runs();                          // the run-table forms
     gl3_prefill_state* p = ctx->pf;
+    auto note_rows = [p](int head, int one, int trio, int pair) { p->attn_rows[0] = head; p->attn_rows[1] = one; p->attn_rows[2] = trio; p->attn_rows[3] = pair; p->attn_rows_set = true; };
     const gl3_model_desc& d = ctx->d;
     hipStream_t s = ctx->stream;
     gl3_layer& L = ctx->layers[l];
@@ -531,49 +580,49 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
         ha.group = bd_group;
         if (fuse_q) { ha.xq_out = p->XQ; ha.xs_out = p->XS; ha.xq_slots = bd_tslots(n); }
         attn_head_dispatch(hs, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(H / bd_group, n), dim3(256), attn_head_smem(hs, bd_group), s, ha); });
+        note_rows(n, 0, 0, 0);
         return fuse_q;
     }
     hipLaunchKernelGGL(pf_rope_kv_kernel, dim3(H + KVH, n), dim3(64), 0, s, ra);
-    // r6: pf_softmax_rows_kernel streams the score rows (no row-fits-LDS limit); GL3_PF_SOFTMAX_ROWS=0: the one-row-per-wavefront kernel
-    const bool rows_softmax = !rows_off && d.ctx % 4 == 0 && d.ctx >= 64 && p->TMX && p->SUMS;
-    const bool tiled = (one_seq >= 0 || ntab > 0) && kvmul <= 4 && (hs == 32 || hs == 64 || hs == 128) && (rows_softmax || (size_t)(max_pos + 1) * 4 <= 60 * 1024);
+    const bool rows_softmax = pf_rows_softmax(ctx);
+    const bool tiled = (one_seq >= 0 || runs) && pf_tiled_shape(hs, kvmul) && (rows_softmax || (size_t)(max_pos + 1) * 4 <= 60 * 1024);
     const bool mfma_shape = kvmul == 4 && (hs == 128 || hs == 64);      // the kernels with their products on the matrix pipe
-    // r4: one launch for scores + softmax + weighted V sum when a tile's score rows fit LDS (GL3_PF_FUSED_ATTN=0: the three kernels)
-    const int fa_sstride = ((max_pos + 1 + 63) & ~63) + 4;      // sized by the deepest row of the step
-    const bool one_launch = !fused_off && 64 * (hs / 4) <= 8 * 64 * kvmul && fa_smem_bytes(hs, kvmul, fa_sstride) <= PF_ATTN_LDS_MAX;      // 8 float4 per thread stage a tile
-    // the table form exists for pf_attn_fused3_kernel / pf_attn_fused2_kernel only: with fused2's rows fitting, one of the two is what the dispatch below picks
-    const bool tab_ok = ntab > 0 && tiled && one_launch && !v1_only && fa2_smem_bytes(hs, kvmul, fa_sstride) <= PF_ATTN_LDS_MAX;
+    const int fa_sstride = pf_fa_sstride(ndeep ? st.tab_max_pos : max_pos);      // sized by the deepest row the one-launch kernels serve: of the step, or of its shallow tiles
+    const bool one_launch = pf_one_launch_fits(hs, kvmul, fa_sstride);
+    const bool tab_ok = ntab > 0 && tiled && pf_tab_fits(hs, kvmul, fa_sstride);
     if (!tiled || (ntab > 0 && !tab_ok)) {      // several sequences, or a shape / depth the tiled kernels do not have: the per-token pair
         const size_t sm1 = ((size_t)kvmul * d.head_size + (size_t)ATT_TT * (d.head_size + 1)) * 4;
         hipLaunchKernelGGL(pf_attn_scores_kernel, dim3(nsplit, KVH, n), dim3(64 * kvmul), sm1, s, aa);
         aa.win = ctx->attn_win;
         hipLaunchKernelGGL(pf_attn_softmax_pv_kernel, dim3(H * ((d.head_size + 63) / 64), n), dim3(64), (size_t)ctx->attn_win * 4 + 16, s, aa);
+        note_rows(0, 0, 0, n);
         return false;
     }
     const int pos0 = max_pos + 1 - n;      // one sequence: token b of the chunk sits at position pos0 + b
-    const float* kc1 = aa.kcache + (size_t)(ntab ? 0 : one_seq) * ctx->kv_seq_stride;      // table form: the tile's record names its sequence
-    const float* vc1 = aa.vcache + (size_t)(ntab ? 0 : one_seq) * ctx->kv_seq_stride;
-    if (one_launch) {
-        const dim3 grid(KVH * (ntab ? ntab : (n + FA_TB - 1) / FA_TB));
-        // r6: > 64 tokens on one rank with head size 128: the output is written quantised for the wo GEMM (pf_gemm3_kernel's operand layout)
-        const bool qao = !qao_off && hs == 128 && pf_chunk_major(n) && d.tp_size == 1 && p->XP && !pf_fused_quant_off();
+    const float* kc1 = aa.kcache + (size_t)(runs ? 0 : one_seq) * ctx->kv_seq_stride;      // table forms: the tile's record names its sequence
+    const float* vc1 = aa.vcache + (size_t)(runs ? 0 : one_seq) * ctx->kv_seq_stride;
+    const size_t sst = ctx->kv_seq_stride;
+    if (one_launch && (ndeep == 0 || ntab > 0)) {
+        const dim3 grid(KVH * (runs ? ntab : (n + FA_TB - 1) / FA_TB));
+        // r6: > 64 tokens on one rank with head size 128: the output is written quantised for the wo GEMM (pf_gemm3_kernel's operand layout).
+        // Not in a step that also has deep tiles: the trio writes f32 rows, and the caller's quantise launch serves all rows of the step
+        const bool qao = ndeep == 0 && !qao_off && hs == 128 && pf_chunk_major(n) && d.tp_size == 1 && p->XP && !pf_fused_quant_off();
         uint8_t* xqo = qao ? p->XQ : nullptr;
         uint4* xpo = qao ? reinterpret_cast<uint4*>(p->XP) : nullptr;
         // r6: products of both phases on the matrix pipe (pf_attn_fused3_kernel); GL3_PF_FUSED_MFMA=0: the VALU kernels.  Else packed-f32 scores + pinned
         // weighted V sum (pf_attn_fused2_kernel) while its 16 KB of query rows still fit; GL3_PF_FUSED_V1=1: the r4 kernel
         const size_t sms = fa_smem_bytes(hs, kvmul, fa_sstride), sms2 = fa2_smem_bytes(hs, kvmul, fa_sstride), sms3 = fa3_smem_bytes(hs, fa_sstride);
-        const size_t sst = ctx->kv_seq_stride;
         if (!mfma_off && !v1_only && mfma_shape && sms3 <= PF_ATTN_LDS_MAX)
             pf_head_dispatch<64>(hs, [&](auto hc) {
                 constexpr int HS_ = decltype(hc)::value;
-                if (ntab) hipLaunchKernelGGL((pf_attn_fused3_kernel<HS_, true>), grid, dim3(512), sms3, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
+                if (runs) hipLaunchKernelGGL((pf_attn_fused3_kernel<HS_, true>), grid, dim3(512), sms3, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
                                              KVH, aa.kv_dim, 0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, p->tiles, sst);
                 else hipLaunchKernelGGL((pf_attn_fused3_kernel<HS_>), grid, dim3(512), sms3, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
                                         KVH, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, (const int4*)nullptr, (size_t)0); });
         else if (!v1_only && sms2 <= PF_ATTN_LDS_MAX)
             pf_head_dispatch<32>(hs, [&](auto hc) {
                 constexpr int HS_ = decltype(hc)::value;
-                if (ntab) hipLaunchKernelGGL((pf_attn_fused2_kernel<HS_, true>), grid, dim3(128 * kvmul), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
+                if (runs) hipLaunchKernelGGL((pf_attn_fused2_kernel<HS_, true>), grid, dim3(128 * kvmul), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
                                              KVH, kvmul, aa.kv_dim, 0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, p->tiles, sst);
                 else hipLaunchKernelGGL((pf_attn_fused2_kernel<HS_>), grid, dim3(128 * kvmul), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
                                         KVH, kvmul, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, (const int4*)nullptr, (size_t)0); });
@@ -581,33 +630,47 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
             pf_head_dispatch<32>(hs, [&](auto hc) {
                 hipLaunchKernelGGL((pf_attn_fused_kernel<decltype(hc)::value>), grid, dim3(128 * kvmul), sms, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
                                    KVH, kvmul, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok); });
-        return qao;
+        if (ndeep == 0) { note_rows(0, n, 0, 0); return qao; }
     }
-    const int ntt = (n + PA_TB - 1) / PA_TB;
+    // The long-context trio over score rows in HBM: one sequence's chunk in token tiles of 16 (weighted V sum: 32 on the ring kernel), or
+    // (ndeep > 0) the deep records of a mixed step in the kernels' table forms, the deepest of which sizes the timestep grid
+    const int4* dtab = p->deep;
+    const int ntt = ndeep ? ndeep : (n + PA_TB - 1) / PA_TB;
     const dim3 g1(nsplit, KVH, ntt), b1(64 * kvmul);
     float* tmx = rows_softmax ? p->TMX : nullptr;
     const bool pk = !pk_off && scores_pk_smem_bytes(hs, kvmul) <= PF_ATTN_LDS_MAX && (kvmul == 4 || kvmul == 2 || kvmul == 1);
     if (rows_softmax && !scm_off && mfma_shape) {      // r6: products on the matrix pipe, query rows resident, K tiles prefetched
-        const dim3 g(nsplit < scm_split ? nsplit : scm_split, KVH, (n + SCM_TB - 1) / SCM_TB);
+        const dim3 g(nsplit < scm_split ? nsplit : scm_split, KVH, ndeep ? ndeep : (n + SCM_TB - 1) / SCM_TB);
         pf_head_dispatch<64>(hs, [&](auto hc) {
-            hipLaunchKernelGGL((pf_scores_mfma_kernel<decltype(hc)::value>), g, dim3(512), scores_mfma_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att, aa.n_heads,
-                               aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); });
+            constexpr int HS_ = decltype(hc)::value;
+            if (ndeep) hipLaunchKernelGGL((pf_scores_mfma_kernel<HS_, true>), g, dim3(512), scores_mfma_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att, aa.n_heads,
+                                          aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, dtab, sst);
+            else hipLaunchKernelGGL((pf_scores_mfma_kernel<HS_>), g, dim3(512), scores_mfma_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att, aa.n_heads,
+                                    aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); });
     } else if (pk)
         pf_head_dispatch<32>(hs, [&](auto hc) { pf_kvmul_dispatch(kvmul, [&](auto mc) {
-            hipLaunchKernelGGL((pf_scores_pk_kernel<decltype(hc)::value, decltype(mc)::value>), g1, b1, scores_pk_smem_bytes(hs, kvmul), s, aa.Q, aa.q_stride, kc1, aa.att,
-                               aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, tmx, p->tmx_tiles); }); });
+            constexpr int HS_ = decltype(hc)::value, KVM_ = decltype(mc)::value;
+            if (ndeep) hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_, true>), g1, b1, scores_pk_smem_bytes(hs, kvmul), s, aa.Q, aa.q_stride, kc1, aa.att,
+                                          aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, tmx, p->tmx_tiles, dtab, sst);
+            else hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_>), g1, b1, scores_pk_smem_bytes(hs, kvmul), s, aa.Q, aa.q_stride, kc1, aa.att,
+                                    aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, tmx, p->tmx_tiles); }); });
     else
         pf_head_dispatch<32>(hs, [&](auto hc) {
-            hipLaunchKernelGGL((pf_scores_tiled_kernel<decltype(hc)::value>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att,
-                               aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, tmx, p->tmx_tiles); });
+            constexpr int HS_ = decltype(hc)::value;
+            if (ndeep) hipLaunchKernelGGL((pf_scores_tiled_kernel<HS_, true>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att,
+                                          aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, tmx, p->tmx_tiles, dtab, sst);
+            else hipLaunchKernelGGL((pf_scores_tiled_kernel<HS_>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att,
+                                    aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, tmx, p->tmx_tiles); });
     const float* sums = nullptr;
     if (rows_softmax) {
-        // r6: R rows per workgroup, the sums as R chains of one wavefront; at least one workgroup per CU when the chunk has the rows
-        const int rows = n * H;
+        // r6: R rows per workgroup, the sums as R chains of one wavefront; at least one workgroup per CU when the chunk has the rows.
+        // A split step: the deep rows only (a shallow row's ATT / TMX were not written in this step)
+        const int rows = (ndeep ? st.deep_rows : n) * H;
+        const int32_t* rlist = ndeep ? p->deep_rows : nullptr;
         sums = p->SUMS;
-        if (rows >= 64 * 256) hipLaunchKernelGGL((pf_softmax_rows_kernel<64>), dim3((rows + 63) / 64), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS);
-        else if (rows >= 32 * 256) hipLaunchKernelGGL((pf_softmax_rows_kernel<32>), dim3((rows + 31) / 32), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS);
-        else hipLaunchKernelGGL((pf_softmax_rows_kernel<16>), dim3((rows + 15) / 16), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS);
+        if (rows >= 64 * 256) hipLaunchKernelGGL((pf_softmax_rows_kernel<64>), dim3((rows + 63) / 64), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, rlist);
+        else if (rows >= 32 * 256) hipLaunchKernelGGL((pf_softmax_rows_kernel<32>), dim3((rows + 31) / 32), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, rlist);
+        else hipLaunchKernelGGL((pf_softmax_rows_kernel<16>), dim3((rows + 15) / 16), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, rlist);
     } else {
         const int npad = (max_pos + 1 + 63) & ~63;
         int wpw = (int)((60 * 1024) / ((size_t)npad * 4));
@@ -616,12 +679,18 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     }
     if (sums && !pvm_off && mfma_shape)                 // r6: products on the matrix pipe (no uniform-address LDS reads)
         pf_head_dispatch<64>(hs, [&](auto hc) {
-            hipLaunchKernelGGL((pf_pv_mfma_kernel<decltype(hc)::value>), dim3(KVH, (n + PVM_TB - 1) / PVM_TB), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });
-    else if (sums && !ring_off)
+            constexpr int HS_ = decltype(hc)::value;
+            if (ndeep) hipLaunchKernelGGL((pf_pv_mfma_kernel<HS_, true>), dim3(KVH, ndeep), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, 0, 0, n, sums, dtab);
+            else hipLaunchKernelGGL((pf_pv_mfma_kernel<HS_>), dim3(KVH, (n + PVM_TB - 1) / PVM_TB), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });
+    else if (sums && (!ring_off || ndeep))              // (pf_pv_tiled_kernel has no table form: GL3_PF_PV_RING=0 does not reach the deep rows of a mixed step)
         pf_head_dispatch<32>(hs, [&](auto hc) {
-            hipLaunchKernelGGL((pf_pv_ring_kernel<decltype(hc)::value>), dim3(H, (n + PVR_TB - 1) / PVR_TB), dim3(64 * PVR_NW), pv_ring_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });
+            constexpr int HS_ = decltype(hc)::value;
+            if (ndeep) hipLaunchKernelGGL((pf_pv_ring_kernel<HS_, true>), dim3(H, ndeep), dim3(64 * PVR_NW), pv_ring_smem_bytes(hs), s, aa, 0, 0, n, sums, dtab);
+            else hipLaunchKernelGGL((pf_pv_ring_kernel<HS_>), dim3(H, (n + PVR_TB - 1) / PVR_TB), dim3(64 * PVR_NW), pv_ring_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });
     else if (hs > 64) hipLaunchKernelGGL((pf_pv_tiled_kernel<2>), dim3(H, ntt), dim3(256), pv_tiled_smem_bytes(hs), s, aa, one_seq, pos0, n, sums);
     else hipLaunchKernelGGL((pf_pv_tiled_kernel<1>), dim3(H, ntt), dim3(256), pv_tiled_smem_bytes(hs), s, aa, one_seq, pos0, n, sums);
+    if (ndeep) note_rows(0, n - st.deep_rows, st.deep_rows, 0);
+    else note_rows(0, 0, n, 0);
     return false;
 }
 
@@ -843,6 +912,13 @@ static int32_t pf_layers(gl3_ctx* ctx, const PfStep& st) {
     return GL3_OK;
 }
 
+int32_t gl3_prefill_attn_rows(gl3_ctx* ctx, int32_t out[4]) {
+    gl3_prefill_state* p = ctx->pf;
+    if (!p || !p->attn_rows_set) GL3_FAIL(GL3_E_STATE, "gl3_get_attn_rows before any batched step");
+    for (int i = 0; i < 4; ++i) out[i] = p->attn_rows[i];
+    return GL3_OK;
+}
+
 float* gl3_prefill_buf(gl3_ctx* ctx, int which) {
     gl3_prefill_state* p = ctx->pf;
     return which == GB_PF_X ? p->X : which == GB_PF_AO ? p->AO : which == GB_PF_HB ? p->HB : p->LOGITS;
@@ -977,6 +1053,7 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
             hipGraphDestroy(g);
         }
         GL3_HIP(hipGraphLaunch(p->step_graphs[n], s));
+        p->attn_rows[0] = n; p->attn_rows[1] = p->attn_rows[2] = p->attn_rows[3] = 0; p->attn_rows_set = true;      // a replay does not pass pf_attention: the captured step is attn_head_kernel's
     } else if ((r = enqueue_step(st)) != GL3_OK) return r;
     if (argmax_out) GL3_HIP(hipMemcpyAsync(argmax_out, p->amax, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (logits_out) {      // un-chunk on the way out: [tp][n][vl] -> [n][vocab]
@@ -995,6 +1072,8 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
 // over (token, sequence, position) rows as in a static-batched step; the attention takes the run-table form (pf_attention); the logits stage
 // runs over the rows the caller flagged only.  Eager: the shape of a step differs from call to call.  One rank, plain row layouts.
 static_assert(BP_TILE_ROWS == FA_TB, "the step plan cuts runs into the attention kernels' token tiles");
+static_assert(BP_DEEP_ROWS == PA_TB && BP_DEEP_ROWS == SCM_TB && BP_DEEP_ROWS == PVM_TB && BP_DEEP_ROWS <= PVR_TB,
+              "the step plan cuts deep rows into the long-context kernels' token tiles (one record per workgroup of pf_pv_ring_kernel)");
 static_assert(sizeof(BatchSpan) == sizeof(int4), "a tile record is read as one int4");
 
 // rows[r] of X -> row r of out (float4 per thread; dim % 4 == 0)
@@ -1025,10 +1104,17 @@ int32_t gl3_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_id
     hipStream_t s = ctx->stream;
     int32_t r = pf_stage_tokens(ctx, tokens, seq_ids, positions, n);
     if (r != GL3_OK) return r;
-    const int ntab = bp.single_rows ? 0 : (int)bp.tiles.size();
-    if (ntab) GL3_HIP(hipMemcpyAsync(p->tiles, bp.tiles.data(), (size_t)ntab * sizeof(BatchSpan), hipMemcpyHostToDevice, s));
+    // a step with a run of several rows: its tiles by depth (shallow: the one-launch table form; deep: the long-context trio), staged with the tokens
+    BatchSplit sp;
+    if (!bp.single_rows) batch_plan_split(bp, p->tab_max_pos, sp);
+    const int ntab = (int)sp.shallow.size(), ndeep = (int)sp.deep.size(), deep_rows = (int)sp.deep_rows.size();
+    if (ntab) GL3_HIP(hipMemcpyAsync(p->tiles, sp.shallow.data(), (size_t)ntab * sizeof(BatchSpan), hipMemcpyHostToDevice, s));
+    if (ndeep) {
+        GL3_HIP(hipMemcpyAsync(p->deep, sp.deep.data(), (size_t)ndeep * sizeof(BatchSpan), hipMemcpyHostToDevice, s));
+        GL3_HIP(hipMemcpyAsync(p->deep_rows, sp.deep_rows.data(), (size_t)deep_rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
     if (n_out) GL3_HIP(hipMemcpyAsync(p->out_rows, bp.out_rows.data(), (size_t)n_out * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if ((r = pf_layers(ctx, PfStep{n, bp.max_pos, -1, ntab})) != GL3_OK) return r;
+    if ((r = pf_layers(ctx, PfStep{n, bp.max_pos, -1, ntab, ndeep, deep_rows, sp.shallow_max_pos})) != GL3_OK) return r;
     // keep the decode path's x in step with the last row (parity tap gl3_get_x)
     hipLaunchKernelGGL(pf_unchunk_row_kernel, dim3(4), dim3(256), 0, s, p->X, n - 1, d.dim, ctx->dim_l, n, ctx->x);
     if (n_out) {      // output RMSNorm + vocabulary projection + greedy ids of the flagged rows, compact

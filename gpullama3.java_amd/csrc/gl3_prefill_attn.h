@@ -199,15 +199,38 @@ __device__ __forceinline__ void score_step16(float& s0, float& s1, const v16f_t&
     }
 }
 constexpr int PA_TB = 16;
-template <int HS>
+// The token tile of a workgroup of the long-context kernels (scores / weighted V sum over score rows in HBM).  One sequence (TAB = false): tile
+// `tile` of TB rows of the chunk, (pos0, ntok) from the arguments.  Run-table form (TAB = true, the deep rows of a mixed step of
+// gl3_forward_batch): `tile` picks a record {first row, rows <= 16, sequence, position of the first row} of the step's deep table
+// (gl3_batch_plan.h: batch_plan_split); the caches move to the record's sequence and pos0 becomes position - row, so that everything behind
+// this prologue — "row b of the step sits at position pos0 + b", the clamps, the per-tile maxima, the e / sum staging — is the one-sequence
+// code unchanged, with ATT / TMX / SUMS indexed by step row.  `tile` is a blockIdx component: the record arrives by a scalar load and the
+// four values are wavefront-uniform (SGPRs), as in fa_tile of the one-launch kernels.
+struct LcTile { int b0, nb, pos0; size_t cache_off; };           // cache_off: floats from the caches' base to the tile's sequence
+template <bool TAB, int TB>
+__device__ __forceinline__ LcTile lc_tile(int tile, int pos0, int ntok, const int4* __restrict__ tab, size_t seq_stride) {
+    LcTile r;
+    if constexpr (TAB) {
+        const int4 rec = tab[tile];
+        r.b0 = __builtin_amdgcn_readfirstlane(rec.x); r.nb = __builtin_amdgcn_readfirstlane(rec.y);
+        r.cache_off = (size_t)__builtin_amdgcn_readfirstlane(rec.z) * seq_stride;
+        r.pos0 = __builtin_amdgcn_readfirstlane(rec.w) - r.b0;
+    } else {
+        r.b0 = tile * TB; r.nb = min(TB, ntok - r.b0); r.pos0 = pos0; r.cache_off = 0;
+    }
+    return r;
+}
+template <int HS, bool TAB = false>
 __global__ __launch_bounds__(256) void pf_scores_tiled_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc,
                                                               float* __restrict__ att, int n_heads, int kvmul, int kv_dim, int ctx,
-                                                              int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles) {
+                                                              int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles,
+                                                              const int4* __restrict__ tab = nullptr, size_t seq_stride = 0) {
     extern __shared__ __attribute__((aligned(16))) float kt[];       // [64][PITCH]
     constexpr int PITCH = HS + 4, H4 = HS / 4;
     const int t = threadIdx.x, nthr = blockDim.x;
-    const int t0 = blockIdx.x * 64, kvh = blockIdx.y, b0 = blockIdx.z * PA_TB;
-    const int nb = min(PA_TB, ntok - b0);
+    const LcTile lt = lc_tile<TAB, PA_TB>(blockIdx.z, pos0, ntok, tab, seq_stride);
+    const int t0 = blockIdx.x * 64, kvh = blockIdx.y, b0 = lt.b0, nb = lt.nb;
+    pos0 = lt.pos0; kc += lt.cache_off;               // of the tile's sequence from here on
     const int tmax = pos0 + b0 + nb - 1;              // last timestep any token of this tile attends to
     if (tmax < t0) return;
     const int t1 = min(tmax + 1, t0 + 64);
@@ -273,16 +296,18 @@ __global__ __launch_bounds__(256) void pf_scores_tiled_kernel(const float* __res
 // query rows per workgroup.)  K rows in registers as before, lane = timestep.  Two wavefronts per SIMD (~210 VGPRs, 65 KB of LDS).
 __host__ __device__ constexpr size_t scores_tiled_smem_bytes(int hs) { return (size_t)64 * (hs + 4) * 4; }                     // pf_scores_tiled_kernel: the K tile
 __host__ __device__ constexpr size_t scores_pk_smem_bytes(int hs, int kvmul) { return scores_tiled_smem_bytes(hs) + (size_t)kvmul * PA_TB * hs * 4; }
-template <int HS, int KVM>
+template <int HS, int KVM, bool TAB = false>
 __global__ __launch_bounds__(64 * KVM) __attribute__((amdgpu_waves_per_eu(2, 2))) void pf_scores_pk_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc,
-        float* __restrict__ att, int n_heads, int kvmul_, int kv_dim, int ctx, int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles) {
+        float* __restrict__ att, int n_heads, int kvmul_, int kv_dim, int ctx, int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles,
+        const int4* __restrict__ tab = nullptr, size_t seq_stride = 0) {
     extern __shared__ __attribute__((aligned(16))) float kt[];       // [64][PITCH] K rows, then [KVM][8 pairs][HS][2] query rows
     constexpr int PITCH = HS + 4, H4 = HS / 4, NGR = HS / 8, NT = 64 * KVM, KPT = 64 * H4 / NT, QPT = H4 / 8, kvmul = KVM;
     static_assert(KPT >= 1 && QPT >= 1, "staging slots per thread");
     float* qs = kt + 64 * PITCH;
     const int t = threadIdx.x;
-    const int t0 = blockIdx.x * 64, kvh = blockIdx.y, b0 = blockIdx.z * PA_TB;
-    const int nb = min(PA_TB, ntok - b0);
+    const LcTile lt = lc_tile<TAB, PA_TB>(blockIdx.z, pos0, ntok, tab, seq_stride);
+    const int t0 = blockIdx.x * 64, kvh = blockIdx.y, b0 = lt.b0, nb = lt.nb;
+    pos0 = lt.pos0; kc += lt.cache_off;               // of the tile's sequence from here on
     const int tmax = pos0 + b0 + nb - 1;
     if (tmax < t0) return;
     const int t1 = min(tmax + 1, t0 + 64);
@@ -394,24 +419,29 @@ __global__ __launch_bounds__(256) void pf_softmax_kernel(const PfAttnArgs a, int
 // (J/tensor/standard/FloatTensor.java:196-219: max, exp, sum, divide).  pf_softmax_kernel keeps ONE row per wavefront in LDS: its row loads
 // are one HBM round trip per 64 scores, its sums one chain per wavefront and at most three rows per workgroup fit at 4608 positions:
 // 640 us per 8B layer at pp512 @ d4096 against ~150 us here.  Needs ctx % 4 == 0 (16-byte row starts).
+// `rows` (null: every row of the step, row i = (token i / n_heads, head i % n_heads)): the deep step rows of a mixed step, ascending — the launch
+// covers rows x n_heads score rows and touches ATT / TMX / SUMS of those step rows only (a shallow row's were not written in this step).
 constexpr int SR_PITCH = 68;
 template <int R>
-__global__ __launch_bounds__(576) void pf_softmax_rows_kernel(const PfAttnArgs a, int nrows_total, const float* __restrict__ tmx, int tmx_tiles, float* __restrict__ sums) {
+__global__ __launch_bounds__(576) void pf_softmax_rows_kernel(const PfAttnArgs a, int nrows_total, const float* __restrict__ tmx, int tmx_tiles, float* __restrict__ sums,
+                                                              const int32_t* __restrict__ rows = nullptr) {
     __shared__ __attribute__((aligned(16))) float E[2][R * SR_PITCH];
     __shared__ float mx_s[R];
     __shared__ int n_s[R];
+    __shared__ int row_s[R];                          // the (step row, head) score row of the workgroup's row r
     __shared__ int nmax_s;
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int row0 = blockIdx.x * R;
     if (t == 0) nmax_s = 0;
     if (t < R * 8) {                                  // 8 lanes fold a row's tile maxima
-        const int r = t >> 3, sub = t & 7, row = row0 + r;
-        const int n = row < nrows_total ? a.pos[row / a.n_heads] + 1 : 0;
+        const int r = t >> 3, sub = t & 7, lrow = min(row0 + r, nrows_total - 1);
+        const int row = rows ? rows[lrow / a.n_heads] * a.n_heads + lrow % a.n_heads : lrow;
+        const int n = row0 + r < nrows_total ? a.pos[row / a.n_heads] + 1 : 0;
         const int nt = (n + 63) >> 6;
         float m = -INFINITY;
         for (int i = sub; i < nt; i += 8) m = fmaxf(m, tmx[(size_t)row * tmx_tiles + i]);
         m = row8_max(m);
-        if (sub == 0) { mx_s[r] = m; n_s[r] = n; }
+        if (sub == 0) { mx_s[r] = m; n_s[r] = n; row_s[r] = row; }
     }
     __syncthreads();
     if (t < R) atomicMax(&nmax_s, n_s[t]);
@@ -424,7 +454,7 @@ __global__ __launch_bounds__(576) void pf_softmax_rows_kernel(const PfAttnArgs a
             __syncthreads();                          // tile k has landed in E[k & 1]; the workers refill it behind the NEXT barrier
             s = seq_sum_lds_ring(&E[k & 1][r * SR_PITCH], 64, s);
         }
-        if (lane < R && row0 + lane < nrows_total) sums[row0 + lane] = s;
+        if (lane < R && row0 + lane < nrows_total) sums[row_s[lane]] = s;
         return;
     }
     constexpr int NS = (R * 16 + 511) / 512;          // 16-byte slots per worker thread and tile
@@ -432,7 +462,7 @@ __global__ __launch_bounds__(576) void pf_softmax_rows_kernel(const PfAttnArgs a
 #pragma unroll
     for (int u = 0; u < NS; ++u) {
         const int q = min(t + 512 * u, R * 16 - 1), r = q >> 4, c4 = q & 15;
-        rowp[u] = a.att + (size_t)min(row0 + r, nrows_total - 1) * a.ctx + 4 * c4;
+        rowp[u] = a.att + (size_t)row_s[r] * a.ctx + 4 * c4;
         mrow[u] = mx_s[r];
         nrow[u] = (t + 512 * u < R * 16) ? n_s[r] - 4 * c4 : 0;       // elements of the row at and behind this slot's first column of tile 0
         ldsoff[u] = r * SR_PITCH + 4 * c4;
@@ -591,18 +621,21 @@ constexpr int PVR_NW = 8, PVR_TB = 4 * PVR_NW;     // 8 wavefronts of 4 tokens: 
         } \
         if (g < ng_) PVR_ACC(va, wa0, wa1, wa2, wa3); } while (0)
 __host__ __device__ constexpr size_t pv_ring_smem_bytes(int hs) { return (size_t)64 * (hs + PVR_TB) * 4; }
-template <int HS>
-__global__ __launch_bounds__(64 * PVR_NW) void pf_pv_ring_kernel(const PfAttnArgs a, int seq, int pos0, int ntok, const float* __restrict__ sums) {
+template <int HS, bool TAB = false>
+__global__ __launch_bounds__(64 * PVR_NW) void pf_pv_ring_kernel(const PfAttnArgs a, int seq, int pos0, int ntok, const float* __restrict__ sums,
+                                                                const int4* __restrict__ tab = nullptr) {
     constexpr int NCOL = HS > 64 ? 2 : 1, H4 = HS / 4, NT = 64 * PVR_NW, VPT = 64 * H4 / NT;
     static_assert(VPT >= 1, "a V tile is at least one 16-byte slot per thread");
     extern __shared__ __attribute__((aligned(16))) float vt[];        // [64][HS] V rows, then [PVR_TB][64] weights
     float* as = vt + 64 * HS;
     const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int kvmul = a.n_heads / a.n_kv_heads, h = blockIdx.x, kvh = h / kvmul, b0 = blockIdx.y * PVR_TB;
-    const int nb = min(PVR_TB, ntok - b0);
+    // table form: one deep record (<= 16 rows) per workgroup; wavefronts 4 - 7 see 4 w >= nb and idle through wmax = -1
+    const LcTile lt = lc_tile<TAB, PVR_TB>(blockIdx.y, pos0, ntok, tab, a.seq_stride);
+    const int kvmul = a.n_heads / a.n_kv_heads, h = blockIdx.x, kvh = h / kvmul, b0 = lt.b0, nb = lt.nb;
+    pos0 = lt.pos0;
     const int tmax = pos0 + b0 + nb - 1, ntile = tmax / 64 + 1;
     const int wmax = 4 * w < nb ? pos0 + b0 + min(4 * w + 3, nb - 1) : -1;     // last position any of this wavefront's four tokens attends to
-    const float* vc = a.vcache + (size_t)seq * a.seq_stride + kvh * HS;
+    const float* vc = a.vcache + (TAB ? lt.cache_off : (size_t)seq * a.seq_stride) + kvh * HS;
     // staging roles: thread = (token w + PVR_NW j, timestep lane) of the weights; 16-byte slots t + NT j of the V tile
     const float* arow[4]; float rsum[4]; int apos[4];
 #pragma unroll
@@ -1285,8 +1318,9 @@ __global__ __launch_bounds__(512) void pf_attn_fused3_kernel(const float* __rest
 // tile's arithmetic.
 constexpr int PVM_TB = 16, PVM_WP = 68;
 __host__ __device__ constexpr size_t pv_mfma_smem_bytes(int hs) { return ((size_t)64 * (hs + 4) + 4 * PVM_TB * PVM_WP) * 4; }
-template <int HS>
-__global__ __launch_bounds__(1024) void pf_pv_mfma_kernel(const PfAttnArgs a, int seq, int pos0, int ntok, const float* __restrict__ sums) {
+template <int HS, bool TAB = false>
+__global__ __launch_bounds__(1024) void pf_pv_mfma_kernel(const PfAttnArgs a, int seq, int pos0, int ntok, const float* __restrict__ sums,
+                                                          const int4* __restrict__ tab = nullptr) {
     constexpr int PITCH = HS + 4, H4 = HS / 4, NT = 1024, VPT = 64 * H4 / NT, KVM = 4;
     static_assert(VPT >= 1, "a V tile is at least one 16-byte slot per thread");
     extern __shared__ __attribute__((aligned(16))) float vt[];        // [64][PITCH] V rows, then [4 heads x 16 tokens][PVM_WP] weights
@@ -1294,10 +1328,11 @@ __global__ __launch_bounds__(1024) void pf_pv_mfma_kernel(const PfAttnArgs a, in
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int rg = wave & 3, cq = wave >> 2;                          // query head of the kv group, 32-column slice
     const int lq = lane >> 4, li = lane & 15, par = lq >> 1, cg = lq & 1;
-    const int kvh = blockIdx.x, b0 = blockIdx.y * PVM_TB;
-    const int nb = min(PVM_TB, ntok - b0);
+    const LcTile lt = lc_tile<TAB, PVM_TB>(blockIdx.y, pos0, ntok, tab, a.seq_stride);
+    const int kvh = blockIdx.x, b0 = lt.b0, nb = lt.nb;
+    pos0 = lt.pos0;
     const int tmax = pos0 + b0 + nb - 1, ntile = tmax / 64 + 1;
-    const float* vc = a.vcache + (size_t)seq * a.seq_stride + kvh * HS;
+    const float* vc = a.vcache + (TAB ? lt.cache_off : (size_t)seq * a.seq_stride) + kvh * HS;
     const v16f_t zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     // staging roles: thread = (row wave + 16 j, timestep lane) of the weights; 16-byte slots t + NT j of the V tile
     const float* arow[4]; float rsum[4]; int apos[4];
@@ -1355,9 +1390,10 @@ __global__ __launch_bounds__(1024) void pf_pv_mfma_kernel(const PfAttnArgs a, in
 // for pf_softmax_rows_kernel: registers -> two cross-row exchanges -> one LDS slot per (quarter, row) -> 64 threads fold the quarters.
 constexpr int SCM_TB = 16, SCM_SPLIT = 4;
 __host__ __device__ constexpr size_t scores_mfma_smem_bytes(int hs) { return ((size_t)64 * (hs + 4) + 4 * SCM_TB * (hs + 2) + 4 * 4 * SCM_TB) * 4; }
-template <int HS>
+template <int HS, bool TAB = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void pf_scores_mfma_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc, float* __restrict__ att,
-                                                             int n_heads, int kv_dim, int ctx, int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles) {
+                                                             int n_heads, int kv_dim, int ctx, int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles,
+                                                             const int4* __restrict__ tab = nullptr, size_t seq_stride = 0) {
     extern __shared__ __attribute__((aligned(16))) float kt[];       // [64][PITCH] K rows, then [64 rows][QP] query rows, then [4][64] quarter maxima
     constexpr int KVM = 4, ROWS = KVM * SCM_TB, PITCH = HS + 4, H4 = HS / 4, QP = HS + 2, NM = HS / 2, NT = 512, KPT = 64 * H4 / NT;
     static_assert(KPT >= 1 && NM % 16 == 0, "staging slots per thread; operand ring of 8 MFMAs");
@@ -1366,8 +1402,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int tq = wave & 3, rp = wave >> 2;
     const int lq = lane >> 4, li = lane & 15, par = lq >> 1, rsel = lq & 1;
-    const int split = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y, b0 = blockIdx.z * SCM_TB;
-    const int nb = min(SCM_TB, ntok - b0);
+    const LcTile lt = lc_tile<TAB, SCM_TB>(blockIdx.z, pos0, ntok, tab, seq_stride);
+    const int split = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y, b0 = lt.b0, nb = lt.nb;
+    pos0 = lt.pos0; kc += lt.cache_off;               // of the tile's sequence from here on
     const int tmax = pos0 + b0 + nb - 1, ntile = tmax / 64 + 1;
     if (split >= ntile) return;
     const float sqrt_hs = (float)sqrt((double)HS);
@@ -1448,6 +1485,11 @@ static int32_t pf_attention_attributes(gl3_ctx* ctx) {
     GL3_ATTR150((pf_scores_pk_kernel<128, 4>)); GL3_ATTR150((pf_scores_pk_kernel<128, 2>)); GL3_ATTR150((pf_scores_pk_kernel<128, 1>));
     GL3_ATTR150((pf_scores_pk_kernel<64, 4>)); GL3_ATTR150((pf_scores_pk_kernel<64, 2>)); GL3_ATTR150((pf_scores_pk_kernel<64, 1>));
     GL3_ATTR150((pf_scores_pk_kernel<32, 4>)); GL3_ATTR150((pf_scores_pk_kernel<32, 2>)); GL3_ATTR150((pf_scores_pk_kernel<32, 1>));
+    // the run-table forms of the long-context kernels (the deep rows of a mixed step)
+    GL3_ATTR150((pf_scores_mfma_kernel<128, true>)); GL3_ATTR150((pf_scores_mfma_kernel<64, true>)); GL3_ATTR150((pf_pv_mfma_kernel<128, true>)); GL3_ATTR150((pf_pv_mfma_kernel<64, true>));
+    GL3_ATTR150((pf_scores_pk_kernel<128, 4, true>)); GL3_ATTR150((pf_scores_pk_kernel<128, 2, true>)); GL3_ATTR150((pf_scores_pk_kernel<128, 1, true>));
+    GL3_ATTR150((pf_scores_pk_kernel<64, 4, true>)); GL3_ATTR150((pf_scores_pk_kernel<64, 2, true>)); GL3_ATTR150((pf_scores_pk_kernel<64, 1, true>));
+    GL3_ATTR150((pf_scores_pk_kernel<32, 4, true>)); GL3_ATTR150((pf_scores_pk_kernel<32, 2, true>)); GL3_ATTR150((pf_scores_pk_kernel<32, 1, true>));
 #undef GL3_ATTR150
     return GL3_OK;
 }

@@ -303,6 +303,13 @@ class HipMasterPlan:
         hip.check(hip.lib().gl3_get_x(self._ctx, _p(out)), self._ctx)
         return out
 
+    def attn_rows(self):
+        """Rows of the last batched step by the attention form that served them (gl3_get_attn_rows): [attn_head_kernel, one-launch tiled
+        kernels, long-context trio, per-row pair]."""
+        out = np.zeros(4, np.int32)
+        hip.check(hip.lib().gl3_get_attn_rows(self._ctx, _p(out)), self._ctx)
+        return out.tolist()
+
     def layer_x(self, layer: int):
         out = np.empty(self.cfg.dim, np.float32)
         hip.check(hip.lib().gl3_get_layer_x(self._ctx, layer, _p(out)), self._ctx)

@@ -288,7 +288,10 @@ GL3_API int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tok
  * run); logits_out: f32[n_out][vocab] or NULL, argmax_out: int32[n_out] or NULL.  n_out == 0 is a pure multi-sequence prefill (no output
  * norm, vocabulary projection or argmax is launched).  Afterwards gl3_get_x returns x of the last row and gl3_get_buffer(4..6) hold all n
  * rows in step order.  The step runs eagerly (its shape differs from call to call); a step whose runs are all single rows and whose rows
- * all want logits is a gl3_forward_decode_batch step.  GL3_E_ARG, before anything is enqueued: null arrays, n <= 0, n > max_batch, a
+ * all want logits is a gl3_forward_decode_batch step.  Attention of a step with a run of several rows, at any depth: its 8-row tiles whose
+ * score rows fit LDS run on the one-launch tiled kernels, its deeper rows on the long-context scores / softmax / weighted-sum kernels (both
+ * in their run-table forms, the split by depth per tile, not per step); head sizes other than 32 / 64 / 128 and more than 4 query heads per
+ * kv head run row by row (gl3_get_attn_rows tells).  GL3_E_ARG, before anything is enqueued: null arrays, n <= 0, n > max_batch, a
  * token / sequence / position out of range or a run ending past ctx, a sequence id in two runs, positions inside a run that are not
  * consecutive ascending.  GL3_E_UNSUPPORTED: max_batch <= 1; tp_size > 1 — the mixed step is built for ONE rank. */
 GL3_API int32_t gl3_forward_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
@@ -306,6 +309,20 @@ GL3_API int32_t gl3_forward_batch_sample(gl3_ctx* ctx, const int32_t* tokens, co
 GL3_API int32_t gl3_debug_batch_plan(const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits, int32_t n,
                                      int32_t n_seqs, int32_t ctx, int32_t capacity, int32_t* runs_out, int32_t* n_runs,
                                      int32_t* tiles_out, int32_t* n_tiles, int32_t* out_rows, int32_t* n_out);
+/* Test hook, no plan and no device: that plan's attention tiles split by depth (batch_plan_split).  fused_max_pos = the largest last position
+ * a tile may have in the one-launch table form (-1: every row is deep; >= ctx: shallow_out is gl3_debug_batch_plan's tiles_out and nothing
+ * is deep).  shallow_out: the tiles with last position <= fused_max_pos, deepest last position first; deep_out: records of at most 16 rows
+ * cut from each run's deep suffix, starting at its first deep row, never across a run boundary, deepest last position first (both
+ * int32[.][4] as above, room for n records each); deep_rows: int32[n], the step rows of the deep records, ascending.  GL3_E_ARG as
+ * gl3_debug_batch_plan. */
+GL3_API int32_t gl3_debug_batch_plan_split(const int32_t* seq_ids, const int32_t* positions, int32_t n, int32_t n_seqs, int32_t ctx,
+                                           int32_t capacity, int32_t fused_max_pos, int32_t* shallow_out, int32_t* n_shallow,
+                                           int32_t* deep_out, int32_t* n_deep, int32_t* deep_rows, int32_t* n_deep_rows);
+/* Dispatch tap: the rows of the last batched step (gl3_forward_prefill_seq, gl3_forward_decode_batch, gl3_forward_batch and their sampled
+ * forms) by the attention form that served them in the last layer — out[0] attn_head_kernel (RoPE + attention in one launch per row),
+ * out[1] the one-launch tiled kernels, out[2] the long-context trio (scores, softmax rows, weighted V sum), out[3] the per-row pair.  The
+ * four sum to the step's n.  Host bookkeeping only.  GL3_E_STATE before any batched step, GL3_E_UNSUPPORTED without max_batch > 1. */
+GL3_API int32_t gl3_get_attn_rows(gl3_ctx* ctx, int32_t out[4]);
 
 /* Parity tap: the probabilities (f32[vocab]) row `row` of the last batched sampled step (or gl3_sample_rows call) was drawn from
  * (GL3_E_STATE for a greedy row or before any such step). */

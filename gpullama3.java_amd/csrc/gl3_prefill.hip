@@ -473,18 +473,20 @@ static void launch_gemm_grouped(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, i
     else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 8, 2, false, BD_TS, true>), grid, dim3(64), 0, ctx->stream, a);
 }
 
-// A head size / kvMul that a prefill attention kernel takes as a template argument: f(std::integral_constant<int, ...>{}).  MIN_HS = 64: the kernels
-// with their products on the matrix pipe, which exist for head sizes 128 and 64 only (their callers have checked the shape).
-template <int MIN_HS, class F>
+// A head size / head-slot count that a prefill attention kernel takes as a template argument: f(std::integral_constant<int, ...>{}).  MIN_HS = 64: the
+// kernels with their products on the matrix pipe, which exist for head sizes 128 and 64 only (their callers have checked the shape).  HS96: the VALU
+// long-context kernels (pf_scores_pk_kernel, pf_scores_tiled_kernel, pf_pv_ring_kernel), the only tiled kernels instantiated for head size 96.
+template <int MIN_HS, bool HS96 = false, class F>
 static inline void pf_head_dispatch(int hs, F&& f) {
     if (hs == 128) f(std::integral_constant<int, 128>{});
     else if (hs == 64) f(std::integral_constant<int, 64>{});
+    else if (HS96 && hs == 96) { if constexpr (HS96) f(std::integral_constant<int, 96>{}); }
     else if constexpr (MIN_HS <= 32) f(std::integral_constant<int, 32>{});
 }
 template <class F>
-static inline void pf_kvmul_dispatch(int kvmul, F&& f) {      // pf_scores_pk_kernel: 4, 2 or 1 query heads per kv head
-    if (kvmul == 4) f(std::integral_constant<int, 4>{});
-    else if (kvmul == 2) f(std::integral_constant<int, 2>{});
+static inline void pf_kvmul_dispatch(int slots, F&& f) {      // pf_scores_pk_kernel: 4, 2 or 1 head slots per workgroup
+    if (slots == 4) f(std::integral_constant<int, 4>{});
+    else if (slots == 2) f(std::integral_constant<int, 2>{});
     else f(std::integral_constant<int, 1>{});
 }
 
@@ -493,19 +495,32 @@ static inline void pf_kvmul_dispatch(int kvmul, F&& f) {      // pf_scores_pk_ke
 static bool pf_sw_rows_off() { static const bool v = getenv("GL3_PF_SOFTMAX_ROWS") && atoi(getenv("GL3_PF_SOFTMAX_ROWS")) == 0; return v; }
 static bool pf_sw_fused_off() { static const bool v = getenv("GL3_PF_FUSED_ATTN") && atoi(getenv("GL3_PF_FUSED_ATTN")) == 0; return v; }
 static bool pf_sw_v1_only() { static const bool v = env_flag("GL3_PF_FUSED_V1", false); return v; }
+static bool pf_sw_ring_off() { static const bool v = getenv("GL3_PF_PV_RING") && atoi(getenv("GL3_PF_PV_RING")) == 0; return v; }
 // r6: pf_softmax_rows_kernel streams the score rows (no row-fits-LDS limit); GL3_PF_SOFTMAX_ROWS=0: the one-row-per-wavefront kernel
 static bool pf_rows_softmax(const gl3_ctx* ctx) {
     return !pf_sw_rows_off() && ctx->d.ctx % 4 == 0 && ctx->d.ctx >= 64 && ctx->pf->TMX && ctx->pf->SUMS;
 }
-static bool pf_tiled_shape(int hs, int kvmul) { return kvmul <= 4 && (hs == 32 || hs == 64 || hs == 128); }      // shapes the tiled kernels exist for
+// A workgroup of the tiled kernels serves a head group (HeadGroup, gl3_prefill_attn.h): pf_group_size(kvMul) head slots, pf_head_groups(kvMul) groups per
+// kv head.  Every LDS size and fit below is asked with the group size: a grouped shape has the limits of kvMul 4 at its head size.
+static int pf_group_size(int kvmul) { return std::min(kvmul, 4); }
+static int pf_head_groups(int kvmul) { const int g = pf_group_size(kvmul); return (kvmul + g - 1) / g; }
+// Shapes the tiled kernels exist for.  kvMul <= 4 at head size 32 / 64 / 128: as ever.  kvMul 5 - 16 (head groups) and head size 96 (the VALU
+// long-context kernels only; the group is orthogonal to the head size, so 96 is served above kvMul 4 too): with pf_softmax_rows_kernel and without
+// the two switches whose kernels know neither (GL3_PF_FUSED_V1=1: pf_attn_fused_kernel, GL3_PF_PV_RING=0: pf_pv_tiled_kernel) — there they keep
+// the per-row pair.
+static bool pf_tiled_shape(int hs, int kvmul, bool rows_softmax) {
+    if (kvmul <= 4 && (hs == 32 || hs == 64 || hs == 128)) return true;
+    return kvmul <= 16 && (hs == 32 || hs == 64 || hs == 96 || hs == 128) && rows_softmax && !pf_sw_v1_only() && !pf_sw_ring_off();
+}
 static int pf_fa_sstride(int max_pos) { return ((max_pos + 1 + 63) & ~63) + 4; }      // floats of a score row of the one-launch kernels whose deepest row is at max_pos
 // r4: one launch for scores + softmax + weighted V sum when a tile's score rows fit LDS (GL3_PF_FUSED_ATTN=0: the three kernels)
-static bool pf_one_launch_fits(int hs, int kvmul, int sstride) {
-    return !pf_sw_fused_off() && 64 * (hs / 4) <= 8 * 64 * kvmul && fa_smem_bytes(hs, kvmul, sstride) <= PF_ATTN_LDS_MAX;      // 8 float4 per thread stage a tile
+// (group = head slots of a workgroup, pf_group_size; no one-launch kernel at head size 96)
+static bool pf_one_launch_fits(int hs, int group, int sstride) {
+    return !pf_sw_fused_off() && hs != 96 && 64 * (hs / 4) <= 8 * 64 * group && fa_smem_bytes(hs, group, sstride) <= PF_ATTN_LDS_MAX;      // 8 float4 per thread stage a tile
 }
 // the table form exists for pf_attn_fused3_kernel / pf_attn_fused2_kernel only: with fused2's rows fitting, one of the two is what the dispatch picks
-static bool pf_tab_fits(int hs, int kvmul, int sstride) {
-    return pf_one_launch_fits(hs, kvmul, sstride) && !pf_sw_v1_only() && fa2_smem_bytes(hs, kvmul, sstride) <= PF_ATTN_LDS_MAX;
+static bool pf_tab_fits(int hs, int group, int sstride) {
+    return pf_one_launch_fits(hs, group, sstride) && !pf_sw_v1_only() && fa2_smem_bytes(hs, group, sstride) <= PF_ATTN_LDS_MAX;
 }
 // fused_max_pos of a plan's mixed steps (batch_plan_split): the largest last position a tile may have in the one-launch table form, -1 for
 // a tiled shape without one.  INT_MAX — no split, the dispatch of a step is by its deepest row as before — where the long-context trio
@@ -513,10 +528,10 @@ static bool pf_tab_fits(int hs, int kvmul, int sstride) {
 // GL3_PF_TAB_MAXPOS=<p> (diagnostic) lowers the limit to min(own, p), so that a short-context model exercises the split.
 static int pf_tab_max_pos(const gl3_ctx* ctx) {
     static const char* env = getenv("GL3_PF_TAB_MAXPOS");
-    const int hs = ctx->d.head_size, kvmul = ctx->d.n_heads / ctx->d.n_kv_heads;
-    if (!pf_rows_softmax(ctx) || !pf_tiled_shape(hs, kvmul)) return INT_MAX;
+    const int hs = ctx->d.head_size, kvmul = ctx->d.n_heads / ctx->d.n_kv_heads, group = pf_group_size(kvmul);
+    if (!pf_rows_softmax(ctx) || !pf_tiled_shape(hs, kvmul, true)) return INT_MAX;
     int fm = -1;
-    for (int k = 1; 64 * (k - 1) < ctx->d.ctx && pf_tab_fits(hs, kvmul, pf_fa_sstride(64 * k - 1)); ++k) fm = 64 * k - 1;      // score rows grow by 64 positions
+    for (int k = 1; 64 * (k - 1) < ctx->d.ctx && pf_tab_fits(hs, group, pf_fa_sstride(64 * k - 1)); ++k) fm = 64 * k - 1;      // score rows grow by 64 positions
     if (env && *env) fm = std::min(fm, atoi(env));
     return fm;
 }
@@ -540,7 +555,7 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     static const bool pk_off = getenv("GL3_PF_SCORES_PK") && atoi(getenv("GL3_PF_SCORES_PK")) == 0;
     static const bool scm_off = getenv("GL3_PF_SCORES_MFMA") && atoi(getenv("GL3_PF_SCORES_MFMA")) == 0;
     static const int scm_split = getenv("GL3_SCM_SPLIT") ? atoi(getenv("GL3_SCM_SPLIT")) : SCM_SPLIT;      // workgroups that share a (kv head, token tile)'s K tiles
-    static const bool ring_off = getenv("GL3_PF_PV_RING") && atoi(getenv("GL3_PF_PV_RING")) == 0;
+    static const bool ring_off = pf_sw_ring_off();
     static const bool pvm_off = getenv("GL3_PF_PV_MFMA") && atoi(getenv("GL3_PF_PV_MFMA")) == 0;
     const int n = st.n, max_pos = st.max_pos, one_seq = st.one_seq, ntab = st.ntab, ndeep = st.ndeep;
     const bool runs = st.runs();                          // the run-table forms
@@ -585,11 +600,13 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     }
     hipLaunchKernelGGL(pf_rope_kv_kernel, dim3(H + KVH, n), dim3(64), 0, s, ra);
     const bool rows_softmax = pf_rows_softmax(ctx);
-    const bool tiled = (one_seq >= 0 || runs) && pf_tiled_shape(hs, kvmul) && (rows_softmax || (size_t)(max_pos + 1) * 4 <= 60 * 1024);
-    const bool mfma_shape = kvmul == 4 && (hs == 128 || hs == 64);      // the kernels with their products on the matrix pipe
+    const bool tiled = (one_seq >= 0 || runs) && pf_tiled_shape(hs, kvmul, rows_softmax) && (rows_softmax || (size_t)(max_pos + 1) * 4 <= 60 * 1024);
+    const int group = pf_group_size(kvmul), NG = pf_head_groups(kvmul);      // head slots of a tiled workgroup, head groups per kv head (kvMul <= 4: kvMul, 1)
+    const bool mfma_shape = group == 4 && (hs == 128 || hs == 64);      // the kernels with their products on the matrix pipe
     const int fa_sstride = pf_fa_sstride(ndeep ? st.tab_max_pos : max_pos);      // sized by the deepest row the one-launch kernels serve: of the step, or of its shallow tiles
-    const bool one_launch = pf_one_launch_fits(hs, kvmul, fa_sstride);
-    const bool tab_ok = ntab > 0 && tiled && pf_tab_fits(hs, kvmul, fa_sstride);
+    // (a grouped shape has no pf_attn_fused_kernel form: its one-launch kernels are those of the table form, fused3 / fused2)
+    const bool one_launch = NG > 1 ? pf_tab_fits(hs, group, fa_sstride) : pf_one_launch_fits(hs, group, fa_sstride);
+    const bool tab_ok = ntab > 0 && tiled && pf_tab_fits(hs, group, fa_sstride);
     if (!tiled || (ntab > 0 && !tab_ok)) {      // several sequences, or a shape / depth the tiled kernels do not have: the per-token pair
         const size_t sm1 = ((size_t)kvmul * d.head_size + (size_t)ATT_TT * (d.head_size + 1)) * 4;
         hipLaunchKernelGGL(pf_attn_scores_kernel, dim3(nsplit, KVH, n), dim3(64 * kvmul), sm1, s, aa);
@@ -603,7 +620,7 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     const float* vc1 = aa.vcache + (size_t)(runs ? 0 : one_seq) * ctx->kv_seq_stride;
     const size_t sst = ctx->kv_seq_stride;
     if (one_launch && (ndeep == 0 || ntab > 0)) {
-        const dim3 grid(KVH * (runs ? ntab : (n + FA_TB - 1) / FA_TB));
+        const dim3 grid(KVH * (runs ? ntab : (n + FA_TB - 1) / FA_TB), NG);
         // r6: > 64 tokens on one rank with head size 128: the output is written quantised for the wo GEMM (pf_gemm3_kernel's operand layout).
         // Not in a step that also has deep tiles: the trio writes f32 rows, and the caller's quantise launch serves all rows of the step
         const bool qao = ndeep == 0 && !qao_off && hs == 128 && pf_chunk_major(n) && d.tp_size == 1 && p->XP && !pf_fused_quant_off();
@@ -611,21 +628,21 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
         uint4* xpo = qao ? reinterpret_cast<uint4*>(p->XP) : nullptr;
         // r6: products of both phases on the matrix pipe (pf_attn_fused3_kernel); GL3_PF_FUSED_MFMA=0: the VALU kernels.  Else packed-f32 scores + pinned
         // weighted V sum (pf_attn_fused2_kernel) while its 16 KB of query rows still fit; GL3_PF_FUSED_V1=1: the r4 kernel
-        const size_t sms = fa_smem_bytes(hs, kvmul, fa_sstride), sms2 = fa2_smem_bytes(hs, kvmul, fa_sstride), sms3 = fa3_smem_bytes(hs, fa_sstride);
+        const size_t sms = fa_smem_bytes(hs, group, fa_sstride), sms2 = fa2_smem_bytes(hs, group, fa_sstride), sms3 = fa3_smem_bytes(hs, fa_sstride);
         if (!mfma_off && !v1_only && mfma_shape && sms3 <= PF_ATTN_LDS_MAX)
             pf_head_dispatch<64>(hs, [&](auto hc) {
                 constexpr int HS_ = decltype(hc)::value;
                 if (runs) hipLaunchKernelGGL((pf_attn_fused3_kernel<HS_, true>), grid, dim3(512), sms3, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
-                                             KVH, aa.kv_dim, 0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, p->tiles, sst);
+                                             KVH, kvmul, aa.kv_dim, 0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, p->tiles, sst);
                 else hipLaunchKernelGGL((pf_attn_fused3_kernel<HS_>), grid, dim3(512), sms3, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
-                                        KVH, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, (const int4*)nullptr, (size_t)0); });
+                                        KVH, kvmul, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, (const int4*)nullptr, (size_t)0); });
         else if (!v1_only && sms2 <= PF_ATTN_LDS_MAX)
             pf_head_dispatch<32>(hs, [&](auto hc) {
                 constexpr int HS_ = decltype(hc)::value;
-                if (runs) hipLaunchKernelGGL((pf_attn_fused2_kernel<HS_, true>), grid, dim3(128 * kvmul), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
-                                             KVH, kvmul, aa.kv_dim, 0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, p->tiles, sst);
-                else hipLaunchKernelGGL((pf_attn_fused2_kernel<HS_>), grid, dim3(128 * kvmul), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
-                                        KVH, kvmul, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, (const int4*)nullptr, (size_t)0); });
+                if (runs) hipLaunchKernelGGL((pf_attn_fused2_kernel<HS_, true>), grid, dim3(128 * group), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
+                                             KVH, group, kvmul, aa.kv_dim, 0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, p->tiles, sst);
+                else hipLaunchKernelGGL((pf_attn_fused2_kernel<HS_>), grid, dim3(128 * group), sms2, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
+                                        KVH, group, kvmul, aa.kv_dim, pos0, n, aa.att_mul, fa_sstride, xqo, xpo, p->xp_tok, (const int4*)nullptr, (size_t)0); });
         else
             pf_head_dispatch<32>(hs, [&](auto hc) {
                 hipLaunchKernelGGL((pf_attn_fused_kernel<decltype(hc)::value>), grid, dim3(128 * kvmul), sms, s, aa.Q, aa.q_stride, kc1, vc1, aa.out, aa.out_stride,
@@ -636,26 +653,26 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     // (ndeep > 0) the deep records of a mixed step in the kernels' table forms, the deepest of which sizes the timestep grid
     const int4* dtab = p->deep;
     const int ntt = ndeep ? ndeep : (n + PA_TB - 1) / PA_TB;
-    const dim3 g1(nsplit, KVH, ntt), b1(64 * kvmul);
+    const dim3 g1(nsplit, KVH * NG, ntt), b1(64 * group);
     float* tmx = rows_softmax ? p->TMX : nullptr;
-    const bool pk = !pk_off && scores_pk_smem_bytes(hs, kvmul) <= PF_ATTN_LDS_MAX && (kvmul == 4 || kvmul == 2 || kvmul == 1);
+    const bool pk = !pk_off && scores_pk_smem_bytes(hs, group) <= PF_ATTN_LDS_MAX && (group == 4 || group == 2 || group == 1);
     if (rows_softmax && !scm_off && mfma_shape) {      // r6: products on the matrix pipe, query rows resident, K tiles prefetched
-        const dim3 g(nsplit < scm_split ? nsplit : scm_split, KVH, ndeep ? ndeep : (n + SCM_TB - 1) / SCM_TB);
+        const dim3 g(nsplit < scm_split ? nsplit : scm_split, KVH * NG, ndeep ? ndeep : (n + SCM_TB - 1) / SCM_TB);
         pf_head_dispatch<64>(hs, [&](auto hc) {
             constexpr int HS_ = decltype(hc)::value;
             if (ndeep) hipLaunchKernelGGL((pf_scores_mfma_kernel<HS_, true>), g, dim3(512), scores_mfma_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att, aa.n_heads,
-                                          aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, dtab, sst);
+                                          kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, dtab, sst);
             else hipLaunchKernelGGL((pf_scores_mfma_kernel<HS_>), g, dim3(512), scores_mfma_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att, aa.n_heads,
-                                    aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); });
+                                    kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); });
     } else if (pk)
-        pf_head_dispatch<32>(hs, [&](auto hc) { pf_kvmul_dispatch(kvmul, [&](auto mc) {
+        pf_head_dispatch<32, true>(hs, [&](auto hc) { pf_kvmul_dispatch(group, [&](auto mc) {
             constexpr int HS_ = decltype(hc)::value, KVM_ = decltype(mc)::value;
-            if (ndeep) hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_, true>), g1, b1, scores_pk_smem_bytes(hs, kvmul), s, aa.Q, aa.q_stride, kc1, aa.att,
+            if (ndeep) hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_, true>), g1, b1, scores_pk_smem_bytes(hs, group), s, aa.Q, aa.q_stride, kc1, aa.att,
                                           aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, tmx, p->tmx_tiles, dtab, sst);
-            else hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_>), g1, b1, scores_pk_smem_bytes(hs, kvmul), s, aa.Q, aa.q_stride, kc1, aa.att,
+            else hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_>), g1, b1, scores_pk_smem_bytes(hs, group), s, aa.Q, aa.q_stride, kc1, aa.att,
                                     aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, tmx, p->tmx_tiles); }); });
     else
-        pf_head_dispatch<32>(hs, [&](auto hc) {
+        pf_head_dispatch<32, true>(hs, [&](auto hc) {
             constexpr int HS_ = decltype(hc)::value;
             if (ndeep) hipLaunchKernelGGL((pf_scores_tiled_kernel<HS_, true>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att,
                                           aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, tmx, p->tmx_tiles, dtab, sst);
@@ -680,10 +697,10 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     if (sums && !pvm_off && mfma_shape)                 // r6: products on the matrix pipe (no uniform-address LDS reads)
         pf_head_dispatch<64>(hs, [&](auto hc) {
             constexpr int HS_ = decltype(hc)::value;
-            if (ndeep) hipLaunchKernelGGL((pf_pv_mfma_kernel<HS_, true>), dim3(KVH, ndeep), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, 0, 0, n, sums, dtab);
-            else hipLaunchKernelGGL((pf_pv_mfma_kernel<HS_>), dim3(KVH, (n + PVM_TB - 1) / PVM_TB), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });
+            if (ndeep) hipLaunchKernelGGL((pf_pv_mfma_kernel<HS_, true>), dim3(KVH * NG, ndeep), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, 0, 0, n, sums, dtab);
+            else hipLaunchKernelGGL((pf_pv_mfma_kernel<HS_>), dim3(KVH * NG, (n + PVM_TB - 1) / PVM_TB), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });
     else if (sums && (!ring_off || ndeep))              // (pf_pv_tiled_kernel has no table form: GL3_PF_PV_RING=0 does not reach the deep rows of a mixed step)
-        pf_head_dispatch<32>(hs, [&](auto hc) {
+        pf_head_dispatch<32, true>(hs, [&](auto hc) {
             constexpr int HS_ = decltype(hc)::value;
             if (ndeep) hipLaunchKernelGGL((pf_pv_ring_kernel<HS_, true>), dim3(H, ndeep), dim3(64 * PVR_NW), pv_ring_smem_bytes(hs), s, aa, 0, 0, n, sums, dtab);
             else hipLaunchKernelGGL((pf_pv_ring_kernel<HS_>), dim3(H, (n + PVR_TB - 1) / PVR_TB), dim3(64 * PVR_NW), pv_ring_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });

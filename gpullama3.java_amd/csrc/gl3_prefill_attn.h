@@ -164,7 +164,7 @@ __global__ __launch_bounds__(64) void pf_attn_softmax_pv_kernel(const PfAttnArgs
 // Prefill of ONE sequence (token b sits at position pos0 + b): the K / V tiles are shared by a tile of PA_TB tokens
 // instead of being re-read for every token.  Per-element arithmetic and order are those of the per-token kernels above.
 //
-// Scores: grid = (64-timestep K tiles, n_kv_heads, token tiles), block = 64 x kvMul (kvMul <= 4).  Thread (head hq,
+// Scores: grid = (64-timestep K tiles, n_kv_heads x head groups, token tiles), block = 64 x head slots (min(kvMul, 4): HeadGroup below).  Thread (head hq,
 // timestep r) keeps its K row in registers and walks the PA_TB query rows of its head (four chains in flight).
 template <int I, int N, int STEP, class F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -220,6 +220,25 @@ __device__ __forceinline__ LcTile lc_tile(int tile, int pos0, int ntok, const in
     }
     return r;
 }
+// The head group of a workgroup of the tiled kernels.  A kv head's kvMul query heads are served `slots` = min(kvMul, 4) consecutive heads at a time:
+// NG = ceil(kvMul / slots) groups, the last of which holds 1 .. slots real heads (kvMul <= 4: one group, every slot real).  Head slot hq of
+// group g is the head h0 + hq; a surplus slot of a ragged last group points at the group's last real head (head_of: never a head of another
+// kv head), computes what that head's slot computes, reaches every barrier and stores nothing (real).  The group index is a grid component
+// beside the token tile of fa_tile / lc_tile — blockIdx.y of the one-launch kernels, folded into the kv-head component (kvh * NG + g) of the
+// long-context kernels, whose three grid components are taken — so it is wavefront-uniform and everything here stays in SGPRs.
+struct HeadGroup {
+    int kvh, h0, nh;                                             // kv head, first head of the group, real heads in it
+    __device__ __forceinline__ int head_of(int hq) const { return h0 + min(hq, nh - 1); }
+    __device__ __forceinline__ bool real(int hq) const { return hq < nh; }
+};
+__device__ __forceinline__ HeadGroup head_group(int kvh, int g, int kvmul, int slots) {
+    HeadGroup r; r.kvh = kvh; r.h0 = kvh * kvmul + slots * g; r.nh = min(slots, kvmul - slots * g);
+    return r;
+}
+__device__ __forceinline__ HeadGroup lc_head_group(int kg, int kvmul, int slots) {      // kg = kvh * NG + g
+    const int ng = (kvmul + slots - 1) / slots, kvh = __builtin_amdgcn_readfirstlane(kg / ng);
+    return head_group(kvh, kg - kvh * ng, kvmul, slots);
+}
 template <int HS, bool TAB = false>
 __global__ __launch_bounds__(256) void pf_scores_tiled_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc,
                                                               float* __restrict__ att, int n_heads, int kvmul, int kv_dim, int ctx,
@@ -229,7 +248,8 @@ __global__ __launch_bounds__(256) void pf_scores_tiled_kernel(const float* __res
     constexpr int PITCH = HS + 4, H4 = HS / 4;
     const int t = threadIdx.x, nthr = blockDim.x;
     const LcTile lt = lc_tile<TAB, PA_TB>(blockIdx.z, pos0, ntok, tab, seq_stride);
-    const int t0 = blockIdx.x * 64, kvh = blockIdx.y, b0 = lt.b0, nb = lt.nb;
+    const HeadGroup hg = lc_head_group(blockIdx.y, kvmul, nthr >> 6);      // one wavefront per head slot
+    const int t0 = blockIdx.x * 64, kvh = hg.kvh, b0 = lt.b0, nb = lt.nb;
     pos0 = lt.pos0; kc += lt.cache_off;               // of the tile's sequence from here on
     const int tmax = pos0 + b0 + nb - 1;              // last timestep any token of this tile attends to
     if (tmax < t0) return;
@@ -245,7 +265,8 @@ __global__ __launch_bounds__(256) void pf_scores_tiled_kernel(const float* __res
 #pragma unroll
     for (int c = 0; c < H4; ++c) kr[c] = *reinterpret_cast<const float4*>(kt + min(r, t1 - t0 - 1) * PITCH + 4 * c);
     const float sqrt_hs = (float)sqrt((double)HS);
-    const int head = kvh * kvmul + hq;
+    const int head = hg.head_of(hq);
+    const bool hreal = hg.real(hq);
     for (int tb = 0; tb < nb; tb += 2) {
         // the two query rows are wavefront-uniform: scalar loads (8 floats per row per step, double-buffered), SGPR
         // operands in the multiplies.  Explicit s_load: the compiler would hoist every load and spill SGPRs.
@@ -275,12 +296,12 @@ __global__ __launch_bounds__(256) void pf_scores_tiled_kernel(const float* __res
         }
         const int b = b0 + tb;
         const float v0 = att_mul != 0.f ? s0 * att_mul : s0 / sqrt_hs, v1 = att_mul != 0.f ? s1 * att_mul : s1 / sqrt_hs;
-        const bool ok0 = t0 + r <= pos0 + b, ok1 = tb + 1 < nb && t0 + r <= pos0 + b + 1;       // (tmax >= pos0 + b: both imply t0 + r < t1)
+        const bool ok0 = hreal && t0 + r <= pos0 + b, ok1 = hreal && tb + 1 < nb && t0 + r <= pos0 + b + 1;       // (tmax >= pos0 + b: both imply t0 + r < t1)
         if (ok0) att[((size_t)b * n_heads + head) * ctx + t0 + r] = v0;
         if (ok1) att[((size_t)(b + 1) * n_heads + head) * ctx + t0 + r] = v1;
         if (tmx) {      // r6: the tile's maximum per (token, head) row for pf_softmax_rows_kernel (max is order-independent)
             const float m0 = wave_max_uniform(ok0 ? v0 : -INFINITY), m1 = wave_max_uniform(ok1 ? v1 : -INFINITY);
-            if (r == 0) {
+            if (r == 0 && hreal) {
                 if (t0 <= pos0 + b) tmx[((size_t)b * n_heads + head) * tmx_tiles + blockIdx.x] = m0;
                 if (tb + 1 < nb && t0 <= pos0 + b + 1) tmx[((size_t)(b + 1) * n_heads + head) * tmx_tiles + blockIdx.x] = m1;
             }
@@ -298,15 +319,16 @@ __host__ __device__ constexpr size_t scores_tiled_smem_bytes(int hs) { return (s
 __host__ __device__ constexpr size_t scores_pk_smem_bytes(int hs, int kvmul) { return scores_tiled_smem_bytes(hs) + (size_t)kvmul * PA_TB * hs * 4; }
 template <int HS, int KVM, bool TAB = false>
 __global__ __launch_bounds__(64 * KVM) __attribute__((amdgpu_waves_per_eu(2, 2))) void pf_scores_pk_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc,
-        float* __restrict__ att, int n_heads, int kvmul_, int kv_dim, int ctx, int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles,
+        float* __restrict__ att, int n_heads, int kvmul, int kv_dim, int ctx, int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles,
         const int4* __restrict__ tab = nullptr, size_t seq_stride = 0) {
     extern __shared__ __attribute__((aligned(16))) float kt[];       // [64][PITCH] K rows, then [KVM][8 pairs][HS][2] query rows
-    constexpr int PITCH = HS + 4, H4 = HS / 4, NGR = HS / 8, NT = 64 * KVM, KPT = 64 * H4 / NT, QPT = H4 / 8, kvmul = KVM;
-    static_assert(KPT >= 1 && QPT >= 1, "staging slots per thread");
+    constexpr int PITCH = HS + 4, H4 = HS / 4, NGR = HS / 8, NT = 64 * KVM, KPT = 64 * H4 / NT, QPT = H4 / 8;
+    static_assert(KPT * NT == 64 * H4 && QPT * 8 == H4, "staging slots per thread");
     float* qs = kt + 64 * PITCH;
     const int t = threadIdx.x;
     const LcTile lt = lc_tile<TAB, PA_TB>(blockIdx.z, pos0, ntok, tab, seq_stride);
-    const int t0 = blockIdx.x * 64, kvh = blockIdx.y, b0 = lt.b0, nb = lt.nb;
+    const HeadGroup hg = lc_head_group(blockIdx.y, kvmul, KVM);      // KVM head slots of the kv head's kvmul query heads
+    const int t0 = blockIdx.x * 64, kvh = hg.kvh, b0 = lt.b0, nb = lt.nb;
     pos0 = lt.pos0; kc += lt.cache_off;               // of the tile's sequence from here on
     const int tmax = pos0 + b0 + nb - 1;
     if (tmax < t0) return;
@@ -322,7 +344,7 @@ __global__ __launch_bounds__(64 * KVM) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
         for (int j = 0; j < QPT; ++j) {                               // slot = (head, token pair, 4 columns): both tokens' float4
             const int i = t + NT * j, c = i % H4, pair = (i / H4) % (PA_TB / 2), hq = i / (H4 * (PA_TB / 2));
-            const float* qp = Q + (size_t)(kvh * kvmul + hq) * HS + 4 * c;
+            const float* qp = Q + (size_t)hg.head_of(hq) * HS + 4 * c;
             qra[j] = *reinterpret_cast<const v4f_native_s*>(qp + (size_t)(b0 + min(2 * pair, nb - 1)) * q_stride);
             qrb[j] = *reinterpret_cast<const v4f_native_s*>(qp + (size_t)(b0 + min(2 * pair + 1, nb - 1)) * q_stride);
         }
@@ -348,7 +370,8 @@ __global__ __launch_bounds__(64 * KVM) __attribute__((amdgpu_waves_per_eu(2, 2))
         kr[2 * c] = x.xy; kr[2 * c + 1] = x.zw;
     }
     const float sqrt_hs = (float)sqrt((double)HS);
-    const int head = kvh * kvmul + hq;
+    const int head = hg.head_of(hq);
+    const bool hreal = hg.real(hq);
     for (int pp = 0; 4 * pp < nb; ++pp) {
         const float* q01 = qs + (size_t)(hq * (PA_TB / 2) + 2 * pp) * HS * 2;      // pairs (4 pp, 4 pp + 1) and (4 pp + 2, 4 pp + 3)
         const float* q23 = q01 + HS * 2;
@@ -381,11 +404,11 @@ __global__ __launch_bounds__(64 * KVM) __attribute__((amdgpu_waves_per_eu(2, 2))
         for (int u = 0; u < 4; ++u) {
             const int tb = 4 * pp + u, b = b0 + tb;
             const float v = att_mul != 0.f ? sv[u] * att_mul : sv[u] / sqrt_hs;
-            const bool ok = tb < nb && t0 + r <= pos0 + b;
+            const bool ok = hreal && tb < nb && t0 + r <= pos0 + b;
             if (ok) att[((size_t)b * n_heads + head) * ctx + t0 + r] = v;
             if (tmx) {
                 const float m = wave_max_uniform(ok ? v : -INFINITY);
-                if (r == 0 && tb < nb && t0 <= pos0 + b) tmx[((size_t)b * n_heads + head) * tmx_tiles + blockIdx.x] = m;
+                if (r == 0 && hreal && tb < nb && t0 <= pos0 + b) tmx[((size_t)b * n_heads + head) * tmx_tiles + blockIdx.x] = m;
             }
         }
     }
@@ -625,7 +648,7 @@ template <int HS, bool TAB = false>
 __global__ __launch_bounds__(64 * PVR_NW) void pf_pv_ring_kernel(const PfAttnArgs a, int seq, int pos0, int ntok, const float* __restrict__ sums,
                                                                 const int4* __restrict__ tab = nullptr) {
     constexpr int NCOL = HS > 64 ? 2 : 1, H4 = HS / 4, NT = 64 * PVR_NW, VPT = 64 * H4 / NT;
-    static_assert(VPT >= 1, "a V tile is at least one 16-byte slot per thread");
+    static_assert(VPT * NT == 64 * H4, "a V tile is a whole number of 16-byte slots per thread");
     extern __shared__ __attribute__((aligned(16))) float vt[];        // [64][HS] V rows, then [PVR_TB][64] weights
     float* as = vt + 64 * HS;
     const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -660,7 +683,7 @@ __global__ __launch_bounds__(64 * PVR_NW) void pf_pv_ring_kernel(const PfAttnArg
     for (int u = 0; u < 4; ++u)
 #pragma unroll
         for (int c = 0; c < NCOL; ++c) acc[u][c] = 0.f;
-    const float* vp = vt + (NCOL == 2 ? 2 * lane : min(lane, HS - 1));
+    const float* vp = vt + (NCOL == 2 ? 2 * min(lane, HS / 2 - 1) : min(lane, HS - 1));      // lanes past the last column (head size 96, 32) repeat it and store nothing
     const float* ap = as + 4 * w * 64;
     PVR_GLOAD(0);
     PVR_LSTORE(0);
@@ -700,6 +723,7 @@ __global__ __launch_bounds__(64 * PVR_NW) void pf_pv_ring_kernel(const PfAttnArg
 //            acc = a_t * v + acc with t ascending (pf_pv_tiled_kernel's inner loop)
 // Tiles are dealt heaviest (latest positions) first, so the triangular work profile does not leave a tail.
 constexpr int FA_TB = 8;
+// (kvmul of the *_smem_bytes functions: the head slots of a workgroup — the head group's size min(kvMul, 4), HeadGroup above)
 __host__ __device__ constexpr size_t fa_smem_bytes(int hs, int kvmul, int sstride) {
     return ((size_t)kvmul * FA_TB * sstride + 2 * 64 * (hs + 4) + 64) * 4;
 }
@@ -709,11 +733,11 @@ __host__ __device__ constexpr size_t fa_smem_bytes(int hs, int kvmul, int sstrid
 // the caches move to the record's sequence and pos0 becomes position - row, so that everything behind this prologue — "row b of the step sits
 // at position pos0 + b" — is the one-sequence code unchanged.  The record's address depends on blockIdx alone: it arrives by a scalar load
 // and the four values are wavefront-uniform (SGPRs), like the arithmetic on blockIdx they replace.
-struct FaTile { int kvh, b0, nb, pos0; size_t cache_off; };      // cache_off: floats from the caches' base to the tile's sequence
+struct FaTile { int kvh, g, b0, nb, pos0; size_t cache_off; };   // g: head group (blockIdx.y); cache_off: floats from the caches' base to the tile's sequence
 template <bool TAB>
 __device__ __forceinline__ FaTile fa_tile(int n_kv_heads, int pos0, int ntok, const int4* __restrict__ tab, size_t seq_stride) {
     FaTile r;
-    r.kvh = blockIdx.x % n_kv_heads;
+    r.kvh = blockIdx.x % n_kv_heads; r.g = blockIdx.y;
     if constexpr (TAB) {
         const int4 rec = tab[blockIdx.x / n_kv_heads];
         r.b0 = __builtin_amdgcn_readfirstlane(rec.x); r.nb = __builtin_amdgcn_readfirstlane(rec.y);
@@ -789,7 +813,8 @@ __device__ __forceinline__ FaTile fa_tile(int n_kv_heads, int pos0, int ntok, co
     const uint32_t Q0_ = (uint32_t)((int)(s0 + copysignf(0.5f, s0)) & 0xFF), Q1_ = (uint32_t)((int)(s1 + copysignf(0.5f, s1)) & 0xFF)
 // FA_STORE_ROWS4: the output of the VALU kernels' phase 3 — the wavefront's four tokens 4 grp .. 4 grp + 3 of its head, lane = columns 2 lane, 2 lane + 1
 // (head size 128) or column lane.  Quantised (head size 128, xq_out): a 32-element block of a token's row = 32 consecutive columns = the 16 lanes
-// of a DPP row, two ADJACENT columns each.  In scope: acc[4][NCOL], grp, nb, b0, head, lane, out, out_stride, xq_out, xp_out, xp_tok.
+// of a DPP row, two ADJACENT columns each.  In scope: acc[4][NCOL], grp, nb, b0, head, hreal (false: the
+// surplus head slot of a ragged head group, which stores nothing), lane, out, out_stride, xq_out, xp_out, xp_tok.
 #define FA_STORE_ROWS4() do { \
     if (NCOL == 2 && xq_out) { \
         _Pragma("unroll") for (int u = 0; u < 4; ++u) { \
@@ -797,7 +822,7 @@ __device__ __forceinline__ FaTile fa_tile(int n_kv_heads, int pos0, int ntok, co
             float amax = fmaxf(fabsf(acc[u][0]), fabsf(acc[u][NCOL - 1])); \
             _Pragma("unroll") for (int m = 1; m < 16; m <<= 1) amax = fmaxf(amax, __shfl_xor(amax, m, 64)); \
             Q8_ROUND_PAIR(amax, acc[u][0], acc[u][NCOL - 1], qs, q0, q1); \
-            if (tb >= nb) continue; \
+            if (tb >= nb || !hreal) continue; \
             const int col = head * HS + 2 * lane, b = b0 + tb; \
             *reinterpret_cast<uint16_t*>(xq_out + ((size_t)(col >> 4) * xp_tok + b) * 16 + (col & 15)) = (uint16_t)(q0 | (q1 << 8)); \
             if ((lane & 15) == 0) { \
@@ -811,7 +836,7 @@ __device__ __forceinline__ FaTile fa_tile(int n_kv_heads, int pos0, int ntok, co
     } \
     _Pragma("unroll") for (int u = 0; u < 4; ++u) { \
         const int tb = 4 * grp + u; \
-        if (tb >= nb) continue; \
+        if (tb >= nb || !hreal) continue; \
         _Pragma("unroll") for (int c = 0; c < NCOL; ++c) { \
             const int j = NCOL == 2 ? 2 * lane + c : lane; \
             if (j < HS) out[(size_t)(b0 + tb) * out_stride + head * HS + j] = acc[u][c]; \
@@ -835,6 +860,7 @@ __global__ __launch_bounds__(512) void pf_attn_fused_kernel(const float* __restr
     const int kvh = blockIdx.x % n_kv_heads, tile = ntile - 1 - blockIdx.x / n_kv_heads;
     const int b0 = tile * FA_TB, nb = min(FA_TB, ntok - b0), tmax = pos0 + b0 + nb - 1;
     const int head = kvh * kvmul + hq;
+    constexpr bool hreal = true;                                    // no head groups here: every wavefront's head is its own
     const float sqrt_hs = (float)sqrt((double)HS);
 
 #ifdef FA_TIMING
@@ -984,10 +1010,11 @@ __global__ __launch_bounds__(512) void pf_attn_fused_kernel(const float* __restr
 // r6 — pf_attn_fused_kernel with the inner loops of pf_scores_pk_kernel (phase 1: query rows interleaved in LDS, two tokens' chains per register pair
 // on packed f32, reads of the next 8 steps pinned under the current group) and pf_pv_ring_kernel (phase 3: masking by zero weights, the next
 // timestep group's LDS reads pinned under the current group's arithmetic).  Same arithmetic in the same order; 16 KB more LDS (query rows).
+// kvmul = head slots of the workgroup (the head group's size: min(kvMul, 4)), kvm = the model's kvMul, which indexes the heads.
 __host__ __device__ constexpr size_t fa2_smem_bytes(int hs, int kvmul, int sstride) { return fa_smem_bytes(hs, kvmul, sstride) + (size_t)kvmul * FA_TB * hs * 4; }
 template <int HS, bool TAB = false>
 __global__ __launch_bounds__(512) void pf_attn_fused2_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc, const float* __restrict__ vc,
-                                                            float* __restrict__ out, int out_stride, int n_kv_heads, int kvmul, int kv_dim,
+                                                            float* __restrict__ out, int out_stride, int n_kv_heads, int kvmul, int kvm, int kv_dim,
                                                             int pos0, int ntok, float att_mul, int sstride,
                                                             uint8_t* __restrict__ xq_out = nullptr, uint4* __restrict__ xp_out = nullptr, int xp_tok = 0,
                                                             const int4* __restrict__ tab = nullptr, size_t seq_stride = 0) {
@@ -1001,10 +1028,12 @@ __global__ __launch_bounds__(512) void pf_attn_fused2_kernel(const float* __rest
     const int nthr = blockDim.x, gthreads = 64 * kvmul;
     const int grp = wave / kvmul, hq = wave % kvmul, gt = t - grp * gthreads;
     const FaTile ft = fa_tile<TAB>(n_kv_heads, pos0, ntok, tab, seq_stride);
+    const HeadGroup hg = head_group(ft.kvh, ft.g, kvm, kvmul);
     const int kvh = ft.kvh, b0 = ft.b0, nb = ft.nb;
     pos0 = ft.pos0; kc += ft.cache_off; vc += ft.cache_off;      // of the tile's sequence from here on
     const int tmax = pos0 + b0 + nb - 1;
-    const int head = kvh * kvmul + hq;
+    const int head = hg.head_of(hq);
+    const bool hreal = hg.real(hq);
     const float sqrt_hs = (float)sqrt((double)HS);
 
 #ifdef FA_TIMING
@@ -1017,7 +1046,7 @@ __global__ __launch_bounds__(512) void pf_attn_fused2_kernel(const float* __rest
     // query rows of the tile's tokens -> LDS, interleaved by token pairs: {q_a[j], q_b[j], q_a[j + 1], q_b[j + 1]} is one 16-byte broadcast read
     for (int i = t; i < kvmul * (FA_TB / 2) * H4; i += nthr) {
         const int c = i % H4, pair = (i / H4) % (FA_TB / 2), qh = i / (H4 * (FA_TB / 2));
-        const float* qp = Q + (size_t)(kvh * kvmul + qh) * HS + 4 * c;
+        const float* qp = Q + (size_t)hg.head_of(qh) * HS + 4 * c;
         const v4f_native_s xa = *reinterpret_cast<const v4f_native_s*>(qp + (size_t)(b0 + min(2 * pair, nb - 1)) * q_stride);
         const v4f_native_s xb = *reinterpret_cast<const v4f_native_s*>(qp + (size_t)(b0 + min(2 * pair + 1, nb - 1)) * q_stride);
         float* d = qs + ((size_t)(qh * (FA_TB / 2) + pair) * HS + 4 * c) * 2;
@@ -1107,7 +1136,8 @@ __global__ __launch_bounds__(512) void pf_attn_fused2_kernel(const float* __rest
 }
 
 
-// r6 — the one-launch prefill attention with the PRODUCTS of phases 1 and 3 on the matrix pipe (kvMul 4: 32 (head, token) rows per workgroup).
+// r6 — the one-launch prefill attention with the PRODUCTS of phases 1 and 3 on the matrix pipe (a head group of 4 slots — kvMul 4, or kvm >= 5
+// in groups, HeadGroup above: 32 (head slot, token) rows per workgroup).
 // pf_attn_fused_kernel / fused2 feed one operand of every multiply from a wavefront-uniform place (SGPRs: lead bounded by the SGPR file; LDS:
 // a uniform-address ds_read_b128 costs 9.2 cycles of the CU's LDS pipe against 4.9 for 64 distinct addresses, scripts/probes/lds_bcast_probe.hip)
 // and both phases end up bound by that delivery.  A K = 1 f32 MFMA with C = 0 is an outer product of two LANE-DISTINCT vectors whose every
@@ -1180,7 +1210,7 @@ __host__ __device__ constexpr size_t fa3_smem_bytes(int hs, int sstride) {
             if (g < ngr_) F3_PV8(wa, va); } while (0)
 template <int HS, bool TAB = false>
 __global__ __launch_bounds__(512) void pf_attn_fused3_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc, const float* __restrict__ vc,
-                                                             float* __restrict__ out, int out_stride, int n_kv_heads, int kv_dim,
+                                                             float* __restrict__ out, int out_stride, int n_kv_heads, int kvm, int kv_dim,
                                                              int pos0, int ntok, float att_mul, int sstride,
                                                              uint8_t* __restrict__ xq_out, uint4* __restrict__ xp_out, int xp_tok,
                                                              const int4* __restrict__ tab = nullptr, size_t seq_stride = 0) {
@@ -1196,6 +1226,7 @@ __global__ __launch_bounds__(512) void pf_attn_fused3_kernel(const float* __rest
     const int grp = wave >> 2, wg = wave & 3, gt = t - grp * gthreads;
     const int lq = lane >> 4, li = lane & 15, par = lq >> 1;        // MFMA block of this lane's operands, index inside it, step parity of the block
     const FaTile ft = fa_tile<TAB>(n_kv_heads, pos0, ntok, tab, seq_stride);
+    const HeadGroup hg = head_group(ft.kvh, ft.g, kvm, KVM);
     const int kvh = ft.kvh, b0 = ft.b0, nb = ft.nb;
     pos0 = ft.pos0; kc += ft.cache_off; vc += ft.cache_off;      // of the tile's sequence from here on
     const int tmax = pos0 + b0 + nb - 1;
@@ -1206,7 +1237,7 @@ __global__ __launch_bounds__(512) void pf_attn_fused3_kernel(const float* __rest
     FA_FETCH(kc, gt, gthreads, min(grp * 64, tmax), max(1, min(64, tmax + 1 - grp * 64)));
     for (int i = t; i < ROWS * H4; i += nthr) {                      // query rows (tokens past the chunk's end repeat its last token: never stored)
         const int row = i / H4, c = i % H4;
-        const float4 x = *reinterpret_cast<const float4*>(Q + (size_t)(b0 + min(row & (FA_TB - 1), nb - 1)) * q_stride + (size_t)(kvh * kvmul + (row >> 3)) * HS + 4 * c);
+        const float4 x = *reinterpret_cast<const float4*>(Q + (size_t)(b0 + min(row & (FA_TB - 1), nb - 1)) * q_stride + (size_t)hg.head_of(row >> 3) * HS + 4 * c);
         float* d = qs + row * QP + 4 * c;
         *reinterpret_cast<float2*>(d) = make_float2(x.x, x.y);
         *reinterpret_cast<float2*>(d + 2) = make_float2(x.z, x.w);
@@ -1287,14 +1318,15 @@ __global__ __launch_bounds__(512) void pf_attn_fused3_kernel(const float* __rest
     const float av[2][4] = {{ac[0], ac[1], ac[2], ac[3]}, {ac[4], ac[5], ac[6], ac[7]}};
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int row = 16 * rg + 4 * lq + r, tb = row & (FA_TB - 1), head = kvh * kvmul + (row >> 3), b = b0 + tb;
+        const int row = 16 * rg + 4 * lq + r, tb = row & (FA_TB - 1), head = hg.h0 + (row >> 3), b = b0 + tb;
+        const bool hreal = hg.real(row >> 3);                        // a surplus head slot of a ragged group stores nothing
         const int col = head * HS + 32 * cq + li;                    // av[0][r]; av[1][r] sits 16 columns further
         if (xq_out) {
             // quantised: this wavefront's 32 columns of a row are one Q8_0 block = the 16 lanes of a DPP row x 2 registers, columns 16 APART
             float amax = fmaxf(fabsf(av[0][r]), fabsf(av[1][r]));
             amax = row8_max(amax); GL3_DPP_MAX(amax, 0x140);
             Q8_ROUND_PAIR(amax, av[0][r], av[1][r], qsc, q0, q1);
-            if (tb >= nb) continue;
+            if (tb >= nb || !hreal) continue;
             xq_out[((size_t)(col >> 4) * xp_tok + b) * 16 + li] = (uint8_t)q0;
             xq_out[((size_t)((col >> 4) + 1) * xp_tok + b) * 16 + li] = (uint8_t)q1;
             if (li == 0) {
@@ -1303,15 +1335,15 @@ __global__ __launch_bounds__(512) void pf_attn_fused3_kernel(const float* __rest
                 xp_out[((size_t)blk * 2 + 0) * xp_tok + b] = so.half0;
                 xp_out[((size_t)blk * 2 + 1) * xp_tok + b] = so.half1;
             }
-        } else if (tb < nb) {
+        } else if (tb < nb && hreal) {
             out[(size_t)b * out_stride + col] = av[0][r];
             out[(size_t)b * out_stride + col + 16] = av[1][r];
         }
     }
 }
 
-// r6 — the weighted V sum behind a long context with its products on the matrix pipe (phase 3 of pf_attn_fused3_kernel as a kernel of its own; kvMul 4).
-// Workgroup = (kv head, 16 tokens) = four row groups (one per query head) x HS / 32 column slices = 16 wavefronts; a wavefront advances its
+// r6 — the weighted V sum behind a long context with its products on the matrix pipe (phase 3 of pf_attn_fused3_kernel as a kernel of its own; a head
+// group of 4 slots).  Workgroup = (kv head and head group, 16 tokens) = four row groups (one per head slot) x HS / 32 column slices = 16 wavefronts; a wavefront advances its
 // 16 rows x 32 columns two timesteps per MFMA: A = w[row][t + parity] (numerator / sum, 0 behind the row's position: staged that way), B = v[t + parity]
 // [column], acc = (acc + P_t) + P_t+1.  Operands are lane-distinct 4-byte LDS reads (pf_pv_ring_kernel's uniform-address weight reads kept the
 // LDS pipe 68 % busy and bound it).  Staging as pf_pv_ring_kernel: the next tile's V rows and numerators travel in registers under the current
@@ -1329,7 +1361,8 @@ __global__ __launch_bounds__(1024) void pf_pv_mfma_kernel(const PfAttnArgs a, in
     const int rg = wave & 3, cq = wave >> 2;                          // query head of the kv group, 32-column slice
     const int lq = lane >> 4, li = lane & 15, par = lq >> 1, cg = lq & 1;
     const LcTile lt = lc_tile<TAB, PVM_TB>(blockIdx.y, pos0, ntok, tab, a.seq_stride);
-    const int kvh = blockIdx.x, b0 = lt.b0, nb = lt.nb;
+    const HeadGroup hg = lc_head_group(blockIdx.x, a.n_heads / a.n_kv_heads, KVM);
+    const int kvh = hg.kvh, b0 = lt.b0, nb = lt.nb;
     pos0 = lt.pos0;
     const int tmax = pos0 + b0 + nb - 1, ntile = tmax / 64 + 1;
     const float* vc = a.vcache + (TAB ? lt.cache_off : (size_t)seq * a.seq_stride) + kvh * HS;
@@ -1340,8 +1373,8 @@ __global__ __launch_bounds__(1024) void pf_pv_mfma_kernel(const PfAttnArgs a, in
     for (int j = 0; j < 4; ++j) {
         const int row = wave + 16 * j, hq = row >> 4, tb = row & 15, b = b0 + min(tb, nb - 1);
         apos[j] = tb < nb ? pos0 + b0 + tb : -1;
-        arow[j] = a.att + ((size_t)b * a.n_heads + kvh * KVM + hq) * a.ctx;
-        rsum[j] = sums[(size_t)b * a.n_heads + kvh * KVM + hq];
+        arow[j] = a.att + ((size_t)b * a.n_heads + hg.head_of(hq)) * a.ctx;
+        rsum[j] = sums[(size_t)b * a.n_heads + hg.head_of(hq)];
     }
     typedef float v4f_native __attribute__((ext_vector_type(4)));
     v4f_native vreg[VPT]; float areg[4];
@@ -1354,7 +1387,7 @@ __global__ __launch_bounds__(1024) void pf_pv_mfma_kernel(const PfAttnArgs a, in
             *reinterpret_cast<v4f_native*>(vt + r * PITCH + 4 * c) = vreg[j]; }); \
         _Pragma("unroll") for (int j = 0; j < 4; ++j) ws[(wave + 16 * j) * PVM_WP + lane] = t0_ + lane <= apos[j] ? areg[j] / rsum[j] : 0.f; } while (0)
     v8f_native ac = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};          // [0..3] column 32 cq + li, [4..7] column 32 cq + 16 + li; tokens 4 lq + r of head rg
-    const bool live = cq < HS / 32;
+    const bool live = cq < HS / 32 && hg.real(rg);                   // (a surplus head slot still stages and reaches every barrier)
     const float* wp = ws + (16 * rg + li) * PVM_WP + par;
     const float* vp = vt + par * PITCH + 32 * cq + 16 * cg + li;
     PVM_GLOAD(0);
@@ -1377,12 +1410,12 @@ __global__ __launch_bounds__(1024) void pf_pv_mfma_kernel(const PfAttnArgs a, in
     for (int r = 0; r < 4; ++r) {
         const int tb = 4 * lq + r;
         if (tb >= nb) continue;
-        float* o = a.out + (size_t)(b0 + tb) * a.out_stride + (size_t)(kvh * KVM + rg) * HS + 32 * cq + li;
+        float* o = a.out + (size_t)(b0 + tb) * a.out_stride + (size_t)(hg.h0 + rg) * HS + 32 * cq + li;
         o[0] = ac[r]; o[16] = ac[4 + r];
     }
 }
 
-// r6 — the scores behind a long context with their products on the matrix pipe (phase 1 of pf_attn_fused3_kernel as a kernel of its own; kvMul 4).
+// r6 — the scores behind a long context with their products on the matrix pipe (phase 1 of pf_attn_fused3_kernel as a kernel of its own; a head group of 4 slots).
 // Workgroup = (kv head, 16 tokens, every S-th K tile): 64 (head, token) rows whose query rows stay in LDS for the workgroup's whole life; 8 wavefronts
 // = 4 quarters of a 64-timestep K tile x 2 pairs of row groups.  Block q of an MFMA = (row group of the pair q & 1, step parity q >> 1): A = k[t][2 m +
 // parity] (the lane's K row, every second element, in registers), B = q[row][2 m + parity] (64 distinct LDS addresses); the chains advance two steps
@@ -1392,7 +1425,7 @@ constexpr int SCM_TB = 16, SCM_SPLIT = 4;
 __host__ __device__ constexpr size_t scores_mfma_smem_bytes(int hs) { return ((size_t)64 * (hs + 4) + 4 * SCM_TB * (hs + 2) + 4 * 4 * SCM_TB) * 4; }
 template <int HS, bool TAB = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void pf_scores_mfma_kernel(const float* __restrict__ Q, int q_stride, const float* __restrict__ kc, float* __restrict__ att,
-                                                             int n_heads, int kv_dim, int ctx, int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles,
+                                                             int n_heads, int kvm, int kv_dim, int ctx, int pos0, int ntok, float att_mul, float* __restrict__ tmx, int tmx_tiles,
                                                              const int4* __restrict__ tab = nullptr, size_t seq_stride = 0) {
     extern __shared__ __attribute__((aligned(16))) float kt[];       // [64][PITCH] K rows, then [64 rows][QP] query rows, then [4][64] quarter maxima
     constexpr int KVM = 4, ROWS = KVM * SCM_TB, PITCH = HS + 4, H4 = HS / 4, QP = HS + 2, NM = HS / 2, NT = 512, KPT = 64 * H4 / NT;
@@ -1403,7 +1436,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int tq = wave & 3, rp = wave >> 2;
     const int lq = lane >> 4, li = lane & 15, par = lq >> 1, rsel = lq & 1;
     const LcTile lt = lc_tile<TAB, SCM_TB>(blockIdx.z, pos0, ntok, tab, seq_stride);
-    const int split = blockIdx.x, nsplit = gridDim.x, kvh = blockIdx.y, b0 = lt.b0, nb = lt.nb;
+    const HeadGroup hg = lc_head_group(blockIdx.y, kvm, KVM);
+    const int split = blockIdx.x, nsplit = gridDim.x, kvh = hg.kvh, b0 = lt.b0, nb = lt.nb;
     pos0 = lt.pos0; kc += lt.cache_off;               // of the tile's sequence from here on
     const int tmax = pos0 + b0 + nb - 1, ntile = tmax / 64 + 1;
     if (split >= ntile) return;
@@ -1417,7 +1451,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     SCM_KLOAD(split);
     for (int i = t; i < ROWS * H4; i += NT) {                        // query rows (tokens past the chunk's end repeat its last token: never stored)
         const int row = i / H4, c = i % H4;
-        const float4 x = *reinterpret_cast<const float4*>(Q + (size_t)(b0 + min(row & (SCM_TB - 1), nb - 1)) * q_stride + (size_t)(kvh * KVM + (row >> 4)) * HS + 4 * c);
+        const float4 x = *reinterpret_cast<const float4*>(Q + (size_t)(b0 + min(row & (SCM_TB - 1), nb - 1)) * q_stride + (size_t)hg.head_of(row >> 4) * HS + 4 * c);
         float* d = qs + row * QP + 4 * c;
         *reinterpret_cast<float2*>(d) = make_float2(x.x, x.y);
         *reinterpret_cast<float2*>(d + 2) = make_float2(x.z, x.w);
@@ -1436,8 +1470,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             F3_SCORE_TILE(krow, (void)0);
 #pragma unroll
             for (int rgp = 0; rgp < 2; ++rgp) {
-                const int tb = li, head = kvh * KVM + 2 * rp + rgp, b = b0 + tb;
-                const int ts0 = t0 + 16 * tq + 4 * lq, lim = tb < nb ? pos0 + b : -1;       // attended: ts <= lim
+                const int tb = li, head = hg.h0 + 2 * rp + rgp, b = b0 + tb;
+                const int ts0 = t0 + 16 * tq + 4 * lq, lim = tb < nb && hg.real(2 * rp + rgp) ? pos0 + b : -1;       // attended: ts <= lim (a surplus head slot: nothing)
                 float v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -1463,9 +1497,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         __syncthreads();
         if (tmx && t < ROWS) {
             const int tb = t & (SCM_TB - 1), b = b0 + tb;
-            if (tb < nb && t0 <= pos0 + b) {
+            if (tb < nb && hg.real(t >> 4) && t0 <= pos0 + b) {
                 const float m = fmaxf(fmaxf(mxs[t], mxs[ROWS + t]), fmaxf(mxs[2 * ROWS + t], mxs[3 * ROWS + t]));
-                tmx[((size_t)b * n_heads + kvh * KVM + (t >> 4)) * tmx_tiles + tile] = m;
+                tmx[((size_t)b * n_heads + hg.h0 + (t >> 4)) * tmx_tiles + tile] = m;
             }
         }
     }
@@ -1485,11 +1519,13 @@ static int32_t pf_attention_attributes(gl3_ctx* ctx) {
     GL3_ATTR150((pf_scores_pk_kernel<128, 4>)); GL3_ATTR150((pf_scores_pk_kernel<128, 2>)); GL3_ATTR150((pf_scores_pk_kernel<128, 1>));
     GL3_ATTR150((pf_scores_pk_kernel<64, 4>)); GL3_ATTR150((pf_scores_pk_kernel<64, 2>)); GL3_ATTR150((pf_scores_pk_kernel<64, 1>));
     GL3_ATTR150((pf_scores_pk_kernel<32, 4>)); GL3_ATTR150((pf_scores_pk_kernel<32, 2>)); GL3_ATTR150((pf_scores_pk_kernel<32, 1>));
+    GL3_ATTR150((pf_scores_pk_kernel<96, 4>)); GL3_ATTR150((pf_scores_pk_kernel<96, 2>)); GL3_ATTR150((pf_scores_pk_kernel<96, 1>));
     // the run-table forms of the long-context kernels (the deep rows of a mixed step)
     GL3_ATTR150((pf_scores_mfma_kernel<128, true>)); GL3_ATTR150((pf_scores_mfma_kernel<64, true>)); GL3_ATTR150((pf_pv_mfma_kernel<128, true>)); GL3_ATTR150((pf_pv_mfma_kernel<64, true>));
     GL3_ATTR150((pf_scores_pk_kernel<128, 4, true>)); GL3_ATTR150((pf_scores_pk_kernel<128, 2, true>)); GL3_ATTR150((pf_scores_pk_kernel<128, 1, true>));
     GL3_ATTR150((pf_scores_pk_kernel<64, 4, true>)); GL3_ATTR150((pf_scores_pk_kernel<64, 2, true>)); GL3_ATTR150((pf_scores_pk_kernel<64, 1, true>));
     GL3_ATTR150((pf_scores_pk_kernel<32, 4, true>)); GL3_ATTR150((pf_scores_pk_kernel<32, 2, true>)); GL3_ATTR150((pf_scores_pk_kernel<32, 1, true>));
+    GL3_ATTR150((pf_scores_pk_kernel<96, 4, true>)); GL3_ATTR150((pf_scores_pk_kernel<96, 2, true>)); GL3_ATTR150((pf_scores_pk_kernel<96, 1, true>));
 #undef GL3_ATTR150
     return GL3_OK;
 }

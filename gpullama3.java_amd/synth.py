@@ -119,6 +119,10 @@ CONFIGS = {
     # ragged everything for the > 64-token GEMM: K = 288 / 864 (9 / 27 blocks: the last K stage holds ONE real block), 288 / 480 / 864 rows
     # (not multiples of the 64- / 96- / 128-row tiles), 9 heads on 3 kv heads
     "ragged-llama": ModelConfig("ragged-llama-random", ARCH_LLAMA, 288, 864, 2, 9, 3, 32, 544, 200, 1e-5, 10000.0, False),
+    # full-size shapes of the families whose prefill attention runs in head groups (kvMul 7: 28 / 4 heads of 128, q/k/v bias, untied) and at
+    # head size 96 (32 / 32 heads): scripts/attn_groups_pp.py measures them with few layers
+    "qwen2.5-7b": ModelConfig("Qwen2.5-7B-random", ARCH_QWEN2, 3584, 18944, 28, 28, 4, 128, 152064, 648, 1e-6, 1000000.0, False),
+    "phi-3-mini": ModelConfig("Phi-3-mini-random", ARCH_PHI3, 3072, 8192, 32, 32, 32, 96, 32064, 648, 1e-5, 10000.0, False),
 }
 
 

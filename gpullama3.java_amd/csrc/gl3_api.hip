@@ -804,6 +804,7 @@ void gl3_destroy(gl3_ctx* ctx) {
     if (ctx->comm) ncclCommDestroy(ctx->comm);
     gl3_prefill_free(ctx);
     gl3_sample_free(ctx);
+    gl3_score_free(ctx);
     for (auto e : ctx->ev) hipEventDestroy(e);
     auto f = [](void* p) { if (p) hipFree(p); };
     f(ctx->emb.w);
@@ -1250,6 +1251,37 @@ int32_t gl3_forward_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int3
     const float* logits; const int32_t* greedy;
     gl3_decode_batch_outputs(ctx, &logits, &greedy);
     return gl3_sample_batch_finish(ctx, logits, greedy, n_out, tokens_out);
+}
+
+// The mixed step + score_rows_kernel over its output rows (gl3_sample.hip); the logits stay on the device.  Always the mixed entry's own
+// step, also when every run is a single wanted row: gl3_get_x and the step buffers then answer as after every mixed step.
+int32_t gl3_forward_batch_score(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits,
+                                int32_t n, const int32_t* targets, const float* temperature, gl3_token_score* scores_out, int32_t* argmax_out) {
+    if (!ctx) return GL3_E_ARG;
+    BatchPlan bp;
+    int32_t r = check_mixed(ctx, tokens, seq_ids, positions, want_logits, n, bp);
+    if (r != GL3_OK) return r;
+    const int n_out = (int)bp.out_rows.size();
+    if (n_out == 0) return gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, nullptr);      // nothing to score: a pure prefill
+    if (!scores_out) GL3_FAIL(GL3_E_ARG, "null scores_out");
+    if ((r = gl3_score_prepare(ctx, n_out, targets, temperature)) != GL3_OK) return r;
+    if ((r = gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, argmax_out, false)) != GL3_OK) return r;
+    const float* logits; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits, &greedy);
+    return gl3_score_finish(ctx, logits, n_out, scores_out);
+}
+
+int32_t gl3_score_rows(gl3_ctx* ctx, const float* logits, int32_t n, const int32_t* targets, const float* temperature, gl3_token_score* scores_out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!logits || !scores_out || n <= 0) GL3_FAIL(GL3_E_ARG, "bad logits / scores_out arrays");
+    int32_t r = check_batch_sampler(ctx);
+    if (r != GL3_OK) return r;
+    if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
+    if ((r = gl3_score_prepare(ctx, n, targets, temperature)) != GL3_OK) return r;
+    if ((r = gl3_decode_batch_load_logits(ctx, logits, n)) != GL3_OK) return r;
+    const float* logits_dev; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits_dev, &greedy);
+    return gl3_score_finish(ctx, logits_dev, n, scores_out);
 }
 
 int32_t gl3_debug_batch_plan(const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits, int32_t n, int32_t n_seqs, int32_t ctx_len,

@@ -158,6 +158,17 @@ struct gl3_sample_state {
     gl3_sample_state(int blocks_, bool graph_) : blocks(blocks_), graph(graph_) {}
 };
 
+// Token scores (score_rows_kernel, gl3_sample.hip): a row's settings as the kernel reads them, and everything scoring keeps on the device
+struct ScoreRow { int target; float temperature; };
+struct gl3_score_state {
+    int rows = 0;                              // capacity of every buffer below
+    ScoreRow* params = nullptr;                // [rows]
+    ScoreRow* h_params = nullptr;              // pinned
+    gl3_token_score* out = nullptr;            // [rows]
+    gl3_token_score* h_out = nullptr;          // pinned
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // GL3_SCORE_TIMING=1 only
+};
+
 struct gl3_ctx {
     gl3_model_desc d{};
     // derived (local = this tensor-parallel rank's share)
@@ -205,6 +216,7 @@ struct gl3_ctx {
     // samplers (gl3_sample.hip): one set of kernels, one state per entry, so each entry's parity tap answers for its own last step
     gl3_sample_state smp_one{256, false};         // gl3_forward_decode_sample: one row, eager launches
     gl3_sample_state smp_rows{64, true};          // static-batched entries: grows with the batch, one hipGraph per (rows, any top-p row)
+    gl3_score_state score;                        // gl3_forward_batch_score / gl3_score_rows
     std::vector<std::pair<void*, size_t>> pinned;     // caller buffers registered with gl3_pin_host_buffer (logits land there directly)
     // upload staging
     uint8_t* staging = nullptr;
@@ -285,6 +297,11 @@ void gl3_sample_free(gl3_ctx* ctx);
 int32_t gl3_sample_batch_prepare(gl3_ctx* ctx, int32_t n, const float* temperature, const float* topp, const float* coins, bool* all_greedy);
 int32_t gl3_sample_batch_finish(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n, int32_t* tokens_out);
 int32_t gl3_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);
+// token scores: prepare = every check + stage (target, temperature) of the n rows (temperature NULL: 1), before the step is enqueued;
+// finish = score_rows_kernel behind the step on the plan's stream, 16 * n bytes back
+int32_t gl3_score_prepare(gl3_ctx* ctx, int32_t n, const int32_t* targets, const float* temperature);
+int32_t gl3_score_finish(gl3_ctx* ctx, const float* logits_dev, int32_t n, gl3_token_score* scores_out);
+void gl3_score_free(gl3_ctx* ctx);
 
 // gl3_prefill.hip
 float* gl3_prefill_buf(gl3_ctx* ctx, int which);

@@ -409,6 +409,79 @@ __global__ __launch_bounds__(256) void btp_pick_kernel(const SmpRow* __restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------------------ token scores
+// gl3_forward_batch_score / gl3_score_rows: the probability softmaxInPlace(logits / temperature) gives ONE known token per row (the next
+// token of a text, a drafted token), FloatTensor.java:203-219 with the arithmetic of the sampler above — but nothing of a row is kept
+// except four floats.  One launch, one workgroup per row, rows a grid dimension, the row's settings read from device memory (ScoreRow):
+//   pass 1  the row's maximum.  Found by a first pass over the row INSIDE this kernel rather than by block maxima in a launch of its own:
+//           the workgroup that sums a row sequentially has to stream the whole row anyway, so a separate launch would add a launch gap
+//           and an O(rows * blocks) buffer to save one read that the second pass then finds in L2 / the Infinity Cache; with many rows
+//           (a perplexity chunk) every CU has a row of its own and the machine is as busy as block maxima would make it.  Division by a
+//           positive temperature is monotone under round-to-nearest, so max_i (l[i] / T) = (max_i l[i]) / T: one division.
+//   pass 2  SM_CHUNK numerators (float) exp((double)(l[i] / T - max)) at a time into LDS, then the strictly sequential f32 sum of the chunk
+//           continued from the exact running value, with bsm_seqsum_kernel's split: exact_seqsum_lds for >= 1024 elements (multiple of 4),
+//           the naive chain for a shorter chunk and for up to 3 trailing elements.  The numerator of the target is picked up from LDS in
+//           the chunk that holds it.
+// No [rows][vocab] intermediate exists: device memory grows by 8 + 16 bytes per row.  The logits are read, never written.
+// n % 4 == 0 (gl3_create: vocab is a multiple of 16), so rows are 16-byte aligned and every global / LDS access is a float4.
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int n, const ScoreRow* __restrict__ rows, gl3_token_score* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    float* xf = reinterpret_cast<float*>(smem);                      // [SM_CHUNK + 32]
+    uint8_t* scratch = smem + (size_t)(SM_CHUNK + 32) * 4;
+    float* sh = reinterpret_cast<float*>(scratch + ss_scratch_bytes(SM_CHUNK));      // [0..3] wavefront maxima, [4] running sum, [5] target numerator
+    const int row = blockIdx.x;
+    const ScoreRow R = rows[row];
+    const float T = R.temperature;
+    const float4* lg4 = reinterpret_cast<const float4*>(logits + (size_t)row * n);
+    const int t = threadIdx.x;
+    float mx = -INFINITY;
+    for (int i = t; i < (n >> 2); i += 256) {
+        const float4 v = lg4[i];
+        mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+    }
+    mx = wave_max(mx);
+    if ((t & 63) == 0) sh[t >> 6] = mx;
+    if (t == 0) { sh[4] = 0.f; sh[5] = 0.f; }
+    __syncthreads();
+    mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3])) / T;      // divideInPlace(temperature), then max
+    const int nchunks = (n + SM_CHUNK - 1) / SM_CHUNK;
+    for (int c = 0; c < nchunks; ++c) {
+        const int base = c * SM_CHUNK, len = min(SM_CHUNK, n - base);
+        for (int i = 4 * t; i < SM_CHUNK + 32; i += 1024) {
+            float4 e = {0.f, 0.f, 0.f, 0.f};                          // zero padding behind the chunk (exact_seqsum_lds reads it)
+            if (i < len) {
+                const float4 v = lg4[(base + i) >> 2];
+                e.x = (float)exp((double)(v.x / T - mx));            // (float) Math.exp(f - maxVal)
+                e.y = (float)exp((double)(v.y / T - mx));
+                e.z = (float)exp((double)(v.z / T - mx));
+                e.w = (float)exp((double)(v.w / T - mx));
+            }
+            *reinterpret_cast<float4*>(xf + i) = e;
+        }
+        __syncthreads();
+        float run = sh[4];
+        const int n4 = len & ~3;
+        if (n4 >= 1024) {
+            BlockBarrier bb;
+            run = exact_seqsum_lds<false>(xf, n4, scratch, t, bb, run);
+            if (n4 < len && t < 64) run = naive_sumsq_lds<false>(xf, n4, len, run);      // at most 3 trailing elements
+        } else if (t < 64) {
+            run = naive_sumsq_lds<false>(xf, 0, len, run);
+        }
+        __syncthreads();
+        if (t == 0) {
+            sh[4] = run;
+            if (R.target >= base && R.target < base + len) sh[5] = xf[R.target - base];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        const float sum = sh[4];
+        const float4 o = {sh[5] / sum, logits[(size_t)row * n + R.target] / T, mx, sum};      // softmaxInPlace(v)[target], v[target], max, sum
+        *reinterpret_cast<float4*>(out + row) = o;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static void sample_drop_graphs(gl3_sample_state* b) {
     for (auto& ge : b->graphs) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }
@@ -583,5 +656,64 @@ int32_t gl3_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out) {      // pa
     if (row < 0 || row >= b->last_n) GL3_FAIL(GL3_E_ARG, "row outside the last batched sampled step");
     if (b->h_params[row].mode == SMP_GREEDY) GL3_FAIL(GL3_E_STATE, "the row was greedy: it has no probabilities");
     GL3_HIP(hipMemcpy(out, b->probs + (size_t)row * ctx->d.vocab, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToHost));
+    return GL3_OK;
+}
+
+// ---- token scores: prepare = every check + stage the rows' settings (before the step is enqueued), finish = the one launch behind the
+// step on the plan's stream and 16 * n bytes back in one copy
+void gl3_score_free(gl3_ctx* ctx) {
+    gl3_score_state* b = &ctx->score;
+    if (b->params) hipFree(b->params);
+    if (b->out) hipFree(b->out);
+    if (b->h_params) hipHostFree(b->h_params);
+    if (b->h_out) hipHostFree(b->h_out);
+    if (b->ev0) hipEventDestroy(b->ev0);
+    if (b->ev1) hipEventDestroy(b->ev1);
+    *b = gl3_score_state{};
+}
+
+int32_t gl3_score_prepare(gl3_ctx* ctx, int32_t n, const int32_t* targets, const float* temperature) {
+    gl3_score_state* b = &ctx->score;
+    if (!targets) GL3_FAIL(GL3_E_ARG, "null targets");
+    for (int i = 0; i < n; ++i) {
+        if (targets[i] < 0 || targets[i] >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "target id out of range");
+        if (temperature && !(temperature[i] > 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be > 0");
+    }
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    if (b->rows < n) {      // all or none, as sample_alloc
+        if (b->rows) GL3_HIP(hipStreamSynchronize(ctx->stream));
+        gl3_score_free(ctx);
+        hipError_t e = hipMalloc((void**)&b->params, (size_t)n * sizeof(ScoreRow));
+        if (e == hipSuccess) e = hipMalloc((void**)&b->out, (size_t)n * sizeof(gl3_token_score));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_params, (size_t)n * sizeof(ScoreRow));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_out, (size_t)n * sizeof(gl3_token_score));
+        if (e != hipSuccess) { gl3_score_free(ctx); GL3_HIP(e); }
+        b->rows = n;
+    }
+    for (int i = 0; i < n; ++i) b->h_params[i] = ScoreRow{targets[i], temperature ? temperature[i] : 1.f};
+    GL3_HIP(hipMemcpyAsync(b->params, b->h_params, (size_t)n * sizeof(ScoreRow), hipMemcpyHostToDevice, ctx->stream));
+    return GL3_OK;
+}
+
+int32_t gl3_score_finish(gl3_ctx* ctx, const float* logits_dev, int32_t n, gl3_token_score* scores_out) {
+    gl3_score_state* b = &ctx->score;
+    hipStream_t s = ctx->stream;
+    const size_t smem = (size_t)(SM_CHUNK + 32) * 4 + ss_scratch_bytes(SM_CHUNK) + 32;
+    static const bool timed = env_flag("GL3_SCORE_TIMING", false);      // measurement switch: HIP events around the launch, its device time on stderr
+    if (timed && !b->ev0) { GL3_HIP(hipEventCreate(&b->ev0)); GL3_HIP(hipEventCreate(&b->ev1)); }
+    if (timed) GL3_HIP(hipEventRecord(b->ev0, s));
+    hipLaunchKernelGGL(score_rows_kernel, dim3(n), dim3(256), smem, s, logits_dev, ctx->d.vocab, b->params, b->out);
+    if (timed) GL3_HIP(hipEventRecord(b->ev1, s));
+    GL3_HIP(hipGetLastError());
+    GL3_HIP(hipMemcpyAsync(b->h_out, b->out, (size_t)n * sizeof(gl3_token_score), hipMemcpyDeviceToHost, s));
+    GL3_HIP(hipStreamSynchronize(s));
+    const int32_t r = gl3_tp_check(ctx);
+    if (r != GL3_OK) return r;
+    if (timed) {
+        float ms = 0.f;
+        GL3_HIP(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+        fprintf(stderr, "gl3 score_rows_kernel rows %d: %.1f us\n", n, ms * 1e3);
+    }
+    memcpy(scores_out, b->h_out, (size_t)n * sizeof(gl3_token_score));
     return GL3_OK;
 }

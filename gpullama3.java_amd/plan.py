@@ -28,6 +28,10 @@ def _p(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# gl3_token_score (include/gpullama3_hip.h): 16 bytes per row
+SCORE_DTYPE = np.dtype([("prob", np.float32), ("logit", np.float32), ("max", np.float32), ("sum", np.float32)])
+
+
 class HipMasterPlan:
     def __init__(self, model, prefill_batch_size: int = 1, device: int = 0, tp_rank: int = 0, tp_size: int = 1,
                  flags: int = 0, unique_id: bytes | None = None, local_group=None, n_seqs: int = 1, p2p_exchange=None):
@@ -239,6 +243,35 @@ class HipMasterPlan:
         ids = np.empty(n, np.int32)
         hip.check(hip.lib().gl3_sample_rows(self._ctx, _p(lg), n, _p(te), _p(tp), _p(co), _p(ids)), self._ctx)
         return ids
+
+    def _score_args(self, targets, temperature, n):
+        """targets int32[n] (None: NULL, which the library refuses), temperature f32[n] or None for 1 everywhere, the result array"""
+        tg = np.ascontiguousarray(targets, np.int32) if targets is not None else None
+        assert tg is None or tg.shape == (n,)
+        te = self._per_row(temperature, n) if temperature is not None else None
+        return tg, te, np.zeros(n, SCORE_DTYPE)
+
+    def forward_batch_score(self, tokens, seq_ids, positions, targets, temperature=None, want_logits=None):
+        """Mixed batched step + the score of one known token per OUTPUT row on the device (gl3_forward_batch_score) -> (scores, greedy ids
+        [n_out]).  scores: structured array [n_out] with fields prob, logit, max, sum; targets: one id per output row; temperature: one
+        entry per output row (a scalar broadcasts), None = 1."""
+        t, s, p, w, n_out = self._mixed_args(tokens, seq_ids, positions, want_logits)
+        tg, te, scores = self._score_args(targets, temperature, n_out)
+        ids = np.empty(n_out, np.int32)
+        hip.check(hip.lib().gl3_forward_batch_score(self._ctx, _p(t), _p(s), _p(p), _p(w) if w is not None else None, t.size,
+                                                    _p(tg) if tg is not None else None, _p(te) if te is not None else None,
+                                                    _p(scores) if n_out else None, _p(ids) if n_out else None), self._ctx)
+        return scores, ids
+
+    def score_rows(self, logits, targets, temperature=None) -> np.ndarray:
+        """The scoring kernel alone on host logits [n][vocab] (no forward pass) -> scores [n] (fields prob, logit, max, sum)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2 and lg.shape[1] == self.cfg.vocab
+        n = lg.shape[0]
+        tg, te, scores = self._score_args(targets, temperature, n)
+        hip.check(hip.lib().gl3_score_rows(self._ctx, _p(lg), n, _p(tg) if tg is not None else None, _p(te) if te is not None else None,
+                                           _p(scores)), self._ctx)
+        return scores
 
     def sample_probs_row(self, row: int) -> np.ndarray:
         """The probabilities row `row` of the last batched sampled step was drawn from."""

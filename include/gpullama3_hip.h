@@ -302,6 +302,26 @@ GL3_API int32_t gl3_forward_batch(gl3_ctx* ctx, const int32_t* tokens, const int
 GL3_API int32_t gl3_forward_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
                                          const int8_t* want_logits, int32_t n, const float* temperature, const float* topp,
                                          const float* coins, int32_t* tokens_out);
+/* What softmaxInPlace(logits row / temperature) (FloatTensor.java:203-219) says about ONE token of an output row, all f32 with the
+ * reference's arithmetic: v[i] = l[i] / T, max = max_i v[i], e[i] = (float) exp((double) (v[i] - max)), sum = the strictly sequential sum
+ * ((0f + e[0]) + e[1]) + ..., prob = e[target] / sum, logit = v[target].  prob underflows to 0 once logit - max is below about -103; a
+ * caller that needs ln p computes (double) (logit - max) - log((double) sum). */
+typedef struct { float prob, logit, max, sum; } gl3_token_score;
+/* The step of gl3_forward_batch + the score of one known token per OUTPUT row (speculative verification at a temperature, perplexity):
+ * targets: int32[n_out], the token whose probability is wanted (the next token of the text, the drafted token); temperature: f32[n_out],
+ * each > 0, or NULL for 1 everywhere; scores_out: gl3_token_score[n_out]; argmax_out: int32[n_out] (the greedy id of every output row, as
+ * gl3_forward_batch gives it) or NULL.  The logits never leave the device and no [rows][vocab] buffer beside them exists: one launch, one
+ * workgroup per row, behind the step on the plan's stream, and 16 * n_out bytes come back in one copy (gl3_sample.hip).  n_out == 0 is a
+ * pure prefill, as in gl3_forward_batch_sample.  GL3_E_ARG, before anything is enqueued: everything gl3_forward_batch refuses, n_out > 0
+ * with targets or scores_out NULL, a target outside [0, vocab), a temperature that is not > 0 (NaN included).  GL3_E_UNSUPPORTED:
+ * max_batch <= 1, tp_size > 1. */
+GL3_API int32_t gl3_forward_batch_score(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
+                                        const int8_t* want_logits, int32_t n, const int32_t* targets, const float* temperature,
+                                        gl3_token_score* scores_out, int32_t* argmax_out);
+/* Parity tap: the same scores on caller-supplied logits (host f32[n][vocab]); no forward pass, no KV change.  Needs a plan with
+ * max_batch > 1; n <= max_batch.  The logits buffer of the batched step is overwritten.  Errors as above. */
+GL3_API int32_t gl3_score_rows(gl3_ctx* ctx, const float* logits, int32_t n, const int32_t* targets, const float* temperature,
+                               gl3_token_score* scores_out);
 /* Test hook, no plan and no device: the host-side plan of a mixed step (csrc/gl3_batch_plan.h) for a plan with n_seqs sequence slots,
  * context length ctx and room for `capacity` rows.  runs_out / tiles_out: int32[.][4] = {first row, rows, sequence, position of the
  * first row}, room for n records each (tiles: at most 8 rows, never across a run boundary, deepest last position first); out_rows:

@@ -637,7 +637,10 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     if (d.dim <= 0 || d.dim % 32 || d.hidden % 32 || d.n_layers <= 0 || d.n_heads <= 0 || d.n_kv_heads <= 0 ||
         d.n_heads % d.n_kv_heads || d.vocab <= 0 || d.ctx <= 0)
         return bail(GL3_E_ARG, "bad model dimensions");
-    if (d.head_size < 32 || d.head_size > 256 || d.head_size % 32)       // 96: Phi-3-mini; 160 / 192 / 224 work the same way
+    // 96: Phi-3-mini.  160 / 192 / 224 / 256 have neither attn_head_kernel (its K / V tiles do not fit LDS) nor tiled prefill kernels: decode runs
+    // the two-launch pair from position 0, batched steps the per-row kernels.  Every head size here and kvMul 1 - 16 is run against the CPU oracle in
+    // all decode regimes, static-batched and mixed steps (tests/test_gpu_attn_shapes.py; the dispatch by shape: DESIGN.md §4)
+    if (d.head_size < 32 || d.head_size > 256 || d.head_size % 32)
         return bail(GL3_E_UNSUPPORTED, "head_size must be a multiple of 32 between 32 and 256");
     const int tp = d.tp_size < 1 ? 1 : d.tp_size;
     ctx->d.tp_size = tp;

@@ -1,0 +1,54 @@
+"""What the attention shape grid (tests/attn_shapes.py) covers, and the dispatch rule it states, checked without a GPU."""
+import attn_shapes as sh
+
+
+def test_the_grid_covers_every_head_size_kvmul_and_family():
+    """Computed from the grid: the head sizes, the kvMul set of each kernel class (looping scores kernel, one-tile scores kernel, 1024-thread
+    workgroups, the attn_head_kernel group forms) and the families at the new head sizes.  Dropping a row must fail: every row is the only
+    one that meets some requirement."""
+    names = sorted(sh.SHAPES)
+    assert sh.missing(names) == []
+    for drop in names:
+        assert sh.missing([n for n in names if n != drop]), "the grid covers the same without %s" % drop
+    assert {sh.head_size_of(n) for n in names} >= {32, 64, 128, 160, 192, 224, 256}
+    assert {sh.kvmul_of(n) for n in names} >= {1, 2, 3, 5, 7, 8, 16}
+    assert all(sh.SHAPES[n][3] >= 2 for n in names if n != "llama-hs256-kv16")
+
+
+def test_every_shape_is_a_tiny_config_the_library_accepts(pkg):
+    for name in sh.SHAPES:
+        c = sh.shape_config(pkg.synth, name, 1100)
+        assert (c.dim, c.hidden, c.n_layers, c.vocab, c.ctx) == (256, 512, 2, 512, 1100)
+        assert c.head_size % 32 == 0 and 32 <= c.head_size <= 256 and c.n_heads % c.n_kv_heads == 0 and c.n_heads // c.n_kv_heads <= 16      # gl3_create
+        assert sh.scores_kernel_lds(c.head_size, c.n_heads // c.n_kv_heads) <= 128 * 1024      # what gl3_create allows attn_scores_kernel
+    assert sh.scores_kernel_lds(256, 16) > 64 * 1024                                                 # ... and more than a launch gets unasked
+
+
+def test_the_dispatch_rule():
+    """attn_head_kernel exists up to head size 128; the group form of a static-batched step up to kvMul 8; the decode regimes change at 128 and 768"""
+    assert [hs for hs in range(32, 257, 32) if sh.has_head_kernel(hs)] == [32, 64, 96, 128]
+    assert sh.attn_head_smem(128) == 134720 and sh.attn_head_smem(160) > sh.LDS_MAX
+    assert [sh.bd_group(128, m) for m in (4, 5, 7, 8, 16)] == [4, 5, 7, 8, 1] and sh.bd_group(64, 16) == 1
+    assert [sh.decode_regime(64, 5, p) for p in (0, 127, 128, 767, 768)] == ["head", "head", "pair", "pair", "long-tile"]
+    assert [sh.decode_regime(64, 5, p, head_kernel=False) for p in (0, 127, 128)] == ["pair"] * 3
+    assert [sh.decode_regime(160, 2, p) for p in (0, 127, 767, 768)] == ["pair", "pair", "pair", "long-tile"]
+    assert sh.decode_regime(128, 3, 768) == sh.decode_regime(64, 2, 1030) == "long-loop" and sh.decode_regime(32, 4, 768) == "long-tile"
+    assert sh.batched_rows(64, [3, 127]) == [2, 0, 0, 0] and sh.batched_rows(64, [3, 128]) == [0, 0, 0, 2] and sh.batched_rows(160, [3]) == [0, 0, 0, 1]
+    assert not any(sh.has_tiled_prefill(hs, 1) for hs in (160, 192, 224, 256)) and sh.has_tiled_prefill(32, 16)
+
+
+def test_the_decode_walk_meets_every_regime_of_every_shape():
+    """The positions at which tests/test_gpu_attn_shapes.py decodes: every shape runs each regime it has, the looping scores kernel sees 2 and 3
+    chain wavefronts at both of its head sizes, the one-tile scores kernel every kvMul on the four-launch path."""
+    names = sorted(sh.SHAPES)
+    for name in names:
+        hs, kvmul = sh.head_size_of(name), sh.kvmul_of(name)
+        seen = {sh.decode_regime(hs, kvmul, p) for p in sh.DECODE_AT}
+        assert seen == ({"head"} if sh.has_head_kernel(hs) else set()) | {"pair", "long-loop" if kvmul <= 4 and hs in (64, 128) else "long-tile"}, name
+    at_768 = lambda n: sh.decode_regime(sh.head_size_of(n), sh.kvmul_of(n), 768)
+    assert {(sh.kvmul_of(n), sh.head_size_of(n)) for n in names if at_768(n) == "long-loop"} == {(2, 64), (3, 64), (2, 128), (3, 128)}
+    assert {sh.kvmul_of(n) for n in names if at_768(n) == "long-tile"} >= {1, 2, 3, 5, 7, 8, 16}
+    assert {127, 128, 767, 768} <= set(sh.DECODE_AT) and max(sh.DECODE_AT) >= sh.PV_ROWS + 6 and max(sh.DECODE_AT) // 64 + 1 > 16
+    assert sh.CTX % 4 == 0 and not set(sh.PREFILL_KV_AT) & set(sh.DECODE_AT)
+    for edge in (64, 128, 768, 1024):
+        assert max(p for p in sh.PREFILL_KV_AT if p < edge) >= edge - 3 and min(p for p in sh.PREFILL_KV_AT if p >= edge) <= edge + 3

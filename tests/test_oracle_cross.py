@@ -49,6 +49,20 @@ def test_numpy_and_c_agree_on_fresh_seed(pkg, orc):
             assert np.array_equal(co.forward(t, pos), no.forward(t, pos))
 
 
+def test_numpy_and_c_agree_on_head_size_256_at_kvmul_16_and_qwen3_at_head_size_160(pkg, orc):
+    """Two rows of the attention shape grid (tests/attn_shapes.py) that no config has: 16 query heads of 256 on one kv head (q_dim 4096 on dim 256),
+    and Qwen3's per-head q / k RMSNorm + NeoX RoPE over 160 elements with 5 query heads per kv head.  tests/test_gpu_attn_shapes.py compares the
+    kernels with the C oracle at these shapes; here the C oracle meets the NumPy restatement there first."""
+    import attn_shapes as sh
+    for name in ("llama-hs256-kv16", "qwen3-hs160-kv5"):
+        m = sh.shape_model(pkg, name, ctx=64, seed=1234)
+        assert (m.cfg.head_size, m.cfg.n_heads // m.cfg.n_kv_heads) in ((256, 16), (160, 5))
+        co = orc.COracle(m)
+        no = oracle_np.NpOracle(m.oracle_cfg(), m.oracle_tensors(), m.rope)
+        for pos, t in enumerate(pkg.javarand.bench_tokens(m.cfg.vocab, 5, seed=9)):
+            assert np.array_equal(co.forward(t, pos), no.forward(t, pos)), (name, pos)
+
+
 def test_moe_routing_known_answers(orc):
     """InferenceCore.java:374-390 on hand-made router logits: the weights are the softmax over ALL experts (not renormalised over
     the chosen ones), selection is by strict > so the lowest index wins a tie, and the order is by descending probability."""

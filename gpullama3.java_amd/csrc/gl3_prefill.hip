@@ -49,8 +49,8 @@ struct gl3_prefill_state {
     float* AO = nullptr;                // [M][q_dim] attention output (rank-chunked)
     float* HB = nullptr;                // [M][hidden] (rank-chunked)
     float* ATT = nullptr;               // [M][n_heads][ctx] scores
-    float* TMX = nullptr;               // [M][n_heads][tmx_tiles] per-64-timestep-tile maxima of the score rows (pf_scores_tiled_kernel -> pf_softmax_rows_kernel)
-    float* SUMS = nullptr;              // [M][n_heads] softmax denominators (pf_softmax_rows_kernel -> pf_pv_tiled_kernel)
+    float* TMX = nullptr;               // [M][n_heads][tmx_tiles] per-64-timestep-tile maxima of the score rows (the scores kernels -> pf_softmax_rows_kernel)
+    float* SUMS = nullptr;              // [M][n_heads] softmax denominators (pf_softmax_rows_kernel -> pf_pv_mfma_kernel / pf_pv_ring_kernel)
     int tmx_tiles = 0;
     int32_t* seqpos = nullptr;          // [2][M]: sequence id, position of every token of the step
     // mixed steps (gl3_forward_batch): the attention tile table and the output rows of the step, staged with the tokens
@@ -492,25 +492,21 @@ static inline void pf_kvmul_dispatch(int slots, F&& f) {      // pf_scores_pk_ke
 
 // The conditions that pf_attention and the split limit of a plan's mixed steps (pf_tab_max_pos) both ask, so they cannot disagree.  The
 // switches are read once per process.
-static bool pf_sw_rows_off() { static const bool v = getenv("GL3_PF_SOFTMAX_ROWS") && atoi(getenv("GL3_PF_SOFTMAX_ROWS")) == 0; return v; }
 static bool pf_sw_fused_off() { static const bool v = getenv("GL3_PF_FUSED_ATTN") && atoi(getenv("GL3_PF_FUSED_ATTN")) == 0; return v; }
 static bool pf_sw_v1_only() { static const bool v = env_flag("GL3_PF_FUSED_V1", false); return v; }
-static bool pf_sw_ring_off() { static const bool v = getenv("GL3_PF_PV_RING") && atoi(getenv("GL3_PF_PV_RING")) == 0; return v; }
-// r6: pf_softmax_rows_kernel streams the score rows (no row-fits-LDS limit); GL3_PF_SOFTMAX_ROWS=0: the one-row-per-wavefront kernel
-static bool pf_rows_softmax(const gl3_ctx* ctx) {
-    return !pf_sw_rows_off() && ctx->d.ctx % 4 == 0 && ctx->d.ctx >= 64 && ctx->pf->TMX && ctx->pf->SUMS;
-}
+// pf_softmax_rows_kernel (the long-context trio's softmax) reads 16-byte pieces of 64-timestep tiles of the score rows; a plan without it has
+// the one-launch kernels and the per-row pair
+static bool pf_rows_softmax(const gl3_ctx* ctx) { return ctx->d.ctx % 4 == 0 && ctx->d.ctx >= 64; }
 // A workgroup of the tiled kernels serves a head group (HeadGroup, gl3_prefill_attn.h): pf_group_size(kvMul) head slots, pf_head_groups(kvMul) groups per
 // kv head.  Every LDS size and fit below is asked with the group size: a grouped shape has the limits of kvMul 4 at its head size.
 static int pf_group_size(int kvmul) { return std::min(kvmul, 4); }
 static int pf_head_groups(int kvmul) { const int g = pf_group_size(kvmul); return (kvmul + g - 1) / g; }
 // Shapes the tiled kernels exist for.  kvMul <= 4 at head size 32 / 64 / 128: as ever.  kvMul 5 - 16 (head groups) and head size 96 (the VALU
 // long-context kernels only; the group is orthogonal to the head size, so 96 is served above kvMul 4 too): with pf_softmax_rows_kernel and without
-// the two switches whose kernels know neither (GL3_PF_FUSED_V1=1: pf_attn_fused_kernel, GL3_PF_PV_RING=0: pf_pv_tiled_kernel) — there they keep
-// the per-row pair.
+// the switch whose kernel knows neither (GL3_PF_FUSED_V1=1: pf_attn_fused_kernel) — there they keep the per-row pair.
 static bool pf_tiled_shape(int hs, int kvmul, bool rows_softmax) {
     if (kvmul <= 4 && (hs == 32 || hs == 64 || hs == 128)) return true;
-    return kvmul <= 16 && (hs == 32 || hs == 64 || hs == 96 || hs == 128) && rows_softmax && !pf_sw_v1_only() && !pf_sw_ring_off();
+    return kvmul <= 16 && (hs == 32 || hs == 64 || hs == 96 || hs == 128) && rows_softmax && !pf_sw_v1_only();
 }
 static int pf_fa_sstride(int max_pos) { return ((max_pos + 1 + 63) & ~63) + 4; }      // floats of a score row of the one-launch kernels whose deepest row is at max_pos
 // r4: one launch for scores + softmax + weighted V sum when a tile's score rows fit LDS (GL3_PF_FUSED_ATTN=0: the three kernels)
@@ -543,19 +539,19 @@ static int pf_tab_max_pos(const gl3_ctx* ctx) {
 // caches.  Its shallow tiles (st.ntab records in p->tiles) take the run-table form of the one-launch kernels, its deep rows (st.ndeep records
 // in p->deep, rows past the depth at which a tile's score rows fit LDS) the run-table form of the long-context trio; a step with both writes
 // its output as f32 and the caller's quantise launch serves all rows.  Shapes without tiled kernels and plans without pf_softmax_rows_kernel
-// are not split (pf_tab_max_pos): there the whole step takes the one-launch table form or, failing that, the per-row pair.
+// are not split (pf_tab_max_pos): there the whole step takes the one-launch kernels (a mixed step: their table form) or, failing that, the
+// per-row pair.
 // Every return notes the step's rows by the form that served them (gl3_get_attn_rows).
 static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool fuse_q) {
     // A/B switches, read once at the first call, whichever branch it takes (they are set for the life of the process; nothing sets one
     // after the first step); each says what it turns off where it is used.  The default-on ones keep the getenv / atoi form: set to the
     // empty string it turns the feature off, where env_flag(x, true) would leave it on
-    static const bool v1_only = pf_sw_v1_only();      // (GL3_PF_SOFTMAX_ROWS, GL3_PF_FUSED_ATTN, GL3_PF_FUSED_V1: above, shared with pf_tab_max_pos)
+    static const bool v1_only = pf_sw_v1_only();      // (GL3_PF_FUSED_ATTN, GL3_PF_FUSED_V1: above, shared with pf_tab_max_pos, which reads GL3_PF_TAB_MAXPOS)
     static const bool qao_off = getenv("GL3_PF_ATTN_QOUT") && atoi(getenv("GL3_PF_ATTN_QOUT")) == 0;
     static const bool mfma_off = getenv("GL3_PF_FUSED_MFMA") && atoi(getenv("GL3_PF_FUSED_MFMA")) == 0;
     static const bool pk_off = getenv("GL3_PF_SCORES_PK") && atoi(getenv("GL3_PF_SCORES_PK")) == 0;
     static const bool scm_off = getenv("GL3_PF_SCORES_MFMA") && atoi(getenv("GL3_PF_SCORES_MFMA")) == 0;
     static const int scm_split = getenv("GL3_SCM_SPLIT") ? atoi(getenv("GL3_SCM_SPLIT")) : SCM_SPLIT;      // workgroups that share a (kv head, token tile)'s K tiles
-    static const bool ring_off = pf_sw_ring_off();
     static const bool pvm_off = getenv("GL3_PF_PV_MFMA") && atoi(getenv("GL3_PF_PV_MFMA")) == 0;
     const int n = st.n, max_pos = st.max_pos, one_seq = st.one_seq, ntab = st.ntab, ndeep = st.ndeep;
     const bool runs = st.runs();                          // the run-table forms
@@ -600,14 +596,16 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     }
     hipLaunchKernelGGL(pf_rope_kv_kernel, dim3(H + KVH, n), dim3(64), 0, s, ra);
     const bool rows_softmax = pf_rows_softmax(ctx);
-    const bool tiled = (one_seq >= 0 || runs) && pf_tiled_shape(hs, kvmul, rows_softmax) && (rows_softmax || (size_t)(max_pos + 1) * 4 <= 60 * 1024);
+    const bool tiled = (one_seq >= 0 || runs) && pf_tiled_shape(hs, kvmul, rows_softmax);
     const int group = pf_group_size(kvmul), NG = pf_head_groups(kvmul);      // head slots of a tiled workgroup, head groups per kv head (kvMul <= 4: kvMul, 1)
     const bool mfma_shape = group == 4 && (hs == 128 || hs == 64);      // the kernels with their products on the matrix pipe
     const int fa_sstride = pf_fa_sstride(ndeep ? st.tab_max_pos : max_pos);      // sized by the deepest row the one-launch kernels serve: of the step, or of its shallow tiles
     // (a grouped shape has no pf_attn_fused_kernel form: its one-launch kernels are those of the table form, fused3 / fused2)
     const bool one_launch = NG > 1 ? pf_tab_fits(hs, group, fa_sstride) : pf_one_launch_fits(hs, group, fa_sstride);
     const bool tab_ok = ntab > 0 && tiled && pf_tab_fits(hs, group, fa_sstride);
-    if (!tiled || (ntab > 0 && !tab_ok)) {      // several sequences, or a shape / depth the tiled kernels do not have: the per-token pair
+    // several sequences, a shape the tiled kernels do not have, or rows past the one-launch kernels with no trio to take them (a table the
+    // one-launch kernels cannot serve, a plan without pf_softmax_rows_kernel): the per-token pair
+    if (!tiled || (ntab > 0 && !tab_ok) || (!rows_softmax && !one_launch)) {
         const size_t sm1 = ((size_t)kvmul * d.head_size + (size_t)ATT_TT * (d.head_size + 1)) * 4;
         hipLaunchKernelGGL(pf_attn_scores_kernel, dim3(nsplit, KVH, n), dim3(64 * kvmul), sm1, s, aa);
         aa.win = ctx->attn_win;
@@ -654,9 +652,8 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     const int4* dtab = p->deep;
     const int ntt = ndeep ? ndeep : (n + PA_TB - 1) / PA_TB;
     const dim3 g1(nsplit, KVH * NG, ntt), b1(64 * group);
-    float* tmx = rows_softmax ? p->TMX : nullptr;
     const bool pk = !pk_off && scores_pk_smem_bytes(hs, group) <= PF_ATTN_LDS_MAX && (group == 4 || group == 2 || group == 1);
-    if (rows_softmax && !scm_off && mfma_shape) {      // r6: products on the matrix pipe, query rows resident, K tiles prefetched
+    if (!scm_off && mfma_shape) {      // r6: products on the matrix pipe, query rows resident, K tiles prefetched
         const dim3 g(nsplit < scm_split ? nsplit : scm_split, KVH * NG, ndeep ? ndeep : (n + SCM_TB - 1) / SCM_TB);
         pf_head_dispatch<64>(hs, [&](auto hc) {
             constexpr int HS_ = decltype(hc)::value;
@@ -668,44 +665,34 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
         pf_head_dispatch<32, true>(hs, [&](auto hc) { pf_kvmul_dispatch(group, [&](auto mc) {
             constexpr int HS_ = decltype(hc)::value, KVM_ = decltype(mc)::value;
             if (ndeep) hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_, true>), g1, b1, scores_pk_smem_bytes(hs, group), s, aa.Q, aa.q_stride, kc1, aa.att,
-                                          aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, tmx, p->tmx_tiles, dtab, sst);
+                                          aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, dtab, sst);
             else hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_>), g1, b1, scores_pk_smem_bytes(hs, group), s, aa.Q, aa.q_stride, kc1, aa.att,
-                                    aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, tmx, p->tmx_tiles); }); });
+                                    aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); }); });
     else
         pf_head_dispatch<32, true>(hs, [&](auto hc) {
             constexpr int HS_ = decltype(hc)::value;
             if (ndeep) hipLaunchKernelGGL((pf_scores_tiled_kernel<HS_, true>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att,
-                                          aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, tmx, p->tmx_tiles, dtab, sst);
+                                          aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, dtab, sst);
             else hipLaunchKernelGGL((pf_scores_tiled_kernel<HS_>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att,
-                                    aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, tmx, p->tmx_tiles); });
-    const float* sums = nullptr;
-    if (rows_softmax) {
-        // r6: R rows per workgroup, the sums as R chains of one wavefront; at least one workgroup per CU when the chunk has the rows.
-        // A split step: the deep rows only (a shallow row's ATT / TMX were not written in this step)
-        const int rows = (ndeep ? st.deep_rows : n) * H;
-        const int32_t* rlist = ndeep ? p->deep_rows : nullptr;
-        sums = p->SUMS;
-        if (rows >= 64 * 256) hipLaunchKernelGGL((pf_softmax_rows_kernel<64>), dim3((rows + 63) / 64), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, rlist);
-        else if (rows >= 32 * 256) hipLaunchKernelGGL((pf_softmax_rows_kernel<32>), dim3((rows + 31) / 32), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, rlist);
-        else hipLaunchKernelGGL((pf_softmax_rows_kernel<16>), dim3((rows + 15) / 16), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, rlist);
-    } else {
-        const int npad = (max_pos + 1 + 63) & ~63;
-        int wpw = (int)((60 * 1024) / ((size_t)npad * 4));
-        wpw = wpw > 4 ? 4 : wpw;
-        hipLaunchKernelGGL(pf_softmax_kernel, dim3((n * H + wpw - 1) / wpw), dim3(256), (size_t)wpw * npad * 4, s, aa, n, wpw, npad);
-    }
-    if (sums && !pvm_off && mfma_shape)                 // r6: products on the matrix pipe (no uniform-address LDS reads)
+                                    aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); });
+    // r6: R rows per workgroup, the sums as R chains of one wavefront; at least one workgroup per CU when the chunk has the rows.
+    // A split step: the deep rows only (a shallow row's ATT / TMX were not written in this step)
+    const int rows = (ndeep ? st.deep_rows : n) * H;
+    const int32_t* rlist = ndeep ? p->deep_rows : nullptr;
+    const float* sums = p->SUMS;
+    if (rows >= 64 * 256) hipLaunchKernelGGL((pf_softmax_rows_kernel<64>), dim3((rows + 63) / 64), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, rlist);
+    else if (rows >= 32 * 256) hipLaunchKernelGGL((pf_softmax_rows_kernel<32>), dim3((rows + 31) / 32), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, rlist);
+    else hipLaunchKernelGGL((pf_softmax_rows_kernel<16>), dim3((rows + 15) / 16), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, rlist);
+    if (!pvm_off && mfma_shape)                         // r6: products on the matrix pipe (no uniform-address LDS reads)
         pf_head_dispatch<64>(hs, [&](auto hc) {
             constexpr int HS_ = decltype(hc)::value;
             if (ndeep) hipLaunchKernelGGL((pf_pv_mfma_kernel<HS_, true>), dim3(KVH * NG, ndeep), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, 0, 0, n, sums, dtab);
             else hipLaunchKernelGGL((pf_pv_mfma_kernel<HS_>), dim3(KVH * NG, (n + PVM_TB - 1) / PVM_TB), dim3(1024), pv_mfma_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });
-    else if (sums && (!ring_off || ndeep))              // (pf_pv_tiled_kernel has no table form: GL3_PF_PV_RING=0 does not reach the deep rows of a mixed step)
+    else
         pf_head_dispatch<32, true>(hs, [&](auto hc) {
             constexpr int HS_ = decltype(hc)::value;
             if (ndeep) hipLaunchKernelGGL((pf_pv_ring_kernel<HS_, true>), dim3(H, ndeep), dim3(64 * PVR_NW), pv_ring_smem_bytes(hs), s, aa, 0, 0, n, sums, dtab);
             else hipLaunchKernelGGL((pf_pv_ring_kernel<HS_>), dim3(H, (n + PVR_TB - 1) / PVR_TB), dim3(64 * PVR_NW), pv_ring_smem_bytes(hs), s, aa, one_seq, pos0, n, sums); });
-    else if (hs > 64) hipLaunchKernelGGL((pf_pv_tiled_kernel<2>), dim3(H, ntt), dim3(256), pv_tiled_smem_bytes(hs), s, aa, one_seq, pos0, n, sums);
-    else hipLaunchKernelGGL((pf_pv_tiled_kernel<1>), dim3(H, ntt), dim3(256), pv_tiled_smem_bytes(hs), s, aa, one_seq, pos0, n, sums);
     if (ndeep) note_rows(0, n - st.deep_rows, st.deep_rows, 0);
     else note_rows(0, 0, n, 0);
     return false;

@@ -414,34 +414,12 @@ __global__ __launch_bounds__(64 * KVM) __attribute__((amdgpu_waves_per_eu(2, 2))
     }
 }
 
-// Softmax of every (token, head) score row, in place: one wavefront per row, wpw rows per workgroup.
-// max -> exp in double -> sequential f32 sum -> divide (InferenceCore.java softmax via FloatTensor.softmaxInPlace).
-__global__ __launch_bounds__(256) void pf_softmax_kernel(const PfAttnArgs a, int ntok, int wpw, int npad) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int pair = blockIdx.x * wpw + w;
-    const bool live = w < wpw && pair < ntok * a.n_heads;
-    const int b = live ? pair / a.n_heads : 0;
-    const int n = live ? a.pos[b] + 1 : 0;
-    float* sc = a.att + (size_t)(live ? pair : 0) * a.ctx;
-    float* e_s = sm + (size_t)(w < wpw ? w : 0) * npad;
-    float mx = -INFINITY;
-    for (int i = lane; i < n; i += 64) { const float v = sc[i]; e_s[i] = v; mx = fmaxf(mx, v); }
-    mx = wave_max(mx);
-    for (int i = lane; i < n; i += 64) e_s[i] = (float)exp((double)(e_s[i] - mx));   // lane-private slots so far
-    __syncthreads();
-    const float sum = seq_sum_lds_ring(e_s, n);      // LDS reads pinned three groups ahead of the adds (~6 instead of ~11 cycles per element)
-    for (int i = lane; i < n; i += 64) sc[i] = e_s[i] / sum;
-}
-
 // r6 — softmax of the score rows at depth, R rows per workgroup: 8 worker wavefronts stream the rows' 64-timestep tiles (loads a tile ahead,
 // e_t = (float) exp((double) (s_t - max)) written back in place and into a double-buffered LDS tile), a ninth wavefront runs the strictly
 // sequential sums with lane = row — R chains side by side, LDS reads pinned ahead of the adds (seq_sum_lds_ring).  The row maxima come from
 // the per-tile maxima pf_scores_tiled_kernel leaves in tmx (max is order-independent); the denominators go to `sums` and the division
-// e_t / sum happens where the weights are staged (pf_pv_tiled_kernel) — same operands, same rounding as FloatTensor.softmaxInPlace
-// (J/tensor/standard/FloatTensor.java:196-219: max, exp, sum, divide).  pf_softmax_kernel keeps ONE row per wavefront in LDS: its row loads
-// are one HBM round trip per 64 scores, its sums one chain per wavefront and at most three rows per workgroup fit at 4608 positions:
-// 640 us per 8B layer at pp512 @ d4096 against ~150 us here.  Needs ctx % 4 == 0 (16-byte row starts).
+// e_t / sum happens where the weights are staged (pf_pv_mfma_kernel / pf_pv_ring_kernel) — same operands, same rounding as
+// FloatTensor.softmaxInPlace (J/tensor/standard/FloatTensor.java:196-219: max, exp, sum, divide).  Needs ctx % 4 == 0 (16-byte row starts).
 // `rows` (null: every row of the step, row i = (token i / n_heads, head i % n_heads)): the deep step rows of a mixed step, ascending — the launch
 // covers rows x n_heads score rows and touches ATT / TMX / SUMS of those step rows only (a shallow row's were not written in this step).
 constexpr int SR_PITCH = 68;
@@ -517,99 +495,9 @@ __global__ __launch_bounds__(576) void pf_softmax_rows_kernel(const PfAttnArgs a
     }
 }
 
-// Weighted V sum: grid = (n_heads, token tiles), block 256.  V tiles of 64 timesteps are staged in LDS once per
-// workgroup; wavefront w carries tokens 4w..4w+3 of the tile, lane j the output columns j (+64): acc = a_t * v + acc,
-// t ascending.  The softmax weights are wavefront-uniform loads.
-__host__ __device__ constexpr size_t pv_tiled_smem_bytes(int hs) { return (size_t)64 * (hs + PA_TB) * 4; }
-template <int NCOL>
-__global__ __launch_bounds__(256) void pf_pv_tiled_kernel(const PfAttnArgs a, int seq, int pos0, int ntok, const float* __restrict__ sums) {
-    extern __shared__ __attribute__((aligned(16))) float vt[];        // [64][hs]
-    const int hs = a.hs, h4 = hs >> 2, kvmul = a.n_heads / a.n_kv_heads;
-    const int t = threadIdx.x, lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int h = blockIdx.x, kvh = h / kvmul, b0 = blockIdx.y * PA_TB;
-    const int nb = min(PA_TB, ntok - b0);
-    const int tmax = pos0 + b0 + nb - 1;
-    const float* vc = a.vcache + (size_t)seq * a.seq_stride;
-    float* as = vt + 64 * hs;                                         // [PA_TB][64] softmax weights of the current tile
-    int posu[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) posu[u] = 4 * w + u < nb ? pos0 + b0 + 4 * w + u : -1;   // -1: no timestep qualifies
-    const int wmax = 4 * w < nb ? pos0 + b0 + min(4 * w + 3, nb - 1) : -1;
-    float acc[4][NCOL];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int c = 0; c < NCOL; ++c) acc[u][c] = 0.f;
-    for (int t0 = 0; t0 <= tmax; t0 += 64) {
-        const int tt = min(64, tmax + 1 - t0);
-        __syncthreads();
-        for (int i = t; i < tt * h4; i += 256) {
-            const int r = i / h4, c = i % h4;
-            *reinterpret_cast<float4*>(vt + r * hs + 4 * c) =
-                *reinterpret_cast<const float4*>(vc + (size_t)(t0 + r) * a.kv_dim + kvh * hs + 4 * c);
-        }
-        for (int i = t; i < PA_TB * 64; i += 256) {                   // entries past a token's position are never used
-            const int tb = i >> 6, r = i & 63;
-            float wv = (tb < nb && t0 + r <= pos0 + b0 + tb) ? a.att[((size_t)(b0 + tb) * a.n_heads + h) * a.ctx + t0 + r] : 0.f;
-            if (sums) wv = wv / sums[(size_t)(b0 + min(tb, nb - 1)) * a.n_heads + h];      // r6: att holds the numerators (pf_softmax_rows_kernel)
-            as[i] = wv;
-        }
-        __syncthreads();
-        const int ttw = min(tt, wmax + 1 - t0);                       // this wavefront's tokens stop at wmax
-        // timesteps every one of the four tokens attends to (t <= position of the first token): no conditions
-        const int rfull = (4 * w + 3 < nb) ? max(0, min(tt, posu[0] + 1 - t0)) & ~3 : 0;
-        auto vload = [&](int r, float (&v)[NCOL]) {
-            if (NCOL == 2) {                                          // lane owns columns 2*lane, 2*lane + 1
-                const float2 v2 = (2 * lane < hs) ? *reinterpret_cast<const float2*>(vt + r * hs + 2 * lane) : make_float2(0.f, 0.f);
-                v[0] = v2.x; v[NCOL - 1] = v2.y;
-            } else {
-                v[0] = lane < hs ? vt[r * hs + lane] : 0.f;
-            }
-        };
-        for (int r = 0; r < rfull; r += 4) {
-            float4 a4[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a4[u] = *reinterpret_cast<const float4*>(as + (4 * w + u) * 64 + r);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float v[NCOL];
-                vload(r + i, v);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const float at = i == 0 ? a4[u].x : i == 1 ? a4[u].y : i == 2 ? a4[u].z : a4[u].w;
-#pragma unroll
-                    for (int c = 0; c < NCOL; ++c) acc[u][c] = at * v[c] + acc[u][c];
-                }
-            }
-        }
-        for (int r = rfull; r < ttw; ++r) {                           // the diagonal: per-token conditions (uniform)
-            float v[NCOL];
-            vload(r, v);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (t0 + r <= posu[u]) {
-                    const float at = as[(4 * w + u) * 64 + r];
-#pragma unroll
-                    for (int c = 0; c < NCOL; ++c) acc[u][c] = at * v[c] + acc[u][c];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int tb = 4 * w + u;
-        if (tb >= nb) continue;
-#pragma unroll
-        for (int c = 0; c < NCOL; ++c) {
-            const int j = NCOL == 2 ? 2 * lane + c : lane;
-            if (j < hs) a.out[(size_t)(b0 + tb) * a.out_stride + h * hs + j] = acc[u][c];
-        }
-    }
-}
-
-// r6 — pf_pv_tiled_kernel with the two latencies taken off its critical path (same arithmetic: acc = a_t * v + acc, t ascending; token tiles of 32):
-//   * the NEXT tile's V rows and softmax numerators are requested into registers before the current tile is consumed and reach LDS behind it
-//     (pf_pv_tiled_kernel loads, waits and stores between two barriers, 72 times per workgroup at 4608 positions);
+// r6 — the weighted V sum on the VALU: grid = (n_heads, token tiles of 32), V tiles of 64 timesteps through LDS, wavefront = 4 tokens, lane = the
+// output column(s): acc = a_t * v + acc, t ascending.  Two latencies are off the critical path:
+//   * the NEXT tile's V rows and softmax numerators are requested into registers before the current tile is consumed and reach LDS behind it;
 //   * inside a tile the LDS reads of timestep group g + 1 (four weights per token, four V rows) are in flight under the 64 multiply-add pairs
 //     of group g, pinned there with sched_barrier (left alone the scheduler sinks every read next to its use).
 // Masking is by weight: timesteps behind a token's position get the weight 0 (0 * v + acc = acc exactly: acc is never -0 and every staged
@@ -720,7 +608,7 @@ __global__ __launch_bounds__(64 * PVR_NW) void pf_pv_ring_kernel(const PfAttnArg
 //   phase 2  softmax rows (FloatTensor.softmaxInPlace): max, exp in double, the strictly sequential sum of ALL rows at once
 //            (lane = row: 32 chains side by side instead of one row per wavefront), divide
 //   phase 3  weighted V sum: V tiles of 64 timesteps through LDS, wavefront = (query head, 4 tokens), lane = 2 columns,
-//            acc = a_t * v + acc with t ascending (pf_pv_tiled_kernel's inner loop)
+//            acc = a_t * v + acc with t ascending
 // Tiles are dealt heaviest (latest positions) first, so the triangular work profile does not leave a tail.
 constexpr int FA_TB = 8;
 // (kvmul of the *_smem_bytes functions: the head slots of a workgroup — the head group's size min(kvMul, 4), HeadGroup above)

@@ -69,8 +69,8 @@ def test_llama3_8b_shaped_layer_prefill512_and_decode(pkg, orc, planmod):
 
 def test_llama3_8b_shaped_layer_prefill_chunks_behind_1000_positions(pkg, orc, planmod):
     """pp512 @ depth: chunks whose score rows no longer fit the one-launch prefill attention (from ~640 positions at kvMul 4, head size 128)
-    take pf_scores_tiled_kernel (tile maxima) -> pf_softmax_rows_kernel (64 / 32 / 16 rows per workgroup for 512- / 256- / 100-token
-    chunks, sums as lane-per-row chains) -> pf_pv_tiled_kernel (divides where it stages the weights): residual stream, KV rows and the
+    take pf_scores_mfma_kernel (tile maxima) -> pf_softmax_rows_kernel (64 / 32 / 16 rows per workgroup for 512- / 256- / 100-token
+    chunks, sums as lane-per-row chains) -> pf_pv_mfma_kernel (divides where it stages the weights): residual stream, KV rows and the
     decode steps behind them against the C oracle."""
     plan_mod, hip = planmod
     m = _model(pkg, "8b-layer", 131, ctx=1500)

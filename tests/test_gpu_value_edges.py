@@ -227,16 +227,16 @@ PREFILL = "(above_64_tokens or attention_regimes) and all"       # cases 7 and 4
 BATCHED = "(above_64_tokens or both_sides_of_128) and all"        # cases 7 and 5: 4 tests
 FORMS = [({"GL3_PF_GEMM3_TALL": "-1"}, PREFILL), ({"GL3_PF_GEMM3_TALL": "4"}, PREFILL), ({"GL3_PF_GEMM3_TALL": "5", "GL3_PF_GEMM3_TALL_KB": "1"}, PREFILL),
          ({"GL3_PF_GEMM3_TALL": "7", "GL3_PF_GEMM3_SHAPE": "1"}, PREFILL), ({"GL3_PF_GEMM3_TALL": "6", "GL3_PF_GEMM3_SHAPE": "2"}, PREFILL),
-         ({"GL3_PF_FUSED_ATTN": "0"}, PREFILL), ({"GL3_PF_FUSED_ATTN": "0", "GL3_PF_SOFTMAX_ROWS": "0"}, PREFILL),
+         ({"GL3_PF_FUSED_ATTN": "0"}, PREFILL),
          ({"GL3_PF_FUSED_ATTN": "0", "GL3_PF_SCORES_MFMA": "0", "GL3_PF_PV_MFMA": "0"}, PREFILL),
-         ({"GL3_PF_FUSED_ATTN": "0", "GL3_PF_SCORES_MFMA": "0", "GL3_PF_SCORES_PK": "0", "GL3_PF_PV_MFMA": "0", "GL3_PF_PV_RING": "0"}, PREFILL),
+         ({"GL3_PF_FUSED_ATTN": "0", "GL3_PF_SCORES_MFMA": "0", "GL3_PF_SCORES_PK": "0", "GL3_PF_PV_MFMA": "0"}, PREFILL),
          ({"GL3_PF_FUSED_MFMA": "0"}, PREFILL), ({"GL3_PF_FUSED_V1": "1"}, PREFILL),
          ({"GL3_NO_FUSED_BD_ATTN": "1"}, BATCHED), ({"GL3_NO_FUSED_QUANT": "1"}, BATCHED), ({"GL3_NO_FUSED_BD_ATTN": "1", "GL3_NO_FUSED_QUANT": "1"}, BATCHED)]
 
 
 @pytest.mark.parametrize("env,sel", FORMS, ids=["-".join("%s=%s" % (k[4:], v) for k, v in e.items()) for e, _ in FORMS])
 def test_the_all_model_under_each_form(env, sel):
-    """The fourteen environments of test_gpu_gemm_forms.py.  The prefill forms run the > 64-token prefill (ragged-llama, tiny-devstral) and the
+    """The thirteen environments of test_gpu_gemm_forms.py.  The prefill forms run the > 64-token prefill (ragged-llama, tiny-devstral) and the
     attention regimes (prefill chunks of 256 under peaked attention: terms that are 0 or f32-subnormal, ties); the forms of the batched step
     run the > 64-token prefill and the step across position 128."""
     out = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-k", sel, "-p", "no:cacheprovider"],

@@ -23,6 +23,7 @@
 #include "gl3_rowlane_kernels.h"
 #include "gl3_veclane_kernels.h"
 #include "gl3_moe_kernels.h"
+#include "gl3_kv_copy.h"
 
 using namespace gl3;
 
@@ -705,6 +706,7 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     TRY(dmalloc(ctx, &ctx->vcache, kvn + (size_t)PVT * ctx->kv_dim_l));      // + PVT rows: attn_pv_kernel's last tile reads past position n - 1 unclamped (masked)
     TRYHIP(hipMemset(ctx->kcache, 0, kvn * 4));
     TRYHIP(hipMemset(ctx->vcache, 0, (kvn + (size_t)PVT * ctx->kv_dim_l) * 4));
+    if (ctx->n_seqs > 1) TRY(dmalloc(ctx, &ctx->kv_copy_dst, ctx->n_seqs));
     TRY(dmalloc(ctx, &ctx->xn, d.dim));
     TRY(dmalloc(ctx, &ctx->qkv, ctx->q_dim_l + 2 * ctx->kv_dim_l));
     if (ctx->use_rccl) {          // gathered buffers live in the tensor-parallel arena (one allocation the peers map, gl3_tp.hip)
@@ -818,7 +820,7 @@ void gl3_destroy(gl3_ctx* ctx) {
         f(L.gate_exps.w); f(L.up_exps.w); f(L.down_exps.w); f(L.gate_inp); f(L.gate_inp_shexp);
     }
     f(ctx->moe_logits); f(ctx->moe_w); f(ctx->moe_sel); f(ctx->moe_hb); f(ctx->moe_y); f(ctx->moe_slots); f(ctx->tp_recs);
-    f(ctx->out_norm); f(ctx->rope_cr); f(ctx->rope_ci); f(ctx->kcache); f(ctx->vcache); f(ctx->xn); f(ctx->qkv);
+    f(ctx->out_norm); f(ctx->rope_cr); f(ctx->rope_ci); f(ctx->kcache); f(ctx->vcache); f(ctx->kv_copy_dst); f(ctx->xn); f(ctx->qkv);
     if (!ctx->arena.base) { f(ctx->x); f(ctx->xb); f(ctx->hb); f(ctx->logits); }
     gl3_tp_arena_free(ctx);
     f(ctx->att); f(ctx->att_t); f(ctx->att_tmax); f(ctx->att_sums); f(ctx->dyn); f(ctx->dyn_seq); f(ctx->argmax); f(ctx->taps); f(ctx->staging);
@@ -1575,6 +1577,46 @@ int32_t gl3_get_kv_seq(gl3_ctx* ctx, int32_t seq, int32_t layer, int32_t pos, fl
     const size_t off = (size_t)seq * ctx->kv_seq_stride + ((size_t)layer * ctx->d.ctx + pos) * ctx->kv_dim_l;
     GL3_HIP(hipMemcpy(k_out, ctx->kcache + off, sizeof(float) * ctx->kv_dim_l, hipMemcpyDeviceToHost));
     GL3_HIP(hipMemcpy(v_out, ctx->vcache + off, sizeof(float) * ctx->kv_dim_l, hipMemcpyDeviceToHost));
+    return GL3_OK;
+}
+
+// Prefix fork (gl3_kv_copy.h).  Everything is checked before anything is enqueued; the launch goes behind the last step on the plan's stream and
+// the call returns once it has completed, so the blocking copies of the taps above and the next step both see the rows.
+int32_t gl3_kv_seq_copy(gl3_ctx* ctx, int32_t src_seq, const int32_t* dst_seqs, int32_t n_dst, int32_t p0, int32_t p1) {
+    if (!ctx) { g_create_err = "gl3_kv_seq_copy: null ctx"; return GL3_E_ARG; }
+    if (!dst_seqs) GL3_FAIL(GL3_E_ARG, "gl3_kv_seq_copy: null dst_seqs");
+    if (n_dst <= 0) GL3_FAIL(GL3_E_ARG, "gl3_kv_seq_copy: n_dst must be positive");
+    if (src_seq < 0 || src_seq >= ctx->n_seqs) GL3_FAIL(GL3_E_ARG, "gl3_kv_seq_copy: source sequence out of range");
+    if (p0 < 0 || p1 > ctx->d.ctx || p0 > p1) GL3_FAIL(GL3_E_ARG, "gl3_kv_seq_copy: need 0 <= p0 <= p1 <= ctx");
+    std::vector<char> seen((size_t)ctx->n_seqs, 0);
+    for (int32_t i = 0; i < n_dst; ++i) {
+        const int32_t s = dst_seqs[i];
+        if (s < 0 || s >= ctx->n_seqs) GL3_FAIL(GL3_E_ARG, "gl3_kv_seq_copy: destination sequence out of range");
+        if (s == src_seq) GL3_FAIL(GL3_E_ARG, "gl3_kv_seq_copy: a destination is the source sequence");
+        if (seen[s]) GL3_FAIL(GL3_E_ARG, "gl3_kv_seq_copy: a destination sequence is listed twice");
+        seen[s] = 1;
+    }
+    if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "gl3_kv_seq_copy before gl3_finalize");
+    if (p0 == p1) return GL3_OK;
+    if (ctx->kv_dim_l % 4) GL3_FAIL(GL3_E_UNSUPPORTED, "gl3_kv_seq_copy: kv_dim per rank is not a multiple of 4 floats");      // never: head sizes are multiples of 32
+    KvCopyArgs a{};
+    a.kcache = ctx->kcache; a.vcache = ctx->vcache;
+    a.n_dst = n_dst; a.src_seq = src_seq; a.n_layers = ctx->d.n_layers;
+    a.seq_stride4 = ctx->kv_seq_stride / 4;
+    a.layer_stride4 = (size_t)ctx->d.ctx * ctx->kv_dim_l / 4;
+    a.span_off4 = (size_t)p0 * ctx->kv_dim_l / 4;
+    a.span4 = (size_t)(p1 - p0) * ctx->kv_dim_l / 4;
+    const size_t per_span = (a.span4 + KVC_CHUNK4 - 1) / KVC_CHUNK4, chunks = 2 * (size_t)a.n_layers * per_span;
+    if (chunks > 0xFFFFFFFFull) GL3_FAIL(GL3_E_UNSUPPORTED, "gl3_kv_seq_copy: more than 2^32 chunks in one call");
+    a.chunks_per_span = (uint32_t)per_span; a.n_chunks = (uint32_t)chunks;
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    int cus = 0;
+    GL3_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->d.device));
+    const size_t cap = (size_t)(cus > 0 ? cus : 1) * KVC_WGS_PER_CU;
+    GL3_HIP(hipMemcpyAsync(ctx->kv_copy_dst, dst_seqs, sizeof(int32_t) * n_dst, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(kv_seq_copy_kernel, dim3((unsigned)(chunks < cap ? chunks : cap)), dim3(KVC_THREADS), 0, ctx->stream, a, (const int*)ctx->kv_copy_dst);
+    GL3_HIP(hipGetLastError());
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
     return GL3_OK;
 }
 

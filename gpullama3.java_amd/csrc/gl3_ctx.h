@@ -194,6 +194,7 @@ struct gl3_ctx {
     float *kcache = nullptr, *vcache = nullptr;   // [n_seqs][L][ctx][kv_dim_l]
     int n_seqs = 1;
     size_t kv_seq_stride = 0;                     // floats per sequence
+    int* kv_copy_dst = nullptr;                   // [n_seqs] destination list of gl3_kv_seq_copy (n_seqs > 1 only)
     float *x = nullptr, *qkv = nullptr, *xb = nullptr, *hb = nullptr, *logits = nullptr, *att = nullptr;
     float *att_t = nullptr, *att_tmax = nullptr, *att_sums = nullptr;   // long-context decode: softmax numerators in attn_pv_kernel's operand order, per-tile score maxima, denominators
     float* xn = nullptr;                          // RMS-normalised activation (F16 / Q4_0 path only)

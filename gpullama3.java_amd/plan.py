@@ -285,6 +285,12 @@ class HipMasterPlan:
         hip.check(hip.lib().gl3_get_kv_seq(self._ctx, seq, layer, pos, _p(k), _p(v)), self._ctx)
         return k, v
 
+    def kv_seq_copy(self, src: int, dsts, p0: int, p1: int):
+        """Fork a prefix (gl3_kv_seq_copy): the K / V rows [p0, p1) of sequence `src`, every layer, into the same positions of every sequence
+        in `dsts`.  Returns after the copy has completed."""
+        d = np.ascontiguousarray(dsts, np.int32)
+        hip.check(hip.lib().gl3_kv_seq_copy(self._ctx, src, _p(d), d.size, p0, p1), self._ctx)
+
     def freeTornadoExecutionPlan(self):
         if getattr(self, "_ctx", None) is not None and self._ctx:
             hip.lib().gl3_destroy(self._ctx)

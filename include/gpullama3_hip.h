@@ -14,6 +14,7 @@
  *   TornadoVMMasterPlanPrefillDecode.tornadoVMForwardPrefill(position)
  *                                          J/tornadovm/TornadoVMMasterPlanPrefillDecode.java:116
  *                                                   -> gl3_forward_prefill(n = 1)
+ * No counterpart in the reference (one sequence per plan): the sequence slots (n_seqs), the batched steps and gl3_kv_seq_copy (prefix fork).
  * In the reference, inputs cross this seam by side effect through the shared State object
  * (J/inference/state/State.java:28-100: embeddingX, wrapXBatch, batchStartPosHolder, wrapLogits) and
  * TornadoWeights (J/inference/weights/tornado/TornadoWeights.java:20-48).  Here every argument is
@@ -338,6 +339,18 @@ GL3_API int32_t gl3_debug_batch_plan(const int32_t* seq_ids, const int32_t* posi
 GL3_API int32_t gl3_debug_batch_plan_split(const int32_t* seq_ids, const int32_t* positions, int32_t n, int32_t n_seqs, int32_t ctx,
                                            int32_t capacity, int32_t fused_max_pos, int32_t* shallow_out, int32_t* n_shallow,
                                            int32_t* deep_out, int32_t* n_deep, int32_t* deep_rows, int32_t* n_deep_rows);
+/* Fork a prefix: copy the K and V rows at positions [p0, p1) of sequence src_seq, every layer, into the same positions of each of the
+ * n_dst sequences dst_seqs[].  Rows outside [p0, p1) of the destinations, every other sequence and the source are untouched.
+ * What the rows mean: a row's arithmetic does not depend on which rows share its step, so the K / V rows at positions 0 .. p of a sequence are
+ * a function of its tokens 0 .. p alone.  After a call with p0 == 0 a destination therefore behaves, for the rows at positions >= p1 that are
+ * forwarded on it next, exactly (bit for bit) as if tokens 0 .. p1 - 1 of the source had been forwarded on it.  K is stored after RoPE, so rows
+ * go to the SAME positions only; there is no shifting.
+ * One launch on the plan's stream, behind whatever step was enqueued last; the call returns after the copy has completed, so gl3_get_kv_seq and
+ * the next step both see it.  Rank-local: under tensor parallelism a rank copies its own kv_dim / tp_size slice, and the caller invokes it on
+ * every rank.  Needs n_seqs > 1, not max_batch > 1.  GL3_E_ARG, before anything is enqueued: null ctx or dst_seqs, n_dst <= 0, src_seq or a
+ * destination outside [0, n_seqs), a destination equal to src_seq or listed twice, p0 < 0, p1 > ctx, p0 > p1.  p0 == p1 is a valid no-op
+ * (GL3_OK, no launch).  GL3_E_STATE: before gl3_finalize. */
+GL3_API int32_t gl3_kv_seq_copy(gl3_ctx* ctx, int32_t src_seq, const int32_t* dst_seqs, int32_t n_dst, int32_t p0, int32_t p1);
 /* Dispatch tap: the rows of the last batched step (gl3_forward_prefill_seq, gl3_forward_decode_batch, gl3_forward_batch and their sampled
  * forms) by the attention form that served them in the last layer — out[0] attn_head_kernel (RoPE + attention in one launch per row),
  * out[1] the one-launch tiled kernels, out[2] the long-context trio (scores, softmax rows, weighted V sum), out[3] the per-row pair.  The

@@ -2,7 +2,7 @@
 // the plan's sequence slots, and every step is ONE gl3_forward_batch — the decode rows of the running requests and prompt chunks of the
 // newly admitted ones in the same pass over the weights.
 //
-//   gl3_batch_run -m model.gguf --prompts file -np SLOTS -b BATCH -n NEW [--stop id,id]
+//   gl3_batch_run -m model.gguf --prompts file -np SLOTS -b BATCH -n NEW [--stop id,id] [--share-prefix]
 //
 // The prompts file has one comma-separated id list per line (one request per line, blank lines ignored).  Prints one
 // "request k: id id ..." line per request (stdout, k = line order) and a summary (stderr).
@@ -12,6 +12,15 @@
 // Scheduling per step: one decode row per running request, then prompt tokens of admitted requests, in slot order, up to BATCH rows; a
 // prompt longer than the room left continues in the next step (a continuation chunk).  A waiting request takes a slot as soon as one
 // finishes and starts again at position 0 there: no cache reset, attention reads nothing above a row's position.
+//
+// --share-prefix: prefix reuse.  Every slot remembers `hist`, the tokens whose K / V rows it holds at positions 0 .. hist.size() - 1 (prompt
+// tokens and generated ids forwarded in a completed step; it outlives its request).  A request admitted to free slot f looks at every slot s,
+// f itself and the running ones included, for c_s = the length of the common prefix of its prompt and s.hist, capped at prompt length - 1 (the
+// last prompt token must be forwarded to get the first id), and takes the largest (ties: f itself, then the lowest slot).  c == 0: position 0
+// as above.  Best slot f itself: it starts at position c with nothing copied ("in place").  Another slot: gl3_kv_seq_copy(s -> f, rows [0, c))
+// and it starts at position c.  Admissions happen one after another in slot order, each seeing the hist the previous one left.  The rows are
+// bit for bit what forwarding the prefix would have written, so the printed ids are the same with and without the flag; the summary gains
+// the line "prefix rows reused: R (C copied in K calls, P in place)" and the first line's rows count is smaller by R.
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -46,7 +55,7 @@ static bool parse_id_list(const std::string& line, std::vector<int32_t>& out) {
 }
 
 static int usage(const char* why) {
-    fprintf(stderr, "gl3_batch_run: %s\nusage: gl3_batch_run -m model.gguf --prompts file -np SLOTS -b BATCH -n NEW [--stop id,id]\n", why);
+    fprintf(stderr, "gl3_batch_run: %s\nusage: gl3_batch_run -m model.gguf --prompts file -np SLOTS -b BATCH -n NEW [--stop id,id] [--share-prefix]\n", why);
     return 2;
 }
 
@@ -64,12 +73,14 @@ struct Slot {
     int fed = 0;             // prompt tokens forwarded so far
     int pos = 0;             // position of the next row
     int32_t cur = 0;         // decode: the id to forward next
+    std::vector<int32_t> hist;   // --share-prefix: the tokens whose K / V rows the slot holds at positions 0 .. hist.size() - 1
 };
 
 int main(int argc, char** argv) {
     std::string path, prompts_path;
     int slots = 0, batch = 0, n_new = 0;
     std::vector<int32_t> stop;
+    bool share_prefix = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() { return i + 1 < argc ? argv[++i] : (char*)""; };
@@ -79,6 +90,7 @@ int main(int argc, char** argv) {
         else if (a == "-b") batch = atoi(val());
         else if (a == "-n") n_new = atoi(val());
         else if (a == "--stop") { if (!parse_id_list(val(), stop)) return usage("--stop takes a comma-separated id list"); }
+        else if (a == "--share-prefix") share_prefix = true;
         else return usage(("unknown argument " + a).c_str());
     }
     if (path.empty() || prompts_path.empty()) return usage("-m model.gguf and --prompts file are required");
@@ -131,11 +143,34 @@ int main(int argc, char** argv) {
     std::vector<int8_t> want;
     std::vector<int> out_slot;           // slot of every output row, in row order
     int steps = 0, mixed_steps = 0;
-    long rows_total = 0;
+    long rows_total = 0, rows_copied = 0, rows_in_place = 0;
+    int copy_calls = 0;
     const double t0 = now_s();
     while (finished < reqs.size()) {
-        for (Slot& s : slot)             // admission: a waiting request takes a free slot and starts at position 0
-            if (s.req < 0 && next_req < reqs.size()) { s = Slot(); s.req = (int)next_req++; }
+        for (int f = 0; f < slots; ++f) {      // admission: a waiting request takes a free slot and starts at position 0, or behind a shared prefix
+            Slot& s = slot[f];
+            if (s.req >= 0 || next_req >= reqs.size()) continue;
+            s.req = (int)next_req++; s.fed = s.pos = 0; s.cur = 0;
+            if (!share_prefix) continue;
+            const std::vector<int32_t>& pr = reqs[s.req].prompt;
+            auto common = [&](const std::vector<int32_t>& h) {
+                size_t c = 0;
+                while (c + 1 < pr.size() && c < h.size() && h[c] == pr[c]) ++c;
+                return (int)c;
+            };
+            int best = f, c = common(s.hist);
+            for (int o = 0; o < slots; ++o) {
+                const int co = o == f ? 0 : common(slot[o].hist);
+                if (co > c) { best = o; c = co; }
+            }
+            if (c > 0 && best != f) {
+                const int32_t dst = f;
+                CK(gl3_kv_seq_copy(ctx, best, &dst, 1, 0, c));
+                ++copy_calls; rows_copied += c;
+            } else rows_in_place += c;
+            s.hist.assign(pr.begin(), pr.begin() + c);
+            s.fed = s.pos = c;
+        }
         tokens.clear(); seqs.clear(); poss.clear(); want.clear(); out_slot.clear();
         auto row = [&](int32_t tok, int sl, int pos, bool w) {
             tokens.push_back(tok); seqs.push_back(sl); poss.push_back(pos); want.push_back(w ? 1 : 0);
@@ -159,6 +194,8 @@ int main(int argc, char** argv) {
         const int n = (int)tokens.size();
         CK(gl3_forward_batch(ctx, tokens.data(), seqs.data(), poss.data(), want.data(), n, nullptr, amax.data()));
         ++steps; rows_total += n;
+        if (share_prefix)
+            for (int i = 0; i < n; ++i) { std::vector<int32_t>& h = slot[seqs[i]].hist; h.resize((size_t)poss[i]); h.push_back(tokens[i]); }
         if (n_decode && (size_t)n > n_decode) ++mixed_steps;
         for (size_t o = 0; o < out_slot.size(); ++o) {
             Slot& s = slot[out_slot[o]];
@@ -176,6 +213,8 @@ int main(int argc, char** argv) {
     }
     fprintf(stderr, "%zu requests on %d slots, %d steps (%d with decode rows and prompt rows together), %ld rows in %.1f ms (%.1f rows/s)\n", reqs.size(), slots, steps,
             mixed_steps, rows_total, (t1 - t0) * 1e3, rows_total / (t1 - t0 + 1e-12));
+    if (share_prefix)
+        fprintf(stderr, "prefix rows reused: %ld (%ld copied in %d calls, %ld in place)\n", rows_copied + rows_in_place, rows_copied, copy_calls, rows_in_place);
     gl3_destroy(ctx);
     return 0;
 }

@@ -52,9 +52,15 @@ static void launch_mv(gl3_ctx* ctx, K kernel, int wgs, int threads, size_t smem,
 
 template <int PRO, int EPI>
 static void launch_matvec_t(gl3_ctx* ctx, const MatvecArgs& a, int wgs, size_t smem, bool nt) {
-    if (a.tp) { launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true, 4, false, true>, wgs, mv_threads(4), smem, a); return; }   // folded gathers
-    if (nt) launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true>, wgs, mv_threads(4), smem, a);
-    else launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, false>, wgs, mv_threads(4), smem, a);
+    const bool segs = a.ng > mv_seg_groups(4, EPI);     // more than one chain segment per strip: sum it under the weight stream
+    if (a.tp) {                                          // folded gathers
+        if (segs) launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true, 4, false, true, true>, wgs, mv_threads(4), smem, a);
+        else launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true, 4, false, true>, wgs, mv_threads(4), smem, a);
+        return;
+    }
+    if (nt && segs) launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true, 4, false, false, true>, wgs, mv_threads(4), smem, a);
+    else if (nt) launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true>, wgs, mv_threads(4), smem, a);
+    else launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, false>, wgs, mv_threads(4), smem, a);      // GL3_NT=0 (debugging): one-pass chain
 }
 
 template <int PRO, int EPI>
@@ -62,6 +68,10 @@ static hipError_t allow_big_lds() {
     hipError_t e = hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, true, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, true, 4, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, true, 4, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
 }
@@ -167,9 +177,14 @@ static void launch_matvec(gl3_ctx* ctx, int pro, int epi, const Q8Mat& w, const 
     if (pro == PRO_RMS && epi == EPI_STORE) launch_matvec_t<PRO_RMS, EPI_STORE>(ctx, a, wgs, smem, nt);
     else if (pro == PRO_QUANT && epi == EPI_RESID) {
         static const int wide_max = getenv("GL3_WIDE_STRIPS") ? atoi(getenv("GL3_WIDE_STRIPS")) : 256;
-        if (w.nstrips <= wide_max && nt && tp)
+        const bool segs = w.ng > mv_seg_groups(8, EPI_RESID);
+        if (w.nstrips <= wide_max && nt && tp && segs)
+            launch_mv(ctx, matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, true, true>, wgs, mv_threads(8), smem, a);
+        else if (w.nstrips <= wide_max && nt && tp)
             launch_mv(ctx, matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, true>, wgs, mv_threads(8), smem, a);
-        else if (w.nstrips <= wide_max && nt)      // one workgroup per CU: 8 producer wavefronts
+        else if (w.nstrips <= wide_max && nt && segs)      // one workgroup per CU: 8 producer wavefronts
+            launch_mv(ctx, matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, false, true>, wgs, mv_threads(8), smem, a);
+        else if (w.nstrips <= wide_max && nt)
             launch_mv(ctx, matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8>, wgs, mv_threads(8), smem, a);
         else launch_matvec_t<PRO_QUANT, EPI_RESID>(ctx, a, wgs, smem, nt);
     }
@@ -739,6 +754,8 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
         }
     }
     TRYHIP(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    TRYHIP(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    TRYHIP(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
 #define GL3_RL_LDS(...) TRYHIP(hipFuncSetAttribute((const void*)matvec_rl_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256))
     GL3_RL_LDS(WT_F16, EPI_STORE); GL3_RL_LDS(WT_F16, EPI_RESID); GL3_RL_LDS(WT_F16, EPI_SWIGLU);
     GL3_RL_LDS(WT_Q4_0, EPI_STORE); GL3_RL_LDS(WT_Q4_0, EPI_RESID); GL3_RL_LDS(WT_Q4_0, EPI_SWIGLU);

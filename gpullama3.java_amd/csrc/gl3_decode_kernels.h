@@ -41,6 +41,11 @@ __host__ __device__ constexpr int mv_threads(int npw) { return 64 * (npw + MV_AU
 
 enum { PRO_RMS = 0, PRO_QUANT = 1 };
 enum { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2 };
+// tiles a producer wavefront keeps in flight, and the tile groups all producers of a workgroup finish as one batch: the segment of the
+// ordered block sum the chain wavefront adds under the next batch's stream (matvec_q8t_kernel<.., SEGS = true>).  A strip of at most
+// one segment has nothing to overlap: the launch code picks SEGS = false for it, which is the one-pass chain.
+__host__ __device__ constexpr int mv_ch(int epi) { return epi == EPI_SWIGLU ? 4 : 8; }
+__host__ __device__ constexpr int mv_seg_groups(int npw, int epi) { return npw * mv_ch(epi); }
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -49,9 +54,19 @@ __device__ long long gl3_mv_stamp[32];
 #define ATT_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) gl3_mv_stamp[i] = wall_clock64(); } while (0)
 #define MV_STAMP(i, cond) do { if (blockIdx.x == 0 && (cond)) gl3_mv_stamp[i] = clock64(); } while (0)
 #define PV_T(...) __VA_ARGS__
+// Per-workgroup stamps of matvec_q8t_kernel on the chip-wide 100 MHz clock (clock64 is only comparable inside one workgroup): the LATEST
+// time any wavefront of workgroup blockIdx.x passed slot s.  Slots: 0 start, 1 products of the last strip done, 2 last chain (segment)
+// begin, 3 chain end, 4 result stored.  The host zeroes the array before a launch (scripts/probes/matvec_stamp_probe.hip).
+constexpr int MV_WG_STAMPS = 1024;
+__device__ unsigned long long gl3_mv_wg_stamp[MV_WG_STAMPS][8];
+// MV_WG_TIME reads the clock into a register; MV_WG_PUT files it later, so that no global access stands in front of a barrier.
+#define MV_WG_TIME(v) v = (unsigned long long)wall_clock64()
+#define MV_WG_PUT(s, v, cond) do { if (blockIdx.x < MV_WG_STAMPS && blockIdx.y == 0 && (cond)) atomicMax(&gl3_mv_wg_stamp[blockIdx.x][s], v); } while (0)
 #else
 #define PV_T(...)
 #define MV_STAMP(i, cond)
+#define MV_WG_TIME(v)
+#define MV_WG_PUT(s, v, cond)
 #define ATT_STAMP(i)
 #endif
 
@@ -303,12 +318,21 @@ __device__ __forceinline__ uint16_t ld2(const uint8_t* p) {
 //       Q8_0 activation quantisation into LDS; waves 5-7 then retire;
 //   chain (wave 4): adds the p's of each row in block order with v_mfma_f32_16x16x4_f32 (B = 1.0) and applies
 //       the epilogue while the producers already stream the next strip.
+// SEGS = true (picked by the launch code for strips of more than one segment, mv_seg_groups): the chain runs in segments under the
+// weight stream.  What the producers finish as one batch (NPW wavefronts x CH tiles = SEG groups, contiguous in K) is handed over at a
+// workgroup barrier (lds_barrier: no vmcnt(0)), and the chain wavefront adds segment s while segment s + 1 streams; acc runs on across
+// the segments, so the adds and their order are those of one pass over the strip.  Every wavefront meets the barrier
+// ceil(ceil(ng / NPW) / CH) times per strip, also one whose tiles end a batch early.  Behind the last byte of a workgroup's last strip
+// only the last segment's adds and the epilogue remain (down at K = 14336: 48 of 112 groups, gate/up at K = 4096: 16 of 32).
+// SEGS = false is the one-pass chain behind one __syncthreads() per strip: for strips of one segment (qkv, wo, logits at K = 4096,
+// every matrix of Llama-3.2-1B) the segment barrier form measured 0.05 us slower per launch and buys nothing.  Figures per class in
+// profiles/matvec_chain_overlap.md; one barrier round costs about 0.05 us, one group of the chain about 0.018 us.
 // Register pressure is the maximum of the roles, not their sum (wave-uniform branches).
 //   LDS: xq[ng*128] | xs[ng*4] f32 | xf[k + 32] f32 (PRO_RMS) | pbuf[2][NM][ng*64] f32 | red[4] | sync[4]
 // TPF (tensor parallel, folded gathers): the aux wavefronts wait for the peers' slices of x before they read it (after the barrier
 // that releases the producers: the weight stream starts while the wait polls), and the chain wavefront stores every result into
 // the peers' arenas as well and publishes the gather (TpRec above).
-template <int PRO, int EPI, bool NT, int NPW = 4, bool SEL = false, bool TPF = false>
+template <int PRO, int EPI, bool NT, int NPW = 4, bool SEL = false, bool TPF = false, bool SEGS = false>
 __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_kernel(const MatvecArgs a_in) {
     MatvecArgs a = a_in;
     if (SEL) {                                          // wave-uniform: one scalar load of the expert id
@@ -333,9 +357,11 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
     constexpr int MV_PRODUCERS = NPW;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
-    constexpr int CH = (NM == 1) ? 8 : 4;             // tiles in flight per producer wave
+    constexpr int CH = mv_ch(EPI);                    // tiles in flight per producer wave
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int nb4 = a.ng * 4;
+    constexpr int SEG = mv_seg_groups(NPW, EPI);       // groups per chain segment = what the producers finish as one batch (contiguous in K)
+    const int nbatch = SEGS ? ((a.ng + NPW - 1) / NPW + CH - 1) / CH : 1;      // barrier rounds per strip, the same for every wavefront
     uint8_t* xq = smem;
     float* xs = reinterpret_cast<float*>(smem + (size_t)nb4 * 32);
     float* xf = xs + nb4;
@@ -344,6 +370,8 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
     int* sync_w = reinterpret_cast<int*>(red + 4);          // [0] aux sub-barrier counter, [1] activation-ready flag
     const size_t strip_bytes = (size_t)a.ng * TILE_BYTES;
     MV_STAMP(0, t == 0);
+    PV_T(unsigned long long wg_t0 = 0, wg_t1 = 0, wg_t2 = 0;)
+    MV_WG_TIME(wg_t0);
     if (t < 2) sync_w[t] = 0;
 
     if (wave < MV_PRODUCERS) {
@@ -392,14 +420,27 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
         int it = 0;
         for (; strip < a.nstrips; strip += gridDim.x, ++it) {
             float* pb = pbuf + (size_t)(it & 1) * NM * a.ng * 64;
+            // batch i0 / CH = groups [i0 / CH * SEG, (i0 / CH + 1) * SEG) of the strip: one chain segment
             for (int i0 = 0; i0 < nt; i0 += CH) {
                 if (it != 0 || i0 != 0) issue(strip, i0);
                 compute(i0, pb);
+                if (SEGS) {
+                    MV_STAMP(4 + 2 * it, t == 0 && it < 4 && i0 + CH >= nt);
+                    MV_WG_TIME(wg_t1);
+                    lds_barrier();                               // hands the segment to the chain wavefront; no vmcnt(0) as __syncthreads() has
+                }
             }
-            MV_STAMP(4 + 2 * it, t == 0 && it < 4);
-            __syncthreads();
+            if (SEGS) {
+                // a wavefront whose tiles end a batch early (ng % NPW != 0) still meets the others once per batch
+                for (int b = (nt + CH - 1) / CH; b < nbatch; ++b) lds_barrier();
+            } else {
+                MV_STAMP(4 + 2 * it, t == 0 && it < 4);
+                MV_WG_TIME(wg_t1);
+                __syncthreads();
+            }
             MV_STAMP(5 + 2 * it, t == 0 && it < 4);
         }
+        MV_WG_PUT(0, wg_t0, t == 0); MV_WG_PUT(1, wg_t1, lane == 0);
         return;
     }
 
@@ -496,29 +537,36 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
     // ---------------------------------------------------------------------- chain wavefront
     int it = 0;
     for (int strip = blockIdx.x; strip < a.nstrips; strip += gridDim.x, ++it) {
-        __syncthreads();
-        MV_STAMP(16 + 2 * it, lane == 0 && it < 4);
         const float* pb = pbuf + (size_t)(it & 1) * NM * a.ng * 64;
         v4f acc[NM];
 #pragma unroll
         for (int m = 0; m < NM; ++m) acc[m] = (v4f){0.f, 0.f, 0.f, 0.f};
-        int g = 0;
-        for (; g + 8 <= a.ng; g += 8) {               // result += p_b, b ascending: 4 blocks x 16 rows per MFMA
-            float av[NM][8];
+        // One segment per producer batch: segment s is summed while the producers stream segment s + 1 (or the next strip), acc runs
+        // on across the segments, so the order of the adds is the one of a single pass over the strip.
+        for (int b = 0; b < nbatch; ++b) {
+            if (SEGS) lds_barrier(); else __syncthreads();      // segment b of this strip (SEGS = false: the whole strip) is in pbuf
+            MV_STAMP(16 + 2 * it, lane == 0 && it < 4 && b == nbatch - 1);
+            MV_WG_TIME(wg_t1);
+            int g = b * SEG;
+            const int ge = SEGS ? min(g + SEG, a.ng) : a.ng;
+            for (; g + 8 <= ge; g += 8) {             // result += p_b, b ascending: 4 blocks x 16 rows per MFMA
+                float av[NM][8];
 #pragma unroll
-            for (int m = 0; m < NM; ++m)
+                for (int m = 0; m < NM; ++m)
 #pragma unroll
-                for (int u = 0; u < 8; ++u) av[m][u] = pb[(size_t)m * a.ng * 64 + (g + u) * 64 + lane];
+                    for (int u = 0; u < 8; ++u) av[m][u] = pb[(size_t)m * a.ng * 64 + (g + u) * 64 + lane];
 #pragma unroll
-            for (int u = 0; u < 8; ++u)
+                for (int u = 0; u < 8; ++u)
 #pragma unroll
-                for (int m = 0; m < NM; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m][u], 1.0f, acc[m], 0, 0, 0);
+                    for (int m = 0; m < NM; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m][u], 1.0f, acc[m], 0, 0, 0);
+            }
+            for (; g < ge; ++g)
+#pragma unroll
+                for (int m = 0; m < NM; ++m)
+                    acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(pb[(size_t)m * a.ng * 64 + g * 64 + lane], 1.0f, acc[m], 0, 0, 0);
         }
-        for (; g < a.ng; ++g)
-#pragma unroll
-            for (int m = 0; m < NM; ++m)
-                acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(pb[(size_t)m * a.ng * 64 + g * 64 + lane], 1.0f, acc[m], 0, 0, 0);
         MV_STAMP(17 + 2 * it, lane == 0 && it < 4);
+        MV_WG_TIME(wg_t2);
         // D[i][j]: row i = 4*(lane>>4) + reg, all 16 columns identical.  Lane l takes row (l & 3) of its own group
         // when (l & 15) < 4, so the 16 rows of the strip are finished by 16 lanes in parallel (one double exp each).
         if ((lane & 15) < 4) {
@@ -538,6 +586,9 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
                 if (TPF) tp_push_store(a.tp->p, a.out + row, res);
             }
         }
+        PV_T(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");)
+        MV_WG_TIME(wg_t0);
+        MV_WG_PUT(2, wg_t1, lane == 0); MV_WG_PUT(3, wg_t2, lane == 0); MV_WG_PUT(4, wg_t0, lane == 0);
     }
     if (TPF && a.tp->p.npeers) tp_publish(a.tp->p, gridDim.x);
 }

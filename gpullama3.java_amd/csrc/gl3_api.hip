@@ -35,10 +35,15 @@ static double now_ms() {
 
 
 // ------------------------------------------------------------------------------------------------ matvec launch
-static size_t matvec_smem(int pro, int epi, const Q8Mat& w) {
-    const int nm = epi == EPI_SWIGLU ? 2 : 1;
-    return (size_t)w.ng * 4 * 32 + (size_t)w.ng * 4 * 4 + (pro == PRO_RMS ? (size_t)(w.k + 32) * 4 : 0) + (size_t)2 * nm * w.ng * 64 * 4 + 128;
+static int q8_tile_groups(int k) { return ((k / 32) + 3) / 4; }      // 128-element tile groups of a Q8_0 row of k elements (Q8Mat.ng)
+// dynamic LDS of matvec_q8t_kernel for rows of k elements: int8 activation | block scales | f32 row (RMS prologue) | two product buffers | flags
+static size_t matvec_smem(int pro, int epi, int k) {
+    const int nm = epi == EPI_SWIGLU ? 2 : 1, ng = q8_tile_groups(k);
+    return (size_t)ng * 4 * 32 + (size_t)ng * 4 * 4 + (pro == PRO_RMS ? (size_t)(k + 32) * 4 : 0) + (size_t)2 * nm * ng * 64 * 4 + 128;
 }
+static size_t matvec_smem(int pro, int epi, const Q8Mat& w) { return matvec_smem(pro, epi, w.k); }
+// what every large-LDS kernel here may ask for (hipFuncAttributeMaxDynamicSharedMemorySize): the CU's 160 KB less the static part
+constexpr size_t GL3_LDS_MAX = 160 * 1024 - 256;
 
 // Instrumented steps (gl3_profile_decode) pass a start / stop event pair INTO the dispatch (hipExtLaunchKernel): the events
 // then carry the kernel's own begin / end timestamps — the quantity rocprofv3 --kernel-trace reports — instead of the
@@ -91,8 +96,7 @@ static void launch_matvec(gl3_ctx* ctx, int pro, int epi, const Q8Mat& w, const 
         const long vl_waves = (long)((w.rows + 7) / 8) * (epi == EPI_SWIGLU ? 2 : 1);
         const bool fuse_rms = pro == PRO_RMS && w.vl && vl_rms && vl_rms_fusable(w.k) && epi != EPI_RESID && !(ksplit_type && vl_waves <= 512);
         if (pro == PRO_RMS && !fuse_rms) {
-            const size_t sm = (size_t)(w.k + 32) * 4 + ss_scratch_bytes(w.k) + 64;
-            hipLaunchKernelGGL(rmsnorm_f32_kernel, dim3(1), dim3(256), sm, s, x, w.k, norm_w, ctx->d.rms_eps, ctx->xn);
+            hipLaunchKernelGGL(rmsnorm_f32_kernel, dim3(1), dim3(256), rmsnorm_smem_bytes(w.k), s, x, w.k, norm_w, ctx->d.rms_eps, ctx->xn);
             x = ctx->xn;
         }
         if (w.vl) {                   // Vector-API order (8 accumulator lanes per row): lane = (row, accumulator), HBM-bound
@@ -531,7 +535,7 @@ static int32_t dmalloc(gl3_ctx* ctx, T** p, size_t n) {
 }
 
 static int32_t alloc_mat(gl3_ctx* ctx, Q8Mat& m, int rows, int k) {
-    m.rows = rows; m.k = k; m.ng = ((k / 32) + 3) / 4; m.nstrips = (rows + 15) / 16; m.fmt = ctx->d.weight_type;
+    m.rows = rows; m.k = k; m.ng = q8_tile_groups(k); m.nstrips = (rows + 15) / 16; m.fmt = ctx->d.weight_type;
     if (m.fmt == GL3_TYPE_Q8_0 && (ctx->d.flags & GL3_FLAG_F32_ACTIVATION)) m.fmt = GL3_FMT_Q8V;
     m.vl = m.fmt == GL3_FMT_Q8V || (m.fmt != GL3_TYPE_Q8_0 && !(ctx->d.flags & GL3_FLAG_SCALAR_DOT));
     GL3_HIP(hipMalloc((void**)&m.w, m.bytes() + GL3_TAIL_PAD));
@@ -653,6 +657,30 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     if (d.dim <= 0 || d.dim % 32 || d.hidden % 32 || d.n_layers <= 0 || d.n_heads <= 0 || d.n_kv_heads <= 0 ||
         d.n_heads % d.n_kv_heads || d.vocab <= 0 || d.ctx <= 0)
         return bail(GL3_E_ARG, "bad model dimensions");
+    {   // Launches whose dynamic LDS grows with an inner dimension and has no other check above: asked of the functions the launches
+        // use, against the attribute the kernels get, and reported here instead of as a failed launch at the first step.
+        // (tests/k_shapes.py restates the formulas and names the largest dim / hidden of each.)
+        auto too_long = [&](const char* what, const char* dim_name, int k, size_t need) {
+            return std::string(what) + ": " + dim_name + " = " + std::to_string(k) + " needs " + std::to_string(need) + " bytes of LDS, the limit is " +
+                   std::to_string(GL3_LDS_MAX);
+        };
+        const int qd_ = d.n_heads * d.head_size;
+        if (d.weight_type == GL3_TYPE_Q8_0 && !q8v) {
+            struct { const char* what; const char* dim_name; int pro, epi, k; } mv[] = {
+                {"Q8_0 qkv / logits matvec", "dim", PRO_RMS, EPI_STORE, d.dim},
+                {"Q8_0 gate/up matvec", "dim", PRO_RMS, EPI_SWIGLU, d.dim},
+                {"Q8_0 wo matvec", "n_heads * head_size", PRO_QUANT, EPI_RESID, qd_},
+                {"Q8_0 down matvec", "hidden", PRO_QUANT, EPI_RESID, d.hidden},
+                {"Q8_0 expert down matvec", "moe_hidden", PRO_QUANT, EPI_RESID, moe ? d.moe_hidden : 0},
+            };
+            for (const auto& c : mv)
+                if (c.k > 0 && matvec_smem(c.pro, c.epi, c.k) > GL3_LDS_MAX)
+                    return bail(GL3_E_UNSUPPORTED, too_long(c.what, c.dim_name, c.k, matvec_smem(c.pro, c.epi, c.k)));
+        } else if (rmsnorm_smem_bytes(d.dim) > GL3_LDS_MAX)
+            return bail(GL3_E_UNSUPPORTED, too_long("F16 / Q4_0 / Q8_0 (f32 activation) RMSNorm launch", "dim", d.dim, rmsnorm_smem_bytes(d.dim)));
+        if (d.max_batch > 1 && gl3_prefill_norm_smem(d.dim) > GL3_LDS_MAX)
+            return bail(GL3_E_UNSUPPORTED, too_long("batched RMSNorm + quantise launch (max_batch > 1)", "dim", d.dim, gl3_prefill_norm_smem(d.dim)));
+    }
     // 96: Phi-3-mini.  160 / 192 / 224 / 256 have neither attn_head_kernel (its K / V tiles do not fit LDS) nor tiled prefill kernels: decode runs
     // the two-launch pair from position 0, batched steps the per-row kernels.  Every head size here and kvMul 1 - 16 is run against the CPU oracle in
     // all decode regimes, static-batched and mixed steps (tests/test_gpu_attn_shapes.py; the dispatch by shape: DESIGN.md §4)

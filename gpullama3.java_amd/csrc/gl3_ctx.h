@@ -307,6 +307,7 @@ void gl3_score_free(gl3_ctx* ctx);
 // gl3_prefill.hip
 float* gl3_prefill_buf(gl3_ctx* ctx, int which);
 int32_t gl3_prefill_alloc(gl3_ctx* ctx);
+size_t gl3_prefill_norm_smem(int k);      // dynamic LDS of the batched RMSNorm + quantise launch for rows of k elements
 void gl3_prefill_free(gl3_ctx* ctx);
 int32_t gl3_prefill_moe_tap(gl3_ctx* ctx, int which, float* out, uint64_t n);      // gl3_get_buffer 9 / 10
 int32_t gl3_prefill_run(gl3_ctx* ctx, int32_t seq, const int32_t* tokens, int32_t n, int32_t start_pos);

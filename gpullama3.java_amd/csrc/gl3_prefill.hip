@@ -239,6 +239,10 @@ __global__ __launch_bounds__(64) void pf_argmax_fold_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------ host side
+// dynamic LDS of pf_norm_quant_kernel<PQ_NORM | PQ_NORM_F32> for rows of k elements: the row, the exact sum of squares' scratch, the result.
+// Above 64 KB (k >= 9344) it needs the attribute gl3_prefill_alloc sets; gl3_create refuses a dim whose request exceeds that.
+static size_t nq_smem(int k) { return (size_t)(k + 32) * 4 + ss_scratch_bytes(k) + 64; }
+size_t gl3_prefill_norm_smem(int k) { return nq_smem(k); }
 static int pf_tab_max_pos(const gl3_ctx* ctx);      // next to pf_attention, whose conditions it shares
 int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     const gl3_model_desc& d = ctx->d;
@@ -275,6 +279,8 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     { const int32_t ar = pf_attention_attributes(ctx); if (ar != GL3_OK) return ar; }
+    GL3_HIP(hipFuncSetAttribute((const void*)pf_norm_quant_kernel<PQ_NORM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    GL3_HIP(hipFuncSetAttribute((const void*)pf_norm_quant_kernel<PQ_NORM_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
     p->tab_max_pos = pf_tab_max_pos(ctx);
     if (p->vl) {       // f32-activation weight types: the GEMMs read f32 rows, no int8 operands
         // XN: normalised / un-chunked f32 operand of the next GEMM (K up to max(dim, q_dim, hidden)); HB2: this rank's up projection
@@ -404,8 +410,6 @@ static bool pf_fused_decode(const gl3_ctx* ctx, const PfStep& st) {
     return ctx->fused_attn_ok && st.max_pos < AF_MAXN && !bd_attn_off && !st.runs();
 }
 
-// dynamic LDS of pf_norm_quant_kernel<PQ_NORM> for rows of k elements: the row, the exact sum of squares' scratch, the result
-static size_t nq_smem(int k) { return (size_t)(k + 32) * 4 + ss_scratch_bytes(k) + 64; }
 
 // Where a quantise launch writes: an int8 operand set in the layout its slot count names (tslots 0: chunk-major with the scales in XP), or,
 // for the f32 modes, plain f32 rows in XS.

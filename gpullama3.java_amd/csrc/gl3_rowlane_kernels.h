@@ -69,6 +69,9 @@ static __global__ __launch_bounds__(256) void embed_rl_kernel(const uint8_t* __r
     }
 }
 
+// dynamic LDS of rmsnorm_f32_kernel for a row of k elements: the padded row, the exact sum of squares' scratch, the result
+__host__ __device__ inline size_t rmsnorm_smem_bytes(int k) { return (size_t)(k + 32) * 4 + ss_scratch_bytes(k) + 64; }
+
 // out[i] = w[i] * (ss * x[i]) with the exact in-order sum of squares (InferenceCore.rmsnorm :39-48).  One workgroup.
 static __global__ __launch_bounds__(256) void rmsnorm_f32_kernel(const float* __restrict__ x, int k, const float* __restrict__ w, float eps,
                                                                  float* __restrict__ out) {

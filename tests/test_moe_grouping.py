@@ -12,7 +12,11 @@ import random
 
 import pytest
 
+import moe_shapes as ms
+
 WAVE = 64
+# every case of the configuration grid (tests/moe_shapes.py) at one token, past the 16-token tile and on the > 64-token path
+GRID_SHAPES = sorted({(n, topk, experts) for experts, topk, _, _, _ in ms.GRID.values() for n in (1, 17, 65)})
 
 
 def max_entries(n, topk, n_experts):
@@ -90,23 +94,34 @@ def random_routing(rng, n, topk, n_experts):
     return sel
 
 
-@pytest.mark.parametrize("n,topk,n_experts", [(1, 2, 8), (1, 4, 60), (3, 2, 8), (17, 2, 8), (96, 2, 8), (5, 4, 60), (32, 4, 60), (80, 4, 60),
-                                              (512, 4, 60), (64, 1, 3), (33, 8, 8), (20, 6, 4096)])
+RANDOM_SHAPES = [(1, 2, 8), (1, 4, 60), (3, 2, 8), (17, 2, 8), (96, 2, 8), (5, 4, 60), (32, 4, 60), (80, 4, 60), (512, 4, 60), (64, 1, 3), (33, 8, 8),
+                 (20, 6, 4096)]
+RANDOM_SHAPES += [s for s in GRID_SHAPES if s not in RANDOM_SHAPES]      # (1, 2, 8) and (17, 2, 8) are grid shapes already
+
+
+@pytest.mark.parametrize("n,topk,n_experts", RANDOM_SHAPES)
 def test_random_routings(n, topk, n_experts):
     rng = random.Random(1000 * n + topk)
     for _ in range(3):
         check(random_routing(rng, n, topk, n_experts), n, topk, n_experts)
 
 
-@pytest.mark.parametrize("n,topk,n_experts", [(1, 1, 8), (40, 1, 8), (16, 1, 60), (512, 1, 60), (23, 2, 8)])
+@pytest.mark.parametrize("n,topk,n_experts", [(1, 1, 8), (40, 1, 8), (16, 1, 60), (512, 1, 60), (23, 2, 8)] + GRID_SHAPES)
 def test_all_tokens_on_one_expert(n, topk, n_experts):
-    """Every token's first choice is expert 5 (the other choices, if any, spread): one expert owns ceil(n / 16) entries."""
+    """Every token's first choice is one expert — 5, or the last one where there are fewer (the grid's 1-expert case) — and the other choices,
+    if any, spread: that expert owns ceil(n / 16) entries."""
     rng = random.Random(n)
+    hot = min(5, n_experts - 1)
     sel = []
     for _ in range(n):
-        sel.extend([5] + rng.sample([e for e in range(n_experts) if e != 5], topk - 1))
+        sel.extend([hot] + rng.sample([e for e in range(n_experts) if e != hot], topk - 1))
     entries = check(sel, n, topk, n_experts)
-    assert sum(1 for e, _, _ in entries if e == 5) == (n + 15) // 16
+    assert sum(1 for e, _, _ in entries if e == hot) == (n + 15) // 16
+
+
+def test_the_grid_shapes_are_in_the_lists():
+    assert set(GRID_SHAPES) <= set(RANDOM_SHAPES) and len(set(RANDOM_SHAPES)) == len(RANDOM_SHAPES)
+    assert len(GRID_SHAPES) == 3 * 8 and (65, 64, 64) in GRID_SHAPES and (17, 6, 130) in GRID_SHAPES and (1, 1, 1) in GRID_SHAPES      # 8 / 2 twice in the grid
 
 
 def test_fewer_assignments_than_experts():

@@ -41,7 +41,6 @@ static size_t matvec_smem(int pro, int epi, int k) {
     const int nm = epi == EPI_SWIGLU ? 2 : 1, ng = q8_tile_groups(k);
     return (size_t)ng * 4 * 32 + (size_t)ng * 4 * 4 + (pro == PRO_RMS ? (size_t)(k + 32) * 4 : 0) + (size_t)2 * nm * ng * 64 * 4 + 128;
 }
-static size_t matvec_smem(int pro, int epi, const Q8Mat& w) { return matvec_smem(pro, epi, w.k); }
 // what every large-LDS kernel here may ask for (hipFuncAttributeMaxDynamicSharedMemorySize): the CU's 160 KB less the static part
 constexpr size_t GL3_LDS_MAX = 160 * 1024 - 256;
 
@@ -49,36 +48,85 @@ constexpr size_t GL3_LDS_MAX = 160 * 1024 - 256;
 // then carry the kernel's own begin / end timestamps — the quantity rocprofv3 --kernel-trace reports — instead of the
 // stream-order time between two recorded events, which also contains the host's launch latency in eager mode.
 #include <hip/hip_ext.h>
-template <typename K>
-static void launch_mv(gl3_ctx* ctx, K kernel, int wgs, int threads, size_t smem, const MatvecArgs& a) {
-    if (ctx->prof_ev0) hipExtLaunchKernelGGL(kernel, dim3(wgs), dim3(threads), (uint32_t)smem, ctx->stream, ctx->prof_ev0, ctx->prof_ev1, 0, a);
-    else hipLaunchKernelGGL(kernel, dim3(wgs), dim3(threads), smem, ctx->stream, a);
+using MvKernel = void (*)(const MatvecArgs);
+static void launch_mv(gl3_ctx* ctx, MvKernel kernel, dim3 grid, int threads, size_t smem, const MatvecArgs& a) {
+    if (ctx->prof_ev0) hipExtLaunchKernelGGL(kernel, grid, dim3(threads), (uint32_t)smem, ctx->stream, ctx->prof_ev0, ctx->prof_ev1, 0, a);
+    else hipLaunchKernelGGL(kernel, grid, dim3(threads), smem, ctx->stream, a);
 }
 
-template <int PRO, int EPI>
-static void launch_matvec_t(gl3_ctx* ctx, const MatvecArgs& a, int wgs, size_t smem, bool nt) {
-    const bool segs = a.ng > mv_seg_groups(4, EPI);     // more than one chain segment per strip: sum it under the weight stream
-    if (a.tp) {                                          // folded gathers
-        if (segs) launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true, 4, false, true, true>, wgs, mv_threads(4), smem, a);
-        else launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true, 4, false, true>, wgs, mv_threads(4), smem, a);
-        return;
+// Every instantiation of matvec_q8t_kernel the library holds, named here and nowhere else (flags: gl3_decode_kernels.h).  launch_q8t
+// finds the entry with the flags its rule gives (a miss ends the process: no_kernel), and gl3_create walks the table for the large-LDS opt-in: what can be launched has it.
+struct MvVariant { int pro, epi, npw; bool sel, tpf, segs; MvKernel kernel; };
+template <int PRO, int EPI, int NPW, bool SEL, bool TPF, bool SEGS>
+constexpr MvVariant mv_variant() { return {PRO, EPI, NPW, SEL, TPF, SEGS, matvec_q8t_kernel<PRO, EPI, NPW, SEL, TPF, SEGS>}; }
+constexpr MvVariant MV_VARIANTS[] = {
+    //         prologue   epilogue  NPW   SEL    TPF    SEGS
+    mv_variant<PRO_RMS,   EPI_STORE,  4, false, false, false>(),      // qkv, logits
+    mv_variant<PRO_RMS,   EPI_STORE,  4, false, false, true>(),
+    mv_variant<PRO_RMS,   EPI_STORE,  4, false, true,  false>(),
+    mv_variant<PRO_RMS,   EPI_STORE,  4, false, true,  true>(),
+    mv_variant<PRO_RMS,   EPI_SWIGLU, 4, false, false, false>(),      // gate/up
+    mv_variant<PRO_RMS,   EPI_SWIGLU, 4, false, false, true>(),
+    mv_variant<PRO_RMS,   EPI_SWIGLU, 4, false, true,  false>(),
+    mv_variant<PRO_RMS,   EPI_SWIGLU, 4, false, true,  true>(),
+    mv_variant<PRO_QUANT, EPI_RESID,  4, false, false, false>(),      // wo, down: more than MV_WIDE_STRIPS strips
+    mv_variant<PRO_QUANT, EPI_RESID,  4, false, false, true>(),
+    mv_variant<PRO_QUANT, EPI_RESID,  4, false, true,  false>(),
+    mv_variant<PRO_QUANT, EPI_RESID,  4, false, true,  true>(),
+    mv_variant<PRO_QUANT, EPI_RESID,  8, false, false, false>(),      // wo, down: one workgroup per CU
+    mv_variant<PRO_QUANT, EPI_RESID,  8, false, false, true>(),
+    mv_variant<PRO_QUANT, EPI_RESID,  8, false, true,  false>(),
+    mv_variant<PRO_QUANT, EPI_RESID,  8, false, true,  true>(),
+    mv_variant<PRO_RMS,   EPI_SWIGLU, 4, true,  false, false>(),      // routed experts (launch_matvec_sel)
+    mv_variant<PRO_QUANT, EPI_RESID,  4, true,  false, false>(),
+};
+constexpr int mv_find(int pro, int epi, int npw, bool sel, bool tpf, bool segs) {
+    int i = 0;
+    for (const MvVariant& v : MV_VARIANTS) {
+        if (v.pro == pro && v.epi == epi && v.npw == npw && v.sel == sel && v.tpf == tpf && v.segs == segs) return i;
+        ++i;
     }
-    if (nt && segs) launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true, 4, false, false, true>, wgs, mv_threads(4), smem, a);
-    else if (nt) launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, true>, wgs, mv_threads(4), smem, a);
-    else launch_mv(ctx, matvec_q8t_kernel<PRO, EPI, false>, wgs, mv_threads(4), smem, a);      // GL3_NT=0 (debugging): one-pass chain
+    return -1;
+}
+// A launch for which no kernel is built: a mistake in the dispatch code of this file, not a state a caller can reach (gl3_create
+// refuses the plans that have no kernels); the launch helpers return nothing, so it ends the process instead of skipping a projection.
+[[noreturn]] static void no_kernel(const char* what, int a, int b) { fprintf(stderr, "gl3: no %s kernel for (%d, %d)\n", what, a, b); abort(); }
+
+// The one rule that picks a variant, and its launch.  slots > 0: the routed experts of a Qwen2-MoE layer, blockIdx.y = slot (SEL; four
+// producers and the one-pass chain at every shape).  a.tp: folded gathers (TPF).
+static void launch_q8t(gl3_ctx* ctx, int pro, int epi, const MatvecArgs& a, int slots = 0) {
+    static const int max_wgs = getenv("GL3_WGS") ? atoi(getenv("GL3_WGS")) : 512;   // 2 resident workgroups per CU
+    const bool sel = slots > 0;
+    const int npw = !sel && pro == PRO_QUANT && epi == EPI_RESID && a.nstrips <= MV_WIDE_STRIPS ? 8 : 4;
+    const bool segs = !sel && a.ng > mv_seg_groups(npw, epi);     // more than one chain segment per strip: sum it under the weight stream
+    const int i = mv_find(pro, epi, npw, sel, a.tp != nullptr, segs);
+    if (i < 0) no_kernel("matvec_q8t_kernel<prologue, epilogue>", pro, epi);
+    launch_mv(ctx, MV_VARIANTS[i].kernel, dim3(a.nstrips < max_wgs ? a.nstrips : max_wgs, sel ? slots : 1), mv_threads(npw), matvec_smem(pro, epi, a.k), a);
 }
 
-template <int PRO, int EPI>
-static hipError_t allow_big_lds() {
-    hipError_t e = hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, true, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, true, 4, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, true, 4, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
+// Run-time weight format (with the F16 accumulator species) and epilogue as compile-time constants for a generic lambda, the way
+// attn_head_dispatch hands over the head size.  The lambdas leave out with `if constexpr` what a kernel family is not built for.
+template <int V> using IntC = std::integral_constant<int, V>;
+template <typename F>
+static void wt_dispatch(int fmt, bool v512, F&& f) {
+    if (fmt == GL3_TYPE_F16 && v512) f(IntC<WT_F16>{}, IntC<512>{});      // 16 accumulator lanes (FP16FloatTensor.vectorDot on a 512-bit species)
+    else if (fmt == GL3_TYPE_F16) f(IntC<WT_F16>{}, IntC<256>{});
+    else if (fmt == GL3_FMT_Q8V) f(IntC<WT_Q8_0>{}, IntC<256>{});
+    else f(IntC<WT_Q4_0>{}, IntC<256>{});
+}
+template <typename F>
+static void epi_dispatch(int epi, F&& f) {
+    if (epi == EPI_STORE) f(IntC<EPI_STORE>{}); else if (epi == EPI_RESID) f(IntC<EPI_RESID>{}); else f(IntC<EPI_SWIGLU>{});
+}
+// The scalar-order matvec of a weight format and epilogue (F16 and Q4_0; Q8_0 with the f32 activation is built in the vector order only)
+using RlKernel = void (*)(const RlArgs);
+static RlKernel rl_kernel(int fmt, int epi) {
+    RlKernel k = nullptr;
+    wt_dispatch(fmt, false, [&](auto wt, auto) { epi_dispatch(epi, [&](auto e) {
+        if constexpr (decltype(wt)::value != WT_Q8_0) k = matvec_rl_kernel<decltype(wt)::value, decltype(e)::value>;
+    }); });
+    if (!k) no_kernel("matvec_rl_kernel<format, epilogue>", fmt, epi);
+    return k;
 }
 
 // rows_valid / out / resid_in may address a slice (tensor parallel row split); w holds exactly that slice.
@@ -86,15 +134,13 @@ static void launch_matvec(gl3_ctx* ctx, int pro, int epi, const Q8Mat& w, const 
                           const float* norm_w, float* out, const float* resid_in, float out_scale = 1.0f, const TpRec* tp = nullptr) {
     if (w.fmt != GL3_TYPE_Q8_0) {      // F16 / Q4_0: element-wise chains, one output row per lane (gl3_rowlane_kernels.h)
         hipStream_t s = ctx->stream;
-        // Vector-order kernels normalise in their own prologue (matvec_vl_kernel<.., RMS>); GL3_VL_RMS=0: separate rmsnorm launch
-        static const bool vl_rms = env_flag("GL3_VL_RMS", true);
-        // ... except for the K-split types when the launch has few 8-row groups (a tensor-parallel rank's slice): the fused kernel
+        // Vector-order kernels normalise in their own prologue (matvec_vl_kernel<.., RMS>),
+        // except for the K-split types when the launch has few 8-row groups (a tensor-parallel rank's slice): the fused kernel
         // keeps one wavefront per group whatever the row count, so a 224-group gate/up slice would take as long as the whole
         // matrix; there the one-workgroup rmsnorm launch + the K-split kernel (16 wavefronts per group) is the faster pair.
-        static const bool ksplit_on = env_flag("GL3_VLQ", true);
-        const bool ksplit_type = ksplit_on && w.vl && (w.fmt == GL3_FMT_Q8V || w.fmt == GL3_TYPE_Q4_0);
+        const bool ksplit_type = w.vl && (w.fmt == GL3_FMT_Q8V || w.fmt == GL3_TYPE_Q4_0);
         const long vl_waves = (long)((w.rows + 7) / 8) * (epi == EPI_SWIGLU ? 2 : 1);
-        const bool fuse_rms = pro == PRO_RMS && w.vl && vl_rms && vl_rms_fusable(w.k) && epi != EPI_RESID && !(ksplit_type && vl_waves <= 512);
+        const bool fuse_rms = pro == PRO_RMS && w.vl && vl_rms_fusable(w.k) && epi != EPI_RESID && !(ksplit_type && vl_waves <= 512);
         if (pro == PRO_RMS && !fuse_rms) {
             hipLaunchKernelGGL(rmsnorm_f32_kernel, dim3(1), dim3(256), rmsnorm_smem_bytes(w.k), s, x, w.k, norm_w, ctx->d.rms_eps, ctx->xn);
             x = ctx->xn;
@@ -103,96 +149,40 @@ static void launch_matvec(gl3_ctx* ctx, int pro, int epi, const Q8Mat& w, const 
             VlArgs v{};
             v.w = w.w; v.w2 = w2 ? w2->w : nullptr; v.rows = w.rows; v.k = w.k; v.x = x; v.out = out; v.resid_in = resid_in; v.out_scale = out_scale;
             v.tp = tp;      // folded gathers (gate/up -> hb, down -> x): producer side only, the consumers get wait launches
-            const dim3 vg(((w.rows + 7) / 8 + VL_WAVES - 1) / VL_WAVES), vb(64 * VL_WAVES);
-            const size_t vs = vl_smem_bytes(w.k);
-            if (fuse_rms) {
-                v.norm_w = norm_w; v.eps = ctx->d.rms_eps;
-                const dim3 rg(((w.rows + 7) / 8 + VL_RMS_WAVES - 1) / VL_RMS_WAVES), rb(64 * VL_RMS_WAVES);
-                const size_t rs = vl_rms_smem_bytes(w.k);
-#define GL3_VLR(WT_) \
-                do { \
-                    if (epi == EPI_STORE) hipLaunchKernelGGL((matvec_vl_kernel<WT_, EPI_STORE, true, VL_RMS_WAVES>), rg, rb, rs, s, v); \
-                    else hipLaunchKernelGGL((matvec_vl_kernel<WT_, EPI_SWIGLU, true, VL_RMS_WAVES>), rg, rb, rs, s, v); \
-                } while (0)
-                if (w.fmt == GL3_TYPE_F16 && (ctx->d.flags & GL3_FLAG_VECTOR_512)) {          // 16 accumulator lanes (FP16FloatTensor.vectorDot on a 512-bit species)
-                    if (epi == EPI_STORE) hipLaunchKernelGGL((matvec_vl_kernel<WT_F16, EPI_STORE, true, VL_RMS_WAVES, 512>), rg, rb, rs, s, v);
-                    else hipLaunchKernelGGL((matvec_vl_kernel<WT_F16, EPI_SWIGLU, true, VL_RMS_WAVES, 512>), rg, rb, rs, s, v);
+            if (fuse_rms) { v.norm_w = norm_w; v.eps = ctx->d.rms_eps; }
+            const int ngroups = (w.rows + 7) / 8;
+            wt_dispatch(w.fmt, ctx->d.flags & GL3_FLAG_VECTOR_512, [&](auto wt, auto species) { epi_dispatch(epi, [&](auto e) {
+                constexpr int WT = decltype(wt)::value, SPECIES = decltype(species)::value, EPI = decltype(e)::value, NM = EPI == EPI_SWIGLU ? 2 : 1;
+                if constexpr (EPI != EPI_RESID)
+                    if (fuse_rms) {
+                        hipLaunchKernelGGL((matvec_vl_kernel<WT, EPI, true, VL_RMS_WAVES, SPECIES>), dim3((ngroups + VL_RMS_WAVES - 1) / VL_RMS_WAVES), dim3(64 * VL_RMS_WAVES),
+                                           vl_rms_smem_bytes(w.k), s, v);
+                        return;
+                    }
+                if constexpr (WT == WT_F16)
+                    hipLaunchKernelGGL((matvec_vl_kernel<WT, EPI, false, VL_WAVES, SPECIES>), dim3((ngroups + VL_WAVES - 1) / VL_WAVES), dim3(64 * VL_WAVES), vl_smem_bytes(w.k), s, v);
+                else {                // Q4_0 / Q8_0-f32act: up to 16 wavefronts split K of one 8-row group (matvec_vlq_kernel)
+                    const int nw = vq_waves<WT>(w.k, NM, ngroups);
+                    auto launch = [&](auto maxw) {
+                        constexpr int MAXW = decltype(maxw)::value;
+                        const size_t qs = vq_smem_bytes<WT, MAXW>(w.k, NM, nw);
+                        hipLaunchKernelGGL((matvec_vlq_kernel<WT, EPI, MAXW>), dim3(ngroups), dim3(64 * nw), qs, s, v);
+                    };
+                    if (nw == 16) launch(IntC<16>{}); else launch(IntC<8>{});
                 }
-                else if (w.fmt == GL3_TYPE_F16) GL3_VLR(WT_F16); else if (w.fmt == GL3_FMT_Q8V) GL3_VLR(WT_Q8_0); else GL3_VLR(WT_Q4_0);
-#undef GL3_VLR
-                return;
-            }
-#define GL3_VL(WT_) \
-            do { \
-                if (epi == EPI_STORE) hipLaunchKernelGGL((matvec_vl_kernel<WT_, EPI_STORE>), vg, vb, vs, s, v); \
-                else if (epi == EPI_RESID) hipLaunchKernelGGL((matvec_vl_kernel<WT_, EPI_RESID>), vg, vb, vs, s, v); \
-                else hipLaunchKernelGGL((matvec_vl_kernel<WT_, EPI_SWIGLU>), vg, vb, vs, s, v); \
-            } while (0)
-            // Q4_0 / Q8_0-f32act: four wavefronts split K of one 8-row group (matvec_vlq_kernel); GL3_VLQ=0 keeps the one-wavefront kernel
-            static const bool ksplit = env_flag("GL3_VLQ", true);
-#define GL3_VLQ_E(WT_, MAXW_) \
-            do { \
-                const size_t qs = vq_smem_bytes<WT_, MAXW_>(w.k, epi == EPI_SWIGLU ? 2 : 1, nw); \
-                if (epi == EPI_STORE) hipLaunchKernelGGL((matvec_vlq_kernel<WT_, EPI_STORE, MAXW_>), qg, qb, qs, s, v); \
-                else if (epi == EPI_RESID) hipLaunchKernelGGL((matvec_vlq_kernel<WT_, EPI_RESID, MAXW_>), qg, qb, qs, s, v); \
-                else hipLaunchKernelGGL((matvec_vlq_kernel<WT_, EPI_SWIGLU, MAXW_>), qg, qb, qs, s, v); \
-            } while (0)
-#define GL3_VLQ(WT_) \
-            do { \
-                const int ngroups = (w.rows + 7) / 8, nw = vq_waves<WT_>(w.k, epi == EPI_SWIGLU ? 2 : 1, ngroups); \
-                const dim3 qg(ngroups), qb(64 * nw); \
-                if (nw == 16) GL3_VLQ_E(WT_, 16); else GL3_VLQ_E(WT_, 8); \
-            } while (0)
-            if (w.fmt == GL3_TYPE_F16 && (ctx->d.flags & GL3_FLAG_VECTOR_512)) {
-                if (epi == EPI_STORE) hipLaunchKernelGGL((matvec_vl_kernel<WT_F16, EPI_STORE, false, VL_WAVES, 512>), vg, vb, vs, s, v);
-                else if (epi == EPI_RESID) hipLaunchKernelGGL((matvec_vl_kernel<WT_F16, EPI_RESID, false, VL_WAVES, 512>), vg, vb, vs, s, v);
-                else hipLaunchKernelGGL((matvec_vl_kernel<WT_F16, EPI_SWIGLU, false, VL_WAVES, 512>), vg, vb, vs, s, v);
-            }
-            else if (w.fmt == GL3_TYPE_F16) GL3_VL(WT_F16);
-            else if (w.fmt == GL3_FMT_Q8V) { if (ksplit) GL3_VLQ(WT_Q8_0); else GL3_VL(WT_Q8_0); }
-            else { if (ksplit) GL3_VLQ(WT_Q4_0); else GL3_VL(WT_Q4_0); }
-#undef GL3_VLQ
-#undef GL3_VLQ_E
-#undef GL3_VL
+            }); });
             return;
         }
         RlArgs a{};
         a.w = w.w; a.w2 = w2 ? w2->w : nullptr; a.rows = w.rows; a.k = w.k; a.x = x; a.out = out; a.resid_in = resid_in; a.out_scale = out_scale;
-        const dim3 grid((w.rows + 63) / 64);
-        const size_t sm = rl_smem_bytes(w.k, epi);
-#define GL3_RL(WT_) \
-        do { \
-            if (epi == EPI_STORE) hipLaunchKernelGGL((matvec_rl_kernel<WT_, EPI_STORE>), grid, dim3(RL_THREADS), sm, s, a); \
-            else if (epi == EPI_RESID) hipLaunchKernelGGL((matvec_rl_kernel<WT_, EPI_RESID>), grid, dim3(RL_THREADS), sm, s, a); \
-            else hipLaunchKernelGGL((matvec_rl_kernel<WT_, EPI_SWIGLU>), grid, dim3(RL_THREADS), sm, s, a); \
-        } while (0)
-        if (w.fmt == GL3_TYPE_F16) GL3_RL(WT_F16); else GL3_RL(WT_Q4_0);
-#undef GL3_RL
+        hipLaunchKernelGGL(rl_kernel(w.fmt, epi), dim3((w.rows + 63) / 64), dim3(RL_THREADS), rl_smem_bytes(w.k, epi), s, a);
         return;
     }
-    static const bool nt = env_flag("GL3_NT", true);
-    static const int max_wgs = getenv("GL3_WGS") ? atoi(getenv("GL3_WGS")) : 512;   // 2 resident workgroups per CU
     MatvecArgs a{};
     a.w = w.w; a.w2 = w2 ? w2->w : nullptr; a.rows = w.rows; a.k = w.k; a.ng = w.ng; a.nstrips = w.nstrips;
     a.x = x; a.norm_w = norm_w; a.eps = ctx->d.rms_eps; a.out = out; a.resid_in = resid_in; a.out_scale = out_scale;
     a.tp = tp;
-    const int wgs = w.nstrips < max_wgs ? w.nstrips : max_wgs;
-    const size_t smem = matvec_smem(pro, epi, w);
-    if (pro == PRO_RMS && epi == EPI_STORE) launch_matvec_t<PRO_RMS, EPI_STORE>(ctx, a, wgs, smem, nt);
-    else if (pro == PRO_QUANT && epi == EPI_RESID) {
-        static const int wide_max = getenv("GL3_WIDE_STRIPS") ? atoi(getenv("GL3_WIDE_STRIPS")) : 256;
-        const bool segs = w.ng > mv_seg_groups(8, EPI_RESID);
-        if (w.nstrips <= wide_max && nt && tp && segs)
-            launch_mv(ctx, matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, true, true>, wgs, mv_threads(8), smem, a);
-        else if (w.nstrips <= wide_max && nt && tp)
-            launch_mv(ctx, matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, true>, wgs, mv_threads(8), smem, a);
-        else if (w.nstrips <= wide_max && nt && segs)      // one workgroup per CU: 8 producer wavefronts
-            launch_mv(ctx, matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, false, true>, wgs, mv_threads(8), smem, a);
-        else if (w.nstrips <= wide_max && nt)
-            launch_mv(ctx, matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8>, wgs, mv_threads(8), smem, a);
-        else launch_matvec_t<PRO_QUANT, EPI_RESID>(ctx, a, wgs, smem, nt);
-    }
-    else launch_matvec_t<PRO_RMS, EPI_SWIGLU>(ctx, a, wgs, smem, nt);
+    launch_q8t(ctx, pro, epi, a);
 }
 
 // Routed experts of a Qwen2-MoE layer: one launch, blockIdx.y = slot of the top-k selection (matvec_q8t_kernel<.., SEL>).
@@ -201,18 +191,13 @@ static void launch_matvec(gl3_ctx* ctx, int pro, int epi, const Q8Mat& w, const 
 static void launch_matvec_sel(gl3_ctx* ctx, int layer, int which, const Q8Mat& stack, const Q8Mat* stack2, int rows, const float* x,
                               const float* norm_w, float* out, int shared_rows) {
     const gl3_model_desc& d = ctx->d;
-    static const int max_wgs = getenv("GL3_WGS") ? atoi(getenv("GL3_WGS")) : 512;
-    Q8Mat sub = stack;
-    sub.rows = rows; sub.nstrips = rows / 16;
     MatvecArgs a{};
-    a.w = stack.w; a.w2 = stack2 ? stack2->w : nullptr; a.rows = rows; a.k = stack.k; a.ng = stack.ng; a.nstrips = sub.nstrips;
+    a.w = stack.w; a.w2 = stack2 ? stack2->w : nullptr; a.rows = rows; a.k = stack.k; a.ng = stack.ng; a.nstrips = rows / 16;
     a.x = x; a.norm_w = norm_w; a.eps = d.rms_eps; a.out = out; a.resid_in = nullptr; a.out_scale = 1.0f;
     a.moe = reinterpret_cast<const MoeSlots*>(ctx->moe_slots) + (size_t)layer * 3 + which;
     const int slots = d.n_experts_used + (which == 0 ? (shared_rows + rows - 1) / rows : 0);
-    const int wgs = sub.nstrips < max_wgs ? sub.nstrips : max_wgs;
-    const dim3 grid(wgs, slots);
-    if (which != 2) hipLaunchKernelGGL((matvec_q8t_kernel<PRO_RMS, EPI_SWIGLU, true, 4, true>), grid, dim3(mv_threads(4)), matvec_smem(PRO_RMS, EPI_SWIGLU, sub), ctx->stream, a);
-    else hipLaunchKernelGGL((matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 4, true>), grid, dim3(mv_threads(4)), matvec_smem(PRO_QUANT, EPI_RESID, sub), ctx->stream, a);
+    if (which != 2) launch_q8t(ctx, PRO_RMS, EPI_SWIGLU, a, slots);
+    else launch_q8t(ctx, PRO_QUANT, EPI_RESID, a, slots);
 }
 
 // The slot records of every layer's two routed-expert launches (MoeSlots, gl3_decode_kernels.h); pointers are final after gl3_create.
@@ -430,9 +415,7 @@ static void launch_attention(gl3_ctx* ctx, int l, int which /* 0 both, 1 scores,
         attn_head_dispatch(d.head_size, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(ctx->heads_l), dim3(256), attn_head_smem(d.head_size), ctx->stream, aa); });
         return;
     }
-    // GL3_ATTN_SCORES_LOOP=0: the one-tile-per-workgroup scores kernel at every depth (A/B switch)
-    static const bool scores_loop = env_flag("GL3_ATTN_SCORES_LOOP", true);
-    if (which != 2 && amode == ATT_LONG && scores_loop && kvmul <= 4 && (d.head_size == 128 || d.head_size == 64)) {
+    if (which != 2 && amode == ATT_LONG && kvmul <= 4 && (d.head_size == 128 || d.head_size == 64)) {
         const dim3 sg(ctx->n_tsplit < SCL_WGS ? ctx->n_tsplit : SCL_WGS, ctx->kv_heads_l), sb(64 * (kvmul + SCL_LOADERS));
         const size_t sml = ((size_t)kvmul * d.head_size + 2 * (size_t)ATT_TT * (d.head_size + 4) + 2 * d.head_size) * 4;
         if (d.head_size == 128) hipLaunchKernelGGL(attn_scores_loop_kernel<128>, sg, sb, sml, ctx->stream, aa, ctx->n_tsplit);
@@ -460,16 +443,16 @@ static int32_t enqueue_decode(gl3_ctx* ctx, bool want_logits, gl3_kernel_times* 
 
     pr.begin(GL3_K_OTHER, (uint64_t)d.dim / 32 * 34);
     const int fold = ctx->tp_fold, fmask = fold ? ctx->tp_fold_mask : 0, L_ = d.n_layers;
-    uint32_t* vl_step = fold ? reinterpret_cast<uint32_t*>(ctx->arena.base + GL3_ARENA_STEP) : (uint32_t*)nullptr;
-    if (ctx->emb.fmt == GL3_TYPE_Q8_0)
+    uint32_t* step_word = fold ? reinterpret_cast<uint32_t*>(ctx->arena.base + GL3_ARENA_STEP) : (uint32_t*)nullptr;
+    if (q8)
         hipLaunchKernelGGL(embed_q8t_kernel, dim3(1), dim3(256), 0, s, ctx->emb.w, ctx->emb.ng, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale,
-                           (fmask & TF_EMBED) ? tp_rec(ctx, L_, 0) : (const TpRec*)nullptr,
-                           fold ? reinterpret_cast<uint32_t*>(ctx->arena.base + GL3_ARENA_STEP) : (uint32_t*)nullptr);
-    else if (ctx->emb.vl && ctx->emb.fmt == GL3_TYPE_F16) hipLaunchKernelGGL((embed_vl_kernel<WT_F16>), dim3(1), dim3(256), 0, s, ctx->emb.w, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale, vl_step);
-    else if (ctx->emb.vl && ctx->emb.fmt == GL3_FMT_Q8V) hipLaunchKernelGGL((embed_vl_kernel<WT_Q8_0>), dim3(1), dim3(256), 0, s, ctx->emb.w, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale, vl_step);
-    else if (ctx->emb.vl) hipLaunchKernelGGL((embed_vl_kernel<WT_Q4_0>), dim3(1), dim3(256), 0, s, ctx->emb.w, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale, vl_step);
-    else if (ctx->emb.fmt == GL3_TYPE_F16) hipLaunchKernelGGL((embed_rl_kernel<WT_F16>), dim3(1), dim3(256), 0, s, ctx->emb.w, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale);
-    else hipLaunchKernelGGL((embed_rl_kernel<WT_Q4_0>), dim3(1), dim3(256), 0, s, ctx->emb.w, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale);
+                           (fmask & TF_EMBED) ? tp_rec(ctx, L_, 0) : (const TpRec*)nullptr, step_word);
+    else wt_dispatch(ctx->emb.fmt, false, [&](auto wt, auto) {
+        constexpr int WT = decltype(wt)::value;
+        if (ctx->emb.vl) hipLaunchKernelGGL((embed_vl_kernel<WT>), dim3(1), dim3(256), 0, s, ctx->emb.w, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale, step_word);
+        else if constexpr (WT != WT_Q8_0) hipLaunchKernelGGL((embed_rl_kernel<WT>), dim3(1), dim3(256), 0, s, ctx->emb.w, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale);
+        else no_kernel("embed_rl_kernel<format>", ctx->emb.fmt, 0);
+    });
     pr.end();
 
     for (int l = 0; l < d.n_layers; ++l) {
@@ -604,7 +587,7 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
         if (d.moe_hidden > (1 << 24) || (int64_t)d.n_experts * d.moe_hidden > INT32_MAX || (int64_t)d.n_experts * d.dim > INT32_MAX)
             return bail(GL3_E_ARG, "qwen2moe: n_experts * moe_hidden / n_experts * dim exceed the supported range");
         // the router keeps the products of MOE_RR rows in LDS (gl3_moe_kernels.h): dim <= ~4500 with 60 experts
-        if (d.dim > 0 && moe_router_smem(d.dim, d.n_experts) > (size_t)160 * 1024 - 256)
+        if (d.dim > 0 && moe_router_smem(d.dim, d.n_experts) > GL3_LDS_MAX)
             return bail(GL3_E_UNSUPPORTED, "qwen2moe: dim too large for the router kernel's LDS staging");
     } else if (d.n_experts || d.n_experts_used || d.moe_hidden)
         return bail(GL3_E_ARG, "n_experts / n_experts_used / moe_hidden belong to GL3_ARCH_QWEN2MOE");
@@ -738,9 +721,7 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
         TRY(dmalloc(ctx, &ctx->moe_hb, (size_t)d.n_experts_used * d.moe_hidden));
         TRY(dmalloc(ctx, &ctx->moe_y, (size_t)(d.n_experts_used + 1) * d.dim));
         TRYHIP(hipMemset(ctx->moe_sel, 0, sizeof(int) * (d.n_experts_used + 1)));
-        TRYHIP(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO_RMS, EPI_SWIGLU, true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-        TRYHIP(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-        TRYHIP(hipFuncSetAttribute((const void*)moe_router_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+        TRYHIP(hipFuncSetAttribute((const void*)moe_router_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
     }
     TRY(dmalloc(ctx, &ctx->out_norm, d.dim));
     ctx->kv_seq_stride = (size_t)d.n_layers * d.ctx * ctx->kv_dim_l;
@@ -769,26 +750,19 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     TRY(dmalloc(ctx, &ctx->att_tmax, (size_t)ctx->heads_l * ctx->n_tsplit));
     TRY(dmalloc(ctx, &ctx->att_sums, (size_t)ctx->heads_l));
     if (moe) TRY(moe_build_slots(ctx));          // after hb: the merged gate/up launch writes the shared expert's SwiGLU output there
-    TRYHIP((allow_big_lds<PRO_RMS, EPI_STORE>()));
-    TRYHIP((allow_big_lds<PRO_QUANT, EPI_RESID>()));
-    TRYHIP((allow_big_lds<PRO_RMS, EPI_SWIGLU>()));
+    for (const MvVariant& v : MV_VARIANTS) TRYHIP(hipFuncSetAttribute((const void*)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
     {
         // one launch per layer for positions < AF_MAXN (attn_head_kernel); head_size 256 does not fit its K / V tiles in LDS
         ctx->fused_attn_ok = d.head_size % 4 == 0 && attn_head_smem(d.head_size) <= 150 * 1024 && !env_flag("GL3_NO_FUSED_ATTN", false);
         if (ctx->fused_attn_ok) {
             hipError_t ae = hipSuccess;
-            attn_head_dispatch(d.head_size, [&](auto kern) { ae = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); });
+            attn_head_dispatch(d.head_size, [&](auto kern) { ae = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX); });
             TRYHIP(ae);
         }
     }
-    TRYHIP(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    TRYHIP(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    TRYHIP(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO_QUANT, EPI_RESID, true, 8, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-#define GL3_RL_LDS(...) TRYHIP(hipFuncSetAttribute((const void*)matvec_rl_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256))
-    GL3_RL_LDS(WT_F16, EPI_STORE); GL3_RL_LDS(WT_F16, EPI_RESID); GL3_RL_LDS(WT_F16, EPI_SWIGLU);
-    GL3_RL_LDS(WT_Q4_0, EPI_STORE); GL3_RL_LDS(WT_Q4_0, EPI_RESID); GL3_RL_LDS(WT_Q4_0, EPI_SWIGLU);
-#undef GL3_RL_LDS
-    TRYHIP(hipFuncSetAttribute((const void*)rmsnorm_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    for (int fmt : {GL3_TYPE_F16, GL3_TYPE_Q4_0})
+        for (int epi : {EPI_STORE, EPI_RESID, EPI_SWIGLU}) TRYHIP(hipFuncSetAttribute((const void*)rl_kernel(fmt, epi), hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
+    TRYHIP(hipFuncSetAttribute((const void*)rmsnorm_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
     TRYHIP(hipFuncSetAttribute((const void*)attn_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     TRYHIP(hipFuncSetAttribute((const void*)attn_scores_loop_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     TRYHIP(hipFuncSetAttribute((const void*)attn_scores_loop_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));

@@ -35,8 +35,9 @@ namespace gl3 {
 
 constexpr int TILE_BYTES = 2176;       // 64 Q8_0 blocks
 constexpr int MV_AUX = 4;               // wavefronts running the prologue; the first one then runs the ordered sums
-// NPW = wavefronts streaming weights: 4, or 8 for matrices with <= 256 strips (wo / down), where only one workgroup
+// NPW = wavefronts streaming weights: 4, or 8 for matrices with <= MV_WIDE_STRIPS strips (wo / down), where only one workgroup
 // lands on a CU and four wavefronts cannot keep enough bytes in flight (each alternates issue -> wait -> dot).
+constexpr int MV_WIDE_STRIPS = 256;
 __host__ __device__ constexpr int mv_threads(int npw) { return 64 * (npw + MV_AUX); }
 
 enum { PRO_RMS = 0, PRO_QUANT = 1 };
@@ -332,7 +333,7 @@ __device__ __forceinline__ uint16_t ld2(const uint8_t* p) {
 // TPF (tensor parallel, folded gathers): the aux wavefronts wait for the peers' slices of x before they read it (after the barrier
 // that releases the producers: the weight stream starts while the wait polls), and the chain wavefront stores every result into
 // the peers' arenas as well and publishes the gather (TpRec above).
-template <int PRO, int EPI, bool NT, int NPW = 4, bool SEL = false, bool TPF = false, bool SEGS = false>
+template <int PRO, int EPI, int NPW = 4, bool SEL = false, bool TPF = false, bool SEGS = false>
 __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_kernel(const MatvecArgs a_in) {
     MatvecArgs a = a_in;
     if (SEL) {                                          // wave-uniform: one scalar load of the expert id
@@ -387,9 +388,9 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
 #pragma unroll
                     for (int m = 0; m < NM; ++m) {
                         const uint8_t* p = (m == 0 ? a.w : a.w2) + (size_t)strip * strip_bytes + (size_t)g * TILE_BYTES;
-                        sc[m][u] = ld2<NT>(p + 2 * lane);
-                        lo[m][u] = ld16<NT>(p + 128 + 16 * lane);
-                        hi[m][u] = ld16<NT>(p + 1152 + 16 * lane);
+                        sc[m][u] = ld2<true>(p + 2 * lane);
+                        lo[m][u] = ld16<true>(p + 128 + 16 * lane);
+                        hi[m][u] = ld16<true>(p + 1152 + 16 * lane);
                     }
                 }
             }

@@ -16,15 +16,15 @@ struct Shape { const char* name; int pro, epi, rows, k; };
 
 template <int PRO, int EPI, int NPW = 4>
 static float run(const MatvecArgs& a, int wgs, size_t smem, int iters, std::vector<uint8_t*>& wbufs, std::vector<uint8_t*>& w2bufs) {
-    CK(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, true, NPW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    CK(hipFuncSetAttribute((const void*)matvec_q8t_kernel<PRO, EPI, NPW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     MatvecArgs b = a;
     for (int i = 0; i < 3; ++i) { b.w = wbufs[i % wbufs.size()]; b.w2 = w2bufs.empty() ? nullptr : w2bufs[i % w2bufs.size()];
-        hipLaunchKernelGGL((matvec_q8t_kernel<PRO, EPI, true, NPW>), dim3(wgs), dim3(mv_threads(NPW)), smem, 0, b); }
+        hipLaunchKernelGGL((matvec_q8t_kernel<PRO, EPI, NPW>), dim3(wgs), dim3(mv_threads(NPW)), smem, 0, b); }
     CK(hipDeviceSynchronize());
     CK(hipEventRecord(e0, 0));
     for (int i = 0; i < iters; ++i) { b.w = wbufs[i % wbufs.size()]; b.w2 = w2bufs.empty() ? nullptr : w2bufs[i % w2bufs.size()];
-        hipLaunchKernelGGL((matvec_q8t_kernel<PRO, EPI, true, NPW>), dim3(wgs), dim3(mv_threads(NPW)), smem, 0, b); }
+        hipLaunchKernelGGL((matvec_q8t_kernel<PRO, EPI, NPW>), dim3(wgs), dim3(mv_threads(NPW)), smem, 0, b); }
     CK(hipEventRecord(e1, 0));
     CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));

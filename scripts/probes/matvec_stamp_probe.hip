@@ -20,7 +20,7 @@ static double median(std::vector<double> v) { std::sort(v.begin(), v.end()); ret
 template <int PRO, int EPI, int NPW>
 static void run(const Shape& sh, const MatvecArgs& a, int wgs, size_t smem, std::vector<uint8_t*>& wb, std::vector<uint8_t*>& w2b, const char* tag) {
     // as launch_matvec: the segmented chain for strips of more than one segment
-    auto kern = a.ng > mv_seg_groups(NPW, EPI) ? matvec_q8t_kernel<PRO, EPI, true, NPW, false, false, true> : matvec_q8t_kernel<PRO, EPI, true, NPW>;
+    auto kern = a.ng > mv_seg_groups(NPW, EPI) ? matvec_q8t_kernel<PRO, EPI, NPW, false, false, true> : matvec_q8t_kernel<PRO, EPI, NPW>;
     CK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
     MatvecArgs b = a;
     const int reps = 24;

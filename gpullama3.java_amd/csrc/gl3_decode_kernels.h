@@ -473,6 +473,12 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
         for (int i = 0; i < NXV; ++i) xv[i] = *reinterpret_cast<const float4*>(a.x + 4 * min(ta + 256 * i, nquads - 1));
     }
     SubBarrier aux_sync{&sync_w[0], MV_AUX, 0};
+    for (int b = (a.k >> 5) + ta; b < nb4; b += 256) {   // zero-padded blocks: nothing of them waits for the sum
+        xs[b] = 0.f;
+        const int4 z = {0, 0, 0, 0};
+        *reinterpret_cast<int4*>(xq + 32 * b) = z;
+        *reinterpret_cast<int4*>(xq + 32 * b + 16) = z;
+    }
     if (PRO == PRO_RMS) {
         if (nquads <= NXV * 256) {
 #pragma unroll
@@ -501,12 +507,6 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
         ss /= (float)a.k;
         ss += a.eps;
         scale = (float)(1.0 / sqrt((double)ss));
-    }
-    for (int b = (a.k >> 5) + ta; b < nb4; b += 256) {   // zero-padded blocks
-        xs[b] = 0.f;
-        const int4 z = {0, 0, 0, 0};
-        *reinterpret_cast<int4*>(xq + 32 * b) = z;
-        *reinterpret_cast<int4*>(xq + 32 * b + 16) = z;
     }
     if (nquads <= NXV * 256) {
 #pragma unroll

@@ -196,40 +196,46 @@ __device__ float exact_seqsum_lds(const float* x, int n, uint8_t* scratch, const
     if (lane == 63) w_tot[wave] = incl;
     sync();
     SS_STAMP(1);
+    // the wave totals in one unconditional read: a loop `for (w < wave)` is divergent to the compiler (a waited LDS round trip per
+    // iteration under an exec mask); adding +0 to P >= 0 changes nothing, so the adds and their order are those of that loop
     float P = start + (incl - qt);
-    for (int w = 0; w < wave; ++w) P += w_tot[w];
+    {
+        const float4 wt = *reinterpret_cast<const float4*>(w_tot);
+        P += wave > 0 ? wt.x : 0.f; P += wave > 1 ? wt.y : 0.f; P += wave > 2 ? wt.z : 0.f;
+    }
 
     // ---- translation D of each segment from two representative starts (even / odd mantissa)
-    uint32_t ev[SS_MAX_SPT], ndp[SS_MAX_SPT];
+    // Straight-line: every criterion is evaluated for every segment and combined with selects, so the five segments' add chains
+    // interleave instead of running one after the other behind five nested exec-mask branches each (2.3 k of the 7.8 k cycles of the
+    // sum at n = 4096, profiles/qkv_prologue.md).  What a hard segment computes past its first failing criterion is discarded.
+    uint32_t ev[SS_MAX_SPT] = {}, ndp[SS_MAX_SPT] = {};
     uint32_t hmask = 0, ndt = 0;
-#pragma unroll
-    for (int i = 0; i < SS_MAX_SPT; ++i) {
-        ev[i] = 0; ndp[i] = ndt;
-        if (i < spt && seg0 + i < nseg) {
-            const uint32_t rb = f2u(P) & ~1u, e = rb >> 23;
-            bool hard = false;
-            uint32_t nd = 0;
-            if (seg0 + i == 0 || e <= 40u || e >= 250u) hard = true;
-            else {
-                const float R0 = u2f(rb), R1 = u2f(rb | 1u);
-                float E0 = R0, E1 = R1;
-                E0 = E0 + a[i].x; E1 = E1 + a[i].x; E0 = E0 + a[i].y; E1 = E1 + a[i].y;
-                E0 = E0 + a[i].z; E1 = E1 + a[i].z; E0 = E0 + a[i].w; E1 = E1 + a[i].w;
-                const float D0 = E0 - R0, D1 = E1 - R1;
-                const float margin = u2f((e - 23u + 13u) << 23);         // 8192 ulp: keeps the fallback rare
-                if (!(D0 == D1) || (f2u(E0) >> 23) != e || (f2u(E1) >> 23) != e || (f2u(R0 - margin) >> 23) != e ||
-                    (f2u(E0 + margin) >> 23) != e)
-                    hard = true;
-                else nd = (uint32_t)(D0 * u2f((277u - e) << 23));        // D / ulp, exact integer < 2^24
-            }
-            ev[i] = e | (hard ? 0x80000000u : 0u);
-            es[seg0 + i] = ev[i];
-            hmask |= (hard ? 1u : 0u) << i;
-            ndt += nd;
-            ndp[i] = ndt;
-            P += qs[i];
-        }
-    }
+    auto translate = [&](const int i) __attribute__((always_inline)) {
+        const bool live = i < spt && seg0 + i < nseg;
+        const uint32_t rb = f2u(P) & ~1u, e = rb >> 23;
+        const bool edge = ((int)(seg0 + i == 0) | (int)(e <= 40u) | (int)(e >= 250u)) != 0;
+        const uint32_t ec = edge ? 127u : e;                         // keeps the discarded arithmetic of an edge segment finite
+        const float R0 = u2f(rb), R1 = u2f(rb | 1u);
+        float E0 = R0, E1 = R1;
+        E0 = E0 + a[i].x; E1 = E1 + a[i].x; E0 = E0 + a[i].y; E1 = E1 + a[i].y;
+        E0 = E0 + a[i].z; E1 = E1 + a[i].z; E0 = E0 + a[i].w; E1 = E1 + a[i].w;
+        const float D0 = E0 - R0, D1 = E1 - R1;
+        const float margin = u2f((ec - 23u + 13u) << 23);            // 8192 ulp: keeps the fallback rare
+        const bool bad = ((int)!(D0 == D1) | (int)((f2u(E0) >> 23) != e) | (int)((f2u(E1) >> 23) != e) |
+                          (int)((f2u(R0 - margin) >> 23) != e) | (int)((f2u(E0 + margin) >> 23) != e)) != 0;
+        const bool hard = edge || bad;
+        const float ndf = hard ? 0.f : D0 * u2f((277u - ec) << 23);  // D / ulp, exact integer < 2^24
+        const uint32_t nd = (uint32_t)ndf;
+        ev[i] = live ? (e | (hard ? 0x80000000u : 0u)) : 0u;
+        if (live) es[seg0 + i] = ev[i];
+        hmask |= ((live && hard) ? 1u : 0u) << i;
+        ndt += live ? nd : 0u;
+        ndp[i] = ndt;
+        P += qs[i];                                                  // qs of a segment past the end is 0 or never used
+    };
+    // short vectors (n <= 2048: Llama-3.2-1B) do not pay for the issue slots of three segments that do not exist
+    if (spt <= 2) { translate(0); translate(1); }
+    else { translate(0); translate(1); translate(2); translate(3); translate(4); }
     SS_STAMP(2);
     // ---- inclusive prefix of nd (mod 2^32: only differences inside one run are used) + hard list
     const uint32_t pin = wave_incl_scan_u32(ndt);
@@ -238,25 +244,31 @@ __device__ float exact_seqsum_lds(const float* x, int n, uint8_t* scratch, const
     if (lane == 63) { w_nd[wave] = pin; w_cnt[wave] = (int)hin; }
     sync();
     SS_STAMP(3);
+    // es[] was complete at the previous sync(): the left neighbour of my first segment, read with a clamped index ahead of its use
+    const uint32_t ep = es[min(max(seg0 - 1, 0), nseg - 1)];
     uint32_t nbase = 0; int hbase = 0;
-    for (int w = 0; w < wave; ++w) { nbase += w_nd[w]; hbase += w_cnt[w]; }
+    {
+        const uint4 wn = *reinterpret_cast<const uint4*>(w_nd);
+        const int4 wc = *reinterpret_cast<const int4*>(w_cnt);
+        nbase += wave > 0 ? wn.x : 0u; nbase += wave > 1 ? wn.y : 0u; nbase += wave > 2 ? wn.z : 0u;
+        hbase += wave > 0 ? wc.x : 0; hbase += wave > 1 ? wc.y : 0; hbase += wave > 2 ? wc.z : 0;
+    }
     {
         const uint32_t nb0 = nbase + pin - ndt;
-        int hpos = hbase + (int)(hin - hc);
+        const int hpos = hbase + (int)(hin - hc);
+        bool viol = false;                               // two easy neighbours in different binades: the predictor was wrong
 #pragma unroll
         for (int i = 0; i < SS_MAX_SPT; ++i) {
-            if (i < spt && seg0 + i < nseg) {
-                pre[seg0 + i] = nb0 + ndp[i];
-                if ((hmask >> i) & 1u) hlist[hpos++] = seg0 + i;
-                else if (i > 0) { if (!(ev[i - 1] >> 31) && (ev[i - 1] & 0x7FFFFFFFu) != (ev[i] & 0x7FFFFFFFu)) misc[0] = 1; }
-            }
+            const bool live = i < spt && seg0 + i < nseg;
+            const bool hard = (hmask >> i) & 1u;
+            if (live) pre[seg0 + i] = nb0 + ndp[i];
+            if (live && hard) hlist[hpos + (int)__popc(hmask & ((1u << i) - 1u))] = seg0 + i;
+            if (i > 0) viol |= live && !hard && !(ev[i - 1] >> 31) && (ev[i - 1] & 0x7FFFFFFFu) != (ev[i] & 0x7FFFFFFFu);
         }
-    }
-    // first segment of the thread vs its left neighbour: es[] was complete at the previous sync(), and the flag must be
-    // set BEFORE the next one — wave 0 reads misc[0] right after it
-    if (seg0 > 0 && seg0 < nseg && !(ev[0] >> 31)) {
-        const uint32_t ep = es[seg0 - 1];
-        if (!(ep >> 31) && ep != ev[0]) misc[0] = 1;
+        // first segment of the thread vs its left neighbour; the flag must be set BEFORE the next sync() — wave 0 reads misc[0]
+        // right after it
+        viol |= seg0 > 0 && seg0 < nseg && !(ev[0] >> 31) && !(ep >> 31) && ep != ev[0];
+        if (viol) misc[0] = 1;
     }
     sync();
     SS_STAMP(4);

@@ -384,51 +384,47 @@ static int32_t all_gather(gl3_ctx* ctx, int which, int count_per_rank, Prof& pr)
     return GL3_OK;
 }
 
-// Decode attention by context depth (the host knows the position): ATT_SHORT = one launch (attn_head_kernel, positions < AF_MAXN),
-// ATT_MID = scores + the r2 softmax-and-PV kernel (two launches; below ~768 positions two more ~5 us launches cost more than the chains
-// they shorten: tg128@d256 18.5 vs 21.8 us per 8B layer, profiles/r05_tg_depth.md), ATT_LONG = scores, exp, sum, PV (gl3_decode_kernels.h).
-enum { ATT_LONG = 0, ATT_SHORT = 1, ATT_MID = 2 };
-static int attn_mode(const gl3_ctx* ctx, int pos) {
-    return (ctx->fused_attn_ok && pos < AF_MAXN) ? ATT_SHORT : pos < ctx->attn_mid ? ATT_MID : ATT_LONG;
+// Decode attention by context depth (the host knows the position).  The regimes, which kernels each one launches, on what grid and with how much
+// LDS: attn_regime / attn_plan (gl3_decode_attn.h).  Here attn_shape hands the plan this context's figures and launch_attention issues what it lists.
+static AttnShape attn_shape(const gl3_ctx* ctx) {
+    const gl3_model_desc& d = ctx->d;
+    return {d.head_size, d.n_heads / d.n_kv_heads, ctx->heads_l, ctx->kv_heads_l, d.ctx, ctx->attn_win, ctx->attn_mid, ctx->fused_attn_ok};
+}
+static int attn_mode(const gl3_ctx* ctx, int pos) { return attn_regime(attn_shape(ctx), pos); }
+
+void gl3_attn_layer_args(const gl3_ctx* ctx, int l, AttnArgs& a) {
+    const gl3_model_desc& d = ctx->d;
+    const gl3_layer& L = ctx->layers[l];
+    const size_t kv_layer = (size_t)d.ctx * ctx->kv_dim_l;
+    a.kcache = ctx->kcache + l * kv_layer; a.vcache = ctx->vcache + l * kv_layer;
+    a.rope_cr = ctx->rope_cr; a.rope_ci = ctx->rope_ci; a.qnorm = L.qnorm; a.knorm = L.knorm; a.bq = L.bq; a.bk = L.bk; a.bv = L.bv;
+    a.n_heads = ctx->heads_l; a.n_kv_heads = ctx->kv_heads_l; a.hs = d.head_size; a.q_dim = ctx->q_dim_l; a.kv_dim = ctx->kv_dim_l; a.ctx = d.ctx;
+    a.eps = d.rms_eps; a.arch = ctx->rope_arch; a.att_mul = ctx->att_mul;
 }
 
-static void launch_attention(gl3_ctx* ctx, int l, int which /* 0 both, 1 scores, 2 softmax+pv */, int amode = ATT_LONG) {
+// part: the whole attention of a step, or only what runs behind the scores (gl3_profile_kernel's GL3_K_OTHER; nothing in ATT_SHORT)
+enum AttnPart { ATTN_WHOLE, ATTN_BEHIND_SCORES };
+static void launch_attention(gl3_ctx* ctx, int l, int amode, AttnPart part = ATTN_WHOLE) {
     const gl3_model_desc& d = ctx->d;
-    gl3_layer& L = ctx->layers[l];
-    const size_t kv_layer = (size_t)d.ctx * ctx->kv_dim_l;
-    const int kvmul = d.n_heads / d.n_kv_heads;
     AttnArgs aa{};
-    aa.qkv = ctx->qkv; aa.kcache = ctx->kcache + l * kv_layer; aa.vcache = ctx->vcache + l * kv_layer;
-    aa.rope_cr = ctx->rope_cr; aa.rope_ci = ctx->rope_ci; aa.qnorm = L.qnorm; aa.knorm = L.knorm; aa.bq = L.bq; aa.bk = L.bk; aa.bv = L.bv;
-    aa.dyn = ctx->dyn_cur; aa.att = ctx->att; aa.xb = ctx->xb + (size_t)d.tp_rank * ctx->q_dim_l;
-    aa.n_heads = ctx->heads_l; aa.n_kv_heads = ctx->kv_heads_l;
-    aa.hs = d.head_size; aa.q_dim = ctx->q_dim_l; aa.kv_dim = ctx->kv_dim_l; aa.ctx = d.ctx;
-    aa.eps = d.rms_eps; aa.arch = ctx->rope_arch; aa.att_mul = ctx->att_mul;
-    const size_t sm1 = ((size_t)kvmul * d.head_size + (size_t)ATT_TT * (d.head_size + 4) + d.head_size) * 4;
-    const int pv_rows = d.ctx < PV_ROWS ? d.ctx : PV_ROWS;
-    aa.win = ctx->attn_win;
-    aa.att_stride = (d.ctx + 3) & ~3;
-    aa.att_t = ctx->att_t; aa.tmax = ctx->att_tmax; aa.sums = ctx->att_sums;
+    gl3_attn_layer_args(ctx, l, aa);
+    aa.qkv = ctx->qkv; aa.dyn = ctx->dyn_cur; aa.att = ctx->att; aa.xb = ctx->xb + (size_t)d.tp_rank * ctx->q_dim_l;
+    aa.win = ctx->attn_win; aa.att_stride = (d.ctx + 3) & ~3; aa.att_t = ctx->att_t; aa.tmax = ctx->att_tmax; aa.sums = ctx->att_sums;
     aa.tp = tp_rec(ctx, l, TR_ATTN);
-    const size_t sm2 = ((size_t)ctx->attn_win + (size_t)pv_rows * PV_COLS) * 4;
-    if (which == 0 && amode == ATT_SHORT && ctx->fused_attn_ok) {      // positions < AF_MAXN: one launch
-        attn_head_dispatch(d.head_size, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(ctx->heads_l), dim3(256), attn_head_smem(d.head_size), ctx->stream, aa); });
-        return;
+    const AttnPlan p = attn_plan(attn_shape(ctx), amode);
+    for (int i = part == ATTN_BEHIND_SCORES ? 1 : 0; i < p.n; ++i) {
+        const AttnLaunch& k = p.launch[i];
+        const auto go = [&](auto kern, auto... more) { hipLaunchKernelGGL(kern, dim3(k.gx, k.gy), dim3(k.block), k.lds, ctx->stream, aa, more...); };
+        switch (k.kernel) {
+        case AK_HEAD: attn_head_dispatch(d.head_size, go); break;
+        case AK_SCORES: go(attn_scores_kernel); break;
+        case AK_SCORES_LOOP: d.head_size == 128 ? go(attn_scores_loop_kernel<128>, ctx->n_tsplit) : go(attn_scores_loop_kernel<64>, ctx->n_tsplit); break;
+        case AK_SOFTMAX_PV: go(attn_softmax_pv_kernel); break;
+        case AK_EXP: go(attn_exp_kernel, ctx->n_tsplit); break;
+        case AK_SUM: go(attn_sum_kernel); break;
+        case AK_PV: go(attn_pv_kernel); break;
+        }
     }
-    if (which != 2 && amode == ATT_LONG && kvmul <= 4 && (d.head_size == 128 || d.head_size == 64)) {
-        const dim3 sg(ctx->n_tsplit < SCL_WGS ? ctx->n_tsplit : SCL_WGS, ctx->kv_heads_l), sb(64 * (kvmul + SCL_LOADERS));
-        const size_t sml = ((size_t)kvmul * d.head_size + 2 * (size_t)ATT_TT * (d.head_size + 4) + 2 * d.head_size) * 4;
-        if (d.head_size == 128) hipLaunchKernelGGL(attn_scores_loop_kernel<128>, sg, sb, sml, ctx->stream, aa, ctx->n_tsplit);
-        else hipLaunchKernelGGL(attn_scores_loop_kernel<64>, sg, sb, sml, ctx->stream, aa, ctx->n_tsplit);
-    }
-    else if (which != 2) hipLaunchKernelGGL(attn_scores_kernel, dim3(ctx->n_tsplit, ctx->kv_heads_l), dim3(64 * kvmul), sm1, ctx->stream, aa);
-    if (which != 1 && amode == ATT_LONG) {
-        const int exp_rows = (d.ctx + EXP_ROW - 1) / EXP_ROW;
-        hipLaunchKernelGGL(attn_exp_kernel, dim3(exp_rows < EXP_GRID_MAX ? exp_rows : EXP_GRID_MAX, ctx->heads_l), dim3(256), 0, ctx->stream, aa, ctx->n_tsplit);
-        hipLaunchKernelGGL(attn_sum_kernel, dim3(ctx->heads_l), dim3(256), attn_sum_smem(), ctx->stream, aa);
-        hipLaunchKernelGGL(attn_pv_kernel, dim3(ctx->kv_heads_l * attn_pv_hq(kvmul) * (d.head_size / PV_COLS16)), dim3(64 * PV_WAVES), attn_pv_smem(), ctx->stream, aa);
-    } else if (which != 1)
-        hipLaunchKernelGGL(attn_softmax_pv_kernel, dim3(ctx->heads_l * (d.head_size / PV_COLS)), dim3(256), sm2, ctx->stream, aa);
 }
 
 // amode: attn_mode(position) — the host knows the position of the step
@@ -463,7 +459,7 @@ static int32_t enqueue_decode(gl3_ctx* ctx, bool want_logits, gl3_kernel_times* 
         pr.end();
 
         pr.begin(GL3_K_ATTENTION, 0);
-        { Gl3Range g("rope + kv write + attention"); launch_attention(ctx, l, 0, amode); }
+        { Gl3Range g("rope + kv write + attention"); launch_attention(ctx, l, amode); }
         pr.end();
         if (fold) fold_wait(ctx, l, TR_WAIT_XB, pr);
         else if ((r = all_gather(ctx, GB_XB, ctx->q_dim_l, pr)) != GL3_OK) return r;
@@ -679,7 +675,7 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     ctx->heads_l = d.n_heads / tp; ctx->kv_heads_l = d.n_kv_heads / tp;
     ctx->q_dim_l = ctx->heads_l * d.head_size; ctx->kv_dim_l = ctx->kv_heads_l * d.head_size;
     ctx->hidden_l = d.hidden / tp; ctx->vocab_l = d.vocab / tp; ctx->dim_l = d.dim / tp;
-    ctx->n_tsplit = (d.ctx + ATT_TT - 1) / ATT_TT;
+    ctx->n_tsplit = attn_n_tsplit(d.ctx);
     // Tensor parallel: Wo is REPLICATED (every rank holds all dim rows) — each rank computes the whole attention output projection
     // from the gathered xb, so the residual stream is complete on every rank without a gather behind it: 3 gathers per layer
     // (xb, hb, x) instead of 4.  Streaming all of Wo (17.9 MB for the 8B model: ~6 us) costs less than a gather hop over xGMI, and
@@ -751,34 +747,37 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     TRY(dmalloc(ctx, &ctx->att_sums, (size_t)ctx->heads_l));
     if (moe) TRY(moe_build_slots(ctx));          // after hb: the merged gate/up launch writes the shared expert's SwiGLU output there
     for (const MvVariant& v : MV_VARIANTS) TRYHIP(hipFuncSetAttribute((const void*)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
-    {
-        // one launch per layer for positions < AF_MAXN (attn_head_kernel); head_size 256 does not fit its K / V tiles in LDS
-        ctx->fused_attn_ok = d.head_size % 4 == 0 && attn_head_smem(d.head_size) <= 150 * 1024 && !env_flag("GL3_NO_FUSED_ATTN", false);
-        if (ctx->fused_attn_ok) {
-            hipError_t ae = hipSuccess;
-            attn_head_dispatch(d.head_size, [&](auto kern) { ae = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX); });
-            TRYHIP(ae);
-        }
-    }
     for (int fmt : {GL3_TYPE_F16, GL3_TYPE_Q4_0})
         for (int epi : {EPI_STORE, EPI_RESID, EPI_SWIGLU}) TRYHIP(hipFuncSetAttribute((const void*)rl_kernel(fmt, epi), hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
     TRYHIP(hipFuncSetAttribute((const void*)rmsnorm_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
-    TRYHIP(hipFuncSetAttribute((const void*)attn_scores_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    TRYHIP(hipFuncSetAttribute((const void*)attn_scores_loop_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    TRYHIP(hipFuncSetAttribute((const void*)attn_scores_loop_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    TRYHIP(hipFuncSetAttribute((const void*)attn_softmax_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    TRYHIP(hipFuncSetAttribute((const void*)attn_sum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_sum_smem()));
-    TRYHIP(hipFuncSetAttribute((const void*)attn_pv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_pv_smem()));
-    // softmax rows longer than the LDS window (16384 positions; GL3_ATTN_WINDOW, a multiple of 1024, shrinks it for tests) run in
-    // windows with the sequential sum carried across them: no cap on the context length (r2 rejected contexts above ~20 k)
-    {
-        const char* wv = getenv("GL3_ATTN_WINDOW");
-        int wmax = wv && *wv ? atoi(wv) : 16384;
-        if (wmax < PV_ROWS || wmax % PV_ROWS != 0 || wmax > 16384) return bail(GL3_E_ARG, "GL3_ATTN_WINDOW must be a multiple of 1024 between 1024 and 16384");
+    {   // Decode attention (gl3_decode_attn.h).  The three switches of its plan: GL3_NO_FUSED_ATTN=1 no attn_head_kernel (one launch per layer for
+        // positions < AF_MAXN) where the head size admits it; GL3_ATTN_WINDOW softmax positions kept in LDS, a multiple of 1024 (shrinks it for tests;
+        // longer rows run in windows with the sequential sum carried across them: no cap on the context length, r2 rejected contexts above ~20 k);
+        // GL3_ATTN_MID depth below which the two-launch attention is used (0 = always the four-launch long-context path)
+        const auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v && *v ? atoi(v) : dflt; };
+        ctx->fused_attn_ok = attn_head_admits(d.head_size) && !env_flag("GL3_NO_FUSED_ATTN", false);
+        const int wmax = env_int("GL3_ATTN_WINDOW", ATTN_WIN_MAX);
+        ctx->attn_mid = env_int("GL3_ATTN_MID", ATTN_MID_DEFAULT);
+        if (wmax < PV_ROWS || wmax % PV_ROWS != 0 || wmax > ATTN_WIN_MAX) return bail(GL3_E_ARG, "GL3_ATTN_WINDOW must be a multiple of 1024 between 1024 and 16384");
         ctx->attn_win = d.ctx <= wmax ? ((d.ctx + 3) & ~3) : wmax;
-        // depth below which the two-launch attention is used (GL3_ATTN_MID: 0 = always the four-launch long-context path)
-        const char* mv = getenv("GL3_ATTN_MID");
-        ctx->attn_mid = mv && *mv ? atoi(mv) : 768;
+        // Every kernel may ask for its cap, and no launch of any regime's plan asks for more: a formula or a cap that changes fails here, not at the first step.
+        const void* head = nullptr;      // the instantiation for this head size, where the plan has ATT_SHORT
+        if (ctx->fused_attn_ok) attn_head_dispatch(d.head_size, [&](auto kern) { head = (const void*)kern; });
+        const struct { int id; const char* name; const void* kernel; } attn_kernels[] = {      // attn_exp_kernel has no dynamic LDS
+            {AK_HEAD, "attn_head_kernel", head}, {AK_SCORES, "attn_scores_kernel", (const void*)attn_scores_kernel},
+            {AK_SCORES_LOOP, "attn_scores_loop_kernel", (const void*)attn_scores_loop_kernel<128>}, {AK_SCORES_LOOP, "attn_scores_loop_kernel", (const void*)attn_scores_loop_kernel<64>},
+            {AK_SOFTMAX_PV, "attn_softmax_pv_kernel", (const void*)attn_softmax_pv_kernel}, {AK_SUM, "attn_sum_kernel", (const void*)attn_sum_kernel},
+            {AK_PV, "attn_pv_kernel", (const void*)attn_pv_kernel}};
+        for (const auto& k : attn_kernels) {
+            if (k.kernel) TRYHIP(hipFuncSetAttribute(k.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attn_lds_cap(k.id)));
+            for (int regime = 0; regime < ATT_REGIMES; ++regime) {
+                const AttnPlan p = attn_plan(attn_shape(ctx), regime);
+                for (int i = 0; i < p.n; ++i)
+                    if (const AttnLaunch& a = p.launch[i]; a.kernel == k.id && a.lds > attn_lds_cap(k.id))
+                        return bail(GL3_E_UNSUPPORTED, std::string(k.name) + ": head_size = " + std::to_string(d.head_size) + " with " + std::to_string(d.n_heads / d.n_kv_heads) +
+                                    " query heads per kv head needs " + std::to_string(a.lds) + " bytes of LDS, the limit is " + std::to_string(attn_lds_cap(k.id)));
+            }
+        }
     }
     TRY(dmalloc(ctx, &ctx->dyn, GL3_DYN_INTS));
     ctx->dyn_cur = ctx->dyn;
@@ -819,12 +818,8 @@ void gl3_destroy(gl3_ctx* ctx) {
     if (!ctx) return;
     hipSetDevice(ctx->d.device);
     if (ctx->stream) hipStreamSynchronize(ctx->stream);
-    if (ctx->graph_exec) hipGraphExecDestroy(ctx->graph_exec);
-    if (ctx->graph_exec_s) hipGraphExecDestroy(ctx->graph_exec_s);
-    if (ctx->graph_exec_m) hipGraphExecDestroy(ctx->graph_exec_m);
-    if (ctx->graph_m) hipGraphDestroy(ctx->graph_m);
-    if (ctx->graph_s) hipGraphDestroy(ctx->graph_s);
-    if (ctx->graph) hipGraphDestroy(ctx->graph);
+    for (hipGraphExec_t ge : ctx->graph_exec) if (ge) hipGraphExecDestroy(ge);
+    for (hipGraph_t g : ctx->graph) if (g) hipGraphDestroy(g);
     if (ctx->comm) ncclCommDestroy(ctx->comm);
     gl3_prefill_free(ctx);
     gl3_sample_free(ctx);
@@ -1045,11 +1040,13 @@ int32_t gl3_finalize(gl3_ctx* ctx) {
     ctx->finalized = true;
     if (!(d.flags & GL3_FLAG_NO_GRAPH) && !env_flag("GL3_NO_GRAPH", false) && !gl3_roctx_on()) {
         const double t0 = now_ms();
-        int32_t r = capture(ctx, true, ATT_LONG, &ctx->graph, &ctx->graph_exec);
-        if (r == GL3_OK && ctx->fused_attn_ok) r = capture(ctx, true, ATT_SHORT, &ctx->graph_s, &ctx->graph_exec_s);
-        if (r == GL3_OK && ctx->attn_mid > (ctx->fused_attn_ok ? AF_MAXN : 0)) r = capture(ctx, true, ATT_MID, &ctx->graph_m, &ctx->graph_exec_m);
+        // the regimes some position of this plan is in; ATT_LONG first: its step is what the others fall back to
+        const bool has[ATT_REGIMES] = {true, ctx->fused_attn_ok, ctx->attn_mid > (ctx->fused_attn_ok ? AF_MAXN : 0)};
+        int32_t r = GL3_OK;
+        for (int m = 0; m < ATT_REGIMES && r == GL3_OK; ++m)
+            if (has[m]) r = capture(ctx, true, m, &ctx->graph[m], &ctx->graph_exec[m]);
         if (r != GL3_OK) {   // e.g. a collective that cannot be captured: run eagerly instead
-            ctx->graph_exec = nullptr; ctx->graph_exec_s = nullptr; ctx->graph_exec_m = nullptr;
+            for (hipGraphExec_t& ge : ctx->graph_exec) ge = nullptr;
             (void)hipGetLastError();
             fprintf(stderr, "[gl3] hipGraph capture failed (%s); falling back to eager launches\n", ctx->err.c_str());
         }
@@ -1072,10 +1069,9 @@ static int32_t set_dyn(gl3_ctx* ctx, int32_t token, int32_t pos, const SmpRow* r
     return GL3_OK;
 }
 
+static_assert(sizeof(gl3_ctx::graph_exec) / sizeof(hipGraphExec_t) == ATT_REGIMES, "one captured step per attention regime");
 static hipGraphExec_t step_graph(gl3_ctx* ctx, int amode) {
-    if (amode == ATT_SHORT && ctx->graph_exec_s) return ctx->graph_exec_s;
-    if (amode == ATT_MID && ctx->graph_exec_m) return ctx->graph_exec_m;
-    return ctx->graph_exec;          // the ATT_LONG step is correct at every position
+    return ctx->graph_exec[amode] ? ctx->graph_exec[amode] : ctx->graph_exec[ATT_LONG];          // the ATT_LONG step is correct at every position
 }
 
 int32_t gl3_forward_decode(gl3_ctx* ctx, int32_t token, int32_t pos, float* logits_out, int32_t* argmax_out) {
@@ -1084,7 +1080,7 @@ int32_t gl3_forward_decode(gl3_ctx* ctx, int32_t token, int32_t pos, float* logi
     if (r != GL3_OK) return r;
     const bool want_logits = logits_out || argmax_out;
     const int amode = attn_mode(ctx, pos);
-    if (ctx->graph_exec && want_logits) GL3_HIP(hipGraphLaunch(step_graph(ctx, amode), ctx->stream));
+    if (ctx->graph_exec[ATT_LONG] && want_logits) GL3_HIP(hipGraphLaunch(step_graph(ctx, amode), ctx->stream));
     else if ((r = enqueue_decode(ctx, want_logits, nullptr, amode)) != GL3_OK) return r;
     if (argmax_out) {
         hipLaunchKernelGGL(argmax_kernel, dim3(AMX_WGS), dim3(256), 0, ctx->stream, ctx->logits, ctx->d.vocab, ctx->argmax);
@@ -1114,7 +1110,7 @@ int32_t gl3_forward_decode_sample(gl3_ctx* ctx, int32_t token, int32_t pos, floa
     int32_t r = set_dyn(ctx, token, pos, &row);
     if (r != GL3_OK) return r;
     const int amode = attn_mode(ctx, pos);
-    if (ctx->graph_exec) GL3_HIP(hipGraphLaunch(step_graph(ctx, amode), ctx->stream));
+    if (ctx->graph_exec[ATT_LONG]) GL3_HIP(hipGraphLaunch(step_graph(ctx, amode), ctx->stream));
     else if ((r = enqueue_decode(ctx, true, nullptr, amode)) != GL3_OK) return r;
     return gl3_sample_run(ctx, ctx->logits, token_out);          // ends with the stream synchronisation and gl3_tp_check
 }
@@ -1344,6 +1340,25 @@ int32_t gl3_debug_batch_plan_split(const int32_t* seq_ids, const int32_t* positi
     return GL3_OK;
 }
 
+int32_t gl3_debug_decode_attn_plan(int32_t head_size, int32_t kvmul, int32_t heads_l, int32_t kv_heads_l, int32_t ctx_len, int32_t window, int32_t attn_mid,
+                                   int32_t head_kernel_allowed, int32_t pos, int32_t group, int32_t* regime_out, int64_t* launches_out, int32_t* n_launches,
+                                   int64_t* head_out) {
+    if (!regime_out || !launches_out || !n_launches || !head_out) return GL3_E_ARG;
+    if (head_size < 32 || head_size > 256 || head_size % 32 || kvmul < 1 || kvmul > 16 || kv_heads_l < 1 || heads_l != kvmul * kv_heads_l) return GL3_E_ARG;
+    if (ctx_len < 1 || pos < 0 || pos >= ctx_len || window < 1 || window > ATTN_WIN_MAX || group < 1) return GL3_E_ARG;
+    const AttnShape s{head_size, kvmul, heads_l, kv_heads_l, ctx_len, window, attn_mid, head_kernel_allowed && attn_head_admits(head_size)};
+    const AttnPlan p = attn_plan(s, attn_regime(s, pos));
+    *regime_out = p.regime;
+    *n_launches = p.n;
+    for (int i = 0; i < p.n; ++i) {
+        const AttnLaunch& k = p.launch[i];
+        const int64_t rec[6] = {k.kernel, k.gx, k.gy, k.block, (int64_t)k.lds, (int64_t)attn_lds_cap(k.kernel)};
+        memcpy(launches_out + 6 * i, rec, sizeof(rec));
+    }
+    head_out[0] = (int64_t)attn_head_smem(head_size, group); head_out[1] = attn_head_admits(head_size); head_out[2] = attn_head_admits(head_size, group);
+    return GL3_OK;
+}
+
 int32_t gl3_get_attn_rows(gl3_ctx* ctx, int32_t out[4]) {
     if (!ctx) return GL3_E_ARG;
     if (!out) GL3_FAIL(GL3_E_ARG, "null out");
@@ -1405,8 +1420,8 @@ int32_t gl3_profile_kernel(gl3_ctx* ctx, int32_t klass, int32_t iters, double* o
             case GL3_K_MATVEC_WO: launch_matvec(ctx, PRO_QUANT, EPI_RESID, L.wo, nullptr, ctx->xb, nullptr, ctx->qkv, nullptr); break;
             case GL3_K_MATVEC_GATEUP: launch_matvec(ctx, PRO_RMS, EPI_SWIGLU, L.w1, &L.w3, ctx->x, L.ffn_norm, ctx->hb + (size_t)rank * ctx->hidden_l, nullptr); break;
             case GL3_K_MATVEC_DOWN: launch_matvec(ctx, PRO_QUANT, EPI_RESID, L.w2, nullptr, ctx->hb, nullptr, ctx->qkv, nullptr); break;
-            case GL3_K_ATTENTION: launch_attention(ctx, l, 0, attn_mode(ctx, ctx->h_dyn[1])); break;   // whole attention at the last position
-            case GL3_K_OTHER: launch_attention(ctx, l, 2, attn_mode(ctx, ctx->h_dyn[1]) == ATT_LONG ? ATT_LONG : ATT_MID); break;          // behind the scores only
+            case GL3_K_ATTENTION: launch_attention(ctx, l, attn_mode(ctx, ctx->h_dyn[1])); break;   // whole attention at the last position
+            case GL3_K_OTHER: launch_attention(ctx, l, attn_mode(ctx, ctx->h_dyn[1]) == ATT_LONG ? ATT_LONG : ATT_MID, ATTN_BEHIND_SCORES); break;
             default: launch_matvec(ctx, PRO_RMS, EPI_STORE, ctx->wcls, nullptr, ctx->x, ctx->out_norm, ctx->logits + (size_t)rank * ctx->vocab_l, nullptr); break;
             }
         }

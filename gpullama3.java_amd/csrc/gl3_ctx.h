@@ -226,13 +226,11 @@ struct gl3_ctx {
     struct gl3_prefill_state* pf = nullptr;
     // execution
     bool finalized = false;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;          // decode step incl. logits
-    hipGraph_t graph_s = nullptr;
-    hipGraphExec_t graph_exec_s = nullptr;        // same step with the fused short-context attention (pos < AF_MAXN)
-    hipGraph_t graph_m = nullptr;
-    hipGraphExec_t graph_exec_m = nullptr;        // same step with the two-launch attention (AF_MAXN <= pos < attn_mid)
-    int attn_mid = 0;                             // see attn_mode (gl3_api.hip)
+    // decode step incl. logits, one capture per attention regime (AttnRegime, gl3_decode_attn.h): [ATT_LONG] exists whenever graphs are
+    // on and is correct at every position, [ATT_SHORT] (pos < AF_MAXN) and [ATT_MID] (pos < attn_mid) where the plan has the regime
+    hipGraph_t graph[3] = {};
+    hipGraphExec_t graph_exec[3] = {};
+    int attn_mid = 0;                             // see attn_regime (gl3_decode_attn.h)
     bool fused_attn_ok = false;                   // shape admits attn_head_kernel (one launch per layer for positions < AF_MAXN)
     ncclComm_t comm = nullptr;
     gl3_local_group* lgrp = nullptr;
@@ -287,6 +285,10 @@ int32_t gl3_tp_arena_alloc(gl3_ctx* ctx);
 void gl3_tp_arena_free(gl3_ctx* ctx);
 int32_t gl3_tp_local_resolve(gl3_ctx* ctx);
 int32_t gl3_tp_check(gl3_ctx* ctx);      // after a stream sync: GL3_E_RCCL if a gather timed out
+namespace gl3 { struct AttnArgs; }       // gl3_decode_attn.h
+// gl3_api.hip: the part of AttnArgs that layer l decides (its caches, rope tables, norms, biases, head counts and dimensions, eps,
+// arch, att_mul); the caller adds the buffers, strides and window of its own launch
+void gl3_attn_layer_args(const gl3_ctx* ctx, int l, gl3::AttnArgs& a);
 
 // gl3_sample.hip
 // single row: the launches behind a decode step whose set_dyn uploaded the row's settings, 8 bytes back

@@ -571,7 +571,7 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     const int qkv_dim = qd + 2 * kvd;
     const size_t kv_layer = (size_t)d.ctx * kvd;
     // one workgroup per (kv head, token) serves the kv head's whole group of query heads when its LDS image fits
-    const int bd_group = (kvmul <= 8 && attn_head_smem(d.head_size, kvmul) <= PF_ATTN_LDS_MAX) ? kvmul : 1;
+    const int bd_group = (kvmul <= 8 && attn_head_admits(d.head_size, kvmul)) ? kvmul : 1;
     const bool fused_decode = pf_fused_decode(ctx, st);
     RopeArgs ra{};
     ra.QKV = p->QKV; ra.qkv_stride = qkv_dim; ra.kcache = ctx->kcache + l * kv_layer; ra.vcache = ctx->vcache + l * kv_layer;
@@ -588,10 +588,9 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
         // static-batched decode at positions < AF_MAXN: RoPE + KV write + scores + softmax + weighted V sum of every
         // (token, head) in ONE launch (attn_head_kernel, grid = heads x tokens) instead of three per-token-grid kernels
         AttnArgs ha{};
-        ha.qkv = p->QKV; ha.qkv_stride = qkv_dim; ha.kcache = ra.kcache; ha.vcache = ra.vcache; ha.rope_cr = ctx->rope_cr; ha.rope_ci = ctx->rope_ci;
-        ha.qnorm = L.qnorm; ha.knorm = L.knorm; ha.bq = L.bq; ha.bk = L.bk; ha.bv = L.bv; ha.dyn = ctx->dyn; ha.att = nullptr;
-        ha.xb = AOr; ha.xb_stride = qd; ha.n_heads = H; ha.n_kv_heads = KVH; ha.hs = hs; ha.q_dim = qd; ha.kv_dim = kvd; ha.ctx = d.ctx;
-        ha.eps = d.rms_eps; ha.arch = ctx->rope_arch; ha.att_mul = ctx->att_mul; ha.seqv = seq; ha.posv = pos; ha.seq_stride = ctx->kv_seq_stride;
+        gl3_attn_layer_args(ctx, l, ha);
+        ha.qkv = p->QKV; ha.qkv_stride = qkv_dim; ha.dyn = ctx->dyn; ha.att = nullptr; ha.xb = AOr; ha.xb_stride = qd;
+        ha.seqv = seq; ha.posv = pos; ha.seq_stride = ctx->kv_seq_stride;
         ha.group = bd_group;
         if (fuse_q) { ha.xq_out = p->XQ; ha.xs_out = p->XS; ha.xq_slots = bd_tslots(n); }
         attn_head_dispatch(hs, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(H / bd_group, n), dim3(256), attn_head_smem(hs, bd_group), s, ha); });

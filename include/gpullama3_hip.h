@@ -339,6 +339,17 @@ GL3_API int32_t gl3_debug_batch_plan(const int32_t* seq_ids, const int32_t* posi
 GL3_API int32_t gl3_debug_batch_plan_split(const int32_t* seq_ids, const int32_t* positions, int32_t n, int32_t n_seqs, int32_t ctx,
                                            int32_t capacity, int32_t fused_max_pos, int32_t* shallow_out, int32_t* n_shallow,
                                            int32_t* deep_out, int32_t* n_deep, int32_t* deep_rows, int32_t* n_deep_rows);
+/* Test hook, no plan and no device: the attention launches of one single-token decode step (csrc/gl3_decode_attn.h: attn_regime, attn_plan)
+ * for a rank with heads_l query and kv_heads_l kv heads of head_size elements (kvmul query heads per kv head), context length ctx, `window`
+ * softmax positions kept in LDS, the two-launch pair below position attn_mid, at position pos.  head_kernel_allowed = 0: a plan made under
+ * GL3_NO_FUSED_ATTN=1.  regime_out: 0 long, 1 short (attn_head_kernel), 2 mid.  launches_out: int64[4][6] = {kernel (0 attn_head_kernel,
+ * 1 attn_scores_kernel, 2 attn_scores_loop_kernel, 3 attn_softmax_pv_kernel, 4 attn_exp_kernel, 5 attn_sum_kernel, 6 attn_pv_kernel),
+ * grid x, grid y, block, dynamic LDS bytes, the kernel's LDS cap} in launch order, *n_launches of them.  head_out: int64[3] =
+ * {attn_head_smem(head_size, group), whether attn_head_kernel admits the head size with one query head per workgroup, and with `group`}.
+ * GL3_E_ARG for a shape gl3_create refuses on these numbers or a position outside the context. */
+GL3_API int32_t gl3_debug_decode_attn_plan(int32_t head_size, int32_t kvmul, int32_t heads_l, int32_t kv_heads_l, int32_t ctx, int32_t window,
+                                           int32_t attn_mid, int32_t head_kernel_allowed, int32_t pos, int32_t group, int32_t* regime_out,
+                                           int64_t* launches_out, int32_t* n_launches, int64_t* head_out);
 /* Fork a prefix: copy the K and V rows at positions [p0, p1) of sequence src_seq, every layer, into the same positions of each of the
  * n_dst sequences dst_seqs[].  Rows outside [p0, p1) of the destinations, every other sequence and the source are untouched.
  * What the rows mean: a row's arithmetic does not depend on which rows share its step, so the K / V rows at positions 0 .. p of a sequence are

@@ -6,14 +6,16 @@ config names the family: tiny-llama (adjacent-pair RoPE), tiny-qwen3 (per-head q
 tiny-phi3 (fused qkv tensor, NeoX RoPE), tiny-granite (attention scale instead of 1 / sqrt(head size)).  head_size * n_heads need not
 be dim.  tests/test_attn_shapes.py asserts what the grid covers (and that every row is needed for it), tests/test_gpu_attn_shapes.py runs it.
 
-The dispatch rule below restates the conditions of gl3_api.hip (attn_mode, launch_attention) and gl3_prefill.hip (pf_fused_decode,
-pf_attention) in Python; the GPU tests compute what plan.attn_rows() must report from it."""
+The dispatch rule below restates in Python the decode attention plan of csrc/gl3_decode_attn.h (attn_regime, attn_plan, the LDS sizes beside
+the kernels and their caps) and the conditions of gl3_prefill.hip (pf_fused_decode, pf_attention); the GPU tests compute what
+plan.attn_rows() must report from it.  tests/test_attn_shapes.py holds the decode part equal to the library's own plan, asked through
+gl3_debug_decode_attn_plan, over every head size, kvMul, regime boundary and switch."""
 
-AF_MAXN = 128          # gl3_decode_kernels.h: positions below it take attn_head_kernel where the shape admits it
-ATTN_MID = 768         # gl3_api.hip: positions below it (and >= AF_MAXN, or from 0 without attn_head_kernel) take the two-launch pair
+AF_MAXN = 128          # gl3_decode_attn.h: positions below it take attn_head_kernel where the shape admits it
+ATTN_MID = 768         # gl3_decode_attn.h (ATTN_MID_DEFAULT; GL3_ATTN_MID): positions below it (and >= AF_MAXN, or from 0 without attn_head_kernel) take the two-launch pair
 PV_ROWS = 1024         # V rows of one slab of attn_softmax_pv_kernel
 PV_G = 4               # query heads per head quad of attn_pv_kernel
-LDS_MAX = 150 * 1024   # what attn_head_kernel may ask for (PF_ATTN_LDS_MAX, and the same figure at gl3_create)
+LDS_MAX = 150 * 1024   # what attn_head_kernel may ask for (ATTN_HEAD_LDS_CAP: gl3_create's fused_attn_ok and pf_attention's bd_group)
 
 # the single-token decode walk of tests/test_gpu_attn_shapes.py: a context that is a multiple of 4 (pf_softmax_rows_kernel) past PV_ROWS and 16 score
 # tiles; decode steps at the start, across AF_MAXN, across ATTN_MID and past PV_ROWS, batched prefill between them; prompt rows compared on both
@@ -82,13 +84,13 @@ def scores_kernel_lds(hs, kvmul):
     return (kvmul * hs + 64 * (hs + 4) + hs) * 4
 
 
-def decode_regime(hs, kvmul, pos, head_kernel=True):
-    """The kernels of a single-token decode step at `pos` (launch_attention); head_kernel=False: a plan made under GL3_NO_FUSED_ATTN=1.
+def decode_regime(hs, kvmul, pos, head_kernel=True, attn_mid=ATTN_MID):
+    """The kernels of a single-token decode step at `pos` (attn_plan); head_kernel=False: a plan made under GL3_NO_FUSED_ATTN=1; attn_mid: GL3_ATTN_MID.
     "head": attn_head_kernel.  "pair": attn_scores_kernel + attn_softmax_pv_kernel.  "long-loop" / "long-tile": attn_scores_loop_kernel /
     attn_scores_kernel, then attn_exp_kernel, attn_sum_kernel, attn_pv_kernel."""
     if head_kernel and has_head_kernel(hs) and pos < AF_MAXN:
         return "head"
-    if pos < ATTN_MID:
+    if pos < attn_mid:
         return "pair"
     return "long-loop" if kvmul <= 4 and hs in (64, 128) else "long-tile"
 

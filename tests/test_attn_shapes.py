@@ -1,5 +1,31 @@
-"""What the attention shape grid (tests/attn_shapes.py) covers, and the dispatch rule it states, checked without a GPU."""
+"""What the attention shape grid (tests/attn_shapes.py) covers, and the dispatch rule it states, checked without a GPU: against fixed
+expectations, and against the library's own decode attention plan (csrc/gl3_decode_attn.h through gl3_debug_decode_attn_plan: plain
+integers in, plain arrays out, no plan, no device)."""
+import ctypes
+from importlib import import_module
+
+import numpy as np
+
+import __graft_entry__ as ge
 import attn_shapes as sh
+
+# launch records of gl3_debug_decode_attn_plan: kernel ids in the order of include/gpullama3_hip.h
+HEAD, SCORES, SCORES_LOOP, SOFTMAX_PV, EXP, SUM, PV = range(7)
+REGIME_OF = {(HEAD,): "head", (SCORES, SOFTMAX_PV): "pair", (SCORES_LOOP, EXP, SUM, PV): "long-loop", (SCORES, EXP, SUM, PV): "long-tile"}
+REGIME_CODE = {"head": 1, "pair": 2, "long-loop": 0, "long-tile": 0}      # AttnRegime: ATT_LONG 0, ATT_SHORT 1, ATT_MID 2
+
+
+def library_plan(hs, kvmul, pos, head_kernel=True, attn_mid=sh.ATTN_MID, ctx=sh.CTX, window=None, group=1, kv_heads=2):
+    """-> (regime code, launches [(kernel, grid x, grid y, block, LDS bytes, LDS cap)], (attn_head_smem(hs, group), admitted, admitted with group))"""
+    ge.load_package()
+    lib = import_module(ge.PKG_NAME + ".hip").lib()
+    regime, n = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    launches, head = np.full((4, 6), -7, np.int64), np.full(3, -7, np.int64)
+    code = lib.gl3_debug_decode_attn_plan(hs, kvmul, kvmul * kv_heads, kv_heads, ctx, window if window is not None else min((ctx + 3) & ~3, 16384), attn_mid,
+                                          int(head_kernel), pos, group, ctypes.byref(regime), launches.ctypes.data_as(ctypes.c_void_p), ctypes.byref(n),
+                                          head.ctypes.data_as(ctypes.c_void_p))
+    assert code == 0, (code, hs, kvmul, pos)
+    return regime.value, [tuple(r) for r in launches[:n.value].tolist()], tuple(head.tolist())
 
 
 def test_the_grid_covers_every_head_size_kvmul_and_family():
@@ -52,3 +78,33 @@ def test_the_decode_walk_meets_every_regime_of_every_shape():
     assert sh.CTX % 4 == 0 and not set(sh.PREFILL_KV_AT) & set(sh.DECODE_AT)
     for edge in (64, 128, 768, 1024):
         assert max(p for p in sh.PREFILL_KV_AT if p < edge) >= edge - 3 and min(p for p in sh.PREFILL_KV_AT if p >= edge) <= edge + 3
+
+
+def test_the_dispatch_rule_is_the_librarys_plan():
+    """decode_regime, has_head_kernel, attn_head_smem, the size condition of bd_group and scores_kernel_lds equal csrc/gl3_decode_attn.h on every
+    head size and kvMul gl3_create accepts, either side of each regime boundary at context 1100, with and without the head kernel, with the
+    two-launch pair at its default depth and switched off; and no launch of any of these plans asks for more LDS than its kernel's cap."""
+    for hs in range(32, 257, 32):
+        for kvmul in range(1, 17):
+            for group in (1, kvmul):
+                smem, admitted, admitted_group = library_plan(hs, kvmul, 0, group=group)[2]
+                assert smem == sh.attn_head_smem(hs, group) and bool(admitted) == sh.has_head_kernel(hs), (hs, kvmul, group)
+                assert bool(admitted_group) == (sh.attn_head_smem(hs, group) <= sh.LDS_MAX), (hs, kvmul, group)
+            assert sh.bd_group(hs, kvmul) == (kvmul if kvmul <= 8 and admitted_group else 1), (hs, kvmul)
+            for head_kernel in (True, False):
+                for attn_mid in (768, 0):
+                    for pos in (0, 127, 128, 767, 768, 1030):
+                        case = (hs, kvmul, pos, head_kernel, attn_mid)
+                        code, launches, _ = library_plan(hs, kvmul, pos, head_kernel, attn_mid)
+                        want = sh.decode_regime(hs, kvmul, pos, head_kernel, attn_mid)
+                        assert REGIME_OF[tuple(k[0] for k in launches)] == want and code == REGIME_CODE[want], case
+                        for kernel, gx, gy, block, lds, cap in launches:
+                            assert 0 <= lds <= cap and gx >= 1 and gy >= 1 and 64 <= block <= 1024, (case, kernel)
+                            if kernel == SCORES:
+                                assert lds == sh.scores_kernel_lds(hs, kvmul), case
+                            if kernel == HEAD:
+                                assert lds == sh.attn_head_smem(hs) and cap == sh.LDS_MAX, case
+    # the largest softmax window (16384 positions of a longer context) stays within attn_softmax_pv_kernel's cap
+    _, launches, _ = library_plan(128, 4, 200, ctx=20000, window=16384)
+    (pv,) = [k for k in launches if k[0] == SOFTMAX_PV]
+    assert pv[4] == (16384 + sh.PV_ROWS * 16) * 4 == 131072 and pv[4] <= pv[5]

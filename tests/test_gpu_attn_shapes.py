@@ -11,7 +11,7 @@ where that tap tells the forms apart (batched and mixed steps, prefill chunks). 
                                                            otherwise attn_scores_kernel; then attn_exp_kernel, attn_sum_kernel (att_t in
                                                            [kv head][head quad][t][4] order) and attn_pv_kernel (ceil(kvMul / 4) head quads)
 
-(gl3_api.hip: attn_mode, launch_attention), so a decode step at position p of shape s runs the kernels decode_regime(hs, kvMul, p) names — the
+(csrc/gl3_decode_attn.h: attn_regime, attn_plan; tests/test_attn_shapes.py holds decode_regime equal to it), so a decode step at position p of shape s runs the kernels decode_regime(hs, kvMul, p) names — the
 positions of the walk meet every regime a shape has (tests/test_attn_shapes.py)."""
 import os
 

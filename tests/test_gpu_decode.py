@@ -271,6 +271,34 @@ def test_fused_short_context_attention_and_the_handover_at_128(pkg, orc, planmod
     plan.freeTornadoExecutionPlan(); plain.freeTornadoExecutionPlan(); deep.freeTornadoExecutionPlan()
 
 
+def test_attention_sweeps_of_the_profiler_in_every_regime(pkg, orc, planmod):
+    """gl3_profile_kernel's two attention classes — the whole attention of a step (`attention`) and the part behind the scores (`other`) — at a
+    position of each regime: 5 (attn_head_kernel; `other` runs attn_softmax_pv_kernel there), 200 (the two-launch pair) and 800 (four launches).
+    Both return GL3_OK and a finite positive time, and the decode step after them equals the oracle.  That step repeats the position: the
+    sweeps run every layer on the last layer's qkv, so they leave that position's K / V rows wrong in the other layers until a step writes them."""
+    import attn_shapes as sh
+    plan_mod, hip = planmod
+    base = pkg.synth.CONFIGS["tiny-llama"]
+    m = pkg.synth.make_numpy(pkg.synth.ModelConfig(**{**base.__dict__, "ctx": 1100}), seed=37)
+    at = (5, 200, 800)
+    assert [sh.decode_regime(base.head_size, base.n_heads // base.n_kv_heads, p) for p in at] == ["head", "pair", "long-tile"]
+    plan = plan_mod.HipMasterPlan.initializeTornadoVMPlan(m, prefill_batch_size=256)
+    o = orc.COracle(m)
+    toks = pkg.javarand.bench_tokens(m.cfg.vocab, 801)
+    for p0 in range(0, 800, 256):
+        plan.tornadoVMForwardBatchPrefill(toks[p0:min(p0 + 256, 800)], p0)
+    o.prefill(toks[:800], 0)
+    for pos in at:                                        # a row is a function of the tokens up to it: a step at a shallower position rewrites it unchanged
+        ref = o.forward(toks[pos], pos)
+        assert np.array_equal(plan.forward_decode(toks[pos], pos), ref), pos
+        for klass in ("attention", "other"):
+            us = plan.profile_kernel(klass, iters=2)["avg_us"]
+            assert np.isfinite(us) and us > 0, (pos, klass, us)
+        got = plan.forward_decode(toks[pos], pos)
+        assert np.array_equal(got, ref), (pos, rel(got, ref))
+    plan.freeTornadoExecutionPlan()
+
+
 def test_sequential_prefill_then_decode(pkg, orc, planmod):
     plan_mod, hip = planmod
     m = pkg.synth.make_numpy(pkg.synth.CONFIGS["tiny-llama"], seed=7)

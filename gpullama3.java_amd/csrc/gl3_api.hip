@@ -824,6 +824,7 @@ void gl3_destroy(gl3_ctx* ctx) {
     gl3_prefill_free(ctx);
     gl3_sample_free(ctx);
     gl3_score_free(ctx);
+    gl3_verify_free(ctx);
     for (auto e : ctx->ev) hipEventDestroy(e);
     auto f = [](void* p) { if (p) hipFree(p); };
     f(ctx->emb.w);
@@ -1302,6 +1303,56 @@ int32_t gl3_score_rows(gl3_ctx* ctx, const float* logits, int32_t n, const int32
     const float* logits_dev; const int32_t* greedy;
     gl3_decode_batch_outputs(ctx, &logits_dev, &greedy);
     return gl3_score_finish(ctx, logits_dev, n, scores_out);
+}
+
+// The mixed step with every row an output row + verify_runs_kernel over its runs (gl3_sample.hip).  A step whose runs are all single rows
+// (nothing drafted) is a static-batched decode step, captured graph and all, as in gl3_forward_batch.
+int32_t gl3_forward_batch_verify(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const float* temperature,
+                                 const float* coins, gl3_verify_result* results_out, int32_t* n_runs_out) {
+    if (!ctx) return GL3_E_ARG;
+    BatchPlan bp;
+    // every row is an output row; check_mixed refuses n > max_batch before the plan looks at a flag, so max_batch flags are enough
+    const std::vector<int8_t> every((size_t)std::max(ctx->d.max_batch, 1), 1);
+    int32_t r = check_mixed(ctx, tokens, seq_ids, positions, every.data(), n, bp);
+    if (r != GL3_OK) return r;
+    if (!results_out || !n_runs_out) GL3_FAIL(GL3_E_ARG, "null results_out / n_runs_out");
+    const int n_runs = (int)bp.runs.size();
+    std::vector<int32_t> row0((size_t)n_runs), rows((size_t)n_runs);
+    for (int k = 0; k < n_runs; ++k) { row0[k] = bp.runs[k].row0; rows[k] = bp.runs[k].rows; }
+    if ((r = gl3_verify_prepare(ctx, n, tokens, coins, n_runs, row0.data(), rows.data(), temperature)) != GL3_OK) return r;
+    r = bp.single_rows ? gl3_decode_batch_run(ctx, tokens, seq_ids, positions, n, nullptr, nullptr, false)
+                       : gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, nullptr, false);
+    if (r != GL3_OK) return r;
+    const float* logits; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits, &greedy);
+    if ((r = gl3_verify_enqueue(ctx, logits, greedy, n_runs)) != GL3_OK) return r;
+    if (bp.single_rows && (r = gl3_prefill_tap_x(ctx, n - 1, n)) != GL3_OK) return r;      // gl3_get_x answers for the last row, as after every mixed step
+    if ((r = gl3_verify_collect(ctx, n_runs, results_out)) != GL3_OK) return r;
+    *n_runs_out = n_runs;
+    return GL3_OK;
+}
+
+int32_t gl3_verify_rows(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs, const float* temperature,
+                        const float* coins, gl3_verify_result* results_out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!logits || !tokens || !run_rows || !results_out || n_runs <= 0) GL3_FAIL(GL3_E_ARG, "bad logits / tokens / run_rows / results_out arrays");
+    int32_t r = check_batch_sampler(ctx);
+    if (r != GL3_OK) return r;
+    std::vector<int32_t> row0((size_t)n_runs);
+    int64_t n = 0;
+    for (int k = 0; k < n_runs; ++k) {
+        if (run_rows[k] < 1) GL3_FAIL(GL3_E_ARG, "a run has at least one row");
+        row0[k] = (int32_t)n;
+        if ((n += run_rows[k]) > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
+    }
+    for (int i = 0; i < (int)n; ++i)
+        if (tokens[i] < 0 || tokens[i] >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
+    if ((r = gl3_verify_prepare(ctx, (int32_t)n, tokens, coins, n_runs, row0.data(), run_rows, temperature)) != GL3_OK) return r;
+    if ((r = gl3_decode_batch_load_logits(ctx, logits, (int32_t)n)) != GL3_OK) return r;
+    const float* logits_dev; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits_dev, &greedy);
+    if ((r = gl3_verify_enqueue(ctx, logits_dev, greedy, n_runs)) != GL3_OK) return r;
+    return gl3_verify_collect(ctx, n_runs, results_out);
 }
 
 int32_t gl3_debug_batch_plan(const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits, int32_t n, int32_t n_seqs, int32_t ctx_len,

@@ -169,6 +169,18 @@ struct gl3_score_state {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // GL3_SCORE_TIMING=1 only
 };
 
+// Draft verification (verify_runs_kernel, gl3_sample.hip): a run and a row of the step as the kernel reads them.  A row's token is the
+// draft of the row before it in its run; accept / emit are the caller's two coins of the row (not looked at on a greedy run).
+struct VerifyRun { int row0, rows; float temperature; int pad; };
+struct VerifyRow { int token; float accept, emit; int pad; };
+struct gl3_verify_state {
+    int cap = 0;                               // rows (and so runs) every buffer below has room for: the plan's max_batch
+    uint8_t* params = nullptr;                 // a step's VerifyRun[n_runs], then its VerifyRow[n]; room for cap of each
+    uint8_t* h_params = nullptr;               // pinned, same layout
+    gl3_verify_result* out = nullptr;          // [cap]
+    gl3_verify_result* h_out = nullptr;        // pinned
+};
+
 struct gl3_ctx {
     gl3_model_desc d{};
     // derived (local = this tensor-parallel rank's share)
@@ -218,6 +230,7 @@ struct gl3_ctx {
     gl3_sample_state smp_one{256, false};         // gl3_forward_decode_sample: one row, eager launches
     gl3_sample_state smp_rows{64, true};          // static-batched entries: grows with the batch, one hipGraph per (rows, any top-p row)
     gl3_score_state score;                        // gl3_forward_batch_score / gl3_score_rows
+    gl3_verify_state verify;                      // gl3_forward_batch_verify / gl3_verify_rows
     std::vector<std::pair<void*, size_t>> pinned;     // caller buffers registered with gl3_pin_host_buffer (logits land there directly)
     // upload staging
     uint8_t* staging = nullptr;
@@ -305,6 +318,14 @@ int32_t gl3_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);
 int32_t gl3_score_prepare(gl3_ctx* ctx, int32_t n, const int32_t* targets, const float* temperature);
 int32_t gl3_score_finish(gl3_ctx* ctx, const float* logits_dev, int32_t n, gl3_token_score* scores_out);
 void gl3_score_free(gl3_ctx* ctx);
+// draft verification: prepare = every check on (temperature, coins) + stage the runs and rows (before the step is enqueued): tokens /
+// coins ([n][2] or NULL) by row, run_row0 / run_rows / temperature (NULL: greedy everywhere) by run; enqueue = verify_runs_kernel and the
+// copy of 8 * n_runs bytes behind the step on the plan's stream; collect = wait and hand the records out
+int32_t gl3_verify_prepare(gl3_ctx* ctx, int32_t n, const int32_t* tokens, const float* coins, int32_t n_runs, const int32_t* run_row0,
+                           const int32_t* run_rows, const float* temperature);
+int32_t gl3_verify_enqueue(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n_runs);
+int32_t gl3_verify_collect(gl3_ctx* ctx, int32_t n_runs, gl3_verify_result* results_out);
+void gl3_verify_free(gl3_ctx* ctx);
 
 // gl3_prefill.hip
 float* gl3_prefill_buf(gl3_ctx* ctx, int which);

@@ -482,6 +482,152 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------------ draft verification
+// gl3_forward_batch_verify / gl3_verify_rows: how many drafted tokens of a run stand and which token follows them.  One launch, one
+// workgroup per RUN (runs are the grid), the run's and its rows' settings read from device memory (VerifyRun, VerifyRow); 8 bytes per run
+// come back.  In a run of m rows, row i predicts the token after its own, so its draft is d = the token of row i + 1; the last row has none.
+//   greedy run (temperature 0)  one thread walks the step's own greedy ids (pf_argmax_*): a = the leading rows whose greedy id equals
+//                               their draft, token = the greedy id of row a.  Nothing of the logits is read.
+//   sampled run                 rows in order, stopping at the first rejection, so a row behind it is never exponentiated.  Per row the two
+//                               passes of score_rows_kernel — the maximum, then SM_CHUNK numerators (float) exp((double) (l / T - max)) at a
+//                               time through LDS into the strictly sequential f32 sum — give p[d] = e[d] / sum, bit for bit
+//                               gl3_token_score.prob; the row accepts iff its accept coin < p[d].  The row a that rejects (or row m - 1,
+//                               which has no draft) then emits: q = e / sum with q[d] = 0f, chunk by chunk into the sequential sum S' whose
+//                               value after every chunk stays in LDS; r = emit coin * S' (no draft: q = p and r = the coin, which is
+//                               CategoricalSampler, so the walk stops at the first chunk whose end exceeds the coin); the first chunk whose
+//                               end exceeds r is recomputed and one thread walks its cdf from the chunk's exact start to the first j
+//                               with r < cdf.  q[d] = 0 leaves the cdf at d where it was at d - 1, so d is never that j.  No chunk end above
+//                               r: the largest index other than d ("in case of rounding errors", CategoricalSampler.java:43).
+// Numerators are recomputed where they are needed a second time (one row and one chunk per run) instead of kept: no [rows][vocab] buffer
+// exists beside the logits, which are read, never written.  n % 4 == 0 as in score_rows_kernel.
+// LDS, all dynamic: xf [SM_CHUNK + 32], the scratch of exact_seqsum_lds, sh [8] ([0..3] wavefront maxima, [4] running sum, [5] numerator
+// of the draft, [6] accept flag / hit chunk), cend [nchunks].
+// The strictly sequential f32 sum of the LDS chunk xf[0 .. len) (all >= 0, zeros behind it up to SM_CHUNK + 32) continued from the exact
+// running value `run`: the exact parallel evaluation (gl3_seqsum.h) for >= 1024 elements (a multiple of 4), the naive chain for a
+// shorter chunk and for up to 3 trailing elements.  All 256 threads call it between two barriers; thread 0 holds the result.  (The split of
+// bsm_seqsum_kernel, btp_pick_kernel and score_rows_kernel, which keep their own copies.)
+__device__ __forceinline__ float chunk_seqsum(const float* xf, int len, uint8_t* scratch, int t, float run) {
+    const int n4 = len & ~3;
+    if (n4 >= 1024) {
+        BlockBarrier bb;
+        run = exact_seqsum_lds<false>(xf, n4, scratch, t, bb, run);
+        if (n4 < len && t < 64) run = naive_sumsq_lds<false>(xf, n4, len, run);
+    } else if (t < 64) {
+        run = naive_sumsq_lds<false>(xf, 0, len, run);
+    }
+    return run;
+}
+
+template <bool EMIT>
+__device__ __forceinline__ void verify_fill_chunk(float* xf, const float4* lg4, int base, int len, float T, float mx, float sum, int d, int t) {
+    for (int i = 4 * t; i < SM_CHUNK + 32; i += 1024) {
+        float4 e = {0.f, 0.f, 0.f, 0.f};                              // zero padding behind the chunk (exact_seqsum_lds reads it)
+        if (i < len) {
+            const float4 v = lg4[(base + i) >> 2];
+            e.x = (float)exp((double)(v.x / T - mx));                // (float) Math.exp(f - maxVal)
+            e.y = (float)exp((double)(v.y / T - mx));
+            e.z = (float)exp((double)(v.z / T - mx));
+            e.w = (float)exp((double)(v.w / T - mx));
+            if (EMIT) {
+                const int j = base + i;
+                e.x = j == d ? 0.f : e.x / sum;                       // divideInPlace(sum); the rejected draft cannot be drawn again
+                e.y = j + 1 == d ? 0.f : e.y / sum;
+                e.z = j + 2 == d ? 0.f : e.z / sum;
+                e.w = j + 3 == d ? 0.f : e.w / sum;
+            }
+        }
+        *reinterpret_cast<float4*>(xf + i) = e;
+    }
+}
+
+__global__ __launch_bounds__(256) void verify_runs_kernel(const float* __restrict__ logits, int n, const VerifyRun* __restrict__ runs, const VerifyRow* __restrict__ rows,
+                                                          const int32_t* __restrict__ greedy, gl3_verify_result* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    float* xf = reinterpret_cast<float*>(smem);                      // [SM_CHUNK + 32]
+    uint8_t* scratch = smem + (size_t)(SM_CHUNK + 32) * 4;
+    float* sh = reinterpret_cast<float*>(scratch + ss_scratch_bytes(SM_CHUNK));
+    float* cend = sh + 8;                                            // [nchunks] S' after every chunk of the emitting row
+    const VerifyRun R = runs[blockIdx.x];
+    const int t = threadIdx.x;
+    if (R.temperature == 0.f) {
+        if (t == 0) {
+            int a = 0;
+            while (a + 1 < R.rows && greedy[R.row0 + a] == rows[R.row0 + a + 1].token) ++a;
+            out[blockIdx.x] = gl3_verify_result{a, greedy[R.row0 + a]};
+        }
+        return;
+    }
+    const float T = R.temperature;
+    const int nchunks = (n + SM_CHUNK - 1) / SM_CHUNK;
+    for (int a = 0; a < R.rows; ++a) {
+        const int row = R.row0 + a;
+        const int d = a + 1 < R.rows ? rows[row + 1].token : -1;
+        const float4* lg4 = reinterpret_cast<const float4*>(logits + (size_t)row * n);
+        float mx = -INFINITY;
+        for (int i = t; i < (n >> 2); i += 256) {
+            const float4 v = lg4[i];
+            mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+        }
+        mx = wave_max(mx);
+        if ((t & 63) == 0) sh[t >> 6] = mx;
+        if (t == 0) { sh[4] = 0.f; sh[5] = 0.f; }
+        __syncthreads();
+        mx = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3])) / T;      // divideInPlace(temperature), then max (score_rows_kernel)
+        for (int c = 0; c < nchunks; ++c) {
+            const int base = c * SM_CHUNK, len = min(SM_CHUNK, n - base);
+            verify_fill_chunk<false>(xf, lg4, base, len, T, mx, 0.f, -1, t);
+            __syncthreads();
+            const float run = chunk_seqsum(xf, len, scratch, t, sh[4]);
+            __syncthreads();
+            if (t == 0) {
+                sh[4] = run;
+                if (d >= base && d < base + len) sh[5] = xf[d - base];
+            }
+            __syncthreads();
+        }
+        const float sum = sh[4];
+        if (t == 0) sh[6] = d >= 0 && rows[row].accept < sh[5] / sum ? 1.f : 0.f;      // accept iff coin < p[d], strictly
+        __syncthreads();
+        if (sh[6] != 0.f) continue;      // every thread read `sum` and the flag; the next row writes sh[4..6] behind barriers of its own
+        // ---- row a emits
+        const float coin = rows[row].emit;
+        if (t == 0) sh[4] = 0.f;
+        __syncthreads();
+        int walked = 0;
+        for (int c = 0; c < nchunks; ++c) {
+            const int base = c * SM_CHUNK, len = min(SM_CHUNK, n - base);
+            verify_fill_chunk<true>(xf, lg4, base, len, T, mx, sum, d, t);
+            __syncthreads();
+            const float run = chunk_seqsum(xf, len, scratch, t, sh[4]);
+            __syncthreads();
+            if (t == 0) { sh[4] = run; cend[c] = run; }
+            __syncthreads();
+            walked = c + 1;
+            if (d < 0 && coin < sh[4]) break;                          // no draft: the cdf of p itself, the first chunk whose end exceeds the coin
+        }
+        const float r = d >= 0 ? coin * sh[4] : coin;                  // coin * S'
+        if (t == 0) {
+            int hit = -1;
+            for (int c = 0; c < walked; ++c) if (r < cend[c]) { hit = c; break; }      // the cdf is non-decreasing
+            sh[6] = (float)hit;
+        }
+        __syncthreads();
+        const int hit = (int)sh[6];
+        int token = d == n - 1 ? n - 2 : n - 1;                        // no j with r < cdf_j: the largest index other than d
+        if (hit >= 0) {
+            const int base = hit * SM_CHUNK, len = min(SM_CHUNK, n - base);
+            verify_fill_chunk<true>(xf, lg4, base, len, T, mx, sum, d, t);
+            __syncthreads();
+            if (t == 0) {
+                float cdf = hit ? cend[hit - 1] : 0.f;
+                for (int i = 0; i < len; ++i) { cdf = cdf + xf[i]; if (r < cdf) { token = base + i; break; } }
+            }
+        }
+        if (t == 0) out[blockIdx.x] = gl3_verify_result{a, token};
+        return;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static void sample_drop_graphs(gl3_sample_state* b) {
     for (auto& ge : b->graphs) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }
@@ -715,5 +861,65 @@ int32_t gl3_score_finish(gl3_ctx* ctx, const float* logits_dev, int32_t n, gl3_t
         fprintf(stderr, "gl3 score_rows_kernel rows %d: %.1f us\n", n, ms * 1e3);
     }
     memcpy(scores_out, b->h_out, (size_t)n * sizeof(gl3_token_score));
+    return GL3_OK;
+}
+
+// ---- draft verification: prepare = every check + stage the runs and rows (before the step is enqueued), enqueue = the one launch behind
+// the step on the plan's stream and the copy of 8 * n_runs bytes, collect = wait for both
+void gl3_verify_free(gl3_ctx* ctx) {
+    gl3_verify_state* b = &ctx->verify;
+    if (b->params) hipFree(b->params);
+    if (b->out) hipFree(b->out);
+    if (b->h_params) hipHostFree(b->h_params);
+    if (b->h_out) hipHostFree(b->h_out);
+    *b = gl3_verify_state{};
+}
+
+int32_t gl3_verify_prepare(gl3_ctx* ctx, int32_t n, const int32_t* tokens, const float* coins, int32_t n_runs, const int32_t* run_row0,
+                           const int32_t* run_rows, const float* temperature) {
+    gl3_verify_state* b = &ctx->verify;
+    for (int k = 0; k < n_runs; ++k) {
+        const float T = temperature ? temperature[k] : 0.f;
+        if (!(T >= 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be >= 0");
+        if (T == 0.f) continue;                                       // greedy: the run's coins are not looked at
+        if (!coins) GL3_FAIL(GL3_E_ARG, "null coins with a run at a temperature > 0");
+        for (int i = 2 * run_row0[k]; i < 2 * (run_row0[k] + run_rows[k]); ++i)
+            if (!(coins[i] >= 0.f && coins[i] < 1.f)) GL3_FAIL(GL3_E_ARG, "coin must be rng.nextFloat(1f): in [0, 1)");
+    }
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    if (!b->cap) {      // once, for the largest step the plan takes (a run has at least one row); all or none, as sample_alloc
+        const size_t cap = (size_t)ctx->d.max_batch, bytes = cap * (sizeof(VerifyRun) + sizeof(VerifyRow));
+        hipError_t e = hipMalloc((void**)&b->params, bytes);
+        if (e == hipSuccess) e = hipMalloc((void**)&b->out, cap * sizeof(gl3_verify_result));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_params, bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_out, cap * sizeof(gl3_verify_result));
+        if (e != hipSuccess) { gl3_verify_free(ctx); GL3_HIP(e); }
+        b->cap = (int)cap;
+    }
+    VerifyRun* hr = reinterpret_cast<VerifyRun*>(b->h_params);      // the n rows lie right behind the n_runs runs: one copy of what the step uses
+    VerifyRow* hw = reinterpret_cast<VerifyRow*>(b->h_params + (size_t)n_runs * sizeof(VerifyRun));
+    for (int k = 0; k < n_runs; ++k) hr[k] = VerifyRun{run_row0[k], run_rows[k], temperature ? temperature[k] : 0.f, 0};
+    for (int i = 0; i < n; ++i) hw[i] = VerifyRow{tokens[i], coins ? coins[2 * i] : 0.f, coins ? coins[2 * i + 1] : 0.f, 0};
+    GL3_HIP(hipMemcpyAsync(b->params, b->h_params, (size_t)n_runs * sizeof(VerifyRun) + (size_t)n * sizeof(VerifyRow), hipMemcpyHostToDevice, ctx->stream));
+    return GL3_OK;
+}
+
+int32_t gl3_verify_enqueue(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n_runs) {
+    gl3_verify_state* b = &ctx->verify;
+    hipStream_t s = ctx->stream;
+    const int v = ctx->d.vocab, nchunks = (v + SM_CHUNK - 1) / SM_CHUNK;
+    const size_t smem = (size_t)(SM_CHUNK + 32) * 4 + ss_scratch_bytes(SM_CHUNK) + 32 + (size_t)nchunks * 4;
+    hipLaunchKernelGGL(verify_runs_kernel, dim3(n_runs), dim3(256), smem, s, logits_dev, v, reinterpret_cast<const VerifyRun*>(b->params),
+                       reinterpret_cast<const VerifyRow*>(b->params + (size_t)n_runs * sizeof(VerifyRun)), greedy_dev, b->out);
+    GL3_HIP(hipGetLastError());
+    GL3_HIP(hipMemcpyAsync(b->h_out, b->out, (size_t)n_runs * sizeof(gl3_verify_result), hipMemcpyDeviceToHost, s));
+    return GL3_OK;
+}
+
+int32_t gl3_verify_collect(gl3_ctx* ctx, int32_t n_runs, gl3_verify_result* results_out) {
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
+    const int32_t r = gl3_tp_check(ctx);
+    if (r != GL3_OK) return r;
+    memcpy(results_out, ctx->verify.h_out, (size_t)n_runs * sizeof(gl3_verify_result));
     return GL3_OK;
 }

@@ -30,6 +30,8 @@ def _p(a: np.ndarray):
 
 # gl3_token_score (include/gpullama3_hip.h): 16 bytes per row
 SCORE_DTYPE = np.dtype([("prob", np.float32), ("logit", np.float32), ("max", np.float32), ("sum", np.float32)])
+# gl3_verify_result: 8 bytes per run
+VERIFY_DTYPE = np.dtype([("accepted", np.int32), ("token", np.int32)])
 
 
 class HipMasterPlan:
@@ -272,6 +274,39 @@ class HipMasterPlan:
         hip.check(hip.lib().gl3_score_rows(self._ctx, _p(lg), n, _p(tg) if tg is not None else None, _p(te) if te is not None else None,
                                            _p(scores)), self._ctx)
         return scores
+
+    @staticmethod
+    def _verify_args(temperature, coins, n_runs, n):
+        """temperature f32[n_runs] (a scalar broadcasts) or None = greedy everywhere, coins f32[n][2] or None"""
+        te = HipMasterPlan._per_row(temperature, n_runs) if temperature is not None else None
+        co = np.ascontiguousarray(coins, np.float32) if coins is not None else None
+        assert co is None or co.shape == (n, 2)
+        return te, co
+
+    def forward_batch_verify(self, tokens, seq_ids, positions, temperature=None, coins=None) -> np.ndarray:
+        """Mixed batched step over runs [last real token, drafts ...] + the decision on the device how many drafts of every run stand
+        (gl3_forward_batch_verify) -> structured array [n_runs] with fields accepted and token.  temperature: one entry per run (a scalar
+        broadcasts), None = greedy everywhere; coins [n][2]: the accept and the emit coin of every row, None when every run is greedy."""
+        t, s, p, _, n_runs = self._mixed_args(tokens, seq_ids, positions, None)
+        te, co = self._verify_args(temperature, coins, n_runs, t.size)
+        res = np.zeros(max(t.size, 1), VERIFY_DTYPE)
+        got = C.c_int32(0)
+        hip.check(hip.lib().gl3_forward_batch_verify(self._ctx, _p(t), _p(s), _p(p), t.size, _p(te) if te is not None else None,
+                                                     _p(co) if co is not None else None, _p(res), C.byref(got)), self._ctx)
+        return res[:got.value].copy()
+
+    def verify_rows(self, logits, tokens, run_rows, temperature=None, coins=None) -> np.ndarray:
+        """The verification kernel alone on host logits [n][vocab] (no forward pass); run_rows: the rows of every run, summing to n ->
+        structured array [n_runs] with fields accepted and token."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2 and lg.shape[1] == self.cfg.vocab
+        t = np.ascontiguousarray(tokens, np.int32); rr = np.ascontiguousarray(run_rows, np.int32)
+        assert t.size == lg.shape[0] == int(rr.sum())      # the C entry takes its row count from run_rows: it cannot see a mismatch
+        te, co = self._verify_args(temperature, coins, rr.size, t.size)
+        res = np.zeros(rr.size, VERIFY_DTYPE)
+        hip.check(hip.lib().gl3_verify_rows(self._ctx, _p(lg), _p(t), _p(rr), rr.size, _p(te) if te is not None else None,
+                                            _p(co) if co is not None else None, _p(res)), self._ctx)
+        return res
 
     def sample_probs_row(self, row: int) -> np.ndarray:
         """The probabilities row `row` of the last batched sampled step was drawn from."""

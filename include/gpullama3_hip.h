@@ -323,6 +323,41 @@ GL3_API int32_t gl3_forward_batch_score(gl3_ctx* ctx, const int32_t* tokens, con
  * max_batch > 1; n <= max_batch.  The logits buffer of the batched step is overwritten.  Errors as above. */
 GL3_API int32_t gl3_score_rows(gl3_ctx* ctx, const float* logits, int32_t n, const int32_t* targets, const float* temperature,
                                gl3_token_score* scores_out);
+/* Speculative decoding: the step of gl3_forward_batch over runs that carry DRAFTED tokens, and the decision, taken on the device, how many
+ * drafts of every run stand and which token follows them.  The rows are the runs of gl3_forward_batch, with the same rules and the same
+ * refusals; every row is an output row.  In a run of m rows with tokens t0 .. t(m-1), t0 is the sequence's last real token and t1 .. t(m-1)
+ * are drafts: row i predicts the token after ti, so its draft is d = t(i+1); the last row has none.  results_out: one record per run, in run
+ * order (*n_runs_out of them; room for n is always enough): accepted = a, the number of leading rows whose draft stands, token = the token
+ * that follows them.  The sequence then continues with t1 .. ta, token.  8 * n_runs bytes come back in one copy; no logits leave the device.
+ * temperature: f32[n_runs], or NULL for greedy everywhere.
+ *   Greedy run (temperature 0): row i accepts iff its greedy id (the first index of the maximum, from the step's own greedy scan) equals d;
+ *   token = the greedy id of row a.  The ids a caller collects this way are those of decoding one token per step.
+ *   Sampled run (T > 0): coins: f32[n][2] drawn by the CALLER from the sequence's own generator, each in [0, 1) — coins[i][0] the accept
+ *   coin of row i, coins[i][1] its emit coin (the library holds no RNG; coins of greedy runs are not looked at, and coins may be NULL when
+ *   every run is greedy).  With p = softmaxInPlace(logits row / T) in the arithmetic of gl3_token_score (p[d] is bit for bit its prob), row
+ *   i accepts iff coins[i][0] < p[d], strictly.  At the first rejecting row a: q = p with q[d] = 0f, S' = the strictly sequential f32 sum of
+ *   q, r = coins[a][1] * S', token = the first j with r < cdf_j (cdf = the sequential f32 sum of q), or the largest index other than d if
+ *   there is none.  If all m - 1 drafts stand, a = m - 1 and token is CategoricalSampler on row m - 1 with the coin coins[m-1][1]: what
+ *   gl3_forward_batch_sample gives that row with topp = 0.  For a draft that is a fixed token this is the speculative-sampling rule with a
+ *   one-hot draft distribution, lossless in distribution: P(first emitted = x) = p(d) [x = d] + (1 - p(d)) q(x) / S' = p(x).  There is no
+ *   top-p here.
+ * KV: the step writes the K / V rows of all m positions of a run that starts at position p.  The rows above position p + a belong to rejected
+ * drafts; the caller's next run on that sequence starts at p + a + 1 and overwrites them before anything reads them, since a row sees the
+ * rows below its position plus its own.  Nothing has to be rolled back.
+ * The decision is one launch behind the step whatever n and the number of runs (gl3_sample.hip).  gl3_get_x and the step buffers answer as
+ * after the gl3_forward_batch step over the same rows.  GL3_E_ARG, before anything is enqueued: everything gl3_forward_batch refuses, NULL
+ * results_out or n_runs_out, a temperature that is negative or NaN, coins == NULL while some run has T > 0, a coin outside [0, 1) on a run
+ * with T > 0.  GL3_E_UNSUPPORTED: max_batch <= 1, tp_size > 1. */
+typedef struct { int32_t accepted, token; } gl3_verify_result;
+GL3_API int32_t gl3_forward_batch_verify(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
+                                         const float* temperature, const float* coins, gl3_verify_result* results_out,
+                                         int32_t* n_runs_out);
+/* Parity tap: the same decision on caller-supplied logits (host f32[n][vocab]); no forward pass, no KV change.  run_rows: int32[n_runs], the
+ * rows of every run, each >= 1, summing to n <= max_batch (the entry has no other row count: logits and tokens must hold that many rows);
+ * tokens: int32[n], each inside the vocabulary.  The logits buffer of the batched
+ * step is overwritten.  Otherwise errors as above. */
+GL3_API int32_t gl3_verify_rows(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs,
+                                const float* temperature, const float* coins, gl3_verify_result* results_out);
 /* Test hook, no plan and no device: the host-side plan of a mixed step (csrc/gl3_batch_plan.h) for a plan with n_seqs sequence slots,
  * context length ctx and room for `capacity` rows.  runs_out / tiles_out: int32[.][4] = {first row, rows, sequence, position of the
  * first row}, room for n records each (tiles: at most 8 rows, never across a run boundary, deepest last position first); out_rows:

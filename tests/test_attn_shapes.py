@@ -108,3 +108,44 @@ def test_the_dispatch_rule_is_the_librarys_plan():
     _, launches, _ = library_plan(128, 4, 200, ctx=20000, window=16384)
     (pv,) = [k for k in launches if k[0] == SOFTMAX_PV]
     assert pv[4] == (16384 + sh.PV_ROWS * 16) * 4 == 131072 and pv[4] <= pv[5]
+
+
+def test_the_tensor_parallel_depth_schedules_hit_what_they_claim(pkg):
+    """tests/tp_depth.py: every position a row-split rank decodes in tests/test_gpu_tp.py falls in the regime its case intends, on the rank's own
+    heads_l / kv_heads_l and under the case's switches, by the library's plan and by the dispatch rule of tests/attn_shapes.py alike; the plan's last
+    launch there is the kernel meant to hand xb to the peers (attn_head_kernel 0, attn_softmax_pv_kernel 3, attn_pv_kernel 6), and each of the three
+    is that kernel at some position of at least three cases.  The main schedule crosses 128, 768 and PV_ROWS with steps on both sides."""
+    import tp_depth as td
+    producer_cases = {HEAD: set(), SOFTMAX_PV: set(), PV: set()}
+    for name, case in td.CASES.items():
+        c = pkg.synth.CONFIGS[case.cfg]
+        assert c.n_heads % case.tp == 0 and c.n_kv_heads % case.tp == 0, name
+        hs, kvmul, kv_heads_l = c.head_size, c.n_heads // c.n_kv_heads, c.n_kv_heads // case.tp
+        head_kernel, attn_mid, window = td.plan_switches(case)
+        pos = td.positions(case.schedule)
+        assert pos == sorted(set(pos)) and case.schedule.prefill <= min(pos) and max(pos) < case.schedule.ctx, name
+        assert sorted(p for lo, hi, _ in case.intent for p in range(lo, hi + 1)) == pos, name       # the intent names every position once
+        for p in pos:
+            want = td.intended(case, p)
+            code, launches, _ = library_plan(hs, kvmul, p, head_kernel, attn_mid, ctx=case.schedule.ctx, window=window, kv_heads=kv_heads_l)
+            kernels = tuple(k[0] for k in launches)
+            assert REGIME_OF[kernels] == want and code == REGIME_CODE[want], (name, p, kernels)
+            assert sh.decode_regime(hs, kvmul, p, head_kernel, attn_mid) == want, (name, p)
+            assert kernels[-1] == td.PRODUCER[want], (name, p, kernels)
+            kernel, gx, gy = launches[-1][:3]
+            heads_l = kvmul * kv_heads_l
+            assert (gx, gy) == {HEAD: (heads_l, 1), SOFTMAX_PV: (heads_l * (hs // 16), 1), PV: (kv_heads_l * ((kvmul + sh.PV_G - 1) // sh.PV_G) * (hs // 16), 1)}[kernel], (name, p)
+            producer_cases[kernel].add(name)
+        if window is not None:                                      # the windowed form: rows longer than the window
+            assert min(pos) + 1 < window < max(pos) + 1 and {td.intended(case, p) for p in pos} == {"pair"}, name
+    assert all(len(v) >= 3 for v in producer_cases.values()), producer_cases
+    m = td.MAIN
+    at = set(td.positions(m))
+    assert {127, 128, 767, 768, sh.PV_ROWS - 1, sh.PV_ROWS} <= at and set(range(m.prefill, 132)) <= at and td.chunks(m) == [64, 56]
+    assert set(td.BOUNDARY_ROWS) <= set(td.kv_rows(m))
+    # kvMul 6: the second head quad of attn_pv_kernel holds two heads of four; one kv head per rank in two cases; four ranks once, as a child process
+    q2 = pkg.synth.CONFIGS["mid-qwen2"]
+    assert q2.n_heads // q2.n_kv_heads == 6 and q2.n_kv_heads // 2 == 1 and pkg.synth.CONFIGS["tiny-llama"].n_kv_heads // 2 == 1
+    assert [n for n, cs in td.CASES.items() if cs.tp > 2] == [n for n, cs in td.CASES.items() if cs.child] == ["mid-llama-q8-tp4"]
+    assert {(cs.cfg, cs.wtype) for cs in td.CASES.values()} >= {("tiny-llama", 8), ("mid-llama", 8), ("mid-qwen3", 8), ("mid-qwen2", 8), ("mid-llama", 2), ("mid-llama", 1)}
+    assert [n for n, cs in td.CASES.items() if cs.fold[0] == 0] == ["tiny-llama-gather"] and td.CASES["tiny-llama-gather"].schedule == td.CASES["tiny-llama-q8"].schedule

@@ -374,3 +374,245 @@ def test_peer_write_transport_between_processes(pkg, orc, cfg, world, wtype, f32
         for i in range(7):
             assert np.array_equal(got[r][0][i], ref[i]), (r, i)
         assert got[r][1][0] == orc.argmax(ref[6])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Row-split ranks at depth: the decode attention regimes behind position 128 and 768 (whose kernels hand xb to the peers themselves under folded
+# gathers), prefill chunks that start deep in the context, and the prefix fork.  Schedules and what each is meant to run: tests/tp_depth.py,
+# checked against the library's plan without a GPU by tests/test_attn_shapes.py.
+def run_ranks(planmod, tp, make_plan, body, env=None, timeout=300):
+    """Start tp rank threads, join them within `timeout` seconds in all, collect results and errors, destroy the group.  Rank r creates its plan
+    with make_plan(r, group), meets the others (and this thread) at a host-level barrier and returns body(r, plan); its plan is freed behind it.
+    `env` is set in os.environ only while the plans are being created (the switches are read in gl3_create / gl3_finalize).  -> [result of rank r]"""
+    import os, time
+    plan_mod, hip = planmod
+    grp = plan_mod.make_local_group(tp)
+    out, err = [None] * tp, [None] * tp
+    created = threading.Barrier(tp + 1)
+
+    def rank_main(r):
+        plan = None
+        try:
+            try:
+                plan = make_plan(r, grp)
+            except BaseException:
+                created.abort()
+                raise
+            created.wait()
+            created.wait()                                        # ... and goes on once the environment is back as it was
+            out[r] = body(r, plan)
+        except Exception as e:   # noqa: BLE001
+            err[r] = e
+        finally:
+            if plan is not None:
+                plan.freeTornadoExecutionPlan()
+
+    th = [threading.Thread(target=rank_main, args=(r,), daemon=True) for r in range(tp)]
+    deadline = time.monotonic() + timeout
+    saved = {k: os.environ.get(k) for k in (env or {})}
+
+    def meet():
+        try:
+            created.wait(max(0.0, deadline - time.monotonic()))
+        except threading.BrokenBarrierError:
+            pass                                                  # a rank failed to create its plan (err says why), or one did not arrive in time
+
+    os.environ.update(env or {})
+    try:
+        [t.start() for t in th]
+        meet()
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    meet()
+    [t.join(timeout=max(0.0, deadline - time.monotonic())) for t in th]
+    assert not any(t.is_alive() for t in th), "a rank is still running after %d s" % timeout      # (the group stays: that rank still uses it)
+    hip.lib().gl3_local_group_destroy(grp)
+    assert all(e is None for e in err), err
+    return out
+
+
+def model_at(pkg, cfg, ctx, wtype, seed):
+    base = pkg.synth.CONFIGS[cfg]
+    return pkg.synth.make_numpy(pkg.synth.ModelConfig(**{**base.__dict__, "ctx": ctx}), wtype=wtype, seed=seed)
+
+
+def kv_slices_equal(got, want, r, kvl):
+    (k, v), (ko, vo) = got, want
+    return np.array_equal(k, ko[r * kvl:(r + 1) * kvl]) and np.array_equal(v, vo[r * kvl:(r + 1) * kvl])
+
+
+_depth_refs = {}
+
+
+def depth_reference(pkg, orc, cfg, wtype, schedule):
+    """(model, tokens by position, {position: oracle logits}, {(layer, row): oracle K / V}) of a schedule; computed once per model and schedule"""
+    import tp_depth as td
+    key = (cfg, wtype, schedule)
+    if key not in _depth_refs:
+        m = model_at(pkg, cfg, schedule.ctx, wtype, seed=17)
+        o = orc.COracle(m, vector_bits=0 if wtype == 8 else 256)
+        toks = pkg.javarand.bench_tokens(m.cfg.vocab, schedule.ctx)
+        if schedule.prefill:
+            o.prefill(toks[:schedule.prefill], 0)
+        logits = {p: o.forward(toks[p], p) for p in td.positions(schedule)}
+        kv = {(l, p): o.kv(l, p) for l in range(m.cfg.n_layers) for p in td.kv_rows(schedule)}
+        assert all(ko.any() and vo.any() for ko, vo in kv.values())
+        _depth_refs[key] = (m, toks, logits, kv)
+    return _depth_refs[key]
+
+
+@pytest.mark.parametrize("name", ["tiny-llama-q8", "mid-llama-q8", "mid-qwen3-q8", "mid-qwen2-q8", "mid-llama-q4", "mid-llama-f16", "mid-llama-q8-eager",
+                                  "mid-llama-q8-tp4", "tiny-llama-nofused", "tiny-llama-window", "tiny-llama-mid0", "tiny-llama-gather"])
+def test_decode_attention_regimes_on_row_split_ranks(pkg, orc, planmod, name):
+    """A rank's decode steps on both sides of positions 128, 768 and 1024 (tests/tp_depth.py): with folded gathers the last attention kernel of a
+    step — attn_head_kernel below 128, attn_softmax_pv_kernel up to 767, attn_pv_kernel from 768 — stores xb into the peers' arenas and publishes
+    the flag, and the step goes from one regime's captured graph to the next with the step word and the ticket counters live.  Every rank's logits
+    at every step, its greedy id at the end of every stretch and its slice of the K / V rows at the hand-overs equal the oracle's; the fold mode
+    says which hand-over ran (tiny-llama-gather: the gather launches, as the control)."""
+    import tp_depth as td
+    plan_mod, hip = planmod
+    case = td.CASES[name]
+    sched = case.schedule
+    if case.child:
+        import os, subprocess, sys
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        r = subprocess.run([sys.executable, os.path.join(root, "scripts", "debug_tp_fold.py"), case.cfg, str(case.tp), "0", str(case.wtype), td.schedule_arg(sched)],
+                           env=dict(os.environ, **case.env), cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+        assert ("fold mode %d mask %d" % case.fold) in r.stdout, r.stdout[-1000:]
+        return
+    m, toks, ref, ref_kv = depth_reference(pkg, orc, case.cfg, case.wtype, sched)
+
+    def make_plan(r, grp):
+        return plan_mod.HipMasterPlan(m, prefill_batch_size=sched.batch, tp_rank=r, tp_size=case.tp, local_group=grp, flags=hip.FLAG_NO_GRAPH if case.no_graph else 0)
+
+    def body(r, plan):
+        pos = 0
+        for c in td.chunks(sched):
+            plan.tornadoVMForwardBatchPrefill(toks[pos:pos + c], pos)
+            pos += c
+        logits = {p: plan.forward_decode(toks[p], p) for p in td.positions(sched)}
+        ids = {hi: plan.forward_decode_argmax(toks[hi], hi) for _, hi in sched.stretches}      # the step repeated: it rewrites its K / V row with the same values
+        return plan.tp_fold_mode(), logits, ids, {key: plan.kv(*key) for key in ref_kv}
+
+    out = run_ranks(planmod, case.tp, make_plan, body, env=case.env)
+    kvl = m.cfg.kv_dim // case.tp
+    for r, (mode, logits, ids, kv) in enumerate(out):
+        assert mode == case.fold, (r, mode)
+        for p in td.positions(sched):
+            assert np.array_equal(logits[p], ref[p]), (r, p, td.intended(case, p))
+        for _, hi in sched.stretches:
+            assert ids[hi] == orc.argmax(ref[hi]), (r, hi)
+        for key in ref_kv:
+            assert kv_slices_equal(kv[key], ref_kv[key], r, kvl), (r,) + key
+
+
+@pytest.mark.parametrize("cfg,ctx,batch,chunks,steps", [("tiny-llama", 1300, 512, [512, 512, 76], 4), ("tiny-qwen3", 1300, 512, [512, 512, 76], 4),
+                                                        ("mid-llama", 400, 128, [100, 128, 57], 2)])
+def test_deep_prefill_chunks_on_row_split_ranks(pkg, orc, planmod, cfg, ctx, batch, chunks, steps):
+    """Batched prefill chunks that start deep in the context, on two ranks: chunks of 512, 512 and 76 (the second and third start at 512 and 1024:
+    the tiled and long-context prefill attention on the rank's heads_l / kv_heads_l, rank-chunked activations), and on mid-llama (16 query heads per
+    rank) chunks of 100, 128 and 57 that straddle 128 and 256.  The decode steps behind them and each rank's K / V slices at the chunk edges
+    equal the oracle's."""
+    plan_mod, hip = planmod
+    tp, n = 2, sum(chunks)
+    m = model_at(pkg, cfg, ctx, 8, seed=31)
+    o = orc.COracle(m)
+    toks = pkg.javarand.bench_tokens(m.cfg.vocab, n + steps)
+    o.prefill(toks[:n], 0)
+    ref = [o.forward(toks[p], p) for p in range(n, n + steps)]
+    edges = np.cumsum(chunks).tolist()
+    rows = sorted({0, n + steps - 1} | {e - 1 for e in edges} | {e for e in edges[:-1]})
+    assert rows == ([0, 511, 512, 1023, 1024, 1099, 1103] if n == 1100 else [0, 99, 100, 227, 228, 284, 286])
+    ref_kv = {(l, p): o.kv(l, p) for l in range(m.cfg.n_layers) for p in rows}
+
+    def make_plan(r, grp):
+        return plan_mod.HipMasterPlan(m, prefill_batch_size=batch, tp_rank=r, tp_size=tp, local_group=grp)
+
+    def body(r, plan):
+        pos = 0
+        for c in chunks:
+            plan.tornadoVMForwardBatchPrefill(toks[pos:pos + c], pos)
+            pos += c
+        return [plan.forward_decode(toks[p], p) for p in range(n, n + steps)], {key: plan.kv(*key) for key in ref_kv}
+
+    out = run_ranks(planmod, tp, make_plan, body)
+    kvl = m.cfg.kv_dim // tp
+    for r, (logits, kv) in enumerate(out):
+        for i in range(steps):
+            assert np.array_equal(logits[i], ref[i]), (r, n + i)
+        for key in ref_kv:
+            assert kv_slices_equal(kv[key], ref_kv[key], r, kvl), (r,) + key
+
+
+def test_prefix_fork_on_row_split_ranks(pkg, orc, planmod):
+    """gl3_kv_seq_copy is rank-local under tensor parallelism: every rank copies its own kv_dim / tp slice.  Two ranks prefill sequence 0 with 140
+    tokens (chunks of 64, 64, 12), fork rows [0, 140) to sequences 1 and 2 and run three static-batched decode steps in which every sequence
+    continues with its own token: logits and greedy ids of every row equal the oracle that was fed that sequence's tokens, the forked rows equal the
+    source's and the oracle's slice, the row behind the last step is still zero.  A second fork of rows [64, 100) into the reset plan leaves the
+    rows on either side of the range zero."""
+    plan_mod, hip = planmod
+    tp, nseq, n, steps = 2, 3, 140, 3
+    m = model_at(pkg, "tiny-llama", 200, 8, seed=53)
+    rng = np.random.default_rng(11)
+    prompt = rng.integers(0, m.cfg.vocab, n).tolist()
+    first = [int(t) for t in rng.choice(m.cfg.vocab, nseq, replace=False)]
+    ref, ref_kv = [], {}
+    for s in range(nseq):
+        o = orc.COracle(m)
+        o.prefill(prompt, 0)
+        t, rows = first[s], []
+        for i in range(steps):
+            rows.append(o.forward(t, n + i))
+            t = orc.argmax(rows[-1])
+        ref.append(rows)
+        for l in range(m.cfg.n_layers):
+            for p in (0, 127, 128, n - 1, n, n + steps - 1):
+                ref_kv[(s, l, p)] = o.kv(l, p)
+    assert not np.array_equal(ref[0][0], ref[1][0]) and not np.array_equal(ref[1][0], ref[2][0])
+    forked = [(s, l, p) for s in (1, 2) for l in range(m.cfg.n_layers) for p in (0, 127, 128, n - 1)]
+    second = [(l, p) for l in range(m.cfg.n_layers) for p in (63, 64, 99, 100)]
+
+    def make_plan(r, grp):
+        return plan_mod.HipMasterPlan(m, prefill_batch_size=64, n_seqs=nseq, tp_rank=r, tp_size=tp, local_group=grp)
+
+    def body(r, plan):
+        plan.prefill_seq(0, prompt, 0)
+        plan.kv_seq_copy(0, [1, 2], 0, n)
+        src = {(l, p): plan.kv_seq(0, l, p) for _, l, p in forked}
+        cur, res = list(first), []
+        for i in range(steps):
+            lg, ids = plan.forward_decode_batch(cur, np.arange(nseq, dtype=np.int32), np.full(nseq, n + i, np.int32))
+            res.append((lg.copy(), ids.copy()))
+            cur = [int(t) for t in ids]
+        kv = {key: plan.kv_seq(*key) for key in ref_kv}
+        behind = {(s, l): plan.kv_seq(s, l, n + steps) for s in range(nseq) for l in range(m.cfg.n_layers)}
+        plan.reset_kv()
+        plan.prefill_seq(0, prompt, 0)
+        plan.kv_seq_copy(0, [1], 64, 100)
+        return res, kv, src, behind, {key: (plan.kv_seq(0, *key), plan.kv_seq(1, *key), plan.kv_seq(2, *key)) for key in second}
+
+    out = run_ranks(planmod, tp, make_plan, body)
+    kvl = m.cfg.kv_dim // tp
+    for r, (res, kv, src, behind, after) in enumerate(out):
+        for i in range(steps):
+            lg, ids = res[i]
+            for s in range(nseq):
+                assert np.array_equal(lg[s], ref[s][i]), (r, i, s)
+                assert int(ids[s]) == orc.argmax(ref[s][i]), (r, i, s)
+        for key in ref_kv:
+            assert kv_slices_equal(kv[key], ref_kv[key], r, kvl), (r,) + key
+        for s, l, p in forked:
+            assert src[(l, p)][0].any() and src[(l, p)][1].any()
+            assert np.array_equal(kv[(s, l, p)][0], src[(l, p)][0]) and np.array_equal(kv[(s, l, p)][1], src[(l, p)][1]), (r, s, l, p)
+        assert all(not k.any() and not v.any() for k, v in behind.values()), r
+        for (l, p), (s0, s1, s2) in after.items():
+            assert s0[0].any() and s0[1].any() and not s2[0].any() and not s2[1].any(), (r, l, p)
+            if 64 <= p < 100:
+                assert np.array_equal(s1[0], s0[0]) and np.array_equal(s1[1], s0[1]), (r, l, p)
+            else:
+                assert not s1[0].any() and not s1[1].any(), (r, l, p)

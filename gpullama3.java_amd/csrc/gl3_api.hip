@@ -1204,8 +1204,21 @@ int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, const int3
 // what the batched sampler does not cover yet is refused, not approximated
 static int32_t check_batch_sampler(gl3_ctx* ctx) {
     if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
-    if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "the batched sampler reads plain [n][vocab] logits: tensor-parallel plans (rank-chunked logits) are not supported yet");
     if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, a Vector-API order: 256 bits, or 512 bits for F16 on one rank)");
+    return GL3_OK;
+}
+
+// Tensor parallel: the gathered logits of a batched step live in the peer arena, which has room for min(max_batch, 64) rows (gl3_tp.hip).
+// Asked with the other argument checks, before anything is staged or enqueued and before a sampler / scorer prepares its state.
+static int32_t check_tp_logits_rows(gl3_ctx* ctx, int rows) {
+    if (ctx->d.tp_size > 1 && rows > ctx->arena.pf_logits_rows)
+        GL3_FAIL(GL3_E_UNSUPPORTED, "tensor-parallel batched steps are limited to 64 output rows (rows with logits) per step");
+    return GL3_OK;
+}
+
+// Draft verification reads plain [n][vocab] logits (verify_runs_kernel): its two entries stay one-rank
+static int32_t check_verify(gl3_ctx* ctx) {
+    if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "draft verification is built for one rank (tp_size == 1): it reads plain [n][vocab] logits");
     return GL3_OK;
 }
 
@@ -1217,6 +1230,7 @@ int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tokens, con
     int32_t r = check_batch_sampler(ctx);
     if (r != GL3_OK) return r;
     if ((r = check_batch(ctx, tokens, seq_ids, positions, n)) != GL3_OK) return r;
+    if ((r = check_tp_logits_rows(ctx, n)) != GL3_OK) return r;
     bool all_greedy = false;
     if ((r = gl3_sample_batch_prepare(ctx, n, temperature, topp, coins, &all_greedy)) != GL3_OK) return r;
     if (all_greedy) return gl3_decode_batch_run(ctx, tokens, seq_ids, positions, n, nullptr, tokens_out);      // Sampler.java:79-81 for every row
@@ -1231,14 +1245,13 @@ static int32_t check_mixed(gl3_ctx* ctx, const int32_t* tokens, const int32_t* s
                            BatchPlan& bp) {
     if (!tokens || !seq_ids || !positions || n <= 0) GL3_FAIL(GL3_E_ARG, "bad batch arrays");
     if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
-    if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "the mixed batched step is built for one rank (tp_size == 1)");
     if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, a Vector-API order: 256 bits, or 512 bits for F16 on one rank)");
     if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
     for (int i = 0; i < n; ++i)
         if (tokens[i] < 0 || tokens[i] >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
     const char* why = batch_plan_build(seq_ids, positions, want_logits, n, ctx->n_seqs, ctx->d.ctx, ctx->d.max_batch, bp);
     if (why) GL3_FAIL(GL3_E_ARG, why);
-    return GL3_OK;
+    return check_tp_logits_rows(ctx, (int)bp.out_rows.size());
 }
 
 int32_t gl3_forward_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits, int32_t n,
@@ -1298,6 +1311,7 @@ int32_t gl3_score_rows(gl3_ctx* ctx, const float* logits, int32_t n, const int32
     int32_t r = check_batch_sampler(ctx);
     if (r != GL3_OK) return r;
     if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
+    if ((r = check_tp_logits_rows(ctx, n)) != GL3_OK) return r;
     if ((r = gl3_score_prepare(ctx, n, targets, temperature)) != GL3_OK) return r;
     if ((r = gl3_decode_batch_load_logits(ctx, logits, n)) != GL3_OK) return r;
     const float* logits_dev; const int32_t* greedy;
@@ -1310,11 +1324,12 @@ int32_t gl3_score_rows(gl3_ctx* ctx, const float* logits, int32_t n, const int32
 int32_t gl3_forward_batch_verify(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const float* temperature,
                                  const float* coins, gl3_verify_result* results_out, int32_t* n_runs_out) {
     if (!ctx) return GL3_E_ARG;
+    int32_t r = check_verify(ctx);
+    if (r != GL3_OK) return r;
     BatchPlan bp;
     // every row is an output row; check_mixed refuses n > max_batch before the plan looks at a flag, so max_batch flags are enough
     const std::vector<int8_t> every((size_t)std::max(ctx->d.max_batch, 1), 1);
-    int32_t r = check_mixed(ctx, tokens, seq_ids, positions, every.data(), n, bp);
-    if (r != GL3_OK) return r;
+    if ((r = check_mixed(ctx, tokens, seq_ids, positions, every.data(), n, bp)) != GL3_OK) return r;
     if (!results_out || !n_runs_out) GL3_FAIL(GL3_E_ARG, "null results_out / n_runs_out");
     const int n_runs = (int)bp.runs.size();
     std::vector<int32_t> row0((size_t)n_runs), rows((size_t)n_runs);
@@ -1336,8 +1351,9 @@ int32_t gl3_verify_rows(gl3_ctx* ctx, const float* logits, const int32_t* tokens
                         const float* coins, gl3_verify_result* results_out) {
     if (!ctx) return GL3_E_ARG;
     if (!logits || !tokens || !run_rows || !results_out || n_runs <= 0) GL3_FAIL(GL3_E_ARG, "bad logits / tokens / run_rows / results_out arrays");
-    int32_t r = check_batch_sampler(ctx);
+    int32_t r = check_verify(ctx);
     if (r != GL3_OK) return r;
+    if ((r = check_batch_sampler(ctx)) != GL3_OK) return r;
     std::vector<int32_t> row0((size_t)n_runs);
     int64_t n = 0;
     for (int k = 0; k < n_runs; ++k) {
@@ -1425,6 +1441,7 @@ int32_t gl3_sample_rows(gl3_ctx* ctx, const float* logits, int32_t n, const floa
     int32_t r = check_batch_sampler(ctx);
     if (r != GL3_OK) return r;
     if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
+    if ((r = check_tp_logits_rows(ctx, n)) != GL3_OK) return r;
     bool all_greedy = false;
     if ((r = gl3_sample_batch_prepare(ctx, n, temperature, topp, coins, &all_greedy)) != GL3_OK) return r;
     if ((r = gl3_decode_batch_load_logits(ctx, logits, n)) != GL3_OK) return r;

@@ -1,5 +1,6 @@
 // gl3_prefill.hip — batched prefill (gl3_forward_prefill with max_batch > 1) and static-batched decode
-// (gl3_forward_decode_batch); tensor-parallel ranks keep gathered activations rank-chunked (see `chunked`).
+// (gl3_forward_decode_batch) and the mixed step (gl3_forward_batch); tensor-parallel ranks keep gathered activations rank-chunked
+// (see `chunked`, gl3_chunked.h).
 //
 // Replaces the reference's batched-prefill task graphs
 //   J/tornadovm/layers/type/q8_0/prefill/LlamaQ8_0LayersBatchPrefillMMA.java:84-219 (tensor-core path, CUDA only) and
@@ -16,6 +17,7 @@
 
 #include "gl3_ctx.h"
 #include "gl3_batch_plan.h"
+#include "gl3_chunked.h"      // chunked(): the rank-chunked layout of every gathered activation
 #include <type_traits>
 #include "gl3_decode_kernels.h"
 
@@ -95,12 +97,7 @@ struct gl3_prefill_state {
 
 
 // ---------------------------------------------------------------------------------------------------
-// token_embedding_table.copyTo per token (batchForwardJavaPrefill :96)
-// Activation layout under tensor parallelism ("rank-chunked"): a [ntok][cols] activation that is produced by row-split
-// matrices is kept as [tp][ntok][cols / tp], so every rank's output is one contiguous chunk and the all-gather is in
-// place; element j of token b sits at (j / cc) * ntok * cc + b * cc + j % cc with cc = cols / tp (tp = 1: the plain layout).
-__device__ __forceinline__ size_t chunked(int b, int j, int cc, int ntok) { return ((size_t)(j / cc) * ntok + b) * cc + (j % cc); }
-
+// token_embedding_table.copyTo per token (batchForwardJavaPrefill :96), written in the rank-chunked layout (chunked(), gl3_chunked.h)
 __global__ __launch_bounds__(256) void pf_embed_kernel(const uint8_t* __restrict__ emb, int ng, int dim,
                                                         const int32_t* __restrict__ tokens, float* __restrict__ X, int cc, float emb_scale) {
     const int token = tokens[blockIdx.x];
@@ -1003,15 +1000,48 @@ void gl3_decode_batch_outputs(gl3_ctx* ctx, const float** logits, const int32_t*
     *logits = ctx->pf->LOGITS; *greedy = ctx->pf->amax;
 }
 
-// Parity tap gl3_sample_rows: caller-supplied logits take the place of a step's (one rank: the plain [n][vocab] layout), followed by
-// the step's own greedy scan.  No forward pass, no KV change; nothing is waited for.
-int32_t gl3_decode_batch_load_logits(gl3_ctx* ctx, const float* logits, int32_t n) {
+// The logits tail of a batched step, shared by the static-batched and the mixed step: output RMSNorm + vocabulary projection of `rows` rows
+// of src (rank-chunked, chunk width src_cc) into this rank's chunk [rows][vocab / tp] of the rank-chunked p->LOGITS, the gather, and the
+// greedy ids of the gathered rows.  One rank: the chunk is the plain [rows][vocab] buffer and nothing is gathered.
+static int32_t pf_logits_tail(gl3_ctx* ctx, const float* src, int src_cc, int rows) {
     gl3_prefill_state* p = ctx->pf;
+    const int vl = ctx->vocab_l;
+    pf_logits_stage(ctx, src, src_cc, rows, p->LOGITS + (size_t)ctx->d.tp_rank * rows * vl, vl);
+    const int32_t r = gl3_all_gather(ctx, GB_PF_LOGITS, (size_t)rows * vl);
+    if (r != GL3_OK) return r;
+    pf_greedy(ctx, rows, vl);
+    return GL3_OK;
+}
+
+// The first `rows` rows of p->LOGITS <-> plain host rows [rows][vocab]: one copy on one rank, one 2D copy per rank chunk of the
+// rank-chunked [tp][rows][vocab / tp] buffer otherwise
+static int32_t pf_logits_copy(gl3_ctx* ctx, float* host, int rows, hipMemcpyKind kind) {
+    gl3_prefill_state* p = ctx->pf;
+    const gl3_model_desc& d = ctx->d;
+    const int vl = ctx->vocab_l;
+    const bool out = kind == hipMemcpyDeviceToHost;
+    if (d.tp_size == 1) {
+        GL3_HIP(hipMemcpyAsync(out ? (void*)host : (void*)p->LOGITS, out ? (const void*)p->LOGITS : (const void*)host, (size_t)rows * d.vocab * 4, kind, ctx->stream));
+        return GL3_OK;
+    }
+    for (int c = 0; c < d.tp_size; ++c) {
+        float* dev = p->LOGITS + (size_t)c * rows * vl;
+        float* hst = host + (size_t)c * vl;
+        if (out) GL3_HIP(hipMemcpy2DAsync(hst, (size_t)d.vocab * 4, dev, (size_t)vl * 4, (size_t)vl * 4, rows, kind, ctx->stream));
+        else GL3_HIP(hipMemcpy2DAsync(dev, (size_t)vl * 4, hst, (size_t)d.vocab * 4, (size_t)vl * 4, rows, kind, ctx->stream));
+    }
+    return GL3_OK;
+}
+
+// Parity taps gl3_sample_rows / gl3_score_rows / gl3_verify_rows: caller-supplied plain [n][vocab] logits take the place of a step's — laid
+// out as a step leaves them, rank-chunked under tensor parallelism, so the taps exercise the chunked readers — followed by the step's own
+// greedy scan.  No forward pass, no KV change, no peer; nothing is waited for.
+int32_t gl3_decode_batch_load_logits(gl3_ctx* ctx, const float* logits, int32_t n) {
     const gl3_model_desc& d = ctx->d;
     GL3_HIP(hipSetDevice(d.device));
     int32_t r = pf_grow_logits(ctx, n);
     if (r != GL3_OK) return r;
-    GL3_HIP(hipMemcpyAsync(p->LOGITS, logits, (size_t)n * d.vocab * 4, hipMemcpyHostToDevice, ctx->stream));
+    if ((r = pf_logits_copy(ctx, const_cast<float*>(logits), n, hipMemcpyHostToDevice)) != GL3_OK) return r;
     pf_greedy(ctx, n, ctx->vocab_l);
     GL3_HIP(hipGetLastError());
     return GL3_OK;
@@ -1029,16 +1059,10 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
     int32_t r = pf_stage_tokens(ctx, tokens, seq_ids, positions, n);
     if (r != GL3_OK) return r;
     hipStream_t s = ctx->stream;
-    const int vl = ctx->vocab_l;
     // the whole step: layers, final RMSNorm + vocabulary projection of every row, greedy ids
     auto enqueue_step = [&](const PfStep& st) -> int32_t {
-        int32_t rr = pf_layers(ctx, st);
-        if (rr != GL3_OK) return rr;
-        // this rank's logits are the chunk [n][vocab / tp] of the rank-chunked buffer
-        pf_logits_stage(ctx, p->X, ctx->dim_l, n, p->LOGITS + (size_t)d.tp_rank * n * vl, vl);
-        if ((rr = gl3_all_gather(ctx, GB_PF_LOGITS, (size_t)n * vl)) != GL3_OK) return rr;
-        pf_greedy(ctx, n, vl);
-        return GL3_OK;
+        const int32_t rr = pf_layers(ctx, st);
+        return rr != GL3_OK ? rr : pf_logits_tail(ctx, p->X, ctx->dim_l, n);
     };
     // ~400 launches per step: replay them as one hipGraph per batch size.  Nothing position-dependent is baked in when every
     // position is below AF_MAXN (the one-launch attention reads sequence ids / positions from device memory).  The three-kernel
@@ -1063,11 +1087,7 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
         p->attn_rows[0] = n; p->attn_rows[1] = p->attn_rows[2] = p->attn_rows[3] = 0; p->attn_rows_set = true;      // a replay does not pass pf_attention: the captured step is attn_head_kernel's
     } else if ((r = enqueue_step(st)) != GL3_OK) return r;
     if (argmax_out) GL3_HIP(hipMemcpyAsync(argmax_out, p->amax, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (logits_out) {      // un-chunk on the way out: [tp][n][vl] -> [n][vocab]
-        for (int c = 0; c < d.tp_size; ++c)
-            GL3_HIP(hipMemcpy2DAsync(logits_out + (size_t)c * vl, (size_t)d.vocab * 4, p->LOGITS + (size_t)c * n * vl, (size_t)vl * 4, (size_t)vl * 4, n,
-                                     hipMemcpyDeviceToHost, s));
-    }
+    if (logits_out && (r = pf_logits_copy(ctx, logits_out, n, hipMemcpyDeviceToHost)) != GL3_OK) return r;      // un-chunked on the way out
     GL3_HIP(hipGetLastError());
     if (!finish) return GL3_OK;          // the batched sampler's launches follow on the same stream (gl3_sample_batch_finish)
     GL3_HIP(hipStreamSynchronize(s));
@@ -1077,17 +1097,23 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
 // ---------------------------------------------------------------------------------------------------
 // Mixed step (gl3_forward_batch): prompt chunks and decode rows of many sequences in one pass over the weights.  The layers are pf_layers
 // over (token, sequence, position) rows as in a static-batched step; the attention takes the run-table form (pf_attention); the logits stage
-// runs over the rows the caller flagged only.  Eager: the shape of a step differs from call to call.  One rank, plain row layouts.
+// runs over the rows the caller flagged only.  Eager: the shape of a step differs from call to call.
+// Tensor parallel: the layers and the run-table attention forms work on this rank's heads and chunks as in every other batched step (the
+// table records name step rows, sequences and positions, nothing per head); the flagged rows are gathered out of the rank-chunked X into
+// plain rows, and the logits tail is the static-batched step's (pf_logits_tail): this rank's vocabulary chunk, the gather into the arena's
+// rank-chunked logits — which hold min(max_batch, 64) rows: a step with more output rows is refused with the arguments (gl3_api.hip) —
+// and the greedy scan.  Every rank then holds every output row, and the sampler / scorer behind the step read them redundantly.
 static_assert(BP_TILE_ROWS == FA_TB, "the step plan cuts runs into the attention kernels' token tiles");
 static_assert(BP_DEEP_ROWS == PA_TB && BP_DEEP_ROWS == SCM_TB && BP_DEEP_ROWS == PVM_TB && BP_DEEP_ROWS <= PVR_TB,
               "the step plan cuts deep rows into the long-context kernels' token tiles (one record per workgroup of pf_pv_ring_kernel)");
 static_assert(sizeof(BatchSpan) == sizeof(int4), "a tile record is read as one int4");
 
-// rows[r] of X -> row r of out (float4 per thread; dim % 4 == 0)
-static __global__ __launch_bounds__(256) void pf_gather_rows_kernel(const float* __restrict__ X, const int32_t* __restrict__ rows, int dim, float* __restrict__ out) {
-    const float4* src = reinterpret_cast<const float4*>(X + (size_t)rows[blockIdx.x] * dim);
+// rows[r] of the ntok rows of X (rank-chunked, chunk width cc; cc = dim: plain rows) -> row r of out, plain (float4 per thread; cc % 4 == 0)
+static __global__ __launch_bounds__(256) void pf_gather_rows_kernel(const float* __restrict__ X, const int32_t* __restrict__ rows, int dim, int cc, int ntok,
+                                                                    float* __restrict__ out) {
+    const int b = rows[blockIdx.x];
     float4* dst = reinterpret_cast<float4*>(out + (size_t)blockIdx.x * dim);
-    for (int i = threadIdx.x; i < (dim >> 2); i += 256) dst[i] = src[i];
+    for (int i = threadIdx.x; i < (dim >> 2); i += 256) dst[i] = *reinterpret_cast<const float4*>(X + chunked(b, 4 * i, cc, ntok));
 }
 
 // x of row `row` of the n-row step the stream just ran -> the decode path's ctx->x (parity tap gl3_get_x), waited for
@@ -1125,16 +1151,15 @@ int32_t gl3_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_id
     // keep the decode path's x in step with the last row (parity tap gl3_get_x)
     hipLaunchKernelGGL(pf_unchunk_row_kernel, dim3(4), dim3(256), 0, s, p->X, n - 1, d.dim, ctx->dim_l, n, ctx->x);
     if (n_out) {      // output RMSNorm + vocabulary projection + greedy ids of the flagged rows, compact
-        hipLaunchKernelGGL(pf_gather_rows_kernel, dim3(n_out), dim3(256), 0, s, p->X, p->out_rows, d.dim, p->XG);
-        pf_logits_stage(ctx, p->XG, d.dim, n_out, p->LOGITS, d.vocab);
-        pf_greedy(ctx, n_out, d.vocab);
+        hipLaunchKernelGGL(pf_gather_rows_kernel, dim3(n_out), dim3(256), 0, s, p->X, p->out_rows, d.dim, ctx->dim_l, n, p->XG);
+        if ((r = pf_logits_tail(ctx, p->XG, d.dim, n_out)) != GL3_OK) return r;
         if (argmax_out) GL3_HIP(hipMemcpyAsync(argmax_out, p->amax, (size_t)n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (logits_out) GL3_HIP(hipMemcpyAsync(logits_out, p->LOGITS, (size_t)n_out * d.vocab * 4, hipMemcpyDeviceToHost, s));
+        if (logits_out && (r = pf_logits_copy(ctx, logits_out, n_out, hipMemcpyDeviceToHost)) != GL3_OK) return r;      // un-chunked on the way out
     }
     GL3_HIP(hipGetLastError());
     if (!finish) return GL3_OK;          // the batched sampler's launches follow on the same stream (gl3_sample_batch_finish)
     GL3_HIP(hipStreamSynchronize(s));
-    return GL3_OK;
+    return gl3_tp_check(ctx);
 }
 
 

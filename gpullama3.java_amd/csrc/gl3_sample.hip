@@ -34,6 +34,13 @@
 // of every row come back in one copy of 8 * n bytes; only rows whose tie flag is set have their probabilities copied out and run through
 // the host heap (topp_sample).  The logits are read, never written.
 //
+// Tensor parallel.  After the logits gather of a batched step every rank holds every row, rank-chunked as [tp][rows][vocab / tp]
+// (gl3_chunked.h).  Each rank samples or scores all rows from them redundantly: the same logits and the same coins give the same ids on
+// every rank, so nothing is communicated behind the logits gather.  Two kernels read logits and take the layout {chunk width, rows}:
+// bsm_scale_max_kernel, whose plain probs rows feed every later sampler stage (tie fallback and parity taps included), and
+// score_rows_kernel.  With one rank the chunk width is the vocabulary and the addresses are the plain rows'.  Draft verification
+// (verify_runs_kernel) reads plain rows only: its entries stay one-rank.
+//
 // The two entries are two instances of gl3_sample_state.  gl3_forward_decode_sample is the n = 1 case: 256 workgroups per element-wise
 // launch, launched eagerly, its SmpRow riding behind the (token, position) pair in ctx->dyn.  The static-batched entries
 // (gl3_forward_decode_batch_sample, gl3_sample_rows) use 64 workgroups per row and replay one hipGraph per (row count, any top-p row).
@@ -43,6 +50,7 @@
 #include <vector>
 
 #include "gl3_ctx.h"
+#include "gl3_chunked.h"      // chunked(), RowLayout: the logits of a tensor-parallel batched step are rank-chunked
 #include "gl3_decode_kernels.h"
 
 using namespace gl3;
@@ -51,7 +59,8 @@ constexpr int SM_CHUNK = 4096;               // elements per exact sequential-su
 
 // aux row layout: `blocks` block maxima, the total, nchunks chunk ends.  blocks = workgroups per row of the element-wise launches
 // (gl3_sample_state::blocks, at most 256: bsm_exp reads one maximum per thread); the maximum does not depend on how rows are split.
-__global__ __launch_bounds__(256) void bsm_scale_max_kernel(const float* __restrict__ logits, int n, const SmpRow* __restrict__ rows, const int32_t* __restrict__ greedy,
+// The one sampler kernel that reads the logits (lay: where element i of a row is, gl3_chunked.h); everything behind it works on probs, plain rows.
+__global__ __launch_bounds__(256) void bsm_scale_max_kernel(const float* __restrict__ logits, int n, const RowLayout lay, const SmpRow* __restrict__ rows, const int32_t* __restrict__ greedy,
                                                             float* __restrict__ probs, float* __restrict__ aux, int aux_stride, int* __restrict__ res, int* __restrict__ n0) {
     __shared__ float red[4];
     const int row = blockIdx.y;
@@ -61,11 +70,10 @@ __global__ __launch_bounds__(256) void bsm_scale_max_kernel(const float* __restr
         if (R.mode == SMP_GREEDY) { res[2 * row] = greedy[row]; res[2 * row + 1] = 0; }
     }
     if (R.mode == SMP_GREEDY) return;
-    const float* lg = logits + (size_t)row * n;
     float* p = probs + (size_t)row * n;
     float mx = -INFINITY;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float v = lg[i] / R.temperature;                         // divideInPlace(temperature)
+        const float v = logits[chunked(row, i, lay.cc, lay.nrows)] / R.temperature;                         // divideInPlace(temperature)
         p[i] = v;
         mx = fmaxf(mx, v);
     }
@@ -424,7 +432,10 @@ __global__ __launch_bounds__(256) void btp_pick_kernel(const SmpRow* __restrict_
 //           the chunk that holds it.
 // No [rows][vocab] intermediate exists: device memory grows by 8 + 16 bytes per row.  The logits are read, never written.
 // n % 4 == 0 (gl3_create: vocab is a multiple of 16), so rows are 16-byte aligned and every global / LDS access is a float4.
-__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int n, const ScoreRow* __restrict__ rows, gl3_token_score* __restrict__ out) {
+// lay: where element i of a row is (gl3_chunked.h).  A chunk width is a multiple of 16, so a quad never straddles two rank chunks; an SM_CHUNK
+// piece may, and a chunk boundary may fall inside a piece: every quad is addressed on its own.
+__global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict__ logits, int n, const RowLayout lay, const ScoreRow* __restrict__ rows,
+                                                         gl3_token_score* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     float* xf = reinterpret_cast<float*>(smem);                      // [SM_CHUNK + 32]
     uint8_t* scratch = smem + (size_t)(SM_CHUNK + 32) * 4;
@@ -432,11 +443,11 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
     const int row = blockIdx.x;
     const ScoreRow R = rows[row];
     const float T = R.temperature;
-    const float4* lg4 = reinterpret_cast<const float4*>(logits + (size_t)row * n);
+    auto quad = [&](int i) { return *reinterpret_cast<const float4*>(logits + chunked(row, i, lay.cc, lay.nrows)); };      // elements i .. i + 3, i % 4 == 0
     const int t = threadIdx.x;
     float mx = -INFINITY;
     for (int i = t; i < (n >> 2); i += 256) {
-        const float4 v = lg4[i];
+        const float4 v = quad(4 * i);
         mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
     }
     mx = wave_max(mx);
@@ -450,7 +461,7 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
         for (int i = 4 * t; i < SM_CHUNK + 32; i += 1024) {
             float4 e = {0.f, 0.f, 0.f, 0.f};                          // zero padding behind the chunk (exact_seqsum_lds reads it)
             if (i < len) {
-                const float4 v = lg4[(base + i) >> 2];
+                const float4 v = quad(base + i);
                 e.x = (float)exp((double)(v.x / T - mx));            // (float) Math.exp(f - maxVal)
                 e.y = (float)exp((double)(v.y / T - mx));
                 e.z = (float)exp((double)(v.z / T - mx));
@@ -477,7 +488,7 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
     }
     if (t == 0) {
         const float sum = sh[4];
-        const float4 o = {sh[5] / sum, logits[(size_t)row * n + R.target] / T, mx, sum};      // softmaxInPlace(v)[target], v[target], max, sum
+        const float4 o = {sh[5] / sum, logits[chunked(row, R.target, lay.cc, lay.nrows)] / T, mx, sum};      // softmaxInPlace(v)[target], v[target], max, sum
         *reinterpret_cast<float4*>(out + row) = o;
     }
 }
@@ -684,13 +695,13 @@ static int32_t sample_alloc(gl3_ctx* ctx, gl3_sample_state* b, int n) {
     return r;
 }
 
-static void sample_enqueue(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, const int32_t* greedy, const SmpRow* params, int n, bool any_topp) {
+static void sample_enqueue(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, RowLayout lay, const int32_t* greedy, const SmpRow* params, int n, bool any_topp) {
     hipStream_t s = ctx->stream;
     const int v = ctx->d.vocab, nb = (v + RS_TILE - 1) / RS_TILE;
     const size_t smem = (size_t)(SM_CHUNK + 32) * 4 + ss_scratch_bytes(SM_CHUNK);
     int* n0 = b->res + 2 * b->rows;
     const dim3 ge(b->blocks, n), gt(nb, n);
-    hipLaunchKernelGGL(bsm_scale_max_kernel, ge, dim3(256), 0, s, logits, v, params, greedy, b->probs, b->aux, b->aux_stride, b->res, n0);
+    hipLaunchKernelGGL(bsm_scale_max_kernel, ge, dim3(256), 0, s, logits, v, lay, params, greedy, b->probs, b->aux, b->aux_stride, b->res, n0);
     hipLaunchKernelGGL(bsm_exp_kernel, ge, dim3(256), 0, s, b->probs, v, params, b->aux, b->aux_stride, b->blocks);
     hipLaunchKernelGGL(bsm_seqsum_kernel<false>, dim3(n), dim3(256), smem, s, b->probs, v, params, b->aux, b->aux_stride, b->blocks, b->res);
     hipLaunchKernelGGL(bsm_div_kernel, ge, dim3(256), 0, s, b->probs, v, params, b->aux, b->aux_stride, b->blocks);
@@ -705,10 +716,10 @@ static void sample_enqueue(gl3_ctx* ctx, gl3_sample_state* b, const float* logit
     hipLaunchKernelGGL(btp_pick_kernel, dim3(n), dim3(256), smem, s, params, b->sort, b->sort_stride, v, n0, b->res);
 }
 
-// The sampler's launches for rows 0..n) of `logits` behind whatever produced them on the plan's stream (params / h_params: the rows'
-// settings on the device / the host), 8 * n bytes back, host heap for top-p rows whose sampled rank is tied.
-static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, const int32_t* greedy, const SmpRow* params, const SmpRow* h_params, int n,
-                             int32_t* tokens_out) {
+// The sampler's launches for rows 0..n) of `logits` (laid out as `lay` says) behind whatever produced them on the plan's stream (params /
+// h_params: the rows' settings on the device / the host), 8 * n bytes back, host heap for top-p rows whose sampled rank is tied.
+static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, RowLayout lay, const int32_t* greedy, const SmpRow* params,
+                             const SmpRow* h_params, int n, int32_t* tokens_out) {
     hipStream_t s = ctx->stream;
     const int v = ctx->d.vocab;
     static const bool host_topp = env_flag("GL3_TOPP_HOST", false);              // A/B switch: no sort launches, every top-p row through the host heap
@@ -720,19 +731,21 @@ static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* log
             sample_drop_graphs(b);
             b->graph_logits = logits; b->graph_greedy = greedy;
         }
+        // A captured launch holds the logits pointer and the layout.  The key covers both: the layout is {vocab / tp, n}, a function of the
+        // row count, and the pointer is checked above (one rank: the buffer moves when it grows; tensor parallel: the arena's, it never moves)
         const size_t slot = (size_t)2 * n + (any_topp ? 1 : 0);
         if (b->graphs.size() <= slot) b->graphs.resize(slot + 1, nullptr);
         if (!b->graphs[slot]) {
             hipGraph_t g = nullptr;
             GL3_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            sample_enqueue(ctx, b, logits, greedy, params, n, any_topp);
+            sample_enqueue(ctx, b, logits, lay, greedy, params, n, any_topp);
             GL3_HIP(hipStreamEndCapture(s, &g));
             GL3_HIP(hipGraphInstantiate(&b->graphs[slot], g, nullptr, nullptr, 0));
             hipGraphDestroy(g);
         }
         GL3_HIP(hipGraphLaunch(b->graphs[slot], s));
     } else {
-        sample_enqueue(ctx, b, logits, greedy, params, n, any_topp);
+        sample_enqueue(ctx, b, logits, lay, greedy, params, n, any_topp);
     }
     GL3_HIP(hipGetLastError());
     GL3_HIP(hipMemcpyAsync(b->h_res, b->res, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -761,7 +774,7 @@ static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* log
 int32_t gl3_sample_run(gl3_ctx* ctx, const float* logits_dev, int32_t* token_out) {
     const int32_t r = sample_alloc(ctx, &ctx->smp_one, 1);
     if (r != GL3_OK) return r;
-    return sample_finish(ctx, &ctx->smp_one, logits_dev, nullptr, reinterpret_cast<const SmpRow*>(ctx->dyn + GL3_DYN_ROW), reinterpret_cast<const SmpRow*>(ctx->h_dyn + GL3_DYN_ROW), 1, token_out);
+    return sample_finish(ctx, &ctx->smp_one, logits_dev, RowLayout{ctx->d.vocab, 1}, nullptr, reinterpret_cast<const SmpRow*>(ctx->dyn + GL3_DYN_ROW), reinterpret_cast<const SmpRow*>(ctx->h_dyn + GL3_DYN_ROW), 1, token_out);
 }
 
 int32_t gl3_sample_probs(gl3_ctx* ctx, float* out) {       // parity tap: the probabilities of the last single-row sampled step
@@ -793,7 +806,8 @@ int32_t gl3_sample_batch_prepare(gl3_ctx* ctx, int32_t n, const float* temperatu
 
 int32_t gl3_sample_batch_finish(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n, int32_t* tokens_out) {
     gl3_sample_state* b = &ctx->smp_rows;
-    return sample_finish(ctx, b, logits_dev, greedy_dev, b->params, b->h_params, n, tokens_out);
+    // a batched step's logits: rank-chunked [tp][n][vocab / tp] (one rank: plain rows), complete on every rank, which samples them redundantly
+    return sample_finish(ctx, b, logits_dev, RowLayout{ctx->vocab_l, n}, greedy_dev, b->params, b->h_params, n, tokens_out);
 }
 
 int32_t gl3_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out) {      // parity tap: what row `row` of the last batched sampled step was drawn from
@@ -848,7 +862,7 @@ int32_t gl3_score_finish(gl3_ctx* ctx, const float* logits_dev, int32_t n, gl3_t
     static const bool timed = env_flag("GL3_SCORE_TIMING", false);      // measurement switch: HIP events around the launch, its device time on stderr
     if (timed && !b->ev0) { GL3_HIP(hipEventCreate(&b->ev0)); GL3_HIP(hipEventCreate(&b->ev1)); }
     if (timed) GL3_HIP(hipEventRecord(b->ev0, s));
-    hipLaunchKernelGGL(score_rows_kernel, dim3(n), dim3(256), smem, s, logits_dev, ctx->d.vocab, b->params, b->out);
+    hipLaunchKernelGGL(score_rows_kernel, dim3(n), dim3(256), smem, s, logits_dev, ctx->d.vocab, RowLayout{ctx->vocab_l, n}, b->params, b->out);
     if (timed) GL3_HIP(hipEventRecord(b->ev1, s));
     GL3_HIP(hipGetLastError());
     GL3_HIP(hipMemcpyAsync(b->h_out, b->out, (size_t)n * sizeof(gl3_token_score), hipMemcpyDeviceToHost, s));

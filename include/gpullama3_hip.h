@@ -275,8 +275,10 @@ GL3_API int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, co
  * else CategoricalSampler.  tokens_out: int32[n]; 8 * n bytes come back, and only a top-p row whose sampled rank is shared by
  * equal probabilities has its probabilities copied out for the reference's heap (counted by gl3_get_topp_counts, one count per
  * non-greedy top-p row).  The number of sampler launches does not depend on n (gl3_sample.hip).  Everything else as
- * gl3_forward_decode_batch; with every temperature 0 the ids are its argmax_out.  GL3_E_UNSUPPORTED: tp_size > 1 (rank-chunked
- * logits), max_batch <= 1. */
+ * gl3_forward_decode_batch; with every temperature 0 the ids are its argmax_out.  Tensor parallel (tp_size > 1): every rank is called
+ * with the same arguments (coins included), samples every row from the gathered, rank-chunked logits and returns the same ids; nothing
+ * is communicated behind the logits gather.  GL3_E_UNSUPPORTED: max_batch <= 1; tp_size > 1 with n > 64 (the gathered logits hold
+ * min(max_batch, 64) rows), refused before anything is staged. */
 GL3_API int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids,
                                                 const int32_t* positions, int32_t n, const float* temperature,
                                                 const float* topp, const float* coins, int32_t* tokens_out);
@@ -288,18 +290,23 @@ GL3_API int32_t gl3_forward_decode_batch_sample(gl3_ctx* ctx, const int32_t* tok
  * for that token and position.  Output rows: the rows with want_logits[i] != 0, in row order (want_logits == NULL: the last row of every
  * run); logits_out: f32[n_out][vocab] or NULL, argmax_out: int32[n_out] or NULL.  n_out == 0 is a pure multi-sequence prefill (no output
  * norm, vocabulary projection or argmax is launched).  Afterwards gl3_get_x returns x of the last row and gl3_get_buffer(4..6) hold all n
- * rows in step order.  The step runs eagerly (its shape differs from call to call); a step whose runs are all single rows and whose rows
+ * rows in step order (after a step on tp_size > 1 ranks rank-chunked, [tp_size][n][cols / tp_size], as after a tensor-parallel prefill).  The step runs eagerly (its shape differs from call to call); a step whose runs are all single rows and whose rows
  * all want logits is a gl3_forward_decode_batch step.  Attention of a step with a run of several rows, at any depth: its 8-row tiles whose
  * score rows fit LDS run on the one-launch tiled kernels, its deeper rows on the long-context scores / softmax / weighted-sum kernels (both
  * in their run-table forms, the split by depth per tile, not per step); head sizes other than 32 / 64 / 128 and more than 4 query heads per
  * kv head run row by row (gl3_get_attn_rows tells).  GL3_E_ARG, before anything is enqueued: null arrays, n <= 0, n > max_batch, a
  * token / sequence / position out of range or a run ending past ctx, a sequence id in two runs, positions inside a run that are not
- * consecutive ascending.  GL3_E_UNSUPPORTED: max_batch <= 1; tp_size > 1 — the mixed step is built for ONE rank. */
+ * consecutive ascending.  Tensor parallel (tp_size > 1): every rank is called with the same arguments and returns the same outputs; the
+ * layers and both attention forms run on the rank's heads and chunks, each rank projects its rows of the vocabulary, and the logits of
+ * the output rows are gathered once per step.  GL3_E_UNSUPPORTED: max_batch <= 1; tp_size > 1 with more than 64 output rows in one
+ * step (the gathered logits hold min(max_batch, 64) rows) — refused with the arguments, before anything is staged or enqueued; the step
+ * itself may still have up to max_batch rows. */
 GL3_API int32_t gl3_forward_batch(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
                                   const int8_t* want_logits, int32_t n, float* logits_out, int32_t* argmax_out);
 /* The same step + the sampler of gl3_forward_decode_batch_sample over the output rows: temperature / topp / coins / tokens_out have one
  * entry per OUTPUT row (n_out > 0 with any of them NULL: GL3_E_ARG).  gl3_get_sample_probs_row (row = output row) and gl3_get_topp_counts
- * answer for it. */
+ * answer for it.  Tensor parallel: as gl3_forward_batch, and every rank samples every output row from the gathered logits with the
+ * caller's coins, so all ranks return the same ids; GL3_E_UNSUPPORTED for more than 64 output rows, before the sampler stages anything. */
 GL3_API int32_t gl3_forward_batch_sample(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
                                          const int8_t* want_logits, int32_t n, const float* temperature, const float* topp,
                                          const float* coins, int32_t* tokens_out);
@@ -314,13 +321,15 @@ typedef struct { float prob, logit, max, sum; } gl3_token_score;
  * gl3_forward_batch gives it) or NULL.  The logits never leave the device and no [rows][vocab] buffer beside them exists: one launch, one
  * workgroup per row, behind the step on the plan's stream, and 16 * n_out bytes come back in one copy (gl3_sample.hip).  n_out == 0 is a
  * pure prefill, as in gl3_forward_batch_sample.  GL3_E_ARG, before anything is enqueued: everything gl3_forward_batch refuses, n_out > 0
- * with targets or scores_out NULL, a target outside [0, vocab), a temperature that is not > 0 (NaN included).  GL3_E_UNSUPPORTED:
- * max_batch <= 1, tp_size > 1. */
+ * with targets or scores_out NULL, a target outside [0, vocab), a temperature that is not > 0 (NaN included).  Tensor parallel: as
+ * gl3_forward_batch; every rank scores every output row from the gathered, rank-chunked logits and returns the same scores.
+ * GL3_E_UNSUPPORTED: max_batch <= 1; tp_size > 1 with more than 64 output rows, before the scorer stages anything. */
 GL3_API int32_t gl3_forward_batch_score(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
                                         const int8_t* want_logits, int32_t n, const int32_t* targets, const float* temperature,
                                         gl3_token_score* scores_out, int32_t* argmax_out);
 /* Parity tap: the same scores on caller-supplied logits (host f32[n][vocab]); no forward pass, no KV change.  Needs a plan with
- * max_batch > 1; n <= max_batch.  The logits buffer of the batched step is overwritten.  Errors as above. */
+ * max_batch > 1; n <= max_batch (tp_size > 1: n <= 64).  The logits buffer of the batched step is overwritten: on tp_size > 1 ranks the
+ * rows are laid out rank-chunked as a step leaves them, so the tap runs the reader a step runs; it needs no peer.  Errors as above. */
 GL3_API int32_t gl3_score_rows(gl3_ctx* ctx, const float* logits, int32_t n, const int32_t* targets, const float* temperature,
                                gl3_token_score* scores_out);
 /* Speculative decoding: the step of gl3_forward_batch over runs that carry DRAFTED tokens, and the decision, taken on the device, how many
@@ -347,7 +356,8 @@ GL3_API int32_t gl3_score_rows(gl3_ctx* ctx, const float* logits, int32_t n, con
  * The decision is one launch behind the step whatever n and the number of runs (gl3_sample.hip).  gl3_get_x and the step buffers answer as
  * after the gl3_forward_batch step over the same rows.  GL3_E_ARG, before anything is enqueued: everything gl3_forward_batch refuses, NULL
  * results_out or n_runs_out, a temperature that is negative or NaN, coins == NULL while some run has T > 0, a coin outside [0, 1) on a run
- * with T > 0.  GL3_E_UNSUPPORTED: max_batch <= 1, tp_size > 1. */
+ * with T > 0.  GL3_E_UNSUPPORTED: max_batch <= 1; tp_size > 1 — draft verification (this entry and gl3_verify_rows) remains ONE-rank:
+ * its kernel reads plain [n][vocab] logits.  Every rank answers so and enqueues nothing. */
 typedef struct { int32_t accepted, token; } gl3_verify_result;
 GL3_API int32_t gl3_forward_batch_verify(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
                                          const float* temperature, const float* coins, gl3_verify_result* results_out,
@@ -407,7 +417,8 @@ GL3_API int32_t gl3_get_attn_rows(gl3_ctx* ctx, int32_t out[4]);
  * (GL3_E_STATE for a greedy row or before any such step). */
 GL3_API int32_t gl3_get_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);
 /* Parity tap: the batched sampler alone on caller-supplied logits (host f32[n][vocab]); no forward pass, no KV change.  Needs a
- * plan with max_batch > 1; n <= max_batch.  The logits buffer of the batched step is overwritten. */
+ * plan with max_batch > 1; n <= max_batch (tp_size > 1: n <= 64, rank-chunked on the device, no peer needed: see gl3_score_rows).  The
+ * logits buffer of the batched step is overwritten. */
 GL3_API int32_t gl3_sample_rows(gl3_ctx* ctx, const float* logits, int32_t n, const float* temperature, const float* topp,
                                 const float* coins, int32_t* tokens_out);
 

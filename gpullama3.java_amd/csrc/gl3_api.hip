@@ -1105,7 +1105,10 @@ int32_t gl3_forward_decode_sample(gl3_ctx* ctx, int32_t token, int32_t pos, floa
     if (!ctx) return GL3_E_ARG;
     if (!token_out) GL3_FAIL(GL3_E_ARG, "null token_out");
     if (!(temperature >= 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be >= 0");
-    if (temperature == 0.f) return gl3_forward_decode(ctx, token, pos, nullptr, token_out);      // Sampler.java:79-81: greedy argmax
+    if (temperature == 0.f) {                                     // Sampler.java:79-81: greedy argmax
+        ctx->last_sample_mode = SMP_GREEDY;
+        return gl3_forward_decode(ctx, token, pos, nullptr, token_out);
+    }
     if (!(coin >= 0.f && coin < 1.f)) GL3_FAIL(GL3_E_ARG, "coin must be rng.nextFloat(1f): in [0, 1)");
     const SmpRow row = gl3_smp_row(temperature, topp, coin);
     int32_t r = set_dyn(ctx, token, pos, &row);
@@ -1113,6 +1116,7 @@ int32_t gl3_forward_decode_sample(gl3_ctx* ctx, int32_t token, int32_t pos, floa
     const int amode = attn_mode(ctx, pos);
     if (ctx->graph_exec[ATT_LONG]) GL3_HIP(hipGraphLaunch(step_graph(ctx, amode), ctx->stream));
     else if ((r = enqueue_decode(ctx, true, nullptr, amode)) != GL3_OK) return r;
+    ctx->last_sample_mode = row.mode;                             // what the probabilities row now is (gl3_draft_probs_put)
     return gl3_sample_run(ctx, ctx->logits, token_out);          // ends with the stream synchronisation and gl3_tp_check
 }
 
@@ -1319,10 +1323,48 @@ int32_t gl3_score_rows(gl3_ctx* ctx, const float* logits, int32_t n, const int32
     return gl3_score_finish(ctx, logits_dev, n, scores_out);
 }
 
+// Draft distributions of a target plan (gl3_sample.hip): the checks every entry shares, then the slot's
+static int32_t check_draft_table(gl3_ctx* ctx, int32_t slot) {
+    int32_t r = check_verify(ctx);
+    if (r != GL3_OK) return r;
+    if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "draft distributions before gl3_finalize");
+    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "draft distributions are read by draft verification, which needs max_batch > 1");
+    if (slot < 0 || slot >= ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "draft-distribution slot outside [0, max_batch)");
+    return GL3_OK;
+}
+
+int32_t gl3_draft_probs_put(gl3_ctx* ctx, int32_t slot, gl3_ctx* draft) {
+    if (!ctx) return GL3_E_ARG;
+    if (!draft || draft == ctx) GL3_FAIL(GL3_E_ARG, "the draft plan must be another plan");
+    if (draft->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "draft verification is built for one rank (tp_size == 1), the draft plan included");
+    const int32_t r = check_draft_table(ctx, slot);
+    if (r != GL3_OK) return r;
+    if (draft->d.vocab != ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "the draft plan has another vocabulary");
+    if (draft->d.device != ctx->d.device) GL3_FAIL(GL3_E_ARG, "the draft plan is on another device");
+    if (draft->last_sample_mode < 0 || !draft->smp_one.last_n) GL3_FAIL(GL3_E_STATE, "the draft plan has sampled nothing yet");
+    if (draft->last_sample_mode == SMP_GREEDY) GL3_FAIL(GL3_E_STATE, "the draft plan's last sample was greedy: it has no probabilities");
+    if (draft->last_sample_mode == SMP_TOPP) GL3_FAIL(GL3_E_STATE, "the draft plan's last sample was top-p: its row is the untruncated softmax, not what the token was drawn from");
+    return gl3_draft_put(ctx, slot, draft);
+}
+
+int32_t gl3_draft_probs_put_host(gl3_ctx* ctx, int32_t slot, const float* q) {
+    if (!ctx) return GL3_E_ARG;
+    if (!q) GL3_FAIL(GL3_E_ARG, "null q");
+    const int32_t r = check_draft_table(ctx, slot);
+    return r != GL3_OK ? r : gl3_draft_put_host(ctx, slot, q);
+}
+
+int32_t gl3_get_draft_probs(gl3_ctx* ctx, int32_t slot, float* out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!out) GL3_FAIL(GL3_E_ARG, "null out");
+    const int32_t r = check_draft_table(ctx, slot);
+    return r != GL3_OK ? r : gl3_draft_get(ctx, slot, out);
+}
+
 // The mixed step with every row an output row + verify_runs_kernel over its runs (gl3_sample.hip).  A step whose runs are all single rows
-// (nothing drafted) is a static-batched decode step, captured graph and all, as in gl3_forward_batch.
-int32_t gl3_forward_batch_verify(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const float* temperature,
-                                 const float* coins, gl3_verify_result* results_out, int32_t* n_runs_out) {
+// (nothing drafted) is a static-batched decode step, captured graph and all, as in gl3_forward_batch.  dist: the _dist entry (q_slots by row)
+static int32_t forward_batch_verify(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const float* temperature,
+                                    const float* coins, bool dist, const int32_t* q_slots, gl3_verify_result* results_out, int32_t* n_runs_out) {
     if (!ctx) return GL3_E_ARG;
     int32_t r = check_verify(ctx);
     if (r != GL3_OK) return r;
@@ -1334,21 +1376,31 @@ int32_t gl3_forward_batch_verify(gl3_ctx* ctx, const int32_t* tokens, const int3
     const int n_runs = (int)bp.runs.size();
     std::vector<int32_t> row0((size_t)n_runs), rows((size_t)n_runs);
     for (int k = 0; k < n_runs; ++k) { row0[k] = bp.runs[k].row0; rows[k] = bp.runs[k].rows; }
-    if ((r = gl3_verify_prepare(ctx, n, tokens, coins, n_runs, row0.data(), rows.data(), temperature)) != GL3_OK) return r;
+    if ((r = gl3_verify_prepare(ctx, n, tokens, coins, n_runs, row0.data(), rows.data(), temperature, dist, q_slots)) != GL3_OK) return r;
     r = bp.single_rows ? gl3_decode_batch_run(ctx, tokens, seq_ids, positions, n, nullptr, nullptr, false)
                        : gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, nullptr, false);
     if (r != GL3_OK) return r;
     const float* logits; const int32_t* greedy;
     gl3_decode_batch_outputs(ctx, &logits, &greedy);
-    if ((r = gl3_verify_enqueue(ctx, logits, greedy, n_runs)) != GL3_OK) return r;
+    if ((r = gl3_verify_enqueue(ctx, logits, greedy, n_runs, dist)) != GL3_OK) return r;
     if (bp.single_rows && (r = gl3_prefill_tap_x(ctx, n - 1, n)) != GL3_OK) return r;      // gl3_get_x answers for the last row, as after every mixed step
     if ((r = gl3_verify_collect(ctx, n_runs, results_out)) != GL3_OK) return r;
     *n_runs_out = n_runs;
     return GL3_OK;
 }
 
-int32_t gl3_verify_rows(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs, const float* temperature,
-                        const float* coins, gl3_verify_result* results_out) {
+int32_t gl3_forward_batch_verify(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const float* temperature,
+                                 const float* coins, gl3_verify_result* results_out, int32_t* n_runs_out) {
+    return forward_batch_verify(ctx, tokens, seq_ids, positions, n, temperature, coins, false, nullptr, results_out, n_runs_out);
+}
+
+int32_t gl3_forward_batch_verify_dist(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const float* temperature,
+                                      const float* coins, const int32_t* q_slots, gl3_verify_result* results_out, int32_t* n_runs_out) {
+    return forward_batch_verify(ctx, tokens, seq_ids, positions, n, temperature, coins, true, q_slots, results_out, n_runs_out);
+}
+
+static int32_t verify_rows(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs, const float* temperature,
+                           const float* coins, bool dist, const int32_t* q_slots, gl3_verify_result* results_out) {
     if (!ctx) return GL3_E_ARG;
     if (!logits || !tokens || !run_rows || !results_out || n_runs <= 0) GL3_FAIL(GL3_E_ARG, "bad logits / tokens / run_rows / results_out arrays");
     int32_t r = check_verify(ctx);
@@ -1363,12 +1415,22 @@ int32_t gl3_verify_rows(gl3_ctx* ctx, const float* logits, const int32_t* tokens
     }
     for (int i = 0; i < (int)n; ++i)
         if (tokens[i] < 0 || tokens[i] >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
-    if ((r = gl3_verify_prepare(ctx, (int32_t)n, tokens, coins, n_runs, row0.data(), run_rows, temperature)) != GL3_OK) return r;
+    if ((r = gl3_verify_prepare(ctx, (int32_t)n, tokens, coins, n_runs, row0.data(), run_rows, temperature, dist, q_slots)) != GL3_OK) return r;
     if ((r = gl3_decode_batch_load_logits(ctx, logits, (int32_t)n)) != GL3_OK) return r;
     const float* logits_dev; const int32_t* greedy;
     gl3_decode_batch_outputs(ctx, &logits_dev, &greedy);
-    if ((r = gl3_verify_enqueue(ctx, logits_dev, greedy, n_runs)) != GL3_OK) return r;
+    if ((r = gl3_verify_enqueue(ctx, logits_dev, greedy, n_runs, dist)) != GL3_OK) return r;
     return gl3_verify_collect(ctx, n_runs, results_out);
+}
+
+int32_t gl3_verify_rows(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs, const float* temperature,
+                        const float* coins, gl3_verify_result* results_out) {
+    return verify_rows(ctx, logits, tokens, run_rows, n_runs, temperature, coins, false, nullptr, results_out);
+}
+
+int32_t gl3_verify_rows_dist(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs, const float* temperature,
+                             const float* coins, const int32_t* q_slots, gl3_verify_result* results_out) {
+    return verify_rows(ctx, logits, tokens, run_rows, n_runs, temperature, coins, true, q_slots, results_out);
 }
 
 int32_t gl3_debug_batch_plan(const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits, int32_t n, int32_t n_seqs, int32_t ctx_len,

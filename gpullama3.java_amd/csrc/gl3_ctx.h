@@ -171,14 +171,24 @@ struct gl3_score_state {
 
 // Draft verification (verify_runs_kernel, gl3_sample.hip): a run and a row of the step as the kernel reads them.  A row's token is the
 // draft of the row before it in its run; accept / emit are the caller's two coins of the row (not looked at on a greedy run).
+// q (the _dist entries only; nothing else reads it): the slot of the draft table that holds the distribution the row's draft was drawn
+// from, -1 = the draft is a fixed token (the one-hot rule).
 struct VerifyRun { int row0, rows; float temperature; int pad; };
-struct VerifyRow { int token; float accept, emit; int pad; };
+struct VerifyRow { int token; float accept, emit; int q; };
 struct gl3_verify_state {
     int cap = 0;                               // rows (and so runs) every buffer below has room for: the plan's max_batch
     uint8_t* params = nullptr;                 // a step's VerifyRun[n_runs], then its VerifyRow[n]; room for cap of each
     uint8_t* h_params = nullptr;               // pinned, same layout
     gl3_verify_result* out = nullptr;          // [cap]
     gl3_verify_result* h_out = nullptr;        // pinned
+};
+
+// Draft distributions of a TARGET plan (gl3_draft_probs_put, gl3_sample.hip): slot s = the f32[vocab] distribution one drafted token was
+// drawn from.  Allocated on the first put, freed with the sampler buffers.
+struct gl3_draft_state {
+    float* q = nullptr;                        // [max_batch][vocab]
+    std::vector<uint8_t> written;              // [max_batch] the slot has been put
+    hipEvent_t copied = nullptr;               // behind the last plan-to-plan copy: the draft plan's stream waits for it before it samples again
 };
 
 struct gl3_ctx {
@@ -230,7 +240,9 @@ struct gl3_ctx {
     gl3_sample_state smp_one{256, false};         // gl3_forward_decode_sample: one row, eager launches
     gl3_sample_state smp_rows{64, true};          // static-batched entries: grows with the batch, one hipGraph per (rows, any top-p row)
     gl3_score_state score;                        // gl3_forward_batch_score / gl3_score_rows
-    gl3_verify_state verify;                      // gl3_forward_batch_verify / gl3_verify_rows
+    gl3_verify_state verify;                      // gl3_forward_batch_verify / gl3_verify_rows and their _dist forms
+    gl3_draft_state draft;                        // the draft distributions the _dist forms read
+    int last_sample_mode = -1;                    // SMP_* of the last gl3_forward_decode_sample (-1: none yet): what gl3_draft_probs_put may copy
     std::vector<std::pair<void*, size_t>> pinned;     // caller buffers registered with gl3_pin_host_buffer (logits land there directly)
     // upload staging
     uint8_t* staging = nullptr;
@@ -318,14 +330,20 @@ int32_t gl3_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);
 int32_t gl3_score_prepare(gl3_ctx* ctx, int32_t n, const int32_t* targets, const float* temperature);
 int32_t gl3_score_finish(gl3_ctx* ctx, const float* logits_dev, int32_t n, gl3_token_score* scores_out);
 void gl3_score_free(gl3_ctx* ctx);
-// draft verification: prepare = every check on (temperature, coins) + stage the runs and rows (before the step is enqueued): tokens /
-// coins ([n][2] or NULL) by row, run_row0 / run_rows / temperature (NULL: greedy everywhere) by run; enqueue = verify_runs_kernel and the
-// copy of 8 * n_runs bytes behind the step on the plan's stream; collect = wait and hand the records out
+// draft verification: prepare = every check on (temperature, coins, q_slots) + stage the runs and rows (before the step is enqueued):
+// tokens / coins ([n][2] or NULL) / q_slots by row, run_row0 / run_rows / temperature (NULL: greedy everywhere) by run; dist = the _dist
+// entries (q_slots must be there; the others pass NULL); enqueue = verify_runs_kernel<dist> and the copy of 8 * n_runs bytes behind the
+// step on the plan's stream; collect = wait and hand the records out
 int32_t gl3_verify_prepare(gl3_ctx* ctx, int32_t n, const int32_t* tokens, const float* coins, int32_t n_runs, const int32_t* run_row0,
-                           const int32_t* run_rows, const float* temperature);
-int32_t gl3_verify_enqueue(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n_runs);
+                           const int32_t* run_rows, const float* temperature, bool dist = false, const int32_t* q_slots = nullptr);
+int32_t gl3_verify_enqueue(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n_runs, bool dist = false);
 int32_t gl3_verify_collect(gl3_ctx* ctx, int32_t n_runs, gl3_verify_result* results_out);
 void gl3_verify_free(gl3_ctx* ctx);
+// draft distributions of a target plan (the argument checks are gl3_api.hip's): one slot from the draft plan's last sampled row, from
+// host memory, and back to the host
+int32_t gl3_draft_put(gl3_ctx* ctx, int32_t slot, gl3_ctx* draft);
+int32_t gl3_draft_put_host(gl3_ctx* ctx, int32_t slot, const float* q);
+int32_t gl3_draft_get(gl3_ctx* ctx, int32_t slot, float* out);
 
 // gl3_prefill.hip
 float* gl3_prefill_buf(gl3_ctx* ctx, int which);

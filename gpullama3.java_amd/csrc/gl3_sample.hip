@@ -39,7 +39,12 @@
 // every rank, so nothing is communicated behind the logits gather.  Two kernels read logits and take the layout {chunk width, rows}:
 // bsm_scale_max_kernel, whose plain probs rows feed every later sampler stage (tie fallback and parity taps included), and
 // score_rows_kernel.  With one rank the chunk width is the vocabulary and the addresses are the plain rows'.  Draft verification
-// (verify_runs_kernel) reads plain rows only: its entries stay one-rank.
+// (verify_runs_kernel) reads plain rows only — the logits and, in its _dist form, the draft distributions: its entries stay one-rank.
+//
+// Draft distributions.  A target plan keeps q[max_batch][vocab] f32 (gl3_draft_state, allocated on the first put): slot s = the
+// distribution ONE drafted token was drawn from, copied on the device from the row a draft PLAN's last gl3_forward_decode_sample left in
+// its smp_one.probs (gl3_draft_probs_put; never a top-p row, which is the untruncated softmax).  verify_runs_kernel<true> reads a slot as
+// float4 beside the logits quad; nothing else of [rows][vocab] size exists for it.
 //
 // The two entries are two instances of gl3_sample_state.  gl3_forward_decode_sample is the n = 1 case: 256 workgroups per element-wise
 // launch, launched eagerly, its SmpRow riding behind the (token, position) pair in ctx->dyn.  The static-batched entries
@@ -509,10 +514,21 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
 //                               end exceeds r is recomputed and one thread walks its cdf from the chunk's exact start to the first j
 //                               with r < cdf.  q[d] = 0 leaves the cdf at d where it was at d - 1, so d is never that j.  No chunk end above
 //                               r: the largest index other than d ("in case of rounding errors", CategoricalSampler.java:43).
+//   sampled run, a row whose    (gl3_forward_batch_verify_dist / gl3_verify_rows_dist, DIST = true, VerifyRow::q >= 0; a row with q = -1 is
+//   draft was drawn from q      decided as above, bit for bit.)  p[d] as above; the row accepts iff accept coin * q[d] < p[d] — one f32
+//                               product, no division: min(1, p[d] / q[d]) without the quotient, and q[d] == 0 accepts iff p[d] > 0.  The
+//                               row that rejects emits from the residual r[j] = fmaxf(e[j] / sum - q[j], 0f), the q quad read beside the
+//                               logits quad: S', the chunk ends and the walk of the hit chunk as above with r = emit coin * S'.  A
+//                               rejection implies q[d] >= p[d], so r[d] == 0 and d cannot come back; nothing special-cases it.  No chunk
+//                               end above r: S' == 0 (p <= q everywhere) -> the row's greedy id from the step's own greedy scan; S' > 0
+//                               (the product rounded up to S') -> the largest j with r[j] > 0, which every thread tracks while it
+//                               fills the chunks.  Lossless for a d drawn from q:
+//                               P(first emitted = x) = q(x) min(1, p(x) / q(x)) + (1 - sum min(p, q)) max(p(x) - q(x), 0) / sum max(p - q, 0)
+//                               = min(p(x), q(x)) + max(p(x) - q(x), 0) = p(x), since 1 - sum min(p, q) = sum max(p - q, 0).
 // Numerators are recomputed where they are needed a second time (one row and one chunk per run) instead of kept: no [rows][vocab] buffer
-// exists beside the logits, which are read, never written.  n % 4 == 0 as in score_rows_kernel.
-// LDS, all dynamic: xf [SM_CHUNK + 32], the scratch of exact_seqsum_lds, sh [8] ([0..3] wavefront maxima, [4] running sum, [5] numerator
-// of the draft, [6] accept flag / hit chunk), cend [nchunks].
+// exists beside the logits (and the draft table), which are read, never written.  n % 4 == 0 as in score_rows_kernel.
+// LDS, all dynamic (verify_smem): xf [SM_CHUNK + 32], the scratch of exact_seqsum_lds, sh [8] ([0..3] wavefront maxima, [4] running sum,
+// [5] numerator of the draft, [6] accept flag / hit chunk; DIST: sh [12], [8] the largest index with a positive residual), cend [nchunks].
 // The strictly sequential f32 sum of the LDS chunk xf[0 .. len) (all >= 0, zeros behind it up to SM_CHUNK + 32) continued from the exact
 // running value `run`: the exact parallel evaluation (gl3_seqsum.h) for >= 1024 elements (a multiple of 4), the naive chain for a
 // shorter chunk and for up to 3 trailing elements.  All 256 threads call it between two barriers; thread 0 holds the result.  (The split of
@@ -551,13 +567,43 @@ __device__ __forceinline__ void verify_fill_chunk(float* xf, const float4* lg4, 
     }
 }
 
+// The residual of a row whose draft was drawn from q: r[j] = fmaxf(e[j] / sum - q[j], 0f), the q quad read beside the logits quad (q4: the
+// slot's row, 16-byte aligned as the logits row is).  Returns the largest index of the chunk this thread gave a positive r, or -1.
+__device__ __forceinline__ int verify_fill_chunk_dist(float* xf, const float4* lg4, const float4* q4, int base, int len, float T, float mx, float sum, int t) {
+    int last = -1;
+    for (int i = 4 * t; i < SM_CHUNK + 32; i += 1024) {
+        float4 e = {0.f, 0.f, 0.f, 0.f};                              // zero padding behind the chunk (exact_seqsum_lds reads it)
+        if (i < len) {
+            const float4 v = lg4[(base + i) >> 2];
+            const float4 q = q4[(base + i) >> 2];
+            e.x = fmaxf((float)exp((double)(v.x / T - mx)) / sum - q.x, 0.f);      // max(p - q, 0): p exactly as the accept test saw it
+            e.y = fmaxf((float)exp((double)(v.y / T - mx)) / sum - q.y, 0.f);
+            e.z = fmaxf((float)exp((double)(v.z / T - mx)) / sum - q.z, 0.f);
+            e.w = fmaxf((float)exp((double)(v.w / T - mx)) / sum - q.w, 0.f);
+            const int j = base + i;
+            last = e.w > 0.f ? j + 3 : e.z > 0.f ? j + 2 : e.y > 0.f ? j + 1 : e.x > 0.f ? j : last;
+        }
+        *reinterpret_cast<float4*>(xf + i) = e;
+    }
+    return last;
+}
+
+// sh words in front of cend.  DIST adds [8] (an int) the largest index with a positive residual.
+constexpr int VERIFY_SH = 8, VERIFY_SH_DIST = 12;
+constexpr size_t verify_smem(int nchunks, bool dist) {
+    return (size_t)(SM_CHUNK + 32) * 4 + ss_scratch_bytes(SM_CHUNK) + (size_t)(dist ? VERIFY_SH_DIST : VERIFY_SH) * 4 + (size_t)nchunks * 4;
+}
+
+// DIST = false: gl3_forward_batch_verify / gl3_verify_rows, every draft a fixed token (qtab is not looked at).  DIST = true: the _dist
+// entries; a row whose VerifyRow::q names a slot of qtab ([slots][n]) is decided against that distribution, every other row as before.
+template <bool DIST>
 __global__ __launch_bounds__(256) void verify_runs_kernel(const float* __restrict__ logits, int n, const VerifyRun* __restrict__ runs, const VerifyRow* __restrict__ rows,
-                                                          const int32_t* __restrict__ greedy, gl3_verify_result* __restrict__ out) {
+                                                          const int32_t* __restrict__ greedy, gl3_verify_result* __restrict__ out, const float* __restrict__ qtab) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     float* xf = reinterpret_cast<float*>(smem);                      // [SM_CHUNK + 32]
     uint8_t* scratch = smem + (size_t)(SM_CHUNK + 32) * 4;
     float* sh = reinterpret_cast<float*>(scratch + ss_scratch_bytes(SM_CHUNK));
-    float* cend = sh + 8;                                            // [nchunks] S' after every chunk of the emitting row
+    float* cend = sh + (DIST ? VERIFY_SH_DIST : VERIFY_SH);          // [nchunks] S' after every chunk of the emitting row
     const VerifyRun R = runs[blockIdx.x];
     const int t = threadIdx.x;
     if (R.temperature == 0.f) {
@@ -574,6 +620,11 @@ __global__ __launch_bounds__(256) void verify_runs_kernel(const float* __restric
         const int row = R.row0 + a;
         const int d = a + 1 < R.rows ? rows[row + 1].token : -1;
         const float4* lg4 = reinterpret_cast<const float4*>(logits + (size_t)row * n);
+        const float4* q4 = nullptr;                                   // DIST: the distribution d was drawn from; null = a fixed token
+        if constexpr (DIST) {
+            const int qs = d >= 0 ? rows[row].q : -1;
+            if (qs >= 0) q4 = reinterpret_cast<const float4*>(qtab + (size_t)qs * n);
+        }
         float mx = -INFINITY;
         for (int i = t; i < (n >> 2); i += 256) {
             const float4 v = lg4[i];
@@ -597,7 +648,11 @@ __global__ __launch_bounds__(256) void verify_runs_kernel(const float* __restric
             __syncthreads();
         }
         const float sum = sh[4];
-        if (t == 0) sh[6] = d >= 0 && rows[row].accept < sh[5] / sum ? 1.f : 0.f;      // accept iff coin < p[d], strictly
+        if (DIST && q4) {
+            if (t == 0) sh[6] = rows[row].accept * reinterpret_cast<const float*>(q4)[d] < sh[5] / sum ? 1.f : 0.f;      // accept iff coin * q[d] < p[d], strictly
+        } else {
+            if (t == 0) sh[6] = d >= 0 && rows[row].accept < sh[5] / sum ? 1.f : 0.f;      // accept iff coin < p[d], strictly
+        }
         __syncthreads();
         if (sh[6] != 0.f) continue;      // every thread read `sum` and the flag; the next row writes sh[4..6] behind barriers of its own
         // ---- row a emits
@@ -605,9 +660,11 @@ __global__ __launch_bounds__(256) void verify_runs_kernel(const float* __restric
         if (t == 0) sh[4] = 0.f;
         __syncthreads();
         int walked = 0;
+        int last = -1;                                                // DIST: the largest index this thread gave a positive residual
         for (int c = 0; c < nchunks; ++c) {
             const int base = c * SM_CHUNK, len = min(SM_CHUNK, n - base);
-            verify_fill_chunk<true>(xf, lg4, base, len, T, mx, sum, d, t);
+            if (DIST && q4) last = max(last, verify_fill_chunk_dist(xf, lg4, q4, base, len, T, mx, sum, t));
+            else verify_fill_chunk<true>(xf, lg4, base, len, T, mx, sum, d, t);
             __syncthreads();
             const float run = chunk_seqsum(xf, len, scratch, t, sh[4]);
             __syncthreads();
@@ -625,9 +682,19 @@ __global__ __launch_bounds__(256) void verify_runs_kernel(const float* __restric
         __syncthreads();
         const int hit = (int)sh[6];
         int token = d == n - 1 ? n - 2 : n - 1;                        // no j with r < cdf_j: the largest index other than d
+        if (DIST && q4 && hit < 0) {
+            // S' == 0 (p <= q everywhere): the row's greedy id.  Else (r rounded up to S'): the largest j with a positive residual
+            int* lastpos = reinterpret_cast<int*>(sh + VERIFY_SH);
+            if (t == 0) *lastpos = -1;
+            __syncthreads();
+            if (last >= 0) atomicMax(lastpos, last);
+            __syncthreads();
+            token = sh[4] == 0.f ? greedy[row] : *lastpos;
+        }
         if (hit >= 0) {
             const int base = hit * SM_CHUNK, len = min(SM_CHUNK, n - base);
-            verify_fill_chunk<true>(xf, lg4, base, len, T, mx, sum, d, t);
+            if (DIST && q4) verify_fill_chunk_dist(xf, lg4, q4, base, len, T, mx, sum, t);
+            else verify_fill_chunk<true>(xf, lg4, base, len, T, mx, sum, d, t);
             __syncthreads();
             if (t == 0) {
                 float cdf = hit ? cend[hit - 1] : 0.f;
@@ -659,9 +726,17 @@ static void sample_free_buffers(gl3_sample_state* b) {
     b->rows = 0; b->last_n = 0;
 }
 
+static void draft_free(gl3_ctx* ctx) {
+    gl3_draft_state* b = &ctx->draft;
+    if (b->q) hipFree(b->q);
+    if (b->copied) hipEventDestroy(b->copied);
+    *b = gl3_draft_state{};
+}
+
 void gl3_sample_free(gl3_ctx* ctx) {
     sample_free_buffers(&ctx->smp_one);
     sample_free_buffers(&ctx->smp_rows);
+    draft_free(ctx);
 }
 
 static int32_t sample_alloc_all(gl3_ctx* ctx, gl3_sample_state* b, int rows) {
@@ -889,9 +964,57 @@ void gl3_verify_free(gl3_ctx* ctx) {
     *b = gl3_verify_state{};
 }
 
+// ---- draft distributions of a target plan: q[max_batch][vocab], the table and its event on the first put, all or none
+static int32_t draft_slot(gl3_ctx* ctx, int32_t slot, float** row) {
+    gl3_draft_state* b = &ctx->draft;
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    if (!b->q) {
+        hipError_t e = hipMalloc((void**)&b->q, (size_t)ctx->d.max_batch * ctx->d.vocab * 4);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&b->copied, hipEventDisableTiming);
+        if (e != hipSuccess) { draft_free(ctx); GL3_HIP(e); }
+        b->written.assign((size_t)ctx->d.max_batch, 0);
+    }
+    *row = b->q + (size_t)slot * ctx->d.vocab;
+    return GL3_OK;
+}
+
+// One device-to-device copy on the TARGET's stream, behind whatever the target enqueued last.  The draft plan's forward has returned, so
+// its stream is idle and the row is complete; the draft's stream then waits for the copy, so its next sampled step cannot overwrite the
+// row under it.  Nothing waits on the host.
+int32_t gl3_draft_put(gl3_ctx* ctx, int32_t slot, gl3_ctx* draft) {
+    float* row = nullptr;
+    const int32_t r = draft_slot(ctx, slot, &row);
+    if (r != GL3_OK) return r;
+    GL3_HIP(hipMemcpyAsync(row, draft->smp_one.probs, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    GL3_HIP(hipEventRecord(ctx->draft.copied, ctx->stream));
+    GL3_HIP(hipStreamWaitEvent(draft->stream, ctx->draft.copied, 0));
+    ctx->draft.written[slot] = 1;
+    return GL3_OK;
+}
+
+int32_t gl3_draft_put_host(gl3_ctx* ctx, int32_t slot, const float* q) {
+    float* row = nullptr;
+    const int32_t r = draft_slot(ctx, slot, &row);
+    if (r != GL3_OK) return r;
+    GL3_HIP(hipMemcpyAsync(row, q, (size_t)ctx->d.vocab * 4, hipMemcpyHostToDevice, ctx->stream));
+    GL3_HIP(hipStreamSynchronize(ctx->stream));      // q is the caller's (pageable) memory: done with it on return
+    ctx->draft.written[slot] = 1;
+    return GL3_OK;
+}
+
+int32_t gl3_draft_get(gl3_ctx* ctx, int32_t slot, float* out) {
+    const gl3_draft_state* b = &ctx->draft;
+    if (!b->q || !b->written[slot]) GL3_FAIL(GL3_E_STATE, "the draft-distribution slot was never written");
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    GL3_HIP(hipMemcpyAsync(out, b->q + (size_t)slot * ctx->d.vocab, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
+    return GL3_OK;
+}
+
 int32_t gl3_verify_prepare(gl3_ctx* ctx, int32_t n, const int32_t* tokens, const float* coins, int32_t n_runs, const int32_t* run_row0,
-                           const int32_t* run_rows, const float* temperature) {
+                           const int32_t* run_rows, const float* temperature, bool dist, const int32_t* q_slots) {
     gl3_verify_state* b = &ctx->verify;
+    if (dist && !q_slots) GL3_FAIL(GL3_E_ARG, "null q_slots");
     for (int k = 0; k < n_runs; ++k) {
         const float T = temperature ? temperature[k] : 0.f;
         if (!(T >= 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be >= 0");
@@ -900,6 +1023,17 @@ int32_t gl3_verify_prepare(gl3_ctx* ctx, int32_t n, const int32_t* tokens, const
         for (int i = 2 * run_row0[k]; i < 2 * (run_row0[k] + run_rows[k]); ++i)
             if (!(coins[i] >= 0.f && coins[i] < 1.f)) GL3_FAIL(GL3_E_ARG, "coin must be rng.nextFloat(1f): in [0, 1)");
     }
+    // q_slots of the rows that look at them: the rows of a sampled run that have a draft (all but the run's last).  Range first, for every
+    // such row, then whether the slot was ever put
+    for (int pass = 0; dist && pass < 2; ++pass)
+        for (int k = 0; k < n_runs; ++k) {
+            if (!temperature || temperature[k] == 0.f) continue;
+            for (int i = run_row0[k]; i + 1 < run_row0[k] + run_rows[k]; ++i) {
+                const int32_t s = q_slots[i];
+                if (pass == 0 && (s < -1 || s >= ctx->d.max_batch)) GL3_FAIL(GL3_E_ARG, "q_slots entry outside [-1, max_batch)");
+                if (pass == 1 && s >= 0 && !(ctx->draft.q && ctx->draft.written[s])) GL3_FAIL(GL3_E_STATE, "q_slots names a draft-distribution slot that was never written");
+            }
+        }
     GL3_HIP(hipSetDevice(ctx->d.device));
     if (!b->cap) {      // once, for the largest step the plan takes (a run has at least one row); all or none, as sample_alloc
         const size_t cap = (size_t)ctx->d.max_batch, bytes = cap * (sizeof(VerifyRun) + sizeof(VerifyRow));
@@ -913,18 +1047,20 @@ int32_t gl3_verify_prepare(gl3_ctx* ctx, int32_t n, const int32_t* tokens, const
     VerifyRun* hr = reinterpret_cast<VerifyRun*>(b->h_params);      // the n rows lie right behind the n_runs runs: one copy of what the step uses
     VerifyRow* hw = reinterpret_cast<VerifyRow*>(b->h_params + (size_t)n_runs * sizeof(VerifyRun));
     for (int k = 0; k < n_runs; ++k) hr[k] = VerifyRun{run_row0[k], run_rows[k], temperature ? temperature[k] : 0.f, 0};
-    for (int i = 0; i < n; ++i) hw[i] = VerifyRow{tokens[i], coins ? coins[2 * i] : 0.f, coins ? coins[2 * i + 1] : 0.f, 0};
+    for (int i = 0; i < n; ++i) hw[i] = VerifyRow{tokens[i], coins ? coins[2 * i] : 0.f, coins ? coins[2 * i + 1] : 0.f, dist ? q_slots[i] : -1};
     GL3_HIP(hipMemcpyAsync(b->params, b->h_params, (size_t)n_runs * sizeof(VerifyRun) + (size_t)n * sizeof(VerifyRow), hipMemcpyHostToDevice, ctx->stream));
     return GL3_OK;
 }
 
-int32_t gl3_verify_enqueue(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n_runs) {
+int32_t gl3_verify_enqueue(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n_runs, bool dist) {
     gl3_verify_state* b = &ctx->verify;
     hipStream_t s = ctx->stream;
     const int v = ctx->d.vocab, nchunks = (v + SM_CHUNK - 1) / SM_CHUNK;
-    const size_t smem = (size_t)(SM_CHUNK + 32) * 4 + ss_scratch_bytes(SM_CHUNK) + 32 + (size_t)nchunks * 4;
-    hipLaunchKernelGGL(verify_runs_kernel, dim3(n_runs), dim3(256), smem, s, logits_dev, v, reinterpret_cast<const VerifyRun*>(b->params),
-                       reinterpret_cast<const VerifyRow*>(b->params + (size_t)n_runs * sizeof(VerifyRun)), greedy_dev, b->out);
+    const VerifyRun* runs = reinterpret_cast<const VerifyRun*>(b->params);
+    const VerifyRow* rows = reinterpret_cast<const VerifyRow*>(b->params + (size_t)n_runs * sizeof(VerifyRun));
+    // the draft table may not exist (every q_slots entry -1): no row then looks at it
+    if (dist) hipLaunchKernelGGL(verify_runs_kernel<true>, dim3(n_runs), dim3(256), verify_smem(nchunks, true), s, logits_dev, v, runs, rows, greedy_dev, b->out, ctx->draft.q);
+    else hipLaunchKernelGGL(verify_runs_kernel<false>, dim3(n_runs), dim3(256), verify_smem(nchunks, false), s, logits_dev, v, runs, rows, greedy_dev, b->out, (const float*)nullptr);
     GL3_HIP(hipGetLastError());
     GL3_HIP(hipMemcpyAsync(b->h_out, b->out, (size_t)n_runs * sizeof(gl3_verify_result), hipMemcpyDeviceToHost, s));
     return GL3_OK;

@@ -308,6 +308,54 @@ class HipMasterPlan:
                                             _p(co) if co is not None else None, _p(res)), self._ctx)
         return res
 
+    def draft_probs_put(self, slot: int, draft_plan: "HipMasterPlan"):
+        """Slot `slot` of this (target) plan's draft table = the row draft_plan.sample_probs() returns, copied on the device
+        (gl3_draft_probs_put)."""
+        hip.check(hip.lib().gl3_draft_probs_put(self._ctx, slot, draft_plan._ctx if draft_plan is not None else None), self._ctx)
+
+    def draft_probs_put_host(self, slot: int, q):
+        """The same slot from host memory, f32[vocab], taken as it is."""
+        q = np.ascontiguousarray(q, np.float32) if q is not None else None
+        assert q is None or q.shape == (self.cfg.vocab,)
+        hip.check(hip.lib().gl3_draft_probs_put_host(self._ctx, slot, _p(q) if q is not None else None), self._ctx)
+
+    def draft_probs(self, slot: int) -> np.ndarray:
+        """Slot `slot` of the draft table back on the host."""
+        out = np.empty(self.cfg.vocab, np.float32)
+        hip.check(hip.lib().gl3_get_draft_probs(self._ctx, slot, _p(out)), self._ctx)
+        return out
+
+    @staticmethod
+    def _q_slots(q_slots, n):
+        """q_slots int32[n] (a scalar broadcasts; None: NULL, which the library refuses)"""
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(q_slots, np.int32), (n,))) if q_slots is not None else None
+
+    def forward_batch_verify_dist(self, tokens, seq_ids, positions, temperature=None, coins=None, q_slots=-1) -> np.ndarray:
+        """forward_batch_verify with q_slots: per row the slot of the draft table its draft was drawn from, -1 = a fixed token
+        (gl3_forward_batch_verify_dist) -> structured array [n_runs] with fields accepted and token."""
+        t, s, p, _, n_runs = self._mixed_args(tokens, seq_ids, positions, None)
+        te, co = self._verify_args(temperature, coins, n_runs, t.size)
+        qs = self._q_slots(q_slots, t.size)
+        res = np.zeros(max(t.size, 1), VERIFY_DTYPE)
+        got = C.c_int32(0)
+        hip.check(hip.lib().gl3_forward_batch_verify_dist(self._ctx, _p(t), _p(s), _p(p), t.size, _p(te) if te is not None else None,
+                                                          _p(co) if co is not None else None, _p(qs) if qs is not None else None,
+                                                          _p(res), C.byref(got)), self._ctx)
+        return res[:got.value].copy()
+
+    def verify_rows_dist(self, logits, tokens, run_rows, temperature=None, coins=None, q_slots=-1) -> np.ndarray:
+        """verify_rows with q_slots (gl3_verify_rows_dist) -> structured array [n_runs] with fields accepted and token."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2 and lg.shape[1] == self.cfg.vocab
+        t = np.ascontiguousarray(tokens, np.int32); rr = np.ascontiguousarray(run_rows, np.int32)
+        assert t.size == lg.shape[0] == int(rr.sum())
+        te, co = self._verify_args(temperature, coins, rr.size, t.size)
+        qs = self._q_slots(q_slots, t.size)
+        res = np.zeros(rr.size, VERIFY_DTYPE)
+        hip.check(hip.lib().gl3_verify_rows_dist(self._ctx, _p(lg), _p(t), _p(rr), rr.size, _p(te) if te is not None else None,
+                                                 _p(co) if co is not None else None, _p(qs) if qs is not None else None, _p(res)), self._ctx)
+        return res
+
     def sample_probs_row(self, row: int) -> np.ndarray:
         """The probabilities row `row` of the last batched sampled step was drawn from."""
         out = np.empty(self.cfg.vocab, np.float32)

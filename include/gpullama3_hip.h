@@ -368,6 +368,45 @@ GL3_API int32_t gl3_forward_batch_verify(gl3_ctx* ctx, const int32_t* tokens, co
  * step is overwritten.  Otherwise errors as above. */
 GL3_API int32_t gl3_verify_rows(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs,
                                 const float* temperature, const float* coins, gl3_verify_result* results_out);
+/* Speculative decoding with a DRAFT MODEL: a second plan in the same process drafts with gl3_forward_decode_sample, and the target plan
+ * verifies each draft against the distribution it was actually drawn from.  The target plan owns a device table q[max_batch][vocab] of f32,
+ * allocated on the first put and freed with the plan; slot s holds the distribution ONE drafted token was drawn from.
+ * gl3_draft_probs_put: slot `slot` of `target` = the row gl3_get_sample_probs(draft) would return, the softmax row of the draft plan's last
+ * gl3_forward_decode_sample.  One device-to-device copy on the target's stream; the call returns once it is enqueued (the draft's forward has
+ * returned, so the row is complete; the draft's stream is made to wait for the copy before it runs anything else, the host waits for
+ * nothing).  GL3_E_ARG: a null plan, draft == target, slot outside [0, max_batch) of the target, different vocabularies, plans on different
+ * devices.  GL3_E_STATE: the draft plan has sampled nothing yet; its last gl3_forward_decode_sample was greedy (temperature 0: there is no
+ * row); it went through ToppSampler (0 < topp < 1: the row is the untruncated softmax, not what the token was drawn from, and verifying
+ * against it would silently stop being lossless).  GL3_E_UNSUPPORTED: a target without max_batch > 1; tp_size > 1 on either plan. */
+GL3_API int32_t gl3_draft_probs_put(gl3_ctx* target, int32_t slot, gl3_ctx* draft);
+/* Parity tap: the same slot from host memory, q: f32[vocab], taken as it is — finite and >= 0 is the caller's contract, nothing scans it. */
+GL3_API int32_t gl3_draft_probs_put_host(gl3_ctx* target, int32_t slot, const float* q);
+/* Parity tap: slot `slot` back to the host (out: f32[vocab]).  GL3_E_STATE for a slot that was never written. */
+GL3_API int32_t gl3_get_draft_probs(gl3_ctx* target, int32_t slot, float* out);
+/* gl3_forward_batch_verify with a draft distribution per row.  Everything — runs, coins [n][2], the KV contract, one decision launch, 8 bytes
+ * per run back, the refusals — is gl3_forward_batch_verify's; the addition is q_slots: int32[n], one entry per row.  For a row i that has a
+ * draft d (every row of a run but its last): q_slots[i] = -1 -> the row is decided by gl3_forward_batch_verify's one-hot rule, bit for bit;
+ * q_slots[i] = s >= 0 -> by the rule below with q = slot s of the draft table.  Greedy runs (temperature 0) and the last row of a run never
+ * look at their entry.
+ *   All in f32, p exactly as in gl3_forward_batch_verify (p[j] = e[j] / sum, gl3_token_score's arithmetic).
+ *   Accept iff coins[i][0] * q[d] < p[d]: one f32 product, strictly less, no division — min(1, p[d] / q[d]) without the quotient; q[d] == 0
+ *   accepts iff p[d] > 0.
+ *   Reject: r[j] = fmaxf(p[j] - q[j], 0f) for every j.  A rejection implies q[d] >= p[d], so r[d] == 0 and d cannot come back; nothing
+ *   special-cases it.  S' = the strictly sequential f32 sum of r, target = coins[i][1] * S', token = the first j with target < cdf_j (cdf =
+ *   the sequential f32 sum of r).  No such j and S' > 0 (the product rounded up to S'): the largest j with r[j] > 0.  S' == 0 (p <= q
+ *   everywhere, e.g. q bitwise equal to p): the row's greedy id, from the step's own greedy scan.
+ *   All drafts of a run stand: the last row is CategoricalSampler with its emit coin, unchanged.
+ *   Lossless in distribution for a draft d drawn from q: P(first emitted = x) = q(x) min(1, p(x) / q(x)) + (1 - sum_y min(p(y), q(y)))
+ *   max(p(x) - q(x), 0) / sum_y max(p(y) - q(y), 0) = min(p(x), q(x)) + max(p(x) - q(x), 0) = p(x), since 1 - sum min(p, q) = sum max(p - q, 0).
+ * GL3_E_ARG, before anything is enqueued: what gl3_forward_batch_verify refuses; q_slots NULL; an entry below -1 or >= max_batch on a row of
+ * a sampled run that has a draft.  GL3_E_STATE: such an entry names a slot that was never written.  GL3_E_UNSUPPORTED: max_batch <= 1;
+ * tp_size > 1 (this entry, gl3_verify_rows_dist and the three draft-table entries are ONE-rank, as gl3_forward_batch_verify is). */
+GL3_API int32_t gl3_forward_batch_verify_dist(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
+                                              const float* temperature, const float* coins, const int32_t* q_slots,
+                                              gl3_verify_result* results_out, int32_t* n_runs_out);
+/* Parity tap: the same decision on caller-supplied logits (host f32[n][vocab]), as gl3_verify_rows; q_slots: int32[n]. */
+GL3_API int32_t gl3_verify_rows_dist(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs,
+                                     const float* temperature, const float* coins, const int32_t* q_slots, gl3_verify_result* results_out);
 /* Test hook, no plan and no device: the host-side plan of a mixed step (csrc/gl3_batch_plan.h) for a plan with n_seqs sequence slots,
  * context length ctx and room for `capacity` rows.  runs_out / tiles_out: int32[.][4] = {first row, rows, sequence, position of the
  * first row}, room for n records each (tiles: at most 8 rows, never across a run boundary, deepest last position first); out_rows:

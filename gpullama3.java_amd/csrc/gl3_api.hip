@@ -1120,6 +1120,58 @@ int32_t gl3_forward_decode_sample(gl3_ctx* ctx, int32_t token, int32_t pos, floa
     return gl3_sample_run(ctx, ctx->logits, token_out);          // ends with the stream synchronisation and gl3_tp_check
 }
 
+// k single-token steps behind one wait.  Everything the host decides about step j — its attention regime, which captured step to replay —
+// depends on position + j alone, so all k steps are enqueued before the first has run; what step j + 1 cannot know on the host, the id
+// step j draws, is handed over on the device (chain_handover_kernel, gl3_sample.hip).  The step and the sampler are the launches of
+// gl3_forward_decode_sample, chosen the same way, so the chain computes what k of those calls compute.
+int32_t gl3_forward_decode_chain(gl3_ctx* ctx, int32_t token, int32_t pos, int32_t k, float temperature, const float* coins, gl3_ctx* target,
+                                 int32_t slot0, int32_t* tokens_out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!tokens_out) GL3_FAIL(GL3_E_ARG, "null tokens_out");
+    if (k <= 0 || k > GL3_CHAIN_MAX) GL3_FAIL(GL3_E_ARG, "chain length outside [1, GL3_CHAIN_MAX]");
+    if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "the decode chain is built for one rank (tp_size == 1): under folded gathers the peers' step counters would have to advance together");
+    if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
+    if (token < 0 || token >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
+    if (pos < 0 || pos > ctx->d.ctx - k) GL3_FAIL(GL3_E_ARG, "chained positions outside the KV cache (context length)");
+    if (!(temperature >= 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be >= 0");
+    const bool sampled = temperature > 0.f;                       // temperature == 0: a greedy chain, the coins are not looked at
+    if (sampled) {
+        if (!coins) GL3_FAIL(GL3_E_ARG, "null coins with a temperature > 0");
+        for (int j = 0; j < k; ++j)
+            if (!(coins[j] >= 0.f && coins[j] < 1.f)) GL3_FAIL(GL3_E_ARG, "coin must be rng.nextFloat(1f): in [0, 1)");
+    }
+    if (target) {                                                 // what k gl3_draft_probs_put(target, slot0 + j, ctx) would refuse, ahead of the first step
+        if (target == ctx) GL3_FAIL(GL3_E_ARG, "the target plan must be another plan");
+        if (target->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "draft verification is built for one rank (tp_size == 1), the target plan included");
+        if (!target->finalized) GL3_FAIL(GL3_E_STATE, "draft distributions before gl3_finalize of the target plan");
+        if (!target->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "draft distributions are read by draft verification, which needs max_batch > 1 on the target plan");
+        if (slot0 < 0 || slot0 > target->d.max_batch - k) GL3_FAIL(GL3_E_ARG, "draft-distribution slots outside [0, max_batch) of the target plan");
+        if (target->d.vocab != ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "the target plan has another vocabulary");
+        if (target->d.device != ctx->d.device) GL3_FAIL(GL3_E_ARG, "the target plan is on another device");
+        if (!sampled) GL3_FAIL(GL3_E_STATE, "a greedy chain has no probabilities to put into the target's table");
+    }
+    float* q_row0 = nullptr;
+    int32_t r = gl3_chain_prepare(ctx, k, sampled ? coins : nullptr, target, slot0, &q_row0);
+    if (r != GL3_OK) return r;
+    const SmpRow row = gl3_smp_row(temperature, 0.f, sampled ? coins[0] : 0.f);
+    if ((r = set_dyn(ctx, token, pos, sampled ? &row : nullptr)) != GL3_OK) return r;
+    for (int j = 0; j < k; ++j) {
+        const int amode = attn_mode(ctx, pos + j);
+        if (ctx->graph_exec[ATT_LONG]) GL3_HIP(hipGraphLaunch(step_graph(ctx, amode), ctx->stream));
+        else if ((r = enqueue_decode(ctx, true, nullptr, amode)) != GL3_OK) return r;
+        if (!sampled) hipLaunchKernelGGL(argmax_kernel, dim3(AMX_WGS), dim3(256), 0, ctx->stream, ctx->logits, ctx->d.vocab, ctx->argmax);
+        else if ((r = gl3_chain_sample(ctx)) != GL3_OK) return r;
+        if ((r = gl3_chain_handover(ctx, j, k, pos + j + 1, sampled, q_row0 ? q_row0 + (size_t)j * ctx->d.vocab : nullptr)) != GL3_OK) return r;
+    }
+    ctx->last_sample_mode = row.mode;
+    if ((r = gl3_chain_collect(ctx, k, sampled, target, slot0, tokens_out)) != GL3_OK) return r;
+    // the host's copy of (token, position, row) as the last single call would have left it (the profiling entries read it)
+    ctx->h_dyn[0] = k > 1 ? tokens_out[k - 2] : token; ctx->h_dyn[1] = pos + k - 1;
+    if (sampled) reinterpret_cast<SmpRow*>(ctx->h_dyn + GL3_DYN_ROW)->coin = coins[k - 1];
+    else *ctx->h_argmax = tokens_out[k - 1];
+    return GL3_OK;
+}
+
 int32_t gl3_tp_fold_mode(gl3_ctx* ctx, int32_t* mode, int32_t* consumer_mask) {
     if (!ctx || !mode || !consumer_mask) return GL3_E_ARG;
     if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "gl3_tp_fold_mode before gl3_finalize");

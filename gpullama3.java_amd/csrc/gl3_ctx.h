@@ -191,6 +191,15 @@ struct gl3_draft_state {
     hipEvent_t copied = nullptr;               // behind the last plan-to-plan copy: the draft plan's stream waits for it before it samples again
 };
 
+// Draft chain (gl3_forward_decode_chain, gl3_sample.hip): the ids the chained steps hand over and the coins they take, on the device.
+// Allocated on the first chain for GL3_CHAIN_MAX entries, all or none, freed with the sampler buffers.
+struct gl3_chain_state {
+    int* ids = nullptr;                        // [GL3_CHAIN_MAX] id of step j, written by its hand-over launch
+    float* coins = nullptr;                    // [GL3_CHAIN_MAX] coin of step j (step 0's also rides in dyn's SmpRow)
+    int* h_ids = nullptr;                      // pinned
+    float* h_coins = nullptr;                  // pinned
+};
+
 struct gl3_ctx {
     gl3_model_desc d{};
     // derived (local = this tensor-parallel rank's share)
@@ -242,7 +251,8 @@ struct gl3_ctx {
     gl3_score_state score;                        // gl3_forward_batch_score / gl3_score_rows
     gl3_verify_state verify;                      // gl3_forward_batch_verify / gl3_verify_rows and their _dist forms
     gl3_draft_state draft;                        // the draft distributions the _dist forms read
-    int last_sample_mode = -1;                    // SMP_* of the last gl3_forward_decode_sample (-1: none yet): what gl3_draft_probs_put may copy
+    gl3_chain_state chain;                        // gl3_forward_decode_chain
+    int last_sample_mode = -1;                    // SMP_* of the last gl3_forward_decode_sample or chained step (-1: none yet): what gl3_draft_probs_put may copy
     std::vector<std::pair<void*, size_t>> pinned;     // caller buffers registered with gl3_pin_host_buffer (logits land there directly)
     // upload staging
     uint8_t* staging = nullptr;
@@ -344,6 +354,13 @@ void gl3_verify_free(gl3_ctx* ctx);
 int32_t gl3_draft_put(gl3_ctx* ctx, int32_t slot, gl3_ctx* draft);
 int32_t gl3_draft_put_host(gl3_ctx* ctx, int32_t slot, const float* q);
 int32_t gl3_draft_get(gl3_ctx* ctx, int32_t slot, float* out);
+// draft chain (the argument checks are gl3_api.hip's): prepare = the lists, the single-row sampler buffers (coins != NULL: a sampled chain)
+// and the target's table on first use, then the k coins up in one copy; sample = the single-row sampler's launches behind a chained step;
+// handover = the launch that passes step j's id (and its probabilities row, q_row != NULL) on; collect = the one wait, 4 * k bytes back
+int32_t gl3_chain_prepare(gl3_ctx* ctx, int32_t k, const float* coins, gl3_ctx* target, int32_t slot0, float** q_row0);
+int32_t gl3_chain_sample(gl3_ctx* ctx);
+int32_t gl3_chain_handover(gl3_ctx* ctx, int32_t j, int32_t k, int32_t next_pos, bool sampled, float* q_row);
+int32_t gl3_chain_collect(gl3_ctx* ctx, int32_t k, bool sampled, gl3_ctx* target, int32_t slot0, int32_t* tokens_out);
 
 // gl3_prefill.hip
 float* gl3_prefill_buf(gl3_ctx* ctx, int which);

@@ -46,6 +46,10 @@
 // its smp_one.probs (gl3_draft_probs_put; never a top-p row, which is the untruncated softmax).  verify_runs_kernel<true> reads a slot as
 // float4 beside the logits quad; nothing else of [rows][vocab] size exists for it.
 //
+// Draft chain (gl3_forward_decode_chain).  k single-row steps of one plan enqueued back to back: behind each step's sampler (or greedy scan)
+// chain_handover_kernel passes the id on to the next step through ctx->dyn and, for a target plan, copies the row into the table itself.
+// The sampler's launches are the single-row entry's (sample_launch); only the copy back and the wait happen once per chain.
+//
 // The two entries are two instances of gl3_sample_state.  gl3_forward_decode_sample is the n = 1 case: 256 workgroups per element-wise
 // launch, launched eagerly, its SmpRow riding behind the (token, position) pair in ctx->dyn.  The static-batched entries
 // (gl3_forward_decode_batch_sample, gl3_sample_rows) use 64 workgroups per row and replay one hipGraph per (row count, any top-p row).
@@ -706,6 +710,28 @@ __global__ __launch_bounds__(256) void verify_runs_kernel(const float* __restric
     }
 }
 
+// Draft chain (gl3_forward_decode_chain): the hand-over between step j and step j + 1 of a chain, one launch behind step j's sampler (or
+// greedy scan).  id_src = smp_one.res (sampled) or ctx->argmax (greedy): [0] is the step's id.  Thread 0 of workgroup 0 files the id in
+// ids[j] and, when a step follows (has_next), makes it that step's input: dyn[0] = id, dyn[1] = next_pos, and on a sampled chain the next
+// coin into the SmpRow behind the pair (temperature, topp and mode stay what the host uploaded).  The chain's last step writes no dyn, so dyn
+// ends as the last single call's upload would leave it.  q4 != NULL: every workgroup copies its share of the probabilities row (n4 float4s;
+// vocab % 16 == 0 at gl3_create) into the target plan's draft table.  The copy is part of this launch, not a hipMemcpyAsync behind it: it
+// has to be on the draft plan's stream ahead of the next step's sampler, which overwrites probs, and here it costs no launch of its own.
+// Plain vector stores only; nothing in the launch reads what it writes.
+__global__ __launch_bounds__(256) void chain_handover_kernel(const int* __restrict__ id_src, int* __restrict__ ids, int j, int* __restrict__ dyn, int has_next, int next_pos,
+                                                             const float* __restrict__ coins, const float4* __restrict__ probs4, float4* __restrict__ q4, int n4) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int id = id_src[0];
+        ids[j] = id;
+        if (has_next) {
+            dyn[0] = id; dyn[1] = next_pos;
+            if (coins) reinterpret_cast<SmpRow*>(dyn + GL3_DYN_ROW)->coin = coins[j + 1];
+        }
+    }
+    if (q4)
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) q4[i] = probs4[i];
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static void sample_drop_graphs(gl3_sample_state* b) {
     for (auto& ge : b->graphs) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }
@@ -733,10 +759,20 @@ static void draft_free(gl3_ctx* ctx) {
     *b = gl3_draft_state{};
 }
 
+static void chain_free(gl3_ctx* ctx) {
+    gl3_chain_state* b = &ctx->chain;
+    if (b->ids) hipFree(b->ids);
+    if (b->coins) hipFree(b->coins);
+    if (b->h_ids) hipHostFree(b->h_ids);
+    if (b->h_coins) hipHostFree(b->h_coins);
+    *b = gl3_chain_state{};
+}
+
 void gl3_sample_free(gl3_ctx* ctx) {
     sample_free_buffers(&ctx->smp_one);
     sample_free_buffers(&ctx->smp_rows);
     draft_free(ctx);
+    chain_free(ctx);
 }
 
 static int32_t sample_alloc_all(gl3_ctx* ctx, gl3_sample_state* b, int rows) {
@@ -791,15 +827,9 @@ static void sample_enqueue(gl3_ctx* ctx, gl3_sample_state* b, const float* logit
     hipLaunchKernelGGL(btp_pick_kernel, dim3(n), dim3(256), smem, s, params, b->sort, b->sort_stride, v, n0, b->res);
 }
 
-// The sampler's launches for rows 0..n) of `logits` (laid out as `lay` says) behind whatever produced them on the plan's stream (params /
-// h_params: the rows' settings on the device / the host), 8 * n bytes back, host heap for top-p rows whose sampled rank is tied.
-static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, RowLayout lay, const int32_t* greedy, const SmpRow* params,
-                             const SmpRow* h_params, int n, int32_t* tokens_out) {
+// The launches alone, eagerly or as the state's captured graph: what sample_finish and a chained step (gl3_chain_sample) both put on the stream
+static int32_t sample_launch(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, RowLayout lay, const int32_t* greedy, const SmpRow* params, int n, bool any_topp) {
     hipStream_t s = ctx->stream;
-    const int v = ctx->d.vocab;
-    static const bool host_topp = env_flag("GL3_TOPP_HOST", false);              // A/B switch: no sort launches, every top-p row through the host heap
-    bool any_topp = false;
-    for (int i = 0; i < n; ++i) any_topp |= h_params[i].mode == SMP_TOPP && !host_topp;
     static const bool graphs_off = getenv("GL3_NO_GRAPH") && atoi(getenv("GL3_NO_GRAPH"));
     if (b->graph && !graphs_off && !gl3_roctx_on() && !(ctx->d.flags & GL3_FLAG_NO_GRAPH)) {
         if (b->graph_logits != logits || b->graph_greedy != greedy) {      // the step's logits buffer has grown: captured launches point at the old one
@@ -823,10 +853,23 @@ static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* log
         sample_enqueue(ctx, b, logits, lay, greedy, params, n, any_topp);
     }
     GL3_HIP(hipGetLastError());
+    return GL3_OK;
+}
+
+// The sampler's launches for rows 0..n) of `logits` (laid out as `lay` says) behind whatever produced them on the plan's stream (params /
+// h_params: the rows' settings on the device / the host), 8 * n bytes back, host heap for top-p rows whose sampled rank is tied.
+static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, RowLayout lay, const int32_t* greedy, const SmpRow* params,
+                             const SmpRow* h_params, int n, int32_t* tokens_out) {
+    hipStream_t s = ctx->stream;
+    const int v = ctx->d.vocab;
+    static const bool host_topp = env_flag("GL3_TOPP_HOST", false);              // A/B switch: no sort launches, every top-p row through the host heap
+    bool any_topp = false;
+    for (int i = 0; i < n; ++i) any_topp |= h_params[i].mode == SMP_TOPP && !host_topp;
+    int32_t r = sample_launch(ctx, b, logits, lay, greedy, params, n, any_topp);
+    if (r != GL3_OK) return r;
     GL3_HIP(hipMemcpyAsync(b->h_res, b->res, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     GL3_HIP(hipStreamSynchronize(s));
-    int32_t r = gl3_tp_check(ctx);
-    if (r != GL3_OK) return r;
+    if ((r = gl3_tp_check(ctx)) != GL3_OK) return r;
     b->last_n = n;
     for (int i = 0; i < n; ++i) {
         const SmpRow& R = h_params[i];
@@ -1008,6 +1051,65 @@ int32_t gl3_draft_get(gl3_ctx* ctx, int32_t slot, float* out) {
     GL3_HIP(hipSetDevice(ctx->d.device));
     GL3_HIP(hipMemcpyAsync(out, b->q + (size_t)slot * ctx->d.vocab, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
     GL3_HIP(hipStreamSynchronize(ctx->stream));
+    return GL3_OK;
+}
+
+// ---- draft chain (gl3_forward_decode_chain; every argument check is gl3_api.hip's and has passed): k single-token steps on the plan's
+// stream, step j + 1 fed by chain_handover_kernel behind step j, one wait at the end
+int32_t gl3_chain_prepare(gl3_ctx* ctx, int32_t k, const float* coins, gl3_ctx* target, int32_t slot0, float** q_row0) {
+    gl3_chain_state* b = &ctx->chain;
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    if (!b->ids) {      // once, for the longest chain; all or none, as gl3_verify_prepare
+        hipError_t e = hipMalloc((void**)&b->ids, GL3_CHAIN_MAX * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&b->coins, GL3_CHAIN_MAX * sizeof(float));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_ids, GL3_CHAIN_MAX * sizeof(int));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_coins, GL3_CHAIN_MAX * sizeof(float));
+        if (e != hipSuccess) { chain_free(ctx); GL3_HIP(e); }
+    }
+    if (coins) {
+        const int32_t r = sample_alloc(ctx, &ctx->smp_one, 1);
+        if (r != GL3_OK) return r;
+    }
+    *q_row0 = nullptr;
+    if (target) {
+        const int32_t r = draft_slot(target, slot0, q_row0);
+        if (r != GL3_OK) { ctx->err = target->err; return r; }
+        // the rows are written on THIS plan's stream: behind whatever the target's stream still holds (a gl3_draft_probs_put of another
+        // draft into the same table).  The call returns after its own wait, so the target needs no event for what follows.
+        GL3_HIP(hipEventRecord(target->draft.copied, target->stream));
+        GL3_HIP(hipStreamWaitEvent(ctx->stream, target->draft.copied, 0));
+    }
+    if (coins) {
+        memcpy(b->h_coins, coins, (size_t)k * sizeof(float));
+        GL3_HIP(hipMemcpyAsync(b->coins, b->h_coins, (size_t)k * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    }
+    return GL3_OK;
+}
+
+// the single-row sampler behind a chained step: gl3_sample_run's launches (never top-p), without its copy and wait
+int32_t gl3_chain_sample(gl3_ctx* ctx) {
+    return sample_launch(ctx, &ctx->smp_one, ctx->logits, RowLayout{ctx->d.vocab, 1}, nullptr, reinterpret_cast<const SmpRow*>(ctx->dyn + GL3_DYN_ROW), 1, false);
+}
+
+int32_t gl3_chain_handover(gl3_ctx* ctx, int32_t j, int32_t k, int32_t next_pos, bool sampled, float* q_row) {
+    const gl3_chain_state* b = &ctx->chain;
+    const int n4 = ctx->d.vocab / 4;
+    const int wgs = q_row ? std::min((n4 + 255) / 256, 256) : 1;
+    hipLaunchKernelGGL(chain_handover_kernel, dim3(wgs), dim3(256), 0, ctx->stream, sampled ? ctx->smp_one.res : ctx->argmax, b->ids, j, ctx->dyn, j + 1 < k ? 1 : 0, next_pos,
+                       sampled ? b->coins : (const float*)nullptr, reinterpret_cast<const float4*>(ctx->smp_one.probs), reinterpret_cast<float4*>(q_row), n4);
+    GL3_HIP(hipGetLastError());
+    return GL3_OK;
+}
+
+int32_t gl3_chain_collect(gl3_ctx* ctx, int32_t k, bool sampled, gl3_ctx* target, int32_t slot0, int32_t* tokens_out) {
+    gl3_chain_state* b = &ctx->chain;
+    GL3_HIP(hipMemcpyAsync(b->h_ids, b->ids, (size_t)k * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
+    const int32_t r = gl3_tp_check(ctx);
+    if (r != GL3_OK) return r;
+    if (sampled) ctx->smp_one.last_n = 1;
+    for (int j = 0; target && j < k; ++j) target->draft.written[slot0 + j] = 1;
+    memcpy(tokens_out, b->h_ids, (size_t)k * sizeof(int));
     return GL3_OK;
 }
 

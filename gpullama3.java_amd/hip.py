@@ -18,6 +18,7 @@ ERR_NAMES = {0: "GL3_OK", -1: "GL3_E_ARG", -2: "GL3_E_UNSUPPORTED", -3: "GL3_E_O
              -6: "GL3_E_STATE"}
 FLAG_NO_GRAPH, FLAG_LAYER_TAPS, FLAG_FORCE_RCCL, FLAG_SCALAR_DOT, FLAG_F32_ACTIVATION = 1, 2, 4, 8, 16
 FLAG_VECTOR_512, FLAG_VECTOR_128 = 32, 64      # -Dllama.VectorBitSize (default 256): see include/gpullama3_hip.h
+CHAIN_MAX = 64                                 # GL3_CHAIN_MAX: the longest gl3_forward_decode_chain
 K_NAMES = ["matvec_qkv", "matvec_wo", "matvec_gateup", "matvec_down", "matvec_logits", "attention", "other", "collective"]
 
 T_IDS = {"token_embd.weight": 0, "output_norm.weight": 1, "output.weight": 2, "attn_norm.weight": 3,
@@ -62,6 +63,7 @@ _SIGS = {  # symbol -> (restype, argtypes): exactly the declarations of include/
     "gl3_finalize": (C.c_int32, [C.c_void_p]),
     "gl3_forward_decode": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gl3_forward_decode_sample": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32)]),
+    "gl3_forward_decode_chain": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "gl3_get_sample_probs": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "gl3_get_topp_counts": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gl3_tp_fold_mode": (C.c_int32, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -396,6 +396,18 @@ class HipMasterPlan:
         hip.check(hip.lib().gl3_forward_decode_sample(self._ctx, token, position, temperature, topp, coin, C.byref(out)), self._ctx)
         return int(out.value)
 
+    def forward_decode_chain(self, token: int, position: int, k: int, temperature: float = 0.0, coins=None, target: "HipMasterPlan" = None,
+                             slot0: int = 0) -> np.ndarray:
+        """k single-token steps behind one wait, each step's id fed to the next on the device (gl3_forward_decode_chain): what k
+        forward_decode_sample(t_j, position + j, temperature, 0.0, coins[j]) calls return, int32[k].  temperature 0: a greedy chain, coins
+        may be None.  target: every step's probabilities row goes into slot slot0 + j of that plan's draft table, as draft_probs_put."""
+        co = np.ascontiguousarray(coins, np.float32) if coins is not None else None
+        assert co is None or co.shape == (k,)      # the C entry reads k coins: it cannot see a shorter array
+        out = np.zeros(max(k, 1), np.int32)
+        hip.check(hip.lib().gl3_forward_decode_chain(self._ctx, token, position, k, temperature, _p(co) if co is not None else None,
+                                                     target._ctx if target is not None else None, slot0, _p(out)), self._ctx)
+        return out[:k]
+
     def sample_probs(self) -> np.ndarray:
         out = np.empty(self.cfg.vocab, np.float32)
         hip.check(hip.lib().gl3_get_sample_probs(self._ctx, _p(out)), self._ctx)

@@ -407,6 +407,32 @@ GL3_API int32_t gl3_forward_batch_verify_dist(gl3_ctx* ctx, const int32_t* token
 /* Parity tap: the same decision on caller-supplied logits (host f32[n][vocab]), as gl3_verify_rows; q_slots: int32[n]. */
 GL3_API int32_t gl3_verify_rows_dist(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs,
                                      const float* temperature, const float* coins, const int32_t* q_slots, gl3_verify_result* results_out);
+/* Draft chain: k single-token steps of ONE plan behind one host wait, the id each step draws fed to the next step on the device.  What a
+ * draft model is called for, and plain "generate k ids without a round trip per id".
+ * Equivalence: the call computes, bit for bit, what k consecutive calls gl3_forward_decode_sample(ctx, t_j, position + j, temperature, 0.f,
+ * coins[j], &tokens_out[j]) compute, with t_0 = token and t_(j+1) = tokens_out[j] (topp 0: CategoricalSampler), each followed, when target
+ * is not NULL, by gl3_draft_probs_put(target, slot0 + j, ctx).  After the call everything observable is what the last of those calls
+ * leaves: gl3_get_sample_probs, gl3_get_x, gl3_get_buffer(0..3), the K / V rows at position .. position + k - 1, what gl3_draft_probs_put
+ * would copy next, what the profiling entries take as the last (token, position), and slots slot0 .. slot0 + k - 1 of the target's table,
+ * which are complete when the call returns.  temperature == 0 is a greedy chain: coins is not looked at and may be NULL.  There is no
+ * top-p: a tied top-p rank is decided by the host heap, and gl3_draft_probs_put refuses a top-p row anyway.
+ * The host uploads (token, position), the row's settings and the k coins once and enqueues, per step, the decode step of position + j (the
+ * captured step of that position's attention regime, or launch by launch under GL3_FLAG_NO_GRAPH, exactly as gl3_forward_decode_sample
+ * chooses), the sampler's launches and one hand-over launch; it waits once and 4 * k bytes come back.
+ * KV contract: the K / V rows of all k positions are written.  Rows past what the caller keeps (drafts a verification rejected) are
+ * overwritten by the next run from the first position not kept, as with gl3_forward_batch_verify.
+ * Refusals, all before anything is uploaded or enqueued; a refused call leaves KV, the sampler state and the target's table untouched.
+ * GL3_E_ARG: ctx or tokens_out NULL; k <= 0 or k > GL3_CHAIN_MAX; token outside the vocabulary; position < 0 or position + k > the context
+ * length; temperature negative or NaN; temperature > 0 with coins NULL or a coin outside [0, 1); target == ctx; slot0 < 0 or slot0 + k >
+ * the target's max_batch; different vocabularies; plans on different devices.  GL3_E_STATE: ctx or target before gl3_finalize; a target
+ * with temperature == 0 (a greedy step has no row, which is what gl3_draft_probs_put answers).  GL3_E_UNSUPPORTED: tp_size > 1 on ctx; a
+ * target gl3_draft_probs_put would refuse (no max_batch > 1, or tp_size > 1).  The chain is ONE-rank: under folded gathers the peers' step
+ * counters would have to advance together, which nobody has looked at.  A step that fails midway with a HIP error returns it; the plan is
+ * then in the state any failed forward leaves. */
+#define GL3_CHAIN_MAX 64
+GL3_API int32_t gl3_forward_decode_chain(gl3_ctx* ctx, int32_t token, int32_t position, int32_t k, float temperature,
+                                         const float* coins /* f32[k] or NULL */, gl3_ctx* target /* or NULL */, int32_t slot0,
+                                         int32_t* tokens_out /* int32[k] */);
 /* Test hook, no plan and no device: the host-side plan of a mixed step (csrc/gl3_batch_plan.h) for a plan with n_seqs sequence slots,
  * context length ctx and room for `capacity` rows.  runs_out / tiles_out: int32[.][4] = {first row, rows, sequence, position of the
  * first row}, room for n records each (tiles: at most 8 rows, never across a run boundary, deepest last position first); out_rows:

@@ -6,7 +6,7 @@
 // distributed as the target model's own samples, whatever the draft model.
 //
 //   gl3_spec_draft_run -m target.gguf -md draft.gguf --ids 1,2,3 -n NEW [--draft K] [-b BATCH] [--temperature T] [--draft-temperature Td]
-//                      [--seed S]
+//                      [--seed S] [--chain]
 //
 // Positions: prompt id k at position k, generated ids behind them (tools/gl3_spec_run's protocol).  Both plans are prefilled with all but the
 // last prompt id.  A step that starts with the last real token at position p:
@@ -15,6 +15,9 @@
 //              gl3_forward_decode_sample(topp 0, one coin) and gl3_draft_probs_put(target, j, draft) for draft j, q_slots[j] = j.
 //              T == 0 or Td == 0: gl3_forward_decode's argmax, a fixed token, q_slots = -1 (the one-hot rule; T == 0: greedy verification,
 //              the ids of plain greedy decoding of the target).
+//              --chain: the k steps and their puts are ONE gl3_forward_decode_chain on the draft plan (target and slot 0 when sampled, no
+//              target when greedy): one host wait per speculation step instead of one per draft.  The same coins in the same order, so the
+//              ids and the counts line are those of a run without it.
 //   verifying  the run [last real token, drafts] of m = k + 1 rows -> {a, token}: the first a drafts and `token` are appended, the target
 //              continues at p + a + 1 and overwrites the K / V rows of the rejected drafts before anything reads them.
 //   draft KV   the draft plan has consumed the ids at p .. p + k - 1.  Rejected positions are overwritten by its next steps, as the
@@ -85,6 +88,7 @@ int main(int argc, char** argv) {
     int n_new = 0, K = 4, batch = 16;
     float T = 0.f, Td = -1.f;
     uint64_t seed = 1234;
+    bool chain = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() { return i + 1 < argc ? argv[++i] : (char*)""; };
@@ -97,6 +101,7 @@ int main(int argc, char** argv) {
         else if (a == "--temperature") T = (float)atof(val());
         else if (a == "--draft-temperature") Td = (float)atof(val());
         else if (a == "--seed") seed = strtoull(val(), nullptr, 10);
+        else if (a == "--chain") chain = true;
         else { fprintf(stderr, "gl3_spec_draft_run: unknown argument %s (see the header of tools/gl3_spec_draft_run.cpp)\n", a.c_str()); return 2; }
     }
     if (path.empty() || draft_path.empty() || prompt.empty() || n_new <= 0) {
@@ -105,6 +110,7 @@ int main(int argc, char** argv) {
     }
     if (Td < 0.f) Td = T;
     if (K < 0 || batch < 2 || !(T >= 0.f) || !(Td >= 0.f)) { fprintf(stderr, "gl3_spec_draft_run: --draft >= 0, -b >= 2, temperatures >= 0\n"); return 2; }
+    if (chain && K > GL3_CHAIN_MAX) { fprintf(stderr, "gl3_spec_draft_run: --chain takes --draft <= %d\n", GL3_CHAIN_MAX); return 2; }
     const bool sampled_draft = T > 0.f && Td > 0.f;
 
     const int N = (int)prompt.size();
@@ -134,7 +140,7 @@ int main(int argc, char** argv) {
     CK(draft, gl3_load_gguf(draft_path.c_str(), &opts, &draft));
 
     std::vector<int32_t> generated, toks, seqs, poss, q_slots;
-    std::vector<float> coins;
+    std::vector<float> coins, draft_coins;
     std::vector<int8_t> none((size_t)batch, 0);
     L32X64MixRandom rng(seed);
     const double t_start = now_s();
@@ -163,7 +169,14 @@ int main(int argc, char** argv) {
         toks.assign(1, last);
         q_slots.assign((size_t)m, -1);
         double t0 = now_s();
-        for (int j = 0; j < k; ++j) {
+        if (chain && k > 0) {
+            toks.resize((size_t)m);
+            draft_coins.resize((size_t)k);
+            if (sampled_draft) for (int j = 0; j < k; ++j) { draft_coins[j] = rng.nextFloat(); q_slots[j] = j; }
+            CK(draft, gl3_forward_decode_chain(draft, last, pos, k, sampled_draft ? Td : 0.f, sampled_draft ? draft_coins.data() : nullptr,
+                                               sampled_draft ? target : nullptr, 0, toks.data() + 1));
+        }
+        for (int j = 0; !chain && j < k; ++j) {
             int32_t id = 0;
             if (sampled_draft) {
                 CK(draft, gl3_forward_decode_sample(draft, toks[j], pos + j, Td, 0.f, rng.nextFloat(), &id));

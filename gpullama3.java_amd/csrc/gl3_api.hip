@@ -1172,6 +1172,71 @@ int32_t gl3_forward_decode_chain(gl3_ctx* ctx, int32_t token, int32_t pos, int32
     return GL3_OK;
 }
 
+// The same for the static-batched step: k steps of n rows behind one wait.  That step reads every row's token, sequence id and position
+// from device memory (gl3_decode_batch_enqueue, gl3_prefill.hip) and the host takes the deepest position alone, which is positions[i] + j,
+// so again everything is enqueued before the first step has run and batch_chain_handover_kernel (gl3_sample.hip) passes the ids on.  Row i
+// takes k_rows[i] steps (non-increasing, so the rows of step j are a prefix and nothing is compacted).  The step and the sampler are the
+// launches of gl3_forward_decode_batch_sample, chosen the same way, so the chain computes what k of those calls compute.
+int32_t gl3_forward_decode_batch_chain(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, int32_t k,
+                                       const int32_t* k_rows, const float* temperature, const float* coins, gl3_ctx* target, const int32_t* slots,
+                                       int32_t* tokens_out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!tokens || !seq_ids || !positions || !temperature || n <= 0) GL3_FAIL(GL3_E_ARG, "bad batch arrays");
+    if (!tokens_out) GL3_FAIL(GL3_E_ARG, "null tokens_out");
+    if (k <= 0 || k > GL3_CHAIN_MAX) GL3_FAIL(GL3_E_ARG, "chain length outside [1, GL3_CHAIN_MAX]");
+    if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "the decode chain is built for one rank (tp_size == 1): under folded gathers the peers' step counters would have to advance together");
+    if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
+    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, a Vector-API order: 256 bits, or 512 bits for F16 on one rank)");
+    if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
+    auto steps = [&](int i) { return k_rows ? k_rows[i] : k; };
+    if (k_rows && k_rows[0] != k) GL3_FAIL(GL3_E_ARG, "k_rows[0] must be k");
+    for (int i = 0; i < n; ++i) {
+        if (steps(i) < 1 || steps(i) > k || (i && steps(i) > steps(i - 1))) GL3_FAIL(GL3_E_ARG, "k_rows must be non-increasing with every entry in [1, k]");
+        if (tokens[i] < 0 || tokens[i] >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
+        if (seq_ids[i] < 0 || seq_ids[i] >= ctx->n_seqs) GL3_FAIL(GL3_E_ARG, "sequence id out of range");
+        if (positions[i] < 0 || positions[i] > ctx->d.ctx - steps(i)) GL3_FAIL(GL3_E_ARG, "chained positions outside the KV cache (context length)");
+        for (int j = 0; j < i; ++j) if (seq_ids[j] == seq_ids[i]) GL3_FAIL(GL3_E_ARG, "duplicate sequence id in one batched step");
+        if (!(temperature[i] >= 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be >= 0");
+        if (temperature[i] == 0.f) continue;                      // a greedy row in every step: its coins are not looked at
+        if (!coins) GL3_FAIL(GL3_E_ARG, "null coins with a row at a temperature > 0");
+        for (int j = 0; j < steps(i); ++j)
+            if (!(coins[(size_t)j * n + i] >= 0.f && coins[(size_t)j * n + i] < 1.f)) GL3_FAIL(GL3_E_ARG, "coin must be rng.nextFloat(1f): in [0, 1)");
+    }
+    if (target) {                                                 // what the gl3_draft_probs_put_row calls would refuse, ahead of the first step
+        if (target == ctx) GL3_FAIL(GL3_E_ARG, "the target plan must be another plan");
+        if (!slots) GL3_FAIL(GL3_E_ARG, "null slots with a target plan");
+        if (target->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "draft verification is built for one rank (tp_size == 1), the target plan included");
+        if (!target->finalized) GL3_FAIL(GL3_E_STATE, "draft distributions before gl3_finalize of the target plan");
+        if (!target->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "draft distributions are read by draft verification, which needs max_batch > 1 on the target plan");
+        if (target->d.vocab != ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "the target plan has another vocabulary");
+        if (target->d.device != ctx->d.device) GL3_FAIL(GL3_E_ARG, "the target plan is on another device");
+        for (int i = 0; i < n; ++i) {
+            if (slots[i] == -1) continue;
+            if (slots[i] < 0 || slots[i] > target->d.max_batch - steps(i)) GL3_FAIL(GL3_E_ARG, "draft-distribution slots outside [0, max_batch) of the target plan");
+            for (int j = 0; j < i; ++j)
+                if (slots[j] >= 0 && slots[i] < slots[j] + steps(j) && slots[j] < slots[i] + steps(i)) GL3_FAIL(GL3_E_ARG, "two rows' draft-distribution slots overlap");
+        }
+        for (int i = 0; i < n; ++i)
+            if (slots[i] >= 0 && temperature[i] == 0.f) GL3_FAIL(GL3_E_STATE, "a greedy row has no probabilities to put into the target's table");
+    }
+    int32_t r = gl3_batch_chain_prepare(ctx, n, k, k_rows, temperature, coins, target, slots);
+    if (r != GL3_OK) return r;
+    if ((r = gl3_decode_batch_stage(ctx, tokens, seq_ids, positions, n)) != GL3_OK) return r;
+    int32_t *tokens_dev, *positions_dev;
+    gl3_decode_batch_inputs(ctx, &tokens_dev, &positions_dev);
+    for (int j = 0; j < k; ++j) {
+        int nj = 0, max_pos = 0;
+        bool sampled_step = false;                                // a step whose rows are all greedy runs no sampler, as the single call
+        for (int i = 0; i < n && steps(i) > j; ++i) { ++nj; max_pos = std::max(max_pos, positions[i] + j); sampled_step |= temperature[i] > 0.f; }
+        if ((r = gl3_decode_batch_enqueue(ctx, nj, max_pos)) != GL3_OK) return r;
+        const float* logits; const int32_t* greedy;
+        gl3_decode_batch_outputs(ctx, &logits, &greedy);
+        if (sampled_step && (r = gl3_batch_chain_sample(ctx, logits, greedy, nj)) != GL3_OK) return r;
+        if ((r = gl3_batch_chain_handover(ctx, j, n, nj, sampled_step, greedy, tokens_dev, positions_dev, target)) != GL3_OK) return r;
+    }
+    return gl3_batch_chain_collect(ctx, n, k, k_rows, temperature, target, slots, tokens_out);
+}
+
 int32_t gl3_tp_fold_mode(gl3_ctx* ctx, int32_t* mode, int32_t* consumer_mask) {
     if (!ctx || !mode || !consumer_mask) return GL3_E_ARG;
     if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "gl3_tp_fold_mode before gl3_finalize");
@@ -1397,6 +1462,23 @@ int32_t gl3_draft_probs_put(gl3_ctx* ctx, int32_t slot, gl3_ctx* draft) {
     if (draft->last_sample_mode == SMP_GREEDY) GL3_FAIL(GL3_E_STATE, "the draft plan's last sample was greedy: it has no probabilities");
     if (draft->last_sample_mode == SMP_TOPP) GL3_FAIL(GL3_E_STATE, "the draft plan's last sample was top-p: its row is the untruncated softmax, not what the token was drawn from");
     return gl3_draft_put(ctx, slot, draft);
+}
+
+// The same from row `row` of the draft plan's last batched sampled step (or gl3_sample_rows call): what gl3_get_sample_probs_row returns
+int32_t gl3_draft_probs_put_row(gl3_ctx* ctx, int32_t slot, gl3_ctx* draft, int32_t row) {
+    if (!ctx) return GL3_E_ARG;
+    if (!draft || draft == ctx) GL3_FAIL(GL3_E_ARG, "the draft plan must be another plan");
+    if (draft->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "draft verification is built for one rank (tp_size == 1), the draft plan included");
+    const int32_t r = check_draft_table(ctx, slot);
+    if (r != GL3_OK) return r;
+    if (draft->d.vocab != ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "the draft plan has another vocabulary");
+    if (draft->d.device != ctx->d.device) GL3_FAIL(GL3_E_ARG, "the draft plan is on another device");
+    const gl3_sample_state& b = draft->smp_rows;
+    if (!b.last_n) GL3_FAIL(GL3_E_STATE, "the draft plan has no batched sampled step yet");
+    if (row < 0 || row >= b.last_n) GL3_FAIL(GL3_E_ARG, "row outside the draft plan's last batched sampled step");
+    if (b.h_params[row].mode == SMP_GREEDY) GL3_FAIL(GL3_E_STATE, "the draft plan's row was greedy: it has no probabilities");
+    if (b.h_params[row].mode == SMP_TOPP) GL3_FAIL(GL3_E_STATE, "the draft plan's row was top-p: its row is the untruncated softmax, not what the token was drawn from");
+    return gl3_draft_put_row(ctx, slot, draft, row);
 }
 
 int32_t gl3_draft_probs_put_host(gl3_ctx* ctx, int32_t slot, const float* q) {

@@ -200,6 +200,19 @@ struct gl3_chain_state {
     float* h_coins = nullptr;                  // pinned
 };
 
+// Batched draft chain (gl3_forward_decode_batch_chain, gl3_sample.hip): the same lists for the n rows of a static-batched step, [step][row]
+// with the call's row count as the stride, and what the hand-over launch needs to know of a row.  Allocated on the first batched chain for
+// GL3_CHAIN_MAX * max_batch entries, all or none, freed with the sampler buffers.
+struct gl3_batch_chain_state {
+    int* ids = nullptr;                        // [k][n] id of row i at step j, written by the step's hand-over launch
+    float* coins = nullptr;                    // [k][n] coin of row i at step j (0 for a greedy row)
+    int* meta = nullptr;                       // [2][n]: steps of row i (k_i), first slot of row i in the target's table or -1
+    int* h_ids = nullptr;                      // pinned
+    float* h_coins = nullptr;                  // pinned
+    int* h_meta = nullptr;                     // pinned
+    bool sampled = false;                      // the running chain has a row at a temperature > 0: the coins are up and the rows' settings staged
+};
+
 struct gl3_ctx {
     gl3_model_desc d{};
     // derived (local = this tensor-parallel rank's share)
@@ -252,6 +265,7 @@ struct gl3_ctx {
     gl3_verify_state verify;                      // gl3_forward_batch_verify / gl3_verify_rows and their _dist forms
     gl3_draft_state draft;                        // the draft distributions the _dist forms read
     gl3_chain_state chain;                        // gl3_forward_decode_chain
+    gl3_batch_chain_state bchain;                 // gl3_forward_decode_batch_chain
     int last_sample_mode = -1;                    // SMP_* of the last gl3_forward_decode_sample or chained step (-1: none yet): what gl3_draft_probs_put may copy
     std::vector<std::pair<void*, size_t>> pinned;     // caller buffers registered with gl3_pin_host_buffer (logits land there directly)
     // upload staging
@@ -361,6 +375,20 @@ int32_t gl3_chain_prepare(gl3_ctx* ctx, int32_t k, const float* coins, gl3_ctx* 
 int32_t gl3_chain_sample(gl3_ctx* ctx);
 int32_t gl3_chain_handover(gl3_ctx* ctx, int32_t j, int32_t k, int32_t next_pos, bool sampled, float* q_row);
 int32_t gl3_chain_collect(gl3_ctx* ctx, int32_t k, bool sampled, gl3_ctx* target, int32_t slot0, int32_t* tokens_out);
+// one slot from row `row` of the draft plan's last batched sampled step (the argument checks are gl3_api.hip's)
+int32_t gl3_draft_put_row(gl3_ctx* ctx, int32_t slot, gl3_ctx* draft, int32_t row);
+// batched draft chain (the argument checks are gl3_api.hip's): prepare = the lists, the batched sampler's buffers and the rows' settings
+// with the step-0 coins (any sampled row), the target's table on first use, then the [k][n] coins and the rows' (k_i, slot) up;
+// sample = the batched sampler's launches behind a chained step of nj rows; handover = the launch that passes step j's ids (and the rows
+// with a slot) on, id_src = {token, tie} pairs of the sampler (sampled_step) or the step's greedy ids; collect = the one wait, 4 * k * n
+// bytes back, -1 where a row has no step, and the sampler state of the last single call
+int32_t gl3_batch_chain_prepare(gl3_ctx* ctx, int32_t n, int32_t k, const int32_t* k_rows, const float* temperature, const float* coins, gl3_ctx* target,
+                                const int32_t* slots);
+int32_t gl3_batch_chain_sample(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t nj);
+int32_t gl3_batch_chain_handover(gl3_ctx* ctx, int32_t j, int32_t n, int32_t nj, bool sampled_step, const int32_t* greedy_dev, int32_t* tokens_dev,
+                                 int32_t* positions_dev, gl3_ctx* target);
+int32_t gl3_batch_chain_collect(gl3_ctx* ctx, int32_t n, int32_t k, const int32_t* k_rows, const float* temperature, gl3_ctx* target, const int32_t* slots,
+                                int32_t* tokens_out);
 
 // gl3_prefill.hip
 float* gl3_prefill_buf(gl3_ctx* ctx, int which);
@@ -372,6 +400,10 @@ int32_t gl3_prefill_run(gl3_ctx* ctx, int32_t seq, const int32_t* tokens, int32_
 int32_t gl3_prefill_profile(gl3_ctx* ctx, int klass, int n, int iters, double* out_us, uint64_t* int8_ops);
 int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
                              float* logits_out, int32_t* argmax_out, bool finish = true);      // finish = false: enqueue only
+// its two halves (a chain of steps stages once): the triples up; one step of n rows whose deepest row is at max_pos; and where the inputs live
+int32_t gl3_decode_batch_stage(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n);
+int32_t gl3_decode_batch_enqueue(gl3_ctx* ctx, int32_t n, int32_t max_pos);
+void gl3_decode_batch_inputs(gl3_ctx* ctx, int32_t** tokens, int32_t** positions);
 namespace gl3 { struct BatchPlan; }      // gl3_batch_plan.h
 // one mixed step (gl3_forward_batch) whose plan the caller built and checked; outputs: the plan's out_rows, compact
 int32_t gl3_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const gl3::BatchPlan& bp,

@@ -1047,17 +1047,25 @@ int32_t gl3_decode_batch_load_logits(gl3_ctx* ctx, const float* logits, int32_t 
     return GL3_OK;
 }
 
-int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
-                             float* logits_out, int32_t* argmax_out, bool finish) {
+// The static-batched step in two halves, so that a chain of steps (gl3_forward_decode_batch_chain) stages once and enqueues k times:
+// stage = room for n logits rows and the n (token, sequence, position) triples up; enqueue = one step of n rows whose deepest row is at
+// max_pos, the only thing the host takes from the positions.  The rows' own positions are read from p->seqpos by every attention form such
+// a step can take (attn_head_kernel: posv; pf_rope_kv_kernel and the per-row pair behind it: RopeArgs / PfAttnArgs::pos).
+int32_t gl3_decode_batch_stage(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n) {
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    const int32_t r = pf_grow_logits(ctx, n);
+    return r != GL3_OK ? r : pf_stage_tokens(ctx, tokens, seq_ids, positions, n);
+}
+
+// The step's inputs on the device: what a chained step's hand-over launch rewrites for the step behind it (gl3_sample.hip)
+void gl3_decode_batch_inputs(gl3_ctx* ctx, int32_t** tokens, int32_t** positions) {
+    *tokens = ctx->pf->tokens; *positions = ctx->pf->seqpos + ctx->pf->max_batch;
+}
+
+int32_t gl3_decode_batch_enqueue(gl3_ctx* ctx, int32_t n, int32_t max_pos) {
     gl3_prefill_state* p = ctx->pf;
     const gl3_model_desc& d = ctx->d;
-    GL3_HIP(hipSetDevice(d.device));
-    int32_t r0 = pf_grow_logits(ctx, n);
-    if (r0 != GL3_OK) return r0;
-    int max_pos = 0;
-    for (int i = 0; i < n; ++i) max_pos = positions[i] > max_pos ? positions[i] : max_pos;
-    int32_t r = pf_stage_tokens(ctx, tokens, seq_ids, positions, n);
-    if (r != GL3_OK) return r;
+    int32_t r;
     hipStream_t s = ctx->stream;
     // the whole step: layers, final RMSNorm + vocabulary projection of every row, greedy ids
     auto enqueue_step = [&](const PfStep& st) -> int32_t {
@@ -1086,6 +1094,19 @@ int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t*
         GL3_HIP(hipGraphLaunch(p->step_graphs[n], s));
         p->attn_rows[0] = n; p->attn_rows[1] = p->attn_rows[2] = p->attn_rows[3] = 0; p->attn_rows_set = true;      // a replay does not pass pf_attention: the captured step is attn_head_kernel's
     } else if ((r = enqueue_step(st)) != GL3_OK) return r;
+    GL3_HIP(hipGetLastError());
+    return GL3_OK;
+}
+
+int32_t gl3_decode_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
+                             float* logits_out, int32_t* argmax_out, bool finish) {
+    gl3_prefill_state* p = ctx->pf;
+    int32_t r = gl3_decode_batch_stage(ctx, tokens, seq_ids, positions, n);
+    if (r != GL3_OK) return r;
+    int max_pos = 0;
+    for (int i = 0; i < n; ++i) max_pos = positions[i] > max_pos ? positions[i] : max_pos;
+    if ((r = gl3_decode_batch_enqueue(ctx, n, max_pos)) != GL3_OK) return r;
+    hipStream_t s = ctx->stream;
     if (argmax_out) GL3_HIP(hipMemcpyAsync(argmax_out, p->amax, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (logits_out && (r = pf_logits_copy(ctx, logits_out, n, hipMemcpyDeviceToHost)) != GL3_OK) return r;      // un-chunked on the way out
     GL3_HIP(hipGetLastError());

@@ -50,6 +50,11 @@
 // chain_handover_kernel passes the id on to the next step through ctx->dyn and, for a target plan, copies the row into the table itself.
 // The sampler's launches are the single-row entry's (sample_launch); only the copy back and the wait happen once per chain.
 //
+// Batched draft chain (gl3_forward_decode_batch_chain).  The same over static-batched steps: behind each step's batched sampler (or, when
+// every row of the step is greedy, its greedy scan) batch_chain_handover_kernel passes every row's id on through the step's own input
+// arrays (tokens, positions) and the row's SmpRow, files it in a [k][n] list, and copies the rows that have a slot into the target's table.
+// gl3_draft_probs_put_row is that copy as an entry of its own: row `row` of smp_rows.probs into a slot (tools/gl3_spec_batch_run --no-chain).
+//
 // The two entries are two instances of gl3_sample_state.  gl3_forward_decode_sample is the n = 1 case: 256 workgroups per element-wise
 // launch, launched eagerly, its SmpRow riding behind the (token, position) pair in ctx->dyn.  The static-batched entries
 // (gl3_forward_decode_batch_sample, gl3_sample_rows) use 64 workgroups per row and replay one hipGraph per (row count, any top-p row).
@@ -732,6 +737,37 @@ __global__ __launch_bounds__(256) void chain_handover_kernel(const int* __restri
         for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) q4[i] = probs4[i];
 }
 
+// Batched draft chain (gl3_forward_decode_batch_chain): the hand-over between step j and step j + 1 of a chain of static-batched steps, one
+// launch behind step j's sampler (or greedy scan) whatever the row count.  Grid = (share of the vocabulary, row of the step): the rows of
+// step j are the prefix whose k_rows[i] > j (k_rows is non-increasing), and the host launches exactly those.  id_src[id_stride * i] is row
+// i's id: the sampler's {token, tie} pairs (stride 2; a greedy row's pair holds the step's greedy id) or, behind a step whose rows are all
+// greedy, the step's greedy ids (stride 1).  Thread 0 of a row's first workgroup files the id in ids[j * n + i] and, when the row has a
+// further step, makes it that step's input: tokens[i] = id, positions[i] += 1 (the one word this launch reads and writes, by this thread
+// alone), and on a chain with sampled rows the next coin into the row's SmpRow (temperature, topp and mode stay what the host staged).  A
+// row's last step writes none of the three, so the step's inputs end as the last single call's upload would leave them.  A row with a slot
+// (slots[i] >= 0, q4 != NULL): every workgroup of the row copies its share of the probabilities row (n4 float4s; vocab % 16 == 0 at
+// gl3_create) into slot slots[i] + j of the target plan's draft table, in this launch for the reason given at chain_handover_kernel.
+// Plain vector loads and stores only; no thread reads what another writes.
+__global__ __launch_bounds__(256) void batch_chain_handover_kernel(const int* __restrict__ id_src, int id_stride, int* __restrict__ ids, int j, int n,
+                                                                   const int* __restrict__ k_rows, const int* __restrict__ slots, int* __restrict__ tokens,
+                                                                   int* __restrict__ positions, SmpRow* __restrict__ params, const float* __restrict__ coins,
+                                                                   const float4* __restrict__ probs4, float4* __restrict__ q4, int n4) {
+    const int i = blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int id = id_src[id_stride * i];
+        ids[j * n + i] = id;
+        if (j + 1 < k_rows[i]) {
+            tokens[i] = id; positions[i] = positions[i] + 1;
+            if (coins) params[i].coin = coins[(j + 1) * n + i];
+        }
+    }
+    const int slot = q4 ? slots[i] : -1;
+    if (slot < 0) return;
+    const float4* src = probs4 + (size_t)i * n4;
+    float4* dst = q4 + (size_t)(slot + j) * n4;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n4; e += gridDim.x * 256) dst[e] = src[e];
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 static void sample_drop_graphs(gl3_sample_state* b) {
     for (auto& ge : b->graphs) if (ge) { hipGraphExecDestroy(ge); ge = nullptr; }
@@ -768,11 +804,23 @@ static void chain_free(gl3_ctx* ctx) {
     *b = gl3_chain_state{};
 }
 
+static void batch_chain_free(gl3_ctx* ctx) {
+    gl3_batch_chain_state* b = &ctx->bchain;
+    if (b->ids) hipFree(b->ids);
+    if (b->coins) hipFree(b->coins);
+    if (b->meta) hipFree(b->meta);
+    if (b->h_ids) hipHostFree(b->h_ids);
+    if (b->h_coins) hipHostFree(b->h_coins);
+    if (b->h_meta) hipHostFree(b->h_meta);
+    *b = gl3_batch_chain_state{};
+}
+
 void gl3_sample_free(gl3_ctx* ctx) {
     sample_free_buffers(&ctx->smp_one);
     sample_free_buffers(&ctx->smp_rows);
     draft_free(ctx);
     chain_free(ctx);
+    batch_chain_free(ctx);
 }
 
 static int32_t sample_alloc_all(gl3_ctx* ctx, gl3_sample_state* b, int rows) {
@@ -1110,6 +1158,110 @@ int32_t gl3_chain_collect(gl3_ctx* ctx, int32_t k, bool sampled, gl3_ctx* target
     if (sampled) ctx->smp_one.last_n = 1;
     for (int j = 0; target && j < k; ++j) target->draft.written[slot0 + j] = 1;
     memcpy(tokens_out, b->h_ids, (size_t)k * sizeof(int));
+    return GL3_OK;
+}
+
+// ---- one slot of a target's table from a row of the draft plan's batched sampler: gl3_draft_put with smp_rows.probs row `row` as the source
+int32_t gl3_draft_put_row(gl3_ctx* ctx, int32_t slot, gl3_ctx* draft, int32_t row) {
+    float* dst = nullptr;
+    const int32_t r = draft_slot(ctx, slot, &dst);
+    if (r != GL3_OK) return r;
+    GL3_HIP(hipMemcpyAsync(dst, draft->smp_rows.probs + (size_t)row * ctx->d.vocab, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    GL3_HIP(hipEventRecord(ctx->draft.copied, ctx->stream));
+    GL3_HIP(hipStreamWaitEvent(draft->stream, ctx->draft.copied, 0));
+    ctx->draft.written[slot] = 1;
+    return GL3_OK;
+}
+
+// ---- batched draft chain (gl3_forward_decode_batch_chain; every argument check is gl3_api.hip's and has passed): k static-batched steps on
+// the plan's stream, step j + 1 fed by batch_chain_handover_kernel behind step j, one wait at the end.  Row i takes k_i = k_rows[i] (NULL: k)
+// steps; the lists are [step][row] with stride n.
+int32_t gl3_batch_chain_prepare(gl3_ctx* ctx, int32_t n, int32_t k, const int32_t* k_rows, const float* temperature, const float* coins, gl3_ctx* target,
+                                const int32_t* slots) {
+    gl3_batch_chain_state* b = &ctx->bchain;
+    ctx->smp_rows.last_n = 0;      // as gl3_sample_batch_prepare: a chain that fails midway leaves no row of a half-run step to hand out
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    if (!b->ids) {      // once, for the longest chain of the widest step; all or none, as gl3_chain_prepare
+        const size_t cap = (size_t)GL3_CHAIN_MAX * ctx->d.max_batch, mcap = (size_t)2 * ctx->d.max_batch;
+        hipError_t e = hipMalloc((void**)&b->ids, cap * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&b->coins, cap * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void**)&b->meta, mcap * sizeof(int));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_ids, cap * sizeof(int));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_coins, cap * sizeof(float));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_meta, mcap * sizeof(int));
+        if (e != hipSuccess) { batch_chain_free(ctx); GL3_HIP(e); }
+    }
+    bool any = false;
+    for (int i = 0; i < n; ++i) any |= temperature[i] > 0.f;
+    b->sampled = any;
+    gl3_sample_state* sm = &ctx->smp_rows;
+    if (any) {      // step 0's gl3_sample_batch_prepare: the rows' settings with the step-0 coins
+        const int32_t r = sample_alloc(ctx, sm, n);
+        if (r != GL3_OK) return r;
+        for (int i = 0; i < n; ++i) sm->h_params[i] = gl3_smp_row(temperature[i], 0.f, temperature[i] > 0.f ? coins[i] : 0.f);
+        GL3_HIP(hipMemcpyAsync(sm->params, sm->h_params, (size_t)n * sizeof(SmpRow), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (target) {
+        float* q0 = nullptr;
+        const int32_t r = draft_slot(target, 0, &q0);
+        if (r != GL3_OK) { ctx->err = target->err; return r; }
+        // as gl3_chain_prepare: the rows are written on THIS plan's stream, behind whatever the target's stream still holds
+        GL3_HIP(hipEventRecord(target->draft.copied, target->stream));
+        GL3_HIP(hipStreamWaitEvent(ctx->stream, target->draft.copied, 0));
+    }
+    for (int i = 0; i < n; ++i) {
+        const int ki = k_rows ? k_rows[i] : k;
+        b->h_meta[i] = ki;
+        b->h_meta[n + i] = target ? slots[i] : -1;
+        for (int j = 0; j < k; ++j) b->h_coins[(size_t)j * n + i] = temperature[i] > 0.f && j < ki ? coins[(size_t)j * n + i] : 0.f;
+    }
+    GL3_HIP(hipMemcpyAsync(b->meta, b->h_meta, (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    if (any) GL3_HIP(hipMemcpyAsync(b->coins, b->h_coins, (size_t)k * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    return GL3_OK;
+}
+
+// the batched sampler behind a chained step of nj rows: gl3_sample_batch_finish's launches (never top-p), without its copy and wait
+int32_t gl3_batch_chain_sample(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t nj) {
+    gl3_sample_state* sm = &ctx->smp_rows;
+    return sample_launch(ctx, sm, logits_dev, RowLayout{ctx->vocab_l, nj}, greedy_dev, sm->params, nj, false);
+}
+
+int32_t gl3_batch_chain_handover(gl3_ctx* ctx, int32_t j, int32_t n, int32_t nj, bool sampled_step, const int32_t* greedy_dev, int32_t* tokens_dev,
+                                 int32_t* positions_dev, gl3_ctx* target) {
+    const gl3_batch_chain_state* b = &ctx->bchain;
+    const gl3_sample_state* sm = &ctx->smp_rows;
+    const int n4 = ctx->d.vocab / 4;
+    bool copies = false;                                  // a row of this step has a slot (only a sampled row can: the step then ran the sampler)
+    for (int i = 0; i < nj; ++i) copies |= b->h_meta[n + i] >= 0;
+    const int wgs = copies ? std::min((n4 + 255) / 256, 64) : 1;
+    hipLaunchKernelGGL(batch_chain_handover_kernel, dim3(wgs, nj), dim3(256), 0, ctx->stream, sampled_step ? sm->res : greedy_dev, sampled_step ? 2 : 1, b->ids, j, n,
+                       b->meta, b->meta + n, tokens_dev, positions_dev, sm->params, b->sampled ? b->coins : (const float*)nullptr,
+                       reinterpret_cast<const float4*>(sm->probs), copies ? reinterpret_cast<float4*>(target->draft.q) : (float4*)nullptr, n4);
+    GL3_HIP(hipGetLastError());
+    return GL3_OK;
+}
+
+int32_t gl3_batch_chain_collect(gl3_ctx* ctx, int32_t n, int32_t k, const int32_t* k_rows, const float* temperature, gl3_ctx* target, const int32_t* slots,
+                                int32_t* tokens_out) {
+    gl3_batch_chain_state* b = &ctx->bchain;
+    gl3_sample_state* sm = &ctx->smp_rows;
+    GL3_HIP(hipMemcpyAsync(b->h_ids, b->ids, (size_t)k * n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
+    const int32_t r = gl3_tp_check(ctx);
+    if (r != GL3_OK) return r;
+    for (int j = 0; j < k; ++j) {
+        // the host's copy of the sampler state as the single call of step j leaves it: the rows' settings with the step's coins and the
+        // step's row count; a step whose rows are all greedy has no sampled rows (gl3_sample_batch_prepare)
+        int nj = 0;
+        bool any = false;
+        for (int i = 0; i < n && (k_rows ? k_rows[i] : k) > j; ++i) { ++nj; any |= temperature[i] > 0.f; }
+        for (int i = 0; any && i < nj; ++i) sm->h_params[i] = gl3_smp_row(temperature[i], 0.f, b->h_coins[(size_t)j * n + i]);
+        sm->last_n = any ? nj : 0;
+        for (int i = 0; i < n; ++i) {
+            tokens_out[(size_t)j * n + i] = i < nj ? b->h_ids[(size_t)j * n + i] : -1;
+            if (target && i < nj && slots[i] >= 0) target->draft.written[slots[i] + j] = 1;
+        }
+    }
     return GL3_OK;
 }
 

@@ -85,6 +85,9 @@ _SIGS = {  # symbol -> (restype, argtypes): exactly the declarations of include/
                                              C.POINTER(C.c_int32)]),
     "gl3_verify_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gl3_draft_probs_put": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "gl3_draft_probs_put_row": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "gl3_forward_decode_batch_chain": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gl3_draft_probs_put_host": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
     "gl3_get_draft_probs": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
     "gl3_forward_batch_verify_dist": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -203,6 +203,28 @@ class HipMasterPlan:
         hip.check(hip.lib().gl3_forward_decode_batch_sample(self._ctx, _p(t), _p(s), _p(p), n, _p(te), _p(tp), _p(co), _p(ids)), self._ctx)
         return ids
 
+    def forward_decode_batch_chain(self, tokens, seq_ids, positions, k: int, temperature=0.0, coins=None, k_rows=None,
+                                   target: "HipMasterPlan" = None, slots=None) -> np.ndarray:
+        """k static-batched decode steps behind one wait, every row's id fed to its next step on the device
+        (gl3_forward_decode_batch_chain): what k forward_decode_batch_sample calls over the rows with k_rows[i] > j return, int32[k][n], -1
+        where a row has no step.  temperature: per row (a scalar broadcasts), 0 = greedy; coins: f32[k][n] or None when every row is greedy;
+        k_rows: int32[n] non-increasing from k, or None (every row k steps); target / slots: row i's step j goes into slot slots[i] + j of
+        that plan's draft table (slots[i] = -1: none), as draft_probs_put_row."""
+        t = np.ascontiguousarray(tokens, np.int32); s = np.ascontiguousarray(seq_ids, np.int32); p = np.ascontiguousarray(positions, np.int32)
+        n = t.size
+        assert s.size == n and p.size == n
+        te = self._per_row(temperature, n)
+        co = np.ascontiguousarray(coins, np.float32) if coins is not None else None
+        assert co is None or co.shape == (k, n)      # the C entry reads k * n coins: it cannot see a shorter array
+        kr = np.ascontiguousarray(k_rows, np.int32) if k_rows is not None else None
+        sl = np.ascontiguousarray(slots, np.int32) if slots is not None else None
+        assert (kr is None or kr.shape == (n,)) and (sl is None or sl.shape == (n,))
+        out = np.zeros((max(k, 1), n), np.int32)
+        hip.check(hip.lib().gl3_forward_decode_batch_chain(self._ctx, _p(t), _p(s), _p(p), n, k, _p(kr) if kr is not None else None, _p(te),
+                                                           _p(co) if co is not None else None, target._ctx if target is not None else None,
+                                                           _p(sl) if sl is not None else None, _p(out)), self._ctx)
+        return out[:k]
+
     def _mixed_args(self, tokens, seq_ids, positions, want_logits):
         """The arrays of a mixed step and its number of output rows (want_logits None: the last row of every run)."""
         t = np.ascontiguousarray(tokens, np.int32); s = np.ascontiguousarray(seq_ids, np.int32); p = np.ascontiguousarray(positions, np.int32)
@@ -312,6 +334,11 @@ class HipMasterPlan:
         """Slot `slot` of this (target) plan's draft table = the row draft_plan.sample_probs() returns, copied on the device
         (gl3_draft_probs_put)."""
         hip.check(hip.lib().gl3_draft_probs_put(self._ctx, slot, draft_plan._ctx if draft_plan is not None else None), self._ctx)
+
+    def draft_probs_put_row(self, slot: int, draft_plan: "HipMasterPlan", row: int):
+        """Slot `slot` of this (target) plan's draft table = sample_probs_row(row) of draft_plan's last batched sampled step, copied on the
+        device (gl3_draft_probs_put_row)."""
+        hip.check(hip.lib().gl3_draft_probs_put_row(self._ctx, slot, draft_plan._ctx if draft_plan is not None else None, row), self._ctx)
 
     def draft_probs_put_host(self, slot: int, q):
         """The same slot from host memory, f32[vocab], taken as it is."""

@@ -379,6 +379,14 @@ GL3_API int32_t gl3_verify_rows(gl3_ctx* ctx, const float* logits, const int32_t
  * row); it went through ToppSampler (0 < topp < 1: the row is the untruncated softmax, not what the token was drawn from, and verifying
  * against it would silently stop being lossless).  GL3_E_UNSUPPORTED: a target without max_batch > 1; tp_size > 1 on either plan. */
 GL3_API int32_t gl3_draft_probs_put(gl3_ctx* target, int32_t slot, gl3_ctx* draft);
+/* The same for a draft plan that drafts many sequences in static-batched steps: slot `slot` of `target` = the row
+ * gl3_get_sample_probs_row(draft, row) would return, the softmax row of row `row` of the draft plan's last batched sampled step
+ * (gl3_forward_decode_batch_sample, or the last step of a gl3_forward_decode_batch_chain) or gl3_sample_rows call.  One
+ * device-to-device copy on the target's stream, ordered against the draft's stream as in gl3_draft_probs_put.  GL3_E_ARG: a null plan,
+ * draft == target, slot outside [0, max_batch) of the target, row outside the rows of that step, different vocabularies, plans on different
+ * devices.  GL3_E_STATE: no batched sampled step yet (or the last one was all greedy); the row was greedy; the row went through top-p.
+ * GL3_E_UNSUPPORTED: a target without max_batch > 1; tp_size > 1 on either plan. */
+GL3_API int32_t gl3_draft_probs_put_row(gl3_ctx* target, int32_t slot, gl3_ctx* draft, int32_t row);
 /* Parity tap: the same slot from host memory, q: f32[vocab], taken as it is — finite and >= 0 is the caller's contract, nothing scans it. */
 GL3_API int32_t gl3_draft_probs_put_host(gl3_ctx* target, int32_t slot, const float* q);
 /* Parity tap: slot `slot` back to the host (out: f32[vocab]).  GL3_E_STATE for a slot that was never written. */
@@ -433,6 +441,38 @@ GL3_API int32_t gl3_verify_rows_dist(gl3_ctx* ctx, const float* logits, const in
 GL3_API int32_t gl3_forward_decode_chain(gl3_ctx* ctx, int32_t token, int32_t position, int32_t k, float temperature,
                                          const float* coins /* f32[k] or NULL */, gl3_ctx* target /* or NULL */, int32_t slot0,
                                          int32_t* tokens_out /* int32[k] */);
+/* Batched draft chain: k STATIC-BATCHED decode steps of one plan behind one host wait, every row's id fed to its next step on the device.
+ * What a draft plan that serves many requests is called for: one pass over its weights per step whatever the number of requests.
+ * Rows: k_i = k_rows ? k_rows[i] : k steps for row i.  k_rows must be non-increasing with k_rows[0] == k and every entry in [1, k], so the
+ * rows of step j are the prefix 0 .. n_j - 1 with n_j = #{i : k_i > j}; no row is ever compacted.
+ * Equivalence: the call computes, bit for bit, what these k calls compute: gl3_forward_decode_batch_sample(ctx, t_j, seq_ids,
+ * positions + j, n_j, temperature, topp = 0, coins + j * n, tokens_out + j * n), with t_0 = tokens and t_(j+1)[i] = tokens_out[j][i]
+ * ("positions + j": every position plus j), each followed, when target is not NULL, for every row i < n_j with slots[i] >= 0, by
+ * gl3_draft_probs_put_row(target, slots[i] + j, ctx, i).  tokens_out[j][i] with i >= n_j is set to -1.  temperature[i] == 0 makes row i
+ * greedy in every step: its coins are not looked at, and coins may be NULL when every row is greedy.  There is no top-p, for the reason
+ * gl3_forward_decode_chain gives.
+ * After the call everything observable is what the last of those calls leaves: gl3_get_sample_probs_row, gl3_get_buffer(3..6),
+ * gl3_get_attn_rows, gl3_get_topp_counts (unchanged), the K / V rows at positions[i] .. positions[i] + k_i - 1 of seq_ids[i], and the
+ * target's slots, which are complete when the call returns.
+ * The host stages tokens, sequence ids and positions once, the rows' sampler settings with the step-0 coins once and the [k][n] coins
+ * once, and enqueues, per step, the static-batched step of n_j rows (the captured step of that row count while the deepest row is in the
+ * one-launch attention's range, launch by launch past it or under GL3_FLAG_NO_GRAPH, exactly as gl3_forward_decode_batch_sample
+ * chooses), the batched sampler's launches unless every row of the step is greedy, and one hand-over launch; it waits once and
+ * 4 * k * n bytes come back.
+ * KV contract: the chain's.  The K / V rows of all k_i positions of row i are written; rows of drafts that a verification rejects are
+ * overwritten by the next run from the first position not kept.
+ * Refusals, all before anything is uploaded or enqueued; a refused call leaves KV, the sampler state and the target's table untouched.
+ * GL3_E_ARG: ctx, tokens, seq_ids, positions, temperature or tokens_out NULL; n <= 0 or n > max_batch; k outside [1, GL3_CHAIN_MAX];
+ * k_rows not non-increasing, k_rows[0] != k or an entry outside [1, k]; a token or sequence id out of range or a duplicate sequence id;
+ * positions[i] < 0 or positions[i] + k_i > the context length; a temperature negative or NaN; a sampled row with coins NULL or one of its
+ * k_i coins outside [0, 1); target == ctx; target with slots NULL; a slot below -1, or a slot range [slots[i], slots[i] + k_i) that
+ * leaves [0, max_batch) of the target or overlaps another row's; different vocabularies; plans on different devices.  GL3_E_STATE: ctx
+ * or target before gl3_finalize; a greedy row with slots[i] >= 0.  GL3_E_UNSUPPORTED: ctx without max_batch > 1; tp_size > 1 on ctx (the
+ * reason of gl3_forward_decode_chain); a target gl3_draft_probs_put would refuse (no max_batch > 1, or tp_size > 1). */
+GL3_API int32_t gl3_forward_decode_batch_chain(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n,
+                                               int32_t k, const int32_t* k_rows /* int32[n] or NULL */, const float* temperature /* f32[n] */,
+                                               const float* coins /* f32[k][n] or NULL */, gl3_ctx* target /* or NULL */,
+                                               const int32_t* slots /* int32[n] or NULL */, int32_t* tokens_out /* int32[k][n] */);
 /* Test hook, no plan and no device: the host-side plan of a mixed step (csrc/gl3_batch_plan.h) for a plan with n_seqs sequence slots,
  * context length ctx and room for `capacity` rows.  runs_out / tiles_out: int32[.][4] = {first row, rows, sequence, position of the
  * first row}, room for n records each (tiles: at most 8 rows, never across a run boundary, deepest last position first); out_rows:

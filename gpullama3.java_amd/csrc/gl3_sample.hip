@@ -14,14 +14,18 @@
 // token — so the stream of random numbers, and with it the sampled ids, are the reference's by construction.
 //
 // Categorical sampling is entirely on the device (4 bytes come back instead of vocab * 4).  Top-p (r5) too, whenever the answer
-// does not hinge on a tie: the reference's heap selection (ToppSampler.java:118-160) emits the candidates in non-increasing VALUE order —
-// its one quirk, siftDown(indices, 0, i - 1, ..) leaving the last leaf out of every sift, never lets a larger value wait behind a
-// smaller one (the leaf left out is <= the value its parent had, and that value is still in the heap) — so the truncation point, the
-// renormalised coin and the RANK the coin lands on are those of a descending sort, evaluated here with a radix sort + the exact chunked
-// f32 prefix sums; only WHICH index stands at a rank shared by equal probabilities is decided by the heap's sift history, which no sort
-// order reproduces.  The device path returns the token and a tie flag (8 bytes); on a tie at the sampled rank (~2 % of the draws on the
-// near-uniform distributions of random-weight test models, rarer on real ones) the probabilities are copied out and the reference's heap
-// runs on the host (same sift order, same choice).
+// does not hinge on the heap's sift history: the reference's heap selection (ToppSampler.java:118-160) emits the candidates in non-increasing
+// VALUE order up to its last three — its one quirk, siftDown(indices, 0, i - 1, ..) leaving the last leaf out of every sift, does not let a
+// larger value wait behind a smaller one while the leaf left out has a parent other than the root (the leaf is <= the value its parent had,
+// and that value is still in the heap); the leaves at heap positions 2 and 1 hang under the root that was just emitted, so the three
+// smallest candidates come out in an order of the heap's own (n0 = 3: the largest, then the two others as they stood; n0 <= 2: sorted) —
+// so a truncation point among the first max(n0 - 3, 1) ranks (all of them for n0 <= 2), the renormalised coin and the RANK the coin lands on
+// are those of a descending sort, evaluated here with a radix sort + the exact chunked f32 prefix sums; WHICH index stands at a rank shared
+// by equal probabilities, and everything about a draw whose cumulative sum does not exceed topp before the heap-ordered tail, is decided by
+// the heap's sift history, which no sort order reproduces.  The device path returns the token and a host flag (8 bytes); on a tie at the
+// sampled rank (~2 % of the draws on the near-uniform distributions of random-weight test models, rarer on real ones) or a truncation point
+// in the tail (a row with a handful of candidates, or a topp so close to the candidates' total that the sum reaches the last three) the
+// probabilities are copied out and the reference's heap runs on the host (same sift order, same choice).
 //
 // One set of kernels serves both entries.  Rows are a grid dimension, and every per-row setting (temperature, topp, coin, mode) is read
 // from a small device array (SmpRow, gl3_ctx.h), so no kernel takes a per-step scalar and a step costs the same launches at every row
@@ -31,7 +35,7 @@
 // A row whose mode does not need a stage returns at once in that stage: greedy rows take the id of the step's own greedy scan
 // (pf_argmax_*), categorical rows skip the sort.  The sequential sums keep one workgroup per row (n rows run side by side on n CUs); the
 // radix sort is segmented by row (histogram [row][digit][tile], one scan workgroup per row, stable scatter inside the row).  {token, tie}
-// of every row come back in one copy of 8 * n bytes; only rows whose tie flag is set have their probabilities copied out and run through
+// of every row come back in one copy of 8 * n bytes; only rows whose flag is set have their probabilities copied out and run through
 // the host heap (topp_sample).  The logits are read, never written.
 //
 // Tensor parallel.  After the logits gather of a batched step every rank holds every row, rank-chunked as [tp][rows][vocab / tp]
@@ -359,8 +363,9 @@ __global__ __launch_bounds__(RS_THREADS) void btp_scatter_kernel(const SmpRow* _
 //   cumulativeProb += value (f32, in order) until it EXCEEDS topp -> last rank (rank n0 - 1 if it never does);
 //   r = coin * cumulativeProb;  cdf += value from rank 0: the first rank with r < cdf, bounded by the last rank.
 // The two strictly sequential prefix scans run 4096 ranks at a time with the exact parallel sum (gl3_seqsum.h) and walk only the
-// chunk in which the threshold falls.  res[row] = {index at the chosen rank, 1 if another candidate has the same probability (then the
-// reference's heap order, not this sort order, names the token: the host re-runs it)}.
+// chunk in which the threshold falls.  res[row] = {index at the chosen rank, 1 if another candidate has the same probability or the sum
+// did not exceed topp within the ranks the reference emits in sorted order (all but its last three, see the head of this file) — then the
+// reference's heap order, not this sort order, names the token: the host re-runs it}.
 __global__ __launch_bounds__(256) void btp_pick_kernel(const SmpRow* __restrict__ rows, uint32_t* __restrict__ sort, size_t stride, int n, const int* __restrict__ n0p,
                                                        int* __restrict__ res) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -380,6 +385,8 @@ __global__ __launch_bounds__(256) void btp_pick_kernel(const SmpRow* __restrict_
     const int n0 = min(n0p[row], n);
     if (n0 <= 0) { if (t == 0) { out[0] = 0; out[1] = 1; } return; }      // no candidate (cannot happen for a normalised row): let the host decide
     if (t == 0) { thr_s = topp; last_s = n0 - 1; cum_s = 0.f; }
+    const int sorted = n0 <= 2 ? n0 : max(n0 - 3, 1);                // ranks the reference's heap emits in descending order
+    bool heap_tail = false;                                          // thread 0: the truncation point is not among them
     for (int phase = 0; phase < 2; ++phase) {
         if (t == 0) { run_s = 0.f; rank_s = -1; }
         __syncthreads();
@@ -415,6 +422,7 @@ __global__ __launch_bounds__(256) void btp_pick_kernel(const SmpRow* __restrict_
         }
         if (t == 0) {
             if (phase == 0) {
+                heap_tail = rank_s < 0 || rank_s >= sorted;            // the sum reaches the ranks whose order is the heap's own: the host decides
                 if (rank_s >= 0) last_s = rank_s;                      // cumulativeProb > topp at this rank (its value included)
                 cum_s = run_s;                                         // else: every candidate, lastIndex = 0 in the reference
                 thr_s = coin * cum_s;                                  // rng.nextFloat(1f) * cumulativeProb
@@ -427,7 +435,7 @@ __global__ __launch_bounds__(256) void btp_pick_kernel(const SmpRow* __restrict_
         const uint32_t k = skeys[r];
         const bool tie = (r > 0 && skeys[r - 1] == k) || (r + 1 < n0 && skeys[r + 1] == k);
         out[0] = sidx[r];
-        out[1] = tie ? 1 : 0;
+        out[1] = tie || heap_tail ? 1 : 0;
     }
 }
 
@@ -905,7 +913,7 @@ static int32_t sample_launch(gl3_ctx* ctx, gl3_sample_state* b, const float* log
 }
 
 // The sampler's launches for rows 0..n) of `logits` (laid out as `lay` says) behind whatever produced them on the plan's stream (params /
-// h_params: the rows' settings on the device / the host), 8 * n bytes back, host heap for top-p rows whose sampled rank is tied.
+// h_params: the rows' settings on the device / the host), 8 * n bytes back, host heap for top-p rows whose flag is set (btp_pick_kernel).
 static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* logits, RowLayout lay, const int32_t* greedy, const SmpRow* params,
                              const SmpRow* h_params, int n, int32_t* tokens_out) {
     hipStream_t s = ctx->stream;
@@ -926,7 +934,7 @@ static int32_t sample_finish(gl3_ctx* ctx, gl3_sample_state* b, const float* log
             if (R.mode == SMP_TOPP) ++ctx->topp_device;
             continue;
         }
-        // a tie at the sampled rank of this row: the reference's heap history decides between equal probabilities — run it
+        // a tie at the sampled rank of this row, or a sum that reaches the heap's own last three: the reference's heap history decides — run it
         GL3_HIP(hipMemcpyAsync(b->h_probs, b->probs + (size_t)i * v, (size_t)v * 4, hipMemcpyDeviceToHost, s));
         GL3_HIP(hipStreamSynchronize(s));
         tokens_out[i] = topp_sample(b->h_probs, v, R.topp, R.coin, ctx->topp_indices);

@@ -243,7 +243,8 @@ GL3_API int32_t gl3_forward_decode_sample(gl3_ctx* ctx, int32_t token, int32_t p
 /* Parity tap: the probabilities (f32[vocab]) the last gl3_forward_decode_sample sampled from. */
 GL3_API int32_t gl3_get_sample_probs(gl3_ctx* ctx, float* out);
 /* Parity / measurement tap: top-p draws of this plan answered by the device path (8 bytes back) and by the host heap (a tie between equal
- * probabilities at the sampled rank: the reference's heap order decides, gl3_sample.hip). */
+ * probabilities at the sampled rank, or a cumulative sum that reaches the last three candidates, which the reference's heap does not emit in
+ * sorted order: the reference's heap order decides, gl3_sample.hip). */
 GL3_API int32_t gl3_get_topp_counts(gl3_ctx* ctx, int64_t* on_device, int64_t* on_host);
 
 /* Optional: page-lock a caller-owned host buffer (e.g. the MemorySegment the Java shim passes as logits_out on every step) so
@@ -273,7 +274,8 @@ GL3_API int32_t gl3_forward_decode_batch(gl3_ctx* ctx, const int32_t* tokens, co
  * have their own settings); temperature[i] == 0 -> the greedy first-max id of row i (its coin is not looked at); otherwise
  * coins[i] = rng.nextFloat(1f) drawn by the CALLER from row i's own RandomGenerator, in [0, 1); 0 < topp[i] < 1 -> ToppSampler,
  * else CategoricalSampler.  tokens_out: int32[n]; 8 * n bytes come back, and only a top-p row whose sampled rank is shared by
- * equal probabilities has its probabilities copied out for the reference's heap (counted by gl3_get_topp_counts, one count per
+ * equal probabilities, or whose cumulative sum does not exceed topp before the last three candidates, has its probabilities copied
+ * out for the reference's heap (counted by gl3_get_topp_counts, one count per
  * non-greedy top-p row).  The number of sampler launches does not depend on n (gl3_sample.hip).  Everything else as
  * gl3_forward_decode_batch; with every temperature 0 the ids are its argmax_out.  Tensor parallel (tp_size > 1): every rank is called
  * with the same arguments (coins included), samples every row from the gathered, rank-chunked logits and returns the same ids; nothing

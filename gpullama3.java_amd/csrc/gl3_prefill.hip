@@ -698,41 +698,65 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     return false;
 }
 
-// Batched matmul of the f32-activation weight types (gl3_prefill_vl.h): out[b][row] (+)= dot(W[row], act[b]) in the Vector-API order
+// Batched matmul of the f32-activation weight types (gl3_prefill_vl.h): out[b][row] (+)= dot(W[row], act[b]) in the Vector-API order.
+// The switches of the choice are read once per process; vl_gemm_plan makes the choice (kernel, tiles, grid).
+static const VlGemmSwitches& vl_gemm_switches() {
+    static const VlGemmSwitches sw = [] {
+        VlGemmSwitches x;
+        x.mfma = env_flag("GL3_VLQ_MFMA", true);
+        x.xcd_tokens = env_flag("GL3_VQM_XCD_TOKENS", true);
+        x.occ2 = env_flag("GL3_VQM_OCC2", false);
+        const char* v = getenv("GL3_VLQ_MFMA_MIN_TILES");
+        if (v && *v && atoi(v) > 0) x.min_tiles = atoi(v);
+        return x;
+    }();
+    return sw;
+}
+
 template <int EPI>
 static void launch_gemm_vl(gl3_ctx* ctx, const Q8Mat& w, int ntok, const float* act, int act_stride, float* out, int out_stride, float out_scale = 1.0f) {
-    static const bool vlq_mfma = env_flag("GL3_VLQ_MFMA", true);
+    const VlGemmSwitches& sw = vl_gemm_switches();
+    const VlGemmPlan pl = vl_gemm_plan(w.fmt, (ctx->d.flags & GL3_FLAG_VECTOR_512) != 0, w.rows, ntok, sw);
     VlGemmArgs a{};
     a.w = w.w; a.rows = w.rows; a.k = w.k; a.X = act; a.x_stride = act_stride; a.ntok = ntok; a.out = out; a.out_stride = out_stride; a.out_scale = out_scale;
-    a.nrt = (w.rows + 63) / 64;
-    if (w.fmt == GL3_TYPE_F16) {
-        a.ntt = (ntok + F16G_TOK - 1) / F16G_TOK;
-        const dim3 g(8 * ((a.nrt * a.ntt + 7) / 8));
-        if (ctx->d.flags & GL3_FLAG_VECTOR_512)          // 16 accumulator lanes: the same tiles, a wavefront pair per sub-tile
-            hipLaunchKernelGGL((gemm_f16_mfma_v512_kernel<EPI>), g, dim3(512), 2 * F16G_STAGE, ctx->stream, a);
-        else hipLaunchKernelGGL((gemm_f16_mfma_kernel<EPI>), g, dim3(256), 2 * F16G_STAGE, ctx->stream, a);
-    } else if (ntok > VLQ_TOK && vlq_mfma && a.nrt * ((ntok + VQM_TOK - 1) / VQM_TOK) >= 192) {
+    a.nrt = pl.nrt; a.ntt = pl.ntt; a.xcd_tokens = pl.xcd_tokens;
+    const dim3 g(pl.grid);
+    switch (pl.kernel) {
+    case VLG_F16_MFMA_V512:                              // 16 accumulator lanes: the same tiles, a wavefront pair per sub-tile
+        hipLaunchKernelGGL((gemm_f16_mfma_v512_kernel<EPI>), g, dim3(512), 2 * F16G_STAGE, ctx->stream, a);
+        break;
+    case VLG_F16_MFMA:
+        hipLaunchKernelGGL((gemm_f16_mfma_kernel<EPI>), g, dim3(256), 2 * F16G_STAGE, ctx->stream, a);
+        break;
+    case VLG_VLQ_MFMA: {
         // enough 64 x 64 tiles to fill the chip: products on the f32 matrix cores (gemm_vlq_mfma_kernel; 8B Q4_0 pp512 2.53 k -> 3.4 k
         // tok/s).  Fewer tiles (short chunks, the 4096-row projections at 128 tokens) keep the 16-token VALU kernel; GL3_VLQ_MFMA=0: always.
-        a.ntt = (ntok + VQM_TOK - 1) / VQM_TOK;
-        static const bool by_tokens = env_flag("GL3_VQM_XCD_TOKENS", true);      // A/B switch of the tile mapping (vqm_tile_of)
-        a.xcd_tokens = by_tokens ? 1 : 0;
-        const dim3 g(by_tokens ? vqm_grid(a.nrt, a.ntt) : 8 * ((a.nrt * a.ntt + 7) / 8));
         const size_t sm = (size_t)2 * VQM_STAGE_FLOATS * 4;
-        static const bool occ2 = env_flag("GL3_VQM_OCC2", false);                // A/B: the 143-register build, one workgroup per CU (5 % slower)
         if (w.fmt == GL3_TYPE_Q4_0) {
-            if (occ2) hipLaunchKernelGGL((gemm_vlq_mfma_kernel<WT_Q4_0, EPI, 2>), g, dim3(512), sm, ctx->stream, a);
+            if (sw.occ2) hipLaunchKernelGGL((gemm_vlq_mfma_kernel<WT_Q4_0, EPI, 2>), g, dim3(512), sm, ctx->stream, a);
             else hipLaunchKernelGGL((gemm_vlq_mfma_kernel<WT_Q4_0, EPI, 4>), g, dim3(512), sm, ctx->stream, a);
         } else {
-            if (occ2) hipLaunchKernelGGL((gemm_vlq_mfma_kernel<WT_Q8_0, EPI, 2>), g, dim3(512), sm, ctx->stream, a);
+            if (sw.occ2) hipLaunchKernelGGL((gemm_vlq_mfma_kernel<WT_Q8_0, EPI, 2>), g, dim3(512), sm, ctx->stream, a);
             else hipLaunchKernelGGL((gemm_vlq_mfma_kernel<WT_Q8_0, EPI, 4>), g, dim3(512), sm, ctx->stream, a);
         }
-    } else {
-        a.ntt = (ntok + VLQ_TOK - 1) / VLQ_TOK;
-        const dim3 g(8 * ((a.nrt * a.ntt + 7) / 8));
+        break;
+    }
+    default:
         if (w.fmt == GL3_TYPE_Q4_0) hipLaunchKernelGGL((gemm_vlq_kernel<WT_Q4_0, EPI>), g, dim3(256), 2 * vlq_stage_floats<WT_Q4_0>() * 4, ctx->stream, a);
         else hipLaunchKernelGGL((gemm_vlq_kernel<WT_Q8_0, EPI>), g, dim3(256), 2 * vlq_stage_floats<WT_Q8_0>() * 4, ctx->stream, a);
     }
+}
+
+int32_t gl3_debug_vl_gemm_plan(int32_t weight_type, uint32_t flags, int32_t rows, int32_t ntok, int32_t out[7]) {
+    if (!out || rows < 1 || ntok < 1) return GL3_E_ARG;
+    if (weight_type != GL3_TYPE_F16 && weight_type != GL3_TYPE_Q4_0 && weight_type != GL3_TYPE_Q8_0) return GL3_E_ARG;
+    // the plans that batch on these GEMMs: Vector-API order; Q8_0 only with the f32 activation, 512 bits only for F16 (gl3_create)
+    if ((flags & GL3_FLAG_SCALAR_DOT) || (flags & GL3_FLAG_VECTOR_128) || ((flags & GL3_FLAG_F32_ACTIVATION) != 0) != (weight_type == GL3_TYPE_Q8_0) ||
+        ((flags & GL3_FLAG_VECTOR_512) && weight_type != GL3_TYPE_F16))
+        return GL3_E_ARG;
+    const VlGemmPlan p = vl_gemm_plan(weight_type == GL3_TYPE_Q8_0 ? GL3_FMT_Q8V : weight_type, (flags & GL3_FLAG_VECTOR_512) != 0, rows, ntok, vl_gemm_switches());
+    out[0] = p.kernel; out[1] = p.nrt; out[2] = p.ntt; out[3] = p.grid; out[4] = p.xcd_tokens; out[5] = p.G; out[6] = p.P;
+    return GL3_OK;
 }
 
 // The same layers for F16 / Q4_0 / Q8_0-with-f32-activation matrices: RMSNorm to f32 (exact sum of squares), GEMMs on the f32

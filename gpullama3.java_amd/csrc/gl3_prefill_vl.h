@@ -443,6 +443,46 @@ __device__ __forceinline__ bool vqm_tile_of(const VlGemmArgs& a, int& rt, int& t
     return rt < a.nrt && tt < a.ntt;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The one host-side choice of a batched GEMM of these weight types: which kernel, its tiles and its grid.  launch_gemm_vl
+// (gl3_prefill.hip) launches what the plan says; gl3_debug_vl_gemm_plan answers from the same function with no device, which is
+// what tests/vl_gemm_shapes.py holds its Python restatement to.
+//   F16: gemm_f16_mfma_kernel (the 512-bit species: gemm_f16_mfma_v512_kernel) at every size, 64 x 64 tiles, vl_tile_of.
+//   Q4_0 / Q8_0-f32act: gemm_vlq_mfma_kernel (64 x 64 tiles) for more than VLQ_TOK tokens whose 64 x 64 tiles number at least
+//   min_tiles (enough to fill the chip); gemm_vlq_kernel (64 rows x 16 tokens, vl_tile_of) otherwise, and always with mfma off.
+enum { VLG_F16_MFMA = 0, VLG_F16_MFMA_V512 = 1, VLG_VLQ_VALU = 2, VLG_VLQ_MFMA = 3 };
+constexpr int VQM_MIN_TILES = 192;
+struct VlGemmSwitches {
+    bool mfma = true;                // GL3_VLQ_MFMA=0: gemm_vlq_kernel at every size
+    bool xcd_tokens = true;          // GL3_VQM_XCD_TOKENS=0: vl_tile_of instead of vqm_tile_of (A/B switch of the tile mapping)
+    bool occ2 = false;               // GL3_VQM_OCC2=1: the 143-register build, one workgroup per CU (5 % slower)
+    int min_tiles = VQM_MIN_TILES;   // GL3_VLQ_MFMA_MIN_TILES=<t>: diagnostic, puts small test shapes on the matrix-pipe kernel
+};
+struct VlGemmPlan {
+    int kernel, nrt, ntt, grid;
+    int xcd_tokens, G, P;            // gemm_vlq_mfma_kernel: the tile mapping and vqm_groups' split (0, 0, 0 for the other kernels)
+};
+inline VlGemmPlan vl_gemm_plan(int fmt, bool v512, int rows, int ntok, const VlGemmSwitches& sw) {
+    VlGemmPlan p{};
+    p.nrt = (rows + 63) / 64;
+    if (fmt == GL3_TYPE_F16) {
+        p.kernel = v512 ? VLG_F16_MFMA_V512 : VLG_F16_MFMA;
+        p.ntt = (ntok + F16G_TOK - 1) / F16G_TOK;
+        p.grid = 8 * ((p.nrt * p.ntt + 7) / 8);
+    } else if (ntok > VLQ_TOK && sw.mfma && p.nrt * ((ntok + VQM_TOK - 1) / VQM_TOK) >= sw.min_tiles) {
+        p.kernel = VLG_VLQ_MFMA;
+        p.ntt = (ntok + VQM_TOK - 1) / VQM_TOK;
+        p.xcd_tokens = sw.xcd_tokens ? 1 : 0;
+        p.grid = sw.xcd_tokens ? vqm_grid(p.nrt, p.ntt) : 8 * ((p.nrt * p.ntt + 7) / 8);
+        if (sw.xcd_tokens) { p.G = vqm_groups(p.ntt); p.P = 8 / p.G; }
+    } else {
+        p.kernel = VLG_VLQ_VALU;
+        p.ntt = (ntok + VLQ_TOK - 1) / VLQ_TOK;
+        p.grid = 8 * ((p.nrt * p.ntt + 7) / 8);
+    }
+    return p;
+}
+
 template <int WT, int EPI, int OCC = 2>
 __global__ __launch_bounds__(512, OCC) void gemm_vlq_mfma_kernel(const VlGemmArgs a) {
     static_assert(WT == WT_Q4_0 || WT == WT_Q8_0, "F16 runs on gemm_f16_mfma_kernel");

@@ -519,6 +519,15 @@ class HipMasterPlan:
             pass
 
 
+def vl_gemm_plan(weight_type: int, flags: int, rows: int, ntok: int) -> dict:
+    """The library's choice for one batched GEMM of the f32-activation weight types (gl3_debug_vl_gemm_plan; no plan, no device):
+    kernel name, row tiles, token tiles, grid, and for gemm_vlq_mfma_kernel the tile mapping and vqm_groups' G / P."""
+    out = np.zeros(7, np.int32)
+    hip.check(hip.lib().gl3_debug_vl_gemm_plan(weight_type, flags, rows, ntok, _p(out)))
+    k, nrt, ntt, grid, xcd, g, p = out.tolist()
+    return dict(kernel=hip.VL_GEMM_KERNELS[k], nrt=nrt, ntt=ntt, grid=grid, xcd_tokens=xcd, G=g, P=p)
+
+
 def make_local_group(n: int):
     """Test transport: n plans in one process on one GPU (one host thread per rank)."""
     g = C.c_void_p()

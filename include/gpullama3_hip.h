@@ -502,6 +502,18 @@ GL3_API int32_t gl3_debug_batch_plan_split(const int32_t* seq_ids, const int32_t
 GL3_API int32_t gl3_debug_decode_attn_plan(int32_t head_size, int32_t kvmul, int32_t heads_l, int32_t kv_heads_l, int32_t ctx, int32_t window,
                                            int32_t attn_mid, int32_t head_kernel_allowed, int32_t pos, int32_t group, int32_t* regime_out,
                                            int64_t* launches_out, int32_t* n_launches, int64_t* head_out);
+/* Test hook, no plan and no device: the choice a batched step makes for ONE GEMM of the f32-activation weight types
+ * (csrc/gl3_prefill_vl.h: vl_gemm_plan, what launch_gemm_vl launches) — a matrix of `rows` rows of weight_type (GL3_TYPE_F16, GL3_TYPE_Q4_0,
+ * or GL3_TYPE_Q8_0 with GL3_FLAG_F32_ACTIVATION in flags; GL3_FLAG_VECTOR_512 with F16 only) over ntok tokens (chunk tokens, batched decode
+ * rows, or the output rows of the logits launch).  out: int32[7] = {kernel (0 gemm_f16_mfma_kernel, 1 gemm_f16_mfma_v512_kernel,
+ * 2 gemm_vlq_kernel, 3 gemm_vlq_mfma_kernel), row tiles of 64, token tiles (64 tokens; 16 for gemm_vlq_kernel), grid, and for
+ * gemm_vlq_mfma_kernel: 1 = token tiles pinned to XCDs (vqm_tile_of) / 0 = vl_tile_of, token groups G and row parts P = 8 / G of vqm_groups
+ * (0, 0, 0 for the other kernels; G = P = 0 under GL3_VQM_XCD_TOKENS=0)}.  Q4_0 / Q8_0 take gemm_vlq_mfma_kernel when ntok > 16 and
+ * row tiles * ceil(ntok / 64) >= 192.  The answer depends on the process's switches, read once: GL3_VLQ_MFMA=0 (never the matrix-pipe kernel),
+ * GL3_VQM_XCD_TOKENS=0, and the diagnostic GL3_VLQ_MFMA_MIN_TILES=<t> (t > 0 replaces the 192; it puts small test shapes on the matrix-pipe
+ * kernel).  GL3_E_ARG: a weight type / flag combination that gl3_create refuses or that batches elsewhere (GL3_FLAG_SCALAR_DOT,
+ * GL3_FLAG_VECTOR_128, Q8_0 without GL3_FLAG_F32_ACTIVATION), rows < 1, ntok < 1, null out. */
+GL3_API int32_t gl3_debug_vl_gemm_plan(int32_t weight_type, uint32_t flags, int32_t rows, int32_t ntok, int32_t out[7]);
 /* Fork a prefix: copy the K and V rows at positions [p0, p1) of sequence src_seq, every layer, into the same positions of each of the
  * n_dst sequences dst_seqs[].  Rows outside [p0, p1) of the destinations, every other sequence and the source are untouched.
  * What the rows mean: a row's arithmetic does not depend on which rows share its step, so the K / V rows at positions 0 .. p of a sequence are

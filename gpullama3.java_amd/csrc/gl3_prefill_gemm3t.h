@@ -8,8 +8,8 @@
 // (8192 = 64 x 128 rows: NFR 4; 9728 = 60.8 x 160: NFR 5 -> 244 workgroups); the host picks the shape with the fewest tile-steps per CU.
 //   * a K stage is KBT blocks (1 or 2): the weight side of a block is 17.5 KB at NFR = 7, a stage of two 51 KB, the ring 3 x 51 = 153 KB.  All 8
 //     wavefronts of a CU share ONE barrier domain here, so both wavefronts of every SIMD sit in the barrier / scale-conversion phase together and the
-//     matrix pipe idles through it (stamps: 429 + 228 of 2685 cycles per one-block stage): two blocks per stage halve those phases.  With KBT = 1 and
-//     NFR odd the loop body is two stages (the result-tile register sets alternate with the global tile count).
+//     matrix pipe idles through it (stamps: 429 + 228 of 2685 cycles per one-block stage): two blocks per stage halve those phases.  With KBT = 1 the
+//     loop body is two stages (the result-tile register sets alternate with the global tile count, the B operand sets with the block count).
 //   * the token fragment's B operands are read once per block and serve NFR tiles; the A operands stream through two register sets, tile
 //     q + 2's fragment is fetched when tile q + 1's MFMAs have been issued.
 //   * gate and up tiles of an output element sit in different wavefronts: after the K loop each wavefront parks half of its tiles in LDS (the ring is
@@ -39,7 +39,10 @@ __global__ __launch_bounds__(512, 2) void pf_gemm3t_kernel(const GemmArgs a) {
     constexpr int NLA = KBT * 2 * NFR, NLB = KBT * BBLK / 1024, NPIECE = NLA + 2 * NLB;  // pieces per stage: weights, int8 activations, activation scale operands
     constexpr int NDMA = (NPIECE + NW - 1) / NW;
     constexpr int NSTEP = KBT * NFR;                                                     // tile steps per stage
-    constexpr int SPB = (NSTEP & 1) ? 2 : 1;                                             // stages per loop body (register-set parity)
+    // stages per loop body: all register-set indices are static, so a body must return both parities to where it found them — the result-tile
+    // sets alternate with the tile count (NSTEP odd: two stages), the B operand sets with the block count (KBT = 1: two stages whatever NFR is;
+    // with one stage per body and NFR even, every stage behind the first read the B set the prologue filled, not the one loaded for it)
+    constexpr int SPB = ((NSTEP & 1) || KBT == 1) ? 2 : 1;
     constexpr int BSTEP = NSTEP - 2, NLATE = 2;                                          // first step that fetches an A fragment of the next stage
     constexpr int NSC = (KBT * AROWS + NT - 1) / NT;                                     // weight scale entries per thread and stage
     static_assert(NFR >= 3 && NDMA <= NSTEP && NSC <= 2, "shape");

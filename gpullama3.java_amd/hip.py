@@ -20,6 +20,8 @@ FLAG_NO_GRAPH, FLAG_LAYER_TAPS, FLAG_FORCE_RCCL, FLAG_SCALAR_DOT, FLAG_F32_ACTIV
 FLAG_VECTOR_512, FLAG_VECTOR_128 = 32, 64      # -Dllama.VectorBitSize (default 256): see include/gpullama3_hip.h
 CHAIN_MAX = 64                                 # GL3_CHAIN_MAX: the longest gl3_forward_decode_chain
 VL_GEMM_KERNELS = ["gemm_f16_mfma_kernel", "gemm_f16_mfma_v512_kernel", "gemm_vlq_kernel", "gemm_vlq_mfma_kernel"]      # gl3_debug_vl_gemm_plan's kernel ids
+GEMM3_KERNELS = ["pf_gemm3_kernel", "pf_gemm3t_kernel"]      # gl3_debug_gemm3_plan's kernel ids
+GEMM3_EPI = {"store": 0, "resid": 1, "swiglu": 2}            # ... and its epilogue ids
 K_NAMES = ["matvec_qkv", "matvec_wo", "matvec_gateup", "matvec_down", "matvec_logits", "attention", "other", "collective"]
 
 T_IDS = {"token_embd.weight": 0, "output_norm.weight": 1, "output.weight": 2, "attn_norm.weight": 3,
@@ -101,6 +103,7 @@ _SIGS = {  # symbol -> (restype, argtypes): exactly the declarations of include/
                                                C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32)]),
     "gl3_debug_decode_attn_plan": (C.c_int32, [C.c_int32] * 10 + [C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "gl3_debug_vl_gemm_plan": (C.c_int32, [C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p]),
+    "gl3_debug_gemm3_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "gl3_kv_seq_copy": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "gl3_get_attn_rows": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "gl3_get_sample_probs_row": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -528,6 +528,16 @@ def vl_gemm_plan(weight_type: int, flags: int, rows: int, ntok: int) -> dict:
     return dict(kernel=hip.VL_GEMM_KERNELS[k], nrt=nrt, ntt=ntt, grid=grid, xcd_tokens=xcd, G=g, P=p)
 
 
+def gemm3_plan(epi: str, rows: int, ntok: int) -> dict:
+    """The library's choice for one > 64-token Q8_0 GEMM (gl3_debug_gemm3_plan; no plan, no device).  epi: "store" | "resid" | "swiglu"
+    (rows = hidden).  Kernel name, workgroup tile (rows per matrix x tokens), blocks per K stage, NFR of the tall tiling, row and token
+    tiles, grid, and whether gate + up writes hb quantised."""
+    out = np.zeros(9, np.int32)
+    hip.check(hip.lib().gl3_debug_gemm3_plan(hip.GEMM3_EPI[epi], rows, ntok, _p(out)))
+    k, tr, tt, kb, nfr, nrt, ntt, grid, qout = out.tolist()
+    return dict(kernel=hip.GEMM3_KERNELS[k], tile_rows=tr, tile_tok=tt, KB=kb, NFR=nfr, nrt=nrt, ntt=ntt, grid=grid, qout=qout)
+
+
 def make_local_group(n: int):
     """Test transport: n plans in one process on one GPU (one host thread per rank)."""
     g = C.c_void_p()

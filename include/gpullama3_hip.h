@@ -514,6 +514,19 @@ GL3_API int32_t gl3_debug_decode_attn_plan(int32_t head_size, int32_t kvmul, int
  * kernel).  GL3_E_ARG: a weight type / flag combination that gl3_create refuses or that batches elsewhere (GL3_FLAG_SCALAR_DOT,
  * GL3_FLAG_VECTOR_128, Q8_0 without GL3_FLAG_F32_ACTIVATION), rows < 1, ntok < 1, null out. */
 GL3_API int32_t gl3_debug_vl_gemm_plan(int32_t weight_type, uint32_t flags, int32_t rows, int32_t ntok, int32_t out[7]);
+/* Test hook, no plan and no device: the choice a batched Q8_0 step of MORE THAN 64 rows makes for ONE GEMM (csrc/gl3_prefill_gemm3.hip: g3_plan,
+ * what g3_dispatch launches) — epi 0 store (qkv, logits), 1 residual (wo, down), 2 SwiGLU (gate + up, rows = hidden) over a matrix of `rows`
+ * rows and ntok tokens (chunk tokens, or the output rows of the logits launch).  out: int32[9] = {kernel (0 pf_gemm3_kernel,
+ * 1 pf_gemm3t_kernel), workgroup tile rows per matrix, tile tokens, blocks per K stage, NFR (row fragments of the tall tiling; 0 for
+ * pf_gemm3_kernel), row tiles, token tiles, grid (tiles rounded up to 8; workgroup lin works on tile J = (lin & 7) * (grid / 8) + (lin >> 3),
+ * row tile J / token tiles, token tile J % token tiles, and leaves when J is past the last tile), 1 when the gate + up launch can write hb
+ * as the down projection's quantised operand (tall tiling, two blocks per stage, rows % 32 == 0)}.  Store / residual: 128 x 128 tiles when
+ * ceil(rows / 128) * ceil(ntok / 128) >= 512, 96 x 128 when rows % 96 == 0 and 128 < ceil(rows / 96) * ceil(ntok / 128) <= 384, else
+ * 64 x 128.  SwiGLU: the fewest tile-steps per SIMD between 128 x 128 (64 + 64 rows) and the tall tiling of NFR 4 .. 7, the first of equal
+ * costs.  The answer depends on the process's switches, read once: GL3_PF_GEMM3_TALL=-1|4..7, GL3_PF_GEMM3_TALL_KB=1,
+ * GL3_PF_GEMM3_SHAPE=1..4 (4: 64 x 64 tiles), GL3_PF_GEMM3_QOUT=0.  GL3_E_ARG: another epi, rows < 1, ntok < 1, null out (ntok <= 64 is
+ * answered by the same rule although such a step runs bdw_gemm_kernel). */
+GL3_API int32_t gl3_debug_gemm3_plan(int32_t epi, int32_t rows, int32_t ntok, int32_t out[9]);
 /* Fork a prefix: copy the K and V rows at positions [p0, p1) of sequence src_seq, every layer, into the same positions of each of the
  * n_dst sequences dst_seqs[].  Rows outside [p0, p1) of the destinations, every other sequence and the source are untouched.
  * What the rows mean: a row's arithmetic does not depend on which rows share its step, so the K / V rows at positions 0 .. p of a sequence are

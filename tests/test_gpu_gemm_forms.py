@@ -3,7 +3,9 @@ parity tests (ragged small shapes to the 8B / 1B layers at 512 tokens) in its ow
    default                     pf_gemm3_kernel for qkv / wo / down, the tall one-round tiling (pf_gemm3t_kernel) or the 128 x 128 tiling for gate + up — normal suite
    GL3_PF_GEMM3_TALL=-1        gate + up on the 128 x 128 tiling everywhere;  =4..7 the tall tiling with that many row fragments on EVERY shape
    GL3_PF_GEMM3_TALL_KB=1      one block per K stage of the tall tiling (default: two)
-   GL3_PF_GEMM3_SHAPE=1|2|3    128 x 128 / 96 x 128 / 64 x 128 workgroup tiles for every non-SwiGLU projection
+   GL3_PF_GEMM3_SHAPE=1|2|3|4  128 x 128 / 96 x 128 / 64 x 128 / 64 x 64 workgroup tiles for every non-SwiGLU projection
+   GL3_PF_GEMM3_QOUT=0         hb leaves the tall tiling as f32 and is quantised by its own launch
+test_gemm3_grid_rows_under_a_form repeats rows of the grid of tests/gemm3_shapes.py (every chunk row compared) under these switches.
 These tilings are what different matrix shapes take by default; the switches force each of them onto the test shapes.  The prefill attention has
 its own forms (test_prefill_attention_forms), and so has the static-batched decode step (test_static_batched_decode_forms:
 GL3_NO_FUSED_BD_ATTN / GL3_NO_FUSED_QUANT)."""
@@ -28,6 +30,27 @@ def test_prefill_parity_of_a_gemm_form(env):
     tail = out.stdout[-1500:] + out.stderr[-500:]
     assert out.returncode == 0, tail
     assert " passed" in out.stdout and "failed" not in out.stdout, tail
+
+
+G3_FORMS = [{"GL3_PF_GEMM3_TALL": "4"}, {"GL3_PF_GEMM3_TALL_KB": "1"}, {"GL3_PF_GEMM3_TALL": "-1"}, {"GL3_PF_GEMM3_SHAPE": "1"}, {"GL3_PF_GEMM3_SHAPE": "2"},
+            {"GL3_PF_GEMM3_SHAPE": "3"}, {"GL3_PF_GEMM3_SHAPE": "4"}, {"GL3_PF_GEMM3_QOUT": "0"}, {"GL3_PF_GEMM3_TALL": "6", "GL3_PF_GEMM3_TALL_KB": "1"}]
+
+
+@pytest.mark.parametrize("env", G3_FORMS, ids=["-".join("%s=%s" % (k[13:].lower(), v) for k, v in e.items()) for e in G3_FORMS])
+def test_gemm3_grid_rows_under_a_form(env):
+    """FORM_ROWS of tests/gemm3_shapes.py (every row of a chunk, K / V of every row, the step behind; logits of every flagged row) under a
+    tiling the grid's defaults do not reach on those shapes: GL3_PF_GEMM3_TALL=4 is the only way NFR 4 runs, and the only way the tall
+    kernel meets a single token tile (65, 97 tokens), fewer rows than one tile (hidden 96) and K of one block; TALL_KB=1 the one-block
+    stages on the default NFR 5 (and NFR 6 everywhere); TALL=-1 the 128 x 128 SwiGLU tiling at hidden 8224; SHAPE=1 the 128 x 128 tile on
+    the residual epilogue (its only run, with every token tail: gemm3_shapes.FORM_ROWS says why), =2 the 96 x 128 tile on row counts 96 does not divide, =3 64 x 128 where 96 x 128 is the default, =4 the
+    64 x 64 tile with its own token tiling; QOUT=0 the f32 hb behind the tall kernel."""
+    import gemm3_shapes as gs
+    select = " or ".join("%s]" % r for r in gs.FORM_ROWS)
+    out = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_gemm3_shapes.py"), "-m", "gpu", "-x", "-q", "-k", select,
+                          "-p", "no:cacheprovider"], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env), cwd=ROOT)
+    tail = out.stdout[-1500:] + out.stderr[-500:]
+    assert out.returncode == 0, tail
+    assert "%d passed" % len(gs.FORM_ROWS) in out.stdout and "failed" not in out.stdout and "skipped" not in out.stdout, tail
 
 
 @pytest.mark.parametrize("env,select", [

@@ -88,6 +88,37 @@ constexpr int BD_TS = 32, BD_TS_MAX = 64;            // token slots: 32 (<= 32 t
 // grid: workgroup id -> (strip, token tile).  The token tiles of a strip stream the same weights, so they sit 8 ids apart: same
 // XCD (= id % 8), i.e. one L2, and dispatched together.
 __host__ __device__ inline int bdw_grid(int strips, int nt) { return ((strips + 7) / 8) * 8 * nt; }
+// ... of a launch of ntg token tiles: the token tile and the unit (strip; QOUT: strip pair) of workgroup id
+__host__ __device__ inline int bdw_place_tile(unsigned id, int ntg) { return (id >> 3) % ntg; }
+__host__ __device__ inline int bdw_place_unit(unsigned id, int ntg) { return (id / (8 * ntg)) * 8 + (id & 7); }
+
+// Token slots of the XQ / XS operand layout above when a step of n tokens runs on bdw_gemm_kernel (n <= 64), 0 for a larger step.
+inline int bd_tslots(int n) { return n <= BD_TS ? BD_TS : n <= BD_TS_MAX ? BD_TS_MAX : 0; }
+
+// The launch of one GEMM of a step of at most 64 tokens: what launch_gemm (gl3_prefill.hip) launches and, with no device, what
+// gl3_debug_bd_gemm_plan answers.  epi: EPI_STORE / EPI_RESID (DA 8) or EPI_SWIGLU (DA 4; quantised_out: the two-strip form that writes hb
+// as the down projection's operand).  tslots 0: more than 64 tokens, not this kernel (every other field 0).
+struct BdGemmPlan {
+    int tslots, DA, qout, threads;                   // TS, ring depth, the quantising form, threads per workgroup
+    int ntt, units, grid;                            // token tiles, strips (qout: strip pairs), workgroups (units padded to 8, x ntt)
+    int ntiles, trips, partial;                      // K: tiles of 4 blocks, full trips of DA tiles, tiles of the partial last trip (0: none)
+};
+inline BdGemmPlan bd_gemm_plan(int epi, int rows, int k, int ntok, bool quantised_out) {
+    BdGemmPlan p{};
+    p.tslots = bd_tslots(ntok);
+    if (!p.tslots) return p;
+    p.DA = epi == EPI_SWIGLU ? 4 : 8;
+    p.qout = epi == EPI_SWIGLU && quantised_out;
+    p.threads = p.qout ? 128 : 64;
+    p.ntt = (ntok + 15) / 16;
+    p.units = p.qout ? (rows + 31) / 32 : (rows + 15) / 16;
+    p.grid = bdw_grid(p.units, p.ntt);
+    const int nb = k / 32;
+    p.ntiles = (nb + 3) / 4;
+    p.trips = (nb >> 2) / p.DA;
+    p.partial = p.ntiles - p.trips * p.DA;
+    return p;
+}
 
 template <int EPI, int DA, int WPE, bool QOUT = false, int TS = BD_TS, bool GRP = false>
 __global__ __launch_bounds__(QOUT ? 128 : 64, WPE) void bdw_gemm_kernel(const GemmArgs a) {
@@ -108,8 +139,8 @@ __global__ __launch_bounds__(QOUT ? 128 : 64, WPE) void bdw_gemm_kernel(const Ge
     float* xsl = xsl_all[wv];
     const int NTG = (a.ntok + 15) >> 4;                                         // token tiles of this launch
     const int nstrips = (a.rows + 15) >> 4;
-    const int h = GRP ? 0 : (blockIdx.x >> 3) % NTG;
-    const int unit = GRP ? (int)(blockIdx.x % a.gspe) : (blockIdx.x / (8 * NTG)) * 8 + (blockIdx.x & 7);   // strip (QOUT: strip pair; GRP: of the entry's expert)
+    const int h = GRP ? 0 : bdw_place_tile(blockIdx.x, NTG);
+    const int unit = GRP ? (int)(blockIdx.x % a.gspe) : bdw_place_unit(blockIdx.x, NTG);                   // strip (QOUT: strip pair; GRP: of the entry's expert)
     int strip = unit * NWV + wv;                                                // QOUT: rows % 32 == 0, so both strips exist
     int gfirst = 0, gcnt = 16, gslot = 0;                                       // GRP: the entry's sorted slots, this lane's slot
     uint32_t tokslot = 16 * h + t;                                              // this lane's token slot of XQ2 / XS2

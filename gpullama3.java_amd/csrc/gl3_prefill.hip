@@ -373,10 +373,8 @@ void gl3_prefill_free(gl3_ctx* ctx) {
     ctx->pf = nullptr;
 }
 
-// Token slots of the XQ / XS operand layout of gl3_bd_gemm.h when a step of n tokens runs on the wave-owned small-batch GEMM
+// bd_tslots(n) (gl3_bd_gemm.h): token slots of the XQ / XS operand layout when a step of n tokens runs on the wave-owned small-batch GEMM
 // (bdw_gemm_kernel: n <= 64), 0 for a larger step.
-static int bd_tslots(int n) { return n <= BD_TS ? BD_TS : n <= BD_TS_MAX ? BD_TS_MAX : 0; }
-
 // The one fact that fixes a step's activation layout: more than 64 tokens run on pf_gemm3_kernel / pf_gemm3t_kernel, which read the
 // chunk-major int8 operand XQ[k / 16][token slot][16 B] and the scale operands XP.  Every producer of a GEMM operand (the quantiser,
 // the attention and gate + up epilogues that quantise their own output) and launch_gemm ask here, so they cannot disagree.
@@ -443,19 +441,31 @@ static void launch_gemm(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int ntok,
         return;
     }
     // static-batched decode / small chunks: one wavefront per (16-row strip, 16 tokens), all of K
-    const int ts = bd_tslots(ntok);
-    a.tslots = ts;
-    const dim3 grid(bdw_grid((w.rows + 15) / 16, (ntok + 15) / 16));
-    const dim3 gridq(bdw_grid((w.rows + 31) / 32, (ntok + 15) / 16));      // quantised output: two strips per workgroup
+    const BdGemmPlan pl = bd_gemm_plan(EPI, w.rows, w.k, ntok, quantised_out);      // quantised output: two strips per workgroup
+    a.tslots = pl.tslots;
+    const dim3 grid(pl.grid), block(pl.threads);
 #define GL3_BDW(TS_) \
     do { \
         if constexpr (EPI == EPI_SWIGLU) { \
-            if (quantised_out) hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, true, TS_>), gridq, dim3(128), 0, ctx->stream, a); \
-            else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, false, TS_>), grid, dim3(64), 0, ctx->stream, a); \
-        } else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 8, 2, false, TS_>), grid, dim3(64), 0, ctx->stream, a); \
+            if (pl.qout) hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, true, TS_>), grid, block, 0, ctx->stream, a); \
+            else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, false, TS_>), grid, block, 0, ctx->stream, a); \
+        } else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 8, 2, false, TS_>), grid, block, 0, ctx->stream, a); \
     } while (0)
-    if (ts == BD_TS) GL3_BDW(BD_TS); else GL3_BDW(BD_TS_MAX);
+    if (pl.tslots == BD_TS) GL3_BDW(BD_TS); else GL3_BDW(BD_TS_MAX);
 #undef GL3_BDW
+}
+
+int32_t gl3_debug_bd_gemm_plan(int32_t epi, int32_t rows, int32_t k, int32_t ntok, int32_t quantised_out, int32_t wg, int32_t out[12]) {
+    if (!out || rows < 1 || k < 32 || k % 32 || ntok < 1 || (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU)) return GL3_E_ARG;
+    const BdGemmPlan p = bd_gemm_plan(epi, rows, k, ntok, quantised_out != 0);
+    out[0] = p.tslots; out[1] = p.DA; out[2] = p.qout; out[3] = p.threads; out[4] = p.ntt; out[5] = p.units; out[6] = p.grid;
+    out[7] = p.ntiles; out[8] = p.trips; out[9] = p.partial;
+    out[10] = out[11] = -1;                              // workgroup wg: its unit and token tile; -1: no such workgroup, or it exits
+    if (p.tslots && wg >= 0 && wg < p.grid) {
+        const int unit = bdw_place_unit((unsigned)wg, p.ntt);
+        if (unit < p.units) { out[10] = unit; out[11] = bdw_place_tile((unsigned)wg, p.ntt); }
+    }
+    return GL3_OK;
 }
 
 // The routed experts of a Qwen2-MoE step: one launch over (tile-table entry, strip of the entry's expert) — bdw_gemm_kernel<.., GRP>.

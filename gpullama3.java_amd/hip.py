@@ -104,6 +104,7 @@ _SIGS = {  # symbol -> (restype, argtypes): exactly the declarations of include/
     "gl3_debug_decode_attn_plan": (C.c_int32, [C.c_int32] * 10 + [C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "gl3_debug_vl_gemm_plan": (C.c_int32, [C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p]),
     "gl3_debug_gemm3_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "gl3_debug_bd_gemm_plan": (C.c_int32, [C.c_int32] * 6 + [C.c_void_p]),
     "gl3_kv_seq_copy": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "gl3_get_attn_rows": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "gl3_get_sample_probs_row": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),

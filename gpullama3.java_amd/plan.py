@@ -538,6 +538,18 @@ def gemm3_plan(epi: str, rows: int, ntok: int) -> dict:
     return dict(kernel=hip.GEMM3_KERNELS[k], tile_rows=tr, tile_tok=tt, KB=kb, NFR=nfr, nrt=nrt, ntt=ntt, grid=grid, qout=qout)
 
 
+def bd_gemm_plan(epi: str, rows: int, k: int, ntok: int, quantised_out: bool = False, wg: int = -1) -> dict:
+    """The library's launch of one Q8_0 GEMM of a step of at most 64 rows (gl3_debug_bd_gemm_plan; no plan, no device).  epi: "store" |
+    "resid" | "swiglu" (rows = hidden).  Token slots (0: more than 64 tokens, not this kernel), DA, the quantising form, threads, token
+    tiles, units, grid, K tiles / full trips / tiles of the partial trip, and `place`: (unit, token tile) of workgroup wg, None when it
+    exits or wg is outside the grid."""
+    out = np.zeros(12, np.int32)
+    hip.check(hip.lib().gl3_debug_bd_gemm_plan(hip.GEMM3_EPI[epi], rows, k, ntok, int(quantised_out), wg, _p(out)))
+    ts, da, qout, threads, ntt, units, grid, ntiles, trips, partial, unit, h = out.tolist()
+    return dict(ts=ts, DA=da, qout=qout, threads=threads, ntt=ntt, units=units, grid=grid, ntiles=ntiles, trips=trips, partial=partial,
+                place=None if unit < 0 else (unit, h))
+
+
 def make_local_group(n: int):
     """Test transport: n plans in one process on one GPU (one host thread per rank)."""
     g = C.c_void_p()

@@ -527,6 +527,17 @@ GL3_API int32_t gl3_debug_vl_gemm_plan(int32_t weight_type, uint32_t flags, int3
  * GL3_PF_GEMM3_SHAPE=1..4 (4: 64 x 64 tiles), GL3_PF_GEMM3_QOUT=0.  GL3_E_ARG: another epi, rows < 1, ntok < 1, null out (ntok <= 64 is
  * answered by the same rule although such a step runs bdw_gemm_kernel). */
 GL3_API int32_t gl3_debug_gemm3_plan(int32_t epi, int32_t rows, int32_t ntok, int32_t out[9]);
+/* Test hook, no plan and no device: the launch a batched Q8_0 step of AT MOST 64 rows makes for ONE GEMM (csrc/gl3_bd_gemm.h: bd_gemm_plan,
+ * what launch_gemm launches as bdw_gemm_kernel) — epi as above over a matrix of `rows` rows and an inner dimension of k elements (a multiple
+ * of 32) and ntok tokens (step rows, or the output rows of the logits launch); quantised_out != 0: the gate + up launch that writes hb as the
+ * down projection's int8 operand (ignored for the other epilogues).  out: int32[12] = {token slots of the operand layout (32 up to 32
+ * tokens, 64 up to 64; 0: more than 64 tokens, not this kernel, and every other field is 0 or -1), tiles in flight DA (8; SwiGLU 4), 1 when
+ * the quantising form runs, threads per workgroup (64; quantising 128), token tiles of 16, units (16-row strips; quantising: 32-row strip
+ * pairs), grid (units rounded up to 8, times token tiles), K tiles of 4 blocks, full trips of DA tiles, tiles of the partial last trip (0:
+ * none; the last of them holds k / 32 % 4 blocks when that is not 0), and for workgroup `wg` of the grid its unit and its token tile
+ * (unit = wg / (8 * token tiles) * 8 + wg % 8, token tile = wg / 8 % token tiles), both -1 when wg is outside the grid or the workgroup
+ * exits at once (unit >= units)}.  GL3_E_ARG: another epi, rows < 1, k < 32 or not a multiple of 32, ntok < 1, null out. */
+GL3_API int32_t gl3_debug_bd_gemm_plan(int32_t epi, int32_t rows, int32_t k, int32_t ntok, int32_t quantised_out, int32_t wg, int32_t out[12]);
 /* Fork a prefix: copy the K and V rows at positions [p0, p1) of sequence src_seq, every layer, into the same positions of each of the
  * n_dst sequences dst_seqs[].  Rows outside [p0, p1) of the destinations, every other sequence and the source are untouched.
  * What the rows mean: a row's arithmetic does not depend on which rows share its step, so the K / V rows at positions 0 .. p of a sequence are

@@ -132,50 +132,45 @@ static RlKernel rl_kernel(int fmt, int epi) {
 // rows_valid / out / resid_in may address a slice (tensor parallel row split); w holds exactly that slice.
 static void launch_matvec(gl3_ctx* ctx, int pro, int epi, const Q8Mat& w, const Q8Mat* w2, const float* x,
                           const float* norm_w, float* out, const float* resid_in, float out_scale = 1.0f, const TpRec* tp = nullptr) {
-    if (w.fmt != GL3_TYPE_Q8_0) {      // F16 / Q4_0: element-wise chains, one output row per lane (gl3_rowlane_kernels.h)
+    if (w.fmt != GL3_TYPE_Q8_0) {      // F16 / Q4_0 / Q8_0-f32act: every choice of the launch is vl_matvec_plan's (gl3_veclane_kernels.h)
         hipStream_t s = ctx->stream;
-        // Vector-order kernels normalise in their own prologue (matvec_vl_kernel<.., RMS>),
-        // except for the K-split types when the launch has few 8-row groups (a tensor-parallel rank's slice): the fused kernel
-        // keeps one wavefront per group whatever the row count, so a 224-group gate/up slice would take as long as the whole
-        // matrix; there the one-workgroup rmsnorm launch + the K-split kernel (16 wavefronts per group) is the faster pair.
-        const bool ksplit_type = w.vl && (w.fmt == GL3_FMT_Q8V || w.fmt == GL3_TYPE_Q4_0);
-        const long vl_waves = (long)((w.rows + 7) / 8) * (epi == EPI_SWIGLU ? 2 : 1);
-        const bool fuse_rms = pro == PRO_RMS && w.vl && vl_rms_fusable(w.k) && epi != EPI_RESID && !(ksplit_type && vl_waves <= 512);
-        if (pro == PRO_RMS && !fuse_rms) {
+        const VlMatvecPlan pl = vl_matvec_plan(ctx->d.weight_type, ctx->d.flags, pro, epi, w.rows, w.k);
+        if (pl.rms_launch) {
             hipLaunchKernelGGL(rmsnorm_f32_kernel, dim3(1), dim3(256), rmsnorm_smem_bytes(w.k), s, x, w.k, norm_w, ctx->d.rms_eps, ctx->xn);
             x = ctx->xn;
         }
-        if (w.vl) {                   // Vector-API order (8 accumulator lanes per row): lane = (row, accumulator), HBM-bound
-            VlArgs v{};
-            v.w = w.w; v.w2 = w2 ? w2->w : nullptr; v.rows = w.rows; v.k = w.k; v.x = x; v.out = out; v.resid_in = resid_in; v.out_scale = out_scale;
-            v.tp = tp;      // folded gathers (gate/up -> hb, down -> x): producer side only, the consumers get wait launches
-            if (fuse_rms) { v.norm_w = norm_w; v.eps = ctx->d.rms_eps; }
-            const int ngroups = (w.rows + 7) / 8;
-            wt_dispatch(w.fmt, ctx->d.flags & GL3_FLAG_VECTOR_512, [&](auto wt, auto species) { epi_dispatch(epi, [&](auto e) {
-                constexpr int WT = decltype(wt)::value, SPECIES = decltype(species)::value, EPI = decltype(e)::value, NM = EPI == EPI_SWIGLU ? 2 : 1;
-                if constexpr (EPI != EPI_RESID)
-                    if (fuse_rms) {
-                        hipLaunchKernelGGL((matvec_vl_kernel<WT, EPI, true, VL_RMS_WAVES, SPECIES>), dim3((ngroups + VL_RMS_WAVES - 1) / VL_RMS_WAVES), dim3(64 * VL_RMS_WAVES),
-                                           vl_rms_smem_bytes(w.k), s, v);
-                        return;
-                    }
-                if constexpr (WT == WT_F16)
-                    hipLaunchKernelGGL((matvec_vl_kernel<WT, EPI, false, VL_WAVES, SPECIES>), dim3((ngroups + VL_WAVES - 1) / VL_WAVES), dim3(64 * VL_WAVES), vl_smem_bytes(w.k), s, v);
-                else {                // Q4_0 / Q8_0-f32act: up to 16 wavefronts split K of one 8-row group (matvec_vlq_kernel)
-                    const int nw = vq_waves<WT>(w.k, NM, ngroups);
-                    auto launch = [&](auto maxw) {
-                        constexpr int MAXW = decltype(maxw)::value;
-                        const size_t qs = vq_smem_bytes<WT, MAXW>(w.k, NM, nw);
-                        hipLaunchKernelGGL((matvec_vlq_kernel<WT, EPI, MAXW>), dim3(ngroups), dim3(64 * nw), qs, s, v);
-                    };
-                    if (nw == 16) launch(IntC<16>{}); else launch(IntC<8>{});
-                }
-            }); });
+        const dim3 grid(pl.grid), block(64 * pl.waves);
+        if (pl.kernel == MVK_RL) {    // scalar order: element-wise chains, one output row per lane (gl3_rowlane_kernels.h)
+            RlArgs a{};
+            a.w = w.w; a.w2 = w2 ? w2->w : nullptr; a.rows = w.rows; a.k = w.k; a.x = x; a.out = out; a.resid_in = resid_in; a.out_scale = out_scale;
+            hipLaunchKernelGGL(rl_kernel(w.fmt, epi), grid, block, pl.smem, s, a);
             return;
         }
-        RlArgs a{};
-        a.w = w.w; a.w2 = w2 ? w2->w : nullptr; a.rows = w.rows; a.k = w.k; a.x = x; a.out = out; a.resid_in = resid_in; a.out_scale = out_scale;
-        hipLaunchKernelGGL(rl_kernel(w.fmt, epi), dim3((w.rows + 63) / 64), dim3(RL_THREADS), rl_smem_bytes(w.k, epi), s, a);
+        // Vector-API order (8 accumulator lanes per row): lane = (row, accumulator), HBM-bound
+        VlArgs v{};
+        v.w = w.w; v.w2 = w2 ? w2->w : nullptr; v.rows = w.rows; v.k = w.k; v.x = x; v.out = out; v.resid_in = resid_in; v.out_scale = out_scale;
+        v.tp = tp;      // folded gathers (gate/up -> hb, down -> x): producer side only, the consumers get wait launches
+        if (pl.kernel == MVK_VL_RMS) { v.norm_w = norm_w; v.eps = ctx->d.rms_eps; }
+        bool launched = false;
+        wt_dispatch(w.fmt, ctx->d.flags & GL3_FLAG_VECTOR_512, [&](auto wt, auto species) { epi_dispatch(epi, [&](auto e) {
+            constexpr int WT = decltype(wt)::value, SPECIES = decltype(species)::value, EPI = decltype(e)::value;
+            if (pl.kernel == MVK_VL_RMS) {
+                if constexpr (EPI != EPI_RESID) {
+                    hipLaunchKernelGGL((matvec_vl_kernel<WT, EPI, true, VL_RMS_WAVES, SPECIES>), grid, block, pl.smem, s, v);
+                    launched = true;
+                }
+            } else if (pl.kernel == MVK_VL) {
+                if constexpr (WT == WT_F16) {
+                    hipLaunchKernelGGL((matvec_vl_kernel<WT, EPI, false, VL_WAVES, SPECIES>), grid, block, pl.smem, s, v);
+                    launched = true;
+                }
+            } else if constexpr (WT != WT_F16) {      // Q4_0 / Q8_0-f32act: up to 16 wavefronts split K of one 8-row group (matvec_vlq_kernel)
+                if (pl.maxw == 16) hipLaunchKernelGGL((matvec_vlq_kernel<WT, EPI, 16>), grid, block, pl.smem, s, v);
+                else hipLaunchKernelGGL((matvec_vlq_kernel<WT, EPI, 8>), grid, block, pl.smem, s, v);
+                launched = true;
+            }
+        }); });
+        if (!launched) no_kernel("vector-order matvec<plan kernel, epilogue>", pl.kernel, epi);
         return;
     }
     MatvecArgs a{};
@@ -747,9 +742,22 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     TRY(dmalloc(ctx, &ctx->att_sums, (size_t)ctx->heads_l));
     if (moe) TRY(moe_build_slots(ctx));          // after hb: the merged gate/up launch writes the shared expert's SwiGLU output there
     for (const MvVariant& v : MV_VARIANTS) TRYHIP(hipFuncSetAttribute((const void*)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
+    hipError_t vq_attr = hipSuccess;
     for (int fmt : {GL3_TYPE_F16, GL3_TYPE_Q4_0})
         for (int epi : {EPI_STORE, EPI_RESID, EPI_SWIGLU}) TRYHIP(hipFuncSetAttribute((const void*)rl_kernel(fmt, epi), hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
     TRYHIP(hipFuncSetAttribute((const void*)rmsnorm_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
+    // matvec_vlq_kernel stages nw * rc chunks, up to one chunk per wavefront more than K: Q4_0 with one matrix asks for 65792 bytes at
+    // K >= 12544 on 16 wavefronts (the 8B down projection on a tensor-parallel rank) and at K >= 14592 on 8 — above the 64 KB default
+    for (int fmt : {(int)GL3_TYPE_Q4_0, GL3_FMT_Q8V})
+        wt_dispatch(fmt, false, [&](auto wt, auto) { for (int epi : {EPI_STORE, EPI_RESID, EPI_SWIGLU}) epi_dispatch(epi, [&](auto e) {
+            constexpr int WT = decltype(wt)::value, EPI = decltype(e)::value;
+            if constexpr (WT != WT_F16) {
+                hipError_t e8 = hipFuncSetAttribute((const void*)matvec_vlq_kernel<WT, EPI, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VQ_LDS_MAX);
+                hipError_t e16 = hipFuncSetAttribute((const void*)matvec_vlq_kernel<WT, EPI, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)VQ_LDS_MAX);
+                if (vq_attr == hipSuccess) vq_attr = e8 != hipSuccess ? e8 : e16;
+            }
+        }); });
+    TRYHIP(vq_attr);
     {   // Decode attention (gl3_decode_attn.h).  The three switches of its plan: GL3_NO_FUSED_ATTN=1 no attn_head_kernel (one launch per layer for
         // positions < AF_MAXN) where the head size admits it; GL3_ATTN_WINDOW softmax positions kept in LDS, a multiple of 1024 (shrinks it for tests;
         // longer rows run in windows with the sequential sum carried across them: no cap on the context length, r2 rejected contexts above ~20 k);
@@ -1619,6 +1627,25 @@ int32_t gl3_debug_decode_attn_plan(int32_t head_size, int32_t kvmul, int32_t hea
         memcpy(launches_out + 6 * i, rec, sizeof(rec));
     }
     head_out[0] = (int64_t)attn_head_smem(head_size, group); head_out[1] = attn_head_admits(head_size); head_out[2] = attn_head_admits(head_size, group);
+    return GL3_OK;
+}
+
+int32_t gl3_debug_matvec_plan(int32_t weight_type, uint32_t flags, int32_t pro, int32_t epi, int32_t rows, int32_t k, int32_t out[12]) {
+    if (!out || rows < 1 || k < 1) return GL3_E_ARG;
+    if ((pro != PRO_RMS && pro != PRO_QUANT) || (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU)) return GL3_E_ARG;
+    // the plans whose decode matvecs go through vl_matvec_plan, with the inner dimensions gl3_create accepts for them
+    const int wt = vl_weight_format(weight_type, flags);
+    const bool scalar = (flags & GL3_FLAG_SCALAR_DOT) != 0;
+    if (!wt || (flags & GL3_FLAG_VECTOR_128) || ((flags & GL3_FLAG_F32_ACTIVATION) != 0) != (wt == WT_Q8_0) || (scalar && wt == WT_Q8_0) ||
+        ((flags & GL3_FLAG_VECTOR_512) && (wt != WT_F16 || scalar)))
+        return GL3_E_ARG;
+    if (k % (scalar ? 64 : vl_chunk_elems(wt)) || (!scalar && vl_smem_bytes(k) > 64 * 1024) ||
+        (scalar && rl_smem_bytes(k, EPI_STORE) > 150 * 1024))
+        return GL3_E_ARG;
+    const VlMatvecPlan p = vl_matvec_plan(weight_type, flags, pro, epi, rows, k);
+    out[0] = p.kernel; out[1] = p.rms_launch; out[2] = p.waves; out[3] = p.maxw; out[4] = p.grid; out[5] = 64 * p.waves;
+    out[6] = (int32_t)p.smem; out[7] = p.kernel == MVK_RL ? (int32_t)GL3_LDS_MAX : p.kernel == MVK_VLQ ? (int32_t)VQ_LDS_MAX : 64 * 1024;
+    out[8] = p.nch; out[9] = p.nrounds; out[10] = p.rc; out[11] = p.rcm;
     return GL3_OK;
 }
 

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/gpullama3_hip.h"      // weight types and plan flags, for vl_matvec_plan
 #include "gl3_rowlane_kernels.h"
 
 namespace gl3 {
@@ -416,22 +417,33 @@ static __global__ __launch_bounds__(64 * VW, WT == WT_F16 ? 1 : 2) void matvec_v
 // kernel's register allocation is fragile (hipcc, ROCm 7.2): equivalent restructurings of the chain loop spilled 130 - 330 bytes.
 template <int WT, int MAXW>
 __host__ __device__ constexpr int vq_round_chunks(int nm) { return (WT == WT_Q4_0 ? 8 : 12) / (MAXW == 16 ? 2 : 1) / nm; }
-template <int WT, int MAXW>
-__host__ __device__ inline int vq_rc(int k, int nm, int nw) {
-    const int nch = k / (WT == WT_Q4_0 ? 256 : 128), cap = nw * vq_round_chunks<WT, MAXW>(nm);
-    const int nrounds = (nch + cap - 1) / cap;
-    return (nch + nw * nrounds - 1) / (nw * nrounds);
+__host__ __device__ constexpr int vq_round_chunks(int wt, int maxw, int nm) {      // the same number from run-time arguments (the host plan)
+    return wt == WT_Q4_0 ? (maxw == 16 ? vq_round_chunks<WT_Q4_0, 16>(nm) : vq_round_chunks<WT_Q4_0, 8>(nm))
+                         : (maxw == 16 ? vq_round_chunks<WT_Q8_0, 16>(nm) : vq_round_chunks<WT_Q8_0, 8>(nm));
 }
-template <int WT, int MAXW>
-__host__ __device__ inline size_t vq_smem_bytes(int k, int nm, int nw) {
-    return (size_t)nm * 64 * 4 + (size_t)nw * vq_rc<WT, MAXW>(k, nm, nw) * (WT == WT_Q4_0 ? 256 : 128) * 4;
+// The one partition of a group's nch chunks over nw wavefronts holding at most rcm chunks each per round: nrounds rounds, rc chunks per
+// wavefront and round; wavefront w of round r owns chunks [(r nw + w) rc, (r nw + w + 1) rc) cut at nch (none when the range starts past
+// it), and the chain runs over them in that order.  Written once: the kernel, its LDS request and the host plan all ask here.
+// (The two steps take the product first and are force-inlined: in this form the kernel's ISA is the one it had with the lines inline.)
+struct VqPartition { int nrounds, rc; };
+__host__ __device__ __forceinline__ int vq_rounds(int cap, int nch) { return (nch + cap - 1) / cap; }        // cap = nw * rcm: the chunks one round takes
+__host__ __device__ __forceinline__ int vq_rc(int turns, int nch) { return (nch + turns - 1) / turns; }      // turns = nw * nrounds: wavefront turns of the chain
+__host__ __device__ inline VqPartition vq_partition(int nch, int nw, int rcm) {
+    const int nrounds = vq_rounds(nw * rcm, nch);
+    return {nrounds, vq_rc(nw * nrounds, nch)};
 }
-template <int WT>
-__host__ inline int vq_waves(int k, int nm, int ngroups) {
-    const int nch = k / (WT == WT_Q4_0 ? 256 : 128);
+// dynamic LDS of matvec_vlq_kernel: the chain values of nm matrices | per wavefront one round's activation slice (rc chunks)
+__host__ __device__ inline size_t vq_smem_bytes(int wt, int nm, int nw, int rc) {
+    return (size_t)nm * 64 * 4 + (size_t)nw * rc * vl_chunk_elems(wt) * 4;
+}
+// ... at most one chunk per wavefront beyond K (rc is rounded up), K <= 16384: more than the 64 KB a kernel gets by default, so gl3_create
+// raises hipFuncAttributeMaxDynamicSharedMemorySize of every instantiation to this
+constexpr size_t VQ_LDS_MAX = 2 * 64 * 4 + (size_t)(16384 + 16 * 256) * 4;
+__host__ inline int vq_waves(int wt, int k, int nm, int ngroups) {
+    const int nch = k / vl_chunk_elems(wt);
     int nw = 4;
     while (nw < 16 && (long)ngroups * nw < 2048) nw *= 2;
-    if (nw == 4 && nch > 4 * vq_round_chunks<WT, 8>(nm)) nw = 8;
+    if (nw == 4 && nch > 4 * vq_round_chunks(wt, 8, nm)) nw = 8;
     while (nw > 4 && nch < nw) nw /= 2;
     return nw;
 }
@@ -450,8 +462,8 @@ static __global__ __launch_bounds__(64 * MAXW) void matvec_vlq_kernel(const VlAr
     const int VQ_WAVES = blockDim.x >> 6;
     const int g = blockIdx.x;
     const int nch = a.k / CE;
-    const int nrounds = (nch + VQ_WAVES * RCM - 1) / (VQ_WAVES * RCM);
-    const int rc = (nch + VQ_WAVES * nrounds - 1) / (VQ_WAVES * nrounds);
+    const int nrounds = vq_rounds(VQ_WAVES * RCM, nch);
+    const int rc = vq_rc(VQ_WAVES * nrounds, nch);
     float* accx = vq_smem;
     float* xT = vq_smem + NM * 64 + wave * (rc * CE);
     const size_t gbytes = vl_group_bytes(WT, a.k);
@@ -604,6 +616,56 @@ static __global__ __launch_bounds__(64 * MAXW) void matvec_vlq_kernel(const VlAr
         if (a.tp) tp_push_store(a.tp->p, a.out + row, o);
     }
     if (a.tp && a.tp->p.npeers) tp_publish(a.tp->p, gridDim.x);      // wavefront 0 of every workgroup
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The one host-side choice of a decode matvec of the f32-activation weight types (F16, Q4_0, Q8_0 with GL3_FLAG_F32_ACTIVATION): which
+// kernel family, whether rmsnorm_f32_kernel runs in front, workgroup, grid and dynamic LDS.  launch_matvec (gl3_api.hip) launches from
+// this struct and nothing else; gl3_debug_matvec_plan answers from the same function with no device, which is what
+// tests/matvec_shapes.py holds its Python restatement to.
+//   scalar order (GL3_FLAG_SCALAR_DOT; F16, Q4_0): matvec_rl_kernel, 64 rows per workgroup; a PRO_RMS launch normalises in front.
+//   vector order, PRO_RMS and not the residual epilogue, K in vl_rms_fusable's range: matvec_vl_kernel with the RMSNorm in its prologue
+//     (VL_RMS_WAVES 8-row groups per workgroup) — except for a K-split type whose launch has at most 512 wavefronts' worth of groups
+//     (groups x matrices: a small matrix, or a tensor-parallel rank's slice): the fused kernel keeps one wavefront per group whatever
+//     the row count, so there rmsnorm_f32_kernel + the K-split kernel is the faster pair.
+//   vector order otherwise: F16 matvec_vl_kernel (VL_WAVES groups per workgroup); Q4_0 / Q8_0-f32act matvec_vlq_kernel, one group per
+//     workgroup of vq_waves wavefronts, MAXW = 16 exactly when that is 16, partition = vq_partition.
+enum { MVK_RL = 0, MVK_VL_RMS = 1, MVK_VL = 2, MVK_VLQ = 3 };
+constexpr int VQ_FUSE_MIN_WAVES = 512;      // a K-split type fuses the prologue only above this many (groups x matrices)
+struct VlMatvecPlan {
+    int kernel;                  // MVK_*
+    bool rms_launch;             // rmsnorm_f32_kernel (one workgroup of 256 threads, rmsnorm_smem_bytes(k)) in front; the matvec then reads its output
+    int waves, maxw;             // wavefronts per workgroup; MAXW of matvec_vlq_kernel (0 for the other kernels)
+    int grid; size_t smem;       // workgroups and dynamic LDS bytes of the matvec
+    int nch, nrounds, rc, rcm;   // matvec_vlq_kernel: chunks of K, vq_partition of them, vq_round_chunks (0 for the other kernels)
+};
+__host__ inline int vl_weight_format(int weight_type, uint32_t flags) {      // WT_* of a plan's matrices; 0: not one of these types
+    if (weight_type == GL3_TYPE_F16) return WT_F16;
+    if (weight_type == GL3_TYPE_Q4_0) return WT_Q4_0;
+    return weight_type == GL3_TYPE_Q8_0 && (flags & GL3_FLAG_F32_ACTIVATION) ? WT_Q8_0 : 0;
+}
+__host__ inline VlMatvecPlan vl_matvec_plan(int weight_type, uint32_t flags, int pro, int epi, int rows, int k) {
+    VlMatvecPlan p{};
+    const int wt = vl_weight_format(weight_type, flags), nm = epi == EPI_SWIGLU ? 2 : 1;
+    const bool vector_order = wt == WT_Q8_0 || !(flags & GL3_FLAG_SCALAR_DOT), ksplit_type = vector_order && wt != WT_F16;
+    const int ngroups = (rows + 7) / 8;
+    const bool fuse_rms = pro == PRO_RMS && vector_order && vl_rms_fusable(k) && epi != EPI_RESID &&
+                          !(ksplit_type && (long)ngroups * nm <= VQ_FUSE_MIN_WAVES);
+    p.rms_launch = pro == PRO_RMS && !fuse_rms;
+    if (!vector_order) {
+        p.kernel = MVK_RL; p.waves = RL_THREADS / 64; p.grid = (rows + 63) / 64; p.smem = rl_smem_bytes(k, epi);
+    } else if (fuse_rms) {
+        p.kernel = MVK_VL_RMS; p.waves = VL_RMS_WAVES; p.grid = (ngroups + VL_RMS_WAVES - 1) / VL_RMS_WAVES; p.smem = vl_rms_smem_bytes(k);
+    } else if (wt == WT_F16) {
+        p.kernel = MVK_VL; p.waves = VL_WAVES; p.grid = (ngroups + VL_WAVES - 1) / VL_WAVES; p.smem = vl_smem_bytes(k);
+    } else {
+        p.kernel = MVK_VLQ; p.waves = vq_waves(wt, k, nm, ngroups); p.maxw = p.waves == 16 ? 16 : 8; p.grid = ngroups;
+        p.nch = k / vl_chunk_elems(wt); p.rcm = vq_round_chunks(wt, p.maxw, nm);
+        const VqPartition part = vq_partition(p.nch, p.waves, p.rcm);
+        p.nrounds = part.nrounds; p.rc = part.rc;
+        p.smem = vq_smem_bytes(wt, nm, p.waves, p.rc);
+    }
+    return p;
 }
 
 }  // namespace gl3

@@ -22,6 +22,8 @@ CHAIN_MAX = 64                                 # GL3_CHAIN_MAX: the longest gl3_
 VL_GEMM_KERNELS = ["gemm_f16_mfma_kernel", "gemm_f16_mfma_v512_kernel", "gemm_vlq_kernel", "gemm_vlq_mfma_kernel"]      # gl3_debug_vl_gemm_plan's kernel ids
 GEMM3_KERNELS = ["pf_gemm3_kernel", "pf_gemm3t_kernel"]      # gl3_debug_gemm3_plan's kernel ids
 GEMM3_EPI = {"store": 0, "resid": 1, "swiglu": 2}            # ... and its epilogue ids
+MATVEC_KERNELS = ["matvec_rl_kernel", "matvec_vl_kernel<RMS>", "matvec_vl_kernel", "matvec_vlq_kernel"]      # gl3_debug_matvec_plan's kernel ids
+MATVEC_PRO = {"rms": 0, "quant": 1}                          # ... and its prologue ids (the epilogue ids are GEMM3_EPI's)
 K_NAMES = ["matvec_qkv", "matvec_wo", "matvec_gateup", "matvec_down", "matvec_logits", "attention", "other", "collective"]
 
 T_IDS = {"token_embd.weight": 0, "output_norm.weight": 1, "output.weight": 2, "attn_norm.weight": 3,
@@ -105,6 +107,7 @@ _SIGS = {  # symbol -> (restype, argtypes): exactly the declarations of include/
     "gl3_debug_vl_gemm_plan": (C.c_int32, [C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p]),
     "gl3_debug_gemm3_plan": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "gl3_debug_bd_gemm_plan": (C.c_int32, [C.c_int32] * 6 + [C.c_void_p]),
+    "gl3_debug_matvec_plan": (C.c_int32, [C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "gl3_kv_seq_copy": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "gl3_get_attn_rows": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "gl3_get_sample_probs_row": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),

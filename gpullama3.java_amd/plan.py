@@ -550,6 +550,17 @@ def bd_gemm_plan(epi: str, rows: int, k: int, ntok: int, quantised_out: bool = F
                 place=None if unit < 0 else (unit, h))
 
 
+def matvec_plan(weight_type: int, flags: int, pro: str, epi: str, rows: int, k: int) -> dict:
+    """The library's launch of one decode projection of the f32-activation weight types (gl3_debug_matvec_plan; no plan, no device).
+    pro: "rms" | "quant"; epi: "store" | "resid" | "swiglu" (rows = hidden).  Kernel name, whether rmsnorm_f32_kernel runs in front,
+    wavefronts per workgroup, MAXW, grid, threads, dynamic LDS bytes and their cap, and matvec_vlq_kernel's nch / nrounds / rc / RCM."""
+    out = np.zeros(12, np.int32)
+    hip.check(hip.lib().gl3_debug_matvec_plan(weight_type, flags, hip.MATVEC_PRO[pro], hip.GEMM3_EPI[epi], rows, k, _p(out)))
+    kern, rms, nw, maxw, grid, threads, lds, cap, nch, nrounds, rc, rcm = out.tolist()
+    return dict(kernel=hip.MATVEC_KERNELS[kern], rms_launch=rms, nw=nw, MAXW=maxw, grid=grid, threads=threads, lds=lds, lds_cap=cap,
+                nch=nch, nrounds=nrounds, rc=rc, RCM=rcm)
+
+
 def make_local_group(n: int):
     """Test transport: n plans in one process on one GPU (one host thread per rank)."""
     g = C.c_void_p()

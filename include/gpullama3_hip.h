@@ -538,6 +538,23 @@ GL3_API int32_t gl3_debug_gemm3_plan(int32_t epi, int32_t rows, int32_t ntok, in
  * (unit = wg / (8 * token tiles) * 8 + wg % 8, token tile = wg / 8 % token tiles), both -1 when wg is outside the grid or the workgroup
  * exits at once (unit >= units)}.  GL3_E_ARG: another epi, rows < 1, k < 32 or not a multiple of 32, ntok < 1, null out. */
 GL3_API int32_t gl3_debug_bd_gemm_plan(int32_t epi, int32_t rows, int32_t k, int32_t ntok, int32_t quantised_out, int32_t wg, int32_t out[12]);
+/* Test hook, no plan and no device: the launch a single-token decode step makes for ONE projection of the f32-activation weight types
+ * (csrc/gl3_veclane_kernels.h: vl_matvec_plan, what launch_matvec launches) — a matrix of `rows` rows and an inner dimension of k elements
+ * of weight_type (GL3_TYPE_F16, GL3_TYPE_Q4_0, or GL3_TYPE_Q8_0 with GL3_FLAG_F32_ACTIVATION in flags; GL3_FLAG_SCALAR_DOT for the scalar
+ * order of F16 / Q4_0, GL3_FLAG_VECTOR_512 with vector-order F16 only), pro 0 = RMSNorm in front of the product (qkv, gate + up, logits) /
+ * 1 = none (wo, down), epi 0 store, 1 residual, 2 SwiGLU (gate + up, rows = hidden).  out: int32[12] = {kernel (0 matvec_rl_kernel,
+ * 1 matvec_vl_kernel with the RMSNorm in its prologue, 2 matvec_vl_kernel, 3 matvec_vlq_kernel), 1 when rmsnorm_f32_kernel is launched in
+ * front, wavefronts per workgroup, MAXW of matvec_vlq_kernel (8 or 16; 0 for the other kernels), grid, threads per workgroup, dynamic LDS
+ * bytes, the LDS bytes the kernel may ask for, and for matvec_vlq_kernel (0 otherwise): chunks of K (256 elements of Q4_0, 128 of Q8_0),
+ * rounds, chunks per wavefront and round rc, and the most a wavefront's registers hold (vq_round_chunks)}.  Scalar order: 64 rows per
+ * workgroup of 9 wavefronts.  Vector order: the prologue form for pro 0, epi != 1 and 1024 <= k <= 5120 — for Q4_0 / Q8_0 only when
+ * ceil(rows / 8) * (2 for SwiGLU) > 512; else F16 takes matvec_vl_kernel (2 groups of 8 rows per workgroup) and Q4_0 / Q8_0
+ * matvec_vlq_kernel, one 8-row group per workgroup of 16 wavefronts below 256 groups, 8 below 512, 4 from there (8 when K has more than
+ * 4 * vq_round_chunks chunks), halved down to 4 while there are fewer chunks than wavefronts.  GL3_E_ARG: a weight type / flag
+ * combination gl3_create refuses or that runs matvec_q8t_kernel (Q8_0 without GL3_FLAG_F32_ACTIVATION), GL3_FLAG_VECTOR_128, another pro
+ * or epi, rows < 1, a k the type does not accept (multiples of 64 for F16 and the scalar order, 256 for vector-order Q4_0, 128 for Q8_0;
+ * at most 16384 in the vector order), null out. */
+GL3_API int32_t gl3_debug_matvec_plan(int32_t weight_type, uint32_t flags, int32_t pro, int32_t epi, int32_t rows, int32_t k, int32_t out[12]);
 /* Fork a prefix: copy the K and V rows at positions [p0, p1) of sequence src_seq, every layer, into the same positions of each of the
  * n_dst sequences dst_seqs[].  Rows outside [p0, p1) of the destinations, every other sequence and the source are untouched.
  * What the rows mean: a row's arithmetic does not depend on which rows share its step, so the K / V rows at positions 0 .. p of a sequence are

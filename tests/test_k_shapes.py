@@ -72,7 +72,9 @@ def test_the_thresholds_are_the_ones_in_the_kernel_sources():
     assert "NXV = (PRO == PRO_RMS) ? %d : %d;" % (ks.Q8_RMS_QUADS, ks.Q8_QUANT_QUADS) in src["gl3_decode_kernels.h"]
     assert "constexpr int MOE_QJ = %d;" % ks.MOE_QJ in src["gl3_moe_kernels.h"] and "constexpr int MOE_RR = %d;" % ks.MOE_RR in src["gl3_moe_kernels.h"]
     assert "ss_scratch_bytes(int n) { return 128 + (size_t)3 * n; }" in src["gl3_seqsum.h"]
-    assert "ksplit_type && vl_waves <= %d" % (ks.KSPLIT_MIN_WAVES - 1) in src["gl3_api.hip"]
+    # the 512-wavefront condition of the K-split types: vl_matvec_plan's (the launch code asks it and holds no copy)
+    assert "constexpr int VQ_FUSE_MIN_WAVES = %d;" % (ks.KSPLIT_MIN_WAVES - 1) in src["gl3_veclane_kernels.h"]
+    assert "!(ksplit_type && (long)ngroups * nm <= VQ_FUSE_MIN_WAVES)" in src["gl3_veclane_kernels.h"] and "ksplit_type" not in src["gl3_api.hip"]
     assert "GL3_LDS_MAX = 160 * 1024 - 256;" in src["gl3_api.hip"]
     for kern in ("pf_norm_quant_kernel<PQ_NORM>", "pf_norm_quant_kernel<PQ_NORM_F32>"):
         assert re.search(r"hipFuncSetAttribute\(\(const void\*\)%s, hipFuncAttributeMaxDynamicSharedMemorySize, 160 \* 1024 - 256\)" % re.escape(kern),

@@ -847,7 +847,7 @@ void gl3_destroy(gl3_ctx* ctx) {
     if (!ctx->arena.base) { f(ctx->x); f(ctx->xb); f(ctx->hb); f(ctx->logits); }
     gl3_tp_arena_free(ctx);
     f(ctx->att); f(ctx->att_t); f(ctx->att_tmax); f(ctx->att_sums); f(ctx->dyn); f(ctx->dyn_seq); f(ctx->argmax); f(ctx->taps); f(ctx->staging);
-    for (auto& pr : ctx->pinned) hipHostUnregister(pr.first);
+    for (auto& pb : ctx->pinned) if (pb.registered) hipHostUnregister(pb.ptr);
     ctx->pinned.clear();
     if (ctx->h_dyn) hipHostFree(ctx->h_dyn);
     if (ctx->h_logits) hipHostFree(ctx->h_logits);
@@ -1099,8 +1099,8 @@ int32_t gl3_forward_decode(gl3_ctx* ctx, int32_t token, int32_t pos, float* logi
     // staging buffer + one host memcpy (513 KB for a 128 k vocabulary: ~40 us per token on the host)
     bool direct = false;
     if (logits_out)
-        for (const auto& pr : ctx->pinned)
-            if ((uint8_t*)logits_out >= (uint8_t*)pr.first && (uint8_t*)logits_out + (size_t)ctx->d.vocab * 4 <= (uint8_t*)pr.first + pr.second) direct = true;
+        for (const auto& pb : ctx->pinned)
+            if ((uint8_t*)logits_out >= (uint8_t*)pb.ptr && (uint8_t*)logits_out + (size_t)ctx->d.vocab * 4 <= (uint8_t*)pb.ptr + pb.bytes) direct = true;
     if (logits_out) GL3_HIP(hipMemcpyAsync(direct ? logits_out : ctx->h_logits, ctx->logits, (size_t)ctx->d.vocab * 4, hipMemcpyDeviceToHost, ctx->stream));
     GL3_HIP(hipStreamSynchronize(ctx->stream));
     if ((r = gl3_tp_check(ctx)) != GL3_OK) return r;
@@ -1753,18 +1753,43 @@ int32_t gl3_pin_host_buffer(gl3_ctx* ctx, void* ptr, uint64_t bytes) {
     // long test runs (round 3).  A page-aligned, page-padded buffer (mmap, posix_memalign, Arena.allocate(n, 4096)) owns its pages.
     if (((uintptr_t)ptr & 4095) || (bytes & 4095)) GL3_FAIL(GL3_E_ARG, "gl3_pin_host_buffer: pointer and size must be multiples of 4096 (the buffer must own its pages)");
     GL3_HIP(hipSetDevice(ctx->d.device));
-    GL3_HIP(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
-    ctx->pinned.emplace_back(ptr, (size_t)bytes);
+    // memory that is page-locked already (gl3_host_alloc) is taken as it is; anything else is registered here.  Neither call may leave its
+    // error behind: the runtime keeps it for the thread, and the next launch check (hipGetLastError) of any plan would report it.
+    hipPointerAttribute_t at;
+    const bool locked = hipPointerGetAttributes(&at, ptr) == hipSuccess && at.type == hipMemoryTypeHost;
+    (void)hipGetLastError();
+    if (!locked) {
+        const hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterDefault);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            GL3_FAIL(GL3_E_HIP, std::string("hipHostRegister: ") + hipGetErrorString(e) + " (gl3_host_alloc returns page-locked memory)");
+        }
+    }
+    ctx->pinned.push_back({ptr, (size_t)bytes, !locked});
     return GL3_OK;
+}
+
+int32_t gl3_host_alloc(uint64_t bytes, void** out) {
+    if (!out || !bytes) return GL3_E_ARG;
+    *out = nullptr;
+    const hipError_t e = hipHostMalloc(out, bytes, hipHostMallocPortable);      // for plans on any device
+    if (e == hipSuccess) return GL3_OK;
+    (void)hipGetLastError();
+    *out = nullptr;
+    return e == hipErrorOutOfMemory ? GL3_E_OOM : GL3_E_HIP;
+}
+
+void gl3_host_free(void* ptr) {
+    if (ptr && hipHostFree(ptr) != hipSuccess) (void)hipGetLastError();
 }
 
 int32_t gl3_unpin_host_buffer(gl3_ctx* ctx, void* ptr) {
     if (!ctx) return GL3_E_ARG;
     for (size_t i = 0; i < ctx->pinned.size(); ++i)
-        if (ctx->pinned[i].first == ptr) {
+        if (ctx->pinned[i].ptr == ptr) {
             GL3_HIP(hipSetDevice(ctx->d.device));
             GL3_HIP(hipStreamSynchronize(ctx->stream));
-            hipHostUnregister(ptr);
+            if (ctx->pinned[i].registered) hipHostUnregister(ptr);
             ctx->pinned.erase(ctx->pinned.begin() + i);
             return GL3_OK;
         }

@@ -267,7 +267,8 @@ struct gl3_ctx {
     gl3_chain_state chain;                        // gl3_forward_decode_chain
     gl3_batch_chain_state bchain;                 // gl3_forward_decode_batch_chain
     int last_sample_mode = -1;                    // SMP_* of the last gl3_forward_decode_sample or chained step (-1: none yet): what gl3_draft_probs_put may copy
-    std::vector<std::pair<void*, size_t>> pinned;     // caller buffers registered with gl3_pin_host_buffer (logits land there directly)
+    struct PinnedBuf { void* ptr; size_t bytes; bool registered; };      // registered: page-locked by this plan (hipHostRegister), which undoes it
+    std::vector<PinnedBuf> pinned;                // caller buffers handed to gl3_pin_host_buffer (logits land there directly)
     // upload staging
     uint8_t* staging = nullptr;
     size_t staging_bytes = 0;

@@ -76,6 +76,8 @@ _SIGS = {  # symbol -> (restype, argtypes): exactly the declarations of include/
     "gl3_tp_pool_trim": (C.c_int32, [C.c_int32]),
     "gl3_pin_host_buffer": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "gl3_unpin_host_buffer": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "gl3_host_alloc": (C.c_int32, [C.c_uint64, C.POINTER(C.c_void_p)]),
+    "gl3_host_free": (None, [C.c_void_p]),
     "gl3_forward_prefill": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
     "gl3_forward_prefill_seq": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "gl3_forward_decode_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -34,6 +34,9 @@ SCORE_DTYPE = np.dtype([("prob", np.float32), ("logit", np.float32), ("max", np.
 VERIFY_DTYPE = np.dtype([("accepted", np.int32), ("token", np.int32)])
 
 
+_spare_logits = {}      # bytes -> addresses of page-locked logits buffers (gl3_host_alloc) that no plan or array uses any more
+
+
 class HipMasterPlan:
     def __init__(self, model, prefill_batch_size: int = 1, device: int = 0, tp_rank: int = 0, tp_size: int = 1,
                  flags: int = 0, unique_id: bytes | None = None, local_group=None, n_seqs: int = 1, p2p_exchange=None):
@@ -89,13 +92,26 @@ class HipMasterPlan:
         self._pin_logits()
 
     def _pin_logits(self):
-        """The logits buffer is reused on every step: page-lock it once so the D2H copy lands in it directly.  Registration pins
-        whole pages, so the buffer is an anonymous mapping of its own (page-aligned, padded to whole pages) — never a slice
-        of the C heap, whose pages it would share with unrelated allocations."""
-        import mmap
+        """The logits buffer is reused on every step: it is page-locked memory, so the D2H copy lands in it directly.  The library
+        allocates it page-locked (gl3_host_alloc: whole pages of its own) — page-locking memory that the process already has
+        (hipHostRegister) is refused where the GPU is passed through to a virtual machine.  The buffer outlives the plan while
+        an array still views it (forward_decode(copy=False)), so it is given up by the garbage collector, on whatever thread
+        that runs; gl3_host_free waits for the whole device there (hipHostFree), other ranks' polling gathers included, so the
+        buffer goes back to a list of this process instead, for the next plan with that vocabulary."""
+        import weakref
         nbytes = (self.cfg.vocab * 4 + 4095) & ~4095
-        self._logits_map = mmap.mmap(-1, nbytes)
-        self._logits = np.frombuffer(self._logits_map, np.float32, self.cfg.vocab)
+        spare = _spare_logits.setdefault(nbytes, [])
+        try:
+            addr = spare.pop()
+        except IndexError:
+            ptr = C.c_void_p()
+            code = hip.lib().gl3_host_alloc(nbytes, C.byref(ptr))
+            if code != hip.GL3_OK:
+                raise hip.Gl3Error(code, "gl3_host_alloc of the %d-byte logits buffer" % nbytes)
+            addr = ptr.value
+        mem = (C.c_float * (nbytes // 4)).from_address(addr)
+        weakref.finalize(mem, spare.append, addr)
+        self._logits = np.frombuffer(mem, np.float32, self.cfg.vocab)
         try:
             hip.check(hip.lib().gl3_pin_host_buffer(self._ctx, _p(self._logits), nbytes), self._ctx)
         except hip.Gl3Error:

@@ -251,9 +251,15 @@ GL3_API int32_t gl3_get_topp_counts(gl3_ctx* ctx, int64_t* on_device, int64_t* o
  * that gl3_forward_decode copies the logits straight into it instead of going through the plan's pinned staging buffer and a
  * host memcpy.  The buffer must stay allocated until gl3_unpin_host_buffer / gl3_destroy.  `ptr` and `bytes` must be multiples
  * of 4096: registration pins and maps whole pages, so the buffer has to own its pages (mmap / posix_memalign /
- * Arena.allocate(bytes, 4096) with the size rounded up); anything else returns GL3_E_ARG and the plan keeps staging. */
+ * Arena.allocate(bytes, 4096) with the size rounded up); anything else returns GL3_E_ARG and the plan keeps staging.
+ * Where the runtime cannot page-lock memory the process already has (hipHostRegister fails, e.g. in a virtual machine: GL3_E_HIP,
+ * the plan keeps staging), take the buffer from gl3_host_alloc: a buffer that is page-locked already is used as it is. */
 GL3_API int32_t gl3_pin_host_buffer(gl3_ctx* ctx, void* ptr, uint64_t bytes);
 GL3_API int32_t gl3_unpin_host_buffer(gl3_ctx* ctx, void* ptr);
+/* Page-locked host memory of the process (hipHostMalloc; page-aligned), for gl3_pin_host_buffer of any plan.  gl3_host_free after the
+ * plans that use it have been unpinned from it or destroyed. */
+GL3_API int32_t gl3_host_alloc(uint64_t bytes, void** out);
+GL3_API void gl3_host_free(void* ptr);
 
 /* Batched prefill of tokens[0..n) at positions start_pos.. (no logits, as the reference skips them).
  * n <= max_batch. */

@@ -20,6 +20,7 @@
 #include "gl3_ctx.h"
 #include "gl3_batch_plan.h"
 #include "gl3_decode_kernels.h"
+#include "gl3_kquant_kernels.h"
 #include "gl3_rowlane_kernels.h"
 #include "gl3_veclane_kernels.h"
 #include "gl3_moe_kernels.h"
@@ -56,9 +57,12 @@ static void launch_mv(gl3_ctx* ctx, MvKernel kernel, dim3 grid, int threads, siz
 
 // Every instantiation of matvec_q8t_kernel the library holds, named here and nowhere else (flags: gl3_decode_kernels.h).  launch_q8t
 // finds the entry with the flags its rule gives (a miss ends the process: no_kernel), and gl3_create walks the table for the large-LDS opt-in: what can be launched has it.
-struct MvVariant { int pro, epi, npw; bool sel, tpf, segs; MvKernel kernel; };
+// kq: the instantiations of matvec_kq_kernel (gl3_kquant_kernels.h: matrices with native Q4_K / Q6_K segments), found by launch_kq.
+struct MvVariant { int pro, epi, npw; bool sel, tpf, segs, kq; MvKernel kernel; };
 template <int PRO, int EPI, int NPW, bool SEL, bool TPF, bool SEGS>
-constexpr MvVariant mv_variant() { return {PRO, EPI, NPW, SEL, TPF, SEGS, matvec_q8t_kernel<PRO, EPI, NPW, SEL, TPF, SEGS>}; }
+constexpr MvVariant mv_variant() { return {PRO, EPI, NPW, SEL, TPF, SEGS, false, matvec_q8t_kernel<PRO, EPI, NPW, SEL, TPF, SEGS>}; }
+template <int PRO, int EPI, bool SEGS>
+constexpr MvVariant mv_variant_kq() { return {PRO, EPI, KQ_NPW, false, false, SEGS, true, matvec_kq_kernel<PRO, EPI, SEGS>}; }
 constexpr MvVariant MV_VARIANTS[] = {
     //         prologue   epilogue  NPW   SEL    TPF    SEGS
     mv_variant<PRO_RMS,   EPI_STORE,  4, false, false, false>(),      // qkv, logits
@@ -79,11 +83,18 @@ constexpr MvVariant MV_VARIANTS[] = {
     mv_variant<PRO_QUANT, EPI_RESID,  8, false, true,  true>(),
     mv_variant<PRO_RMS,   EPI_SWIGLU, 4, true,  false, false>(),      // routed experts (launch_matvec_sel)
     mv_variant<PRO_QUANT, EPI_RESID,  4, true,  false, false>(),
+    //            prologue   epilogue    SEGS      native K-quant segments: KQ_NPW producers, one rank, no experts
+    mv_variant_kq<PRO_RMS,   EPI_STORE,  false>(),                    // qkv, logits
+    mv_variant_kq<PRO_RMS,   EPI_STORE,  true>(),
+    mv_variant_kq<PRO_RMS,   EPI_SWIGLU, false>(),                    // gate/up
+    mv_variant_kq<PRO_RMS,   EPI_SWIGLU, true>(),
+    mv_variant_kq<PRO_QUANT, EPI_RESID,  false>(),                    // wo, down
+    mv_variant_kq<PRO_QUANT, EPI_RESID,  true>(),
 };
-constexpr int mv_find(int pro, int epi, int npw, bool sel, bool tpf, bool segs) {
+constexpr int mv_find(int pro, int epi, int npw, bool sel, bool tpf, bool segs, bool kq = false) {
     int i = 0;
     for (const MvVariant& v : MV_VARIANTS) {
-        if (v.pro == pro && v.epi == epi && v.npw == npw && v.sel == sel && v.tpf == tpf && v.segs == segs) return i;
+        if (v.pro == pro && v.epi == epi && v.npw == npw && v.sel == sel && v.tpf == tpf && v.segs == segs && v.kq == kq) return i;
         ++i;
     }
     return -1;
@@ -102,6 +113,14 @@ static void launch_q8t(gl3_ctx* ctx, int pro, int epi, const MatvecArgs& a, int 
     const int i = mv_find(pro, epi, npw, sel, a.tp != nullptr, segs);
     if (i < 0) no_kernel("matvec_q8t_kernel<prologue, epilogue>", pro, epi);
     launch_mv(ctx, MV_VARIANTS[i].kernel, dim3(a.nstrips < max_wgs ? a.nstrips : max_wgs, sel ? slots : 1), mv_threads(npw), matvec_smem(pro, epi, a.k), a);
+}
+
+// A matrix with native K-quant segments (a.kq): KQ_NPW producers at every shape, the chain in segments for strips of more than
+// kq_seg_groups tile groups, one workgroup per CU.  Same dynamic LDS as matvec_q8t_kernel (the layout is shared).
+static void launch_kq(gl3_ctx* ctx, int pro, int epi, const MatvecArgs& a) {
+    const int i = mv_find(pro, epi, KQ_NPW, false, false, a.ng > kq_seg_groups(epi), true);
+    if (i < 0) no_kernel("matvec_kq_kernel<prologue, epilogue>", pro, epi);
+    launch_mv(ctx, MV_VARIANTS[i].kernel, dim3(a.nstrips < 256 ? a.nstrips : 256), KQ_THREADS, matvec_smem(pro, epi, a.k), a);
 }
 
 // Run-time weight format (with the F16 accumulator species) and epilogue as compile-time constants for a generic lambda, the way
@@ -177,6 +196,7 @@ static void launch_matvec(gl3_ctx* ctx, int pro, int epi, const Q8Mat& w, const 
     a.w = w.w; a.w2 = w2 ? w2->w : nullptr; a.rows = w.rows; a.k = w.k; a.ng = w.ng; a.nstrips = w.nstrips;
     a.x = x; a.norm_w = norm_w; a.eps = ctx->d.rms_eps; a.out = out; a.resid_in = resid_in; a.out_scale = out_scale;
     a.tp = tp;
+    if (w.kq_rec) { a.kq = static_cast<const KqRec*>(w.kq_rec); launch_kq(ctx, pro, epi, a); return; }
     launch_q8t(ctx, pro, epi, a);
 }
 
@@ -435,7 +455,9 @@ static int32_t enqueue_decode(gl3_ctx* ctx, bool want_logits, gl3_kernel_times* 
     pr.begin(GL3_K_OTHER, (uint64_t)d.dim / 32 * 34);
     const int fold = ctx->tp_fold, fmask = fold ? ctx->tp_fold_mask : 0, L_ = d.n_layers;
     uint32_t* step_word = fold ? reinterpret_cast<uint32_t*>(ctx->arena.base + GL3_ARENA_STEP) : (uint32_t*)nullptr;
-    if (q8)
+    if (q8 && ctx->emb.nseg)
+        hipLaunchKernelGGL(embed_kq_kernel, dim3(1), dim3(256), 0, s, ctx->emb.seg[0].w, ctx->emb.seg[0].fmt, ctx->emb.ng, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale);
+    else if (q8)
         hipLaunchKernelGGL(embed_q8t_kernel, dim3(1), dim3(256), 0, s, ctx->emb.w, ctx->emb.ng, d.dim, ctx->dyn_cur, ctx->x, ctx->emb_scale,
                            (fmask & TF_EMBED) ? tp_rec(ctx, L_, 0) : (const TpRec*)nullptr, step_word);
     else wt_dispatch(ctx->emb.fmt, false, [&](auto wt, auto) {
@@ -512,6 +534,7 @@ static int32_t alloc_mat(gl3_ctx* ctx, Q8Mat& m, int rows, int k) {
     m.rows = rows; m.k = k; m.ng = q8_tile_groups(k); m.nstrips = (rows + 15) / 16; m.fmt = ctx->d.weight_type;
     if (m.fmt == GL3_TYPE_Q8_0 && (ctx->d.flags & GL3_FLAG_F32_ACTIVATION)) m.fmt = GL3_FMT_Q8V;
     m.vl = m.fmt == GL3_FMT_Q8V || (m.fmt != GL3_TYPE_Q8_0 && !(ctx->d.flags & GL3_FLAG_SCALAR_DOT));
+    if (ctx->kq_native) { m.deferred = true; return GL3_OK; }      // allocated by upload_kq, in the format of what arrives
     GL3_HIP(hipMalloc((void**)&m.w, m.bytes() + GL3_TAIL_PAD));
     if (m.fmt != GL3_TYPE_Q8_0) GL3_HIP(hipMemset(m.w, 0, m.bytes()));      // padded rows of the last 64-row group
     return GL3_OK;
@@ -590,6 +613,15 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     }
     if (d.weight_type != GL3_TYPE_Q8_0 && d.weight_type != GL3_TYPE_F16 && d.weight_type != GL3_TYPE_Q4_0)
         return bail(GL3_E_UNSUPPORTED, "matrix weight type must be Q8_0, F16 or Q4_0");
+    if (d.flags & GL3_FLAG_KQUANT_NATIVE) {      // single-token decode on one rank: the batched GEMMs read Q8T tiles only
+        if (d.weight_type != GL3_TYPE_Q8_0 || (d.flags & GL3_FLAG_F32_ACTIVATION))
+            return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: Q8_0 plans with the int8 activation only (K-quant tensors are rebuilt as Q8_0 blocks)");
+        if (moe) return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: qwen2moe experts have no native K-quant kernel");
+        if (d.tp_size > 1) return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: tensor parallelism is not built");
+        if (d.max_batch > 1 || d.n_seqs > 1)
+            return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: batched prefill and static-batched decode (max_batch > 1, n_seqs > 1) are not built");
+        ctx->kq_native = true;
+    }
     const bool q8v = d.weight_type == GL3_TYPE_Q8_0 && (d.flags & GL3_FLAG_F32_ACTIVATION);
     {   // the Vector-API species (-Dllama.VectorBitSize; include/gpullama3_hip.h): 256 by default, 512 for F16 on one rank (decode, batched prefill, batched decode), the rest refused
         const bool species_type = d.weight_type == GL3_TYPE_F16 || d.weight_type == GL3_TYPE_Q4_0 || q8v;
@@ -835,10 +867,12 @@ void gl3_destroy(gl3_ctx* ctx) {
     gl3_verify_free(ctx);
     for (auto e : ctx->ev) hipEventDestroy(e);
     auto f = [](void* p) { if (p) hipFree(p); };
-    f(ctx->emb.w);
-    if (ctx->wcls_owned) f(ctx->wcls.w);
+    auto fm = [&](Q8Mat& m) { f(m.w); for (int i = 0; i < m.nseg; ++i) f(m.seg[i].w); };
+    fm(ctx->emb);
+    if (ctx->wcls_owned) fm(ctx->wcls);
+    f(ctx->kq_recs);
     for (auto& L : ctx->layers) {
-        f(L.wqkv.w); f(L.wo.w); f(L.w1.w); f(L.w3.w); f(L.w2.w);
+        fm(L.wqkv); fm(L.wo); fm(L.w1); fm(L.w3); fm(L.w2);
         f(L.attn_norm); f(L.ffn_norm); f(L.qnorm); f(L.knorm); f(L.bq); f(L.bk); f(L.bv);
         f(L.gate_exps.w); f(L.up_exps.w); f(L.down_exps.w); f(L.gate_inp); f(L.gate_inp_shexp);
     }
@@ -868,6 +902,94 @@ static int32_t stage(gl3_ctx* ctx, const void* host, size_t bytes) {
     return GL3_OK;
 }
 
+static int32_t upload_q8(gl3_ctx* ctx, Q8Mat& m, int dst_row0, int sub_rows, const void* host, uint64_t bytes, int rows_full, int k_full, long r0);
+
+// GL3_FLAG_KQUANT_NATIVE plans: the tensor (ctx->upload_type: Q8_0, Q4_K or Q6_K) becomes a row segment of m in its own format and
+// allocation (Q8Mat::seg; layouts: gl3_kquant_kernels.h).  A whole Q8_0 matrix takes the plain Q8T allocation instead.
+static int32_t upload_kq(gl3_ctx* ctx, Q8Mat& m, int dst_row0, int sub_rows, const void* host, uint64_t bytes, int rows_full, int k_full, long r0) {
+    const int type = ctx->upload_type, nb = k_full / 32;
+    const bool native = type != GL3_TYPE_Q8_0;
+    if (native && k_full % 256) GL3_FAIL(GL3_E_ARG, "a K-quant row is whole super-blocks of 256 elements");
+    const size_t row_bytes = type == GL3_TYPE_Q4_K ? (size_t)(k_full / 256) * 144 : type == GL3_TYPE_Q6_K ? (size_t)(k_full / 256) * 210 : (size_t)nb * 34;
+    if (bytes != (uint64_t)rows_full * row_bytes) GL3_FAIL(GL3_E_ARG, "tensor byte size does not match its shape");
+    if (dst_row0 % 16) GL3_FAIL(GL3_E_UNSUPPORTED, "sub-matrix row offset must be a multiple of 16");
+    if (!native && m.nseg == 0 && dst_row0 == 0 && sub_rows == m.rows) {
+        m.deferred = false;
+        GL3_HIP(hipMalloc((void**)&m.w, m.bytes() + GL3_TAIL_PAD));
+        return upload_q8(ctx, m, dst_row0, sub_rows, host, bytes, rows_full, k_full, r0);
+    }
+    int i = 0;
+    while (i < m.nseg && m.seg[i].row0 != dst_row0) ++i;
+    if (i == 3) GL3_FAIL(GL3_E_ARG, "more than three row segments in one matrix");
+    if (i < m.nseg) hipFree(m.seg[i].w); else ++m.nseg;
+    Q8Mat::Seg& sg = m.seg[i];
+    sg = {nullptr, dst_row0, sub_rows, type};
+    GL3_HIP(hipMalloc((void**)&sg.w, m.seg_bytes(sg)));
+    int32_t r = stage(ctx, (const uint8_t*)host + (size_t)r0 * row_bytes, (size_t)sub_rows * row_bytes);
+    if (r != GL3_OK) return r;
+    const long total = (long)((sub_rows + 15) & ~15) * m.ng * 4;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (type == GL3_TYPE_Q4_K) hipLaunchKernelGGL(repack_q4k_kernel, grid, dim3(256), 0, ctx->stream, ctx->staging, sg.w, sub_rows, nb, m.ng);
+    else if (type == GL3_TYPE_Q6_K) hipLaunchKernelGGL(repack_q6k_kernel, grid, dim3(256), 0, ctx->stream, ctx->staging, sg.w, sub_rows, nb, m.ng);
+    else hipLaunchKernelGGL(repack_q8t_kernel, grid, dim3(256), 0, ctx->stream, ctx->staging, sg.w, sub_rows, nb, m.ng, 0L, 0, nb);
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
+    return GL3_OK;
+}
+
+// What gl3_finalize does with the segments of a GL3_FLAG_KQUANT_NATIVE plan: order them, check that they cover the matrix, fold a
+// matrix of Q8T segments only (a fused qkv of three Q8_0 uploads) into the one allocation every other plan has, and write the KqRec of
+// every decode launch that meets a native segment.
+static int32_t kq_finalize(gl3_ctx* ctx) {
+    std::vector<Q8Mat*> mats{&ctx->emb};
+    if (ctx->wcls_owned) mats.push_back(&ctx->wcls);
+    for (auto& L : ctx->layers) for (Q8Mat* m : {&L.wqkv, &L.wo, &L.w1, &L.w3, &L.w2}) mats.push_back(m);
+    for (Q8Mat* m : mats) {
+        if (!m->nseg) continue;
+        for (int i = 1; i < m->nseg; ++i) for (int j = i; j > 0 && m->seg[j].row0 < m->seg[j - 1].row0; --j) std::swap(m->seg[j], m->seg[j - 1]);
+        int next = 0;
+        bool q8t_only = true;
+        for (int i = 0; i < m->nseg; ++i) {
+            if (m->seg[i].row0 != next) GL3_FAIL(GL3_E_STATE, "a matrix is not covered by its uploaded row segments");
+            next += m->seg[i].rows;
+            q8t_only = q8t_only && m->seg[i].fmt == GL3_TYPE_Q8_0;
+        }
+        if (next != m->rows) GL3_FAIL(GL3_E_STATE, "a matrix is not covered by its uploaded row segments");
+        if (!q8t_only) continue;
+        Q8Mat whole = *m;
+        whole.nseg = 0;
+        GL3_HIP(hipMalloc((void**)&whole.w, whole.bytes() + GL3_TAIL_PAD));
+        for (int i = 0; i < m->nseg; ++i) {
+            GL3_HIP(hipMemcpy(whole.w + (size_t)(m->seg[i].row0 / 16) * m->ng * TILE_BYTES, m->seg[i].w, m->seg_bytes(m->seg[i]), hipMemcpyDeviceToDevice));
+            hipFree(m->seg[i].w);
+        }
+        whole.deferred = false;
+        *m = whole;
+    }
+    return GL3_OK;
+}
+static int32_t kq_build_recs(gl3_ctx* ctx) {
+    std::vector<KqRec> h;
+    std::vector<Q8Mat*> lead;
+    auto add = [&](Q8Mat& w, const Q8Mat* w2) {
+        if (!w.nseg && !(w2 && w2->nseg)) return;
+        KqRec r;
+        for (KqSeg& s : r.seg) s = {nullptr, INT32_MAX, GL3_TYPE_Q8_0};
+        if (!w.nseg) r.seg[0] = {w.w, 0, GL3_TYPE_Q8_0};
+        for (int i = 0; i < w.nseg; ++i) r.seg[i] = {w.seg[i].w, w.seg[i].row0 / 16, w.seg[i].fmt};
+        r.seg2 = {nullptr, 0, GL3_TYPE_Q8_0};
+        if (w2) r.seg2 = w2->nseg ? KqSeg{w2->seg[0].w, 0, w2->seg[0].fmt} : KqSeg{w2->w, 0, GL3_TYPE_Q8_0};
+        h.push_back(r); lead.push_back(&w);
+    };
+    for (auto& L : ctx->layers) { add(L.wqkv, nullptr); add(L.wo, nullptr); add(L.w1, &L.w3); add(L.w2, nullptr); }
+    add(ctx->wcls, nullptr);
+    if (h.empty()) return GL3_OK;
+    GL3_HIP(hipMalloc(&ctx->kq_recs, h.size() * sizeof(KqRec)));
+    GL3_HIP(hipMemcpyAsync(ctx->kq_recs, h.data(), h.size() * sizeof(KqRec), hipMemcpyHostToDevice, ctx->stream));
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < lead.size(); ++i) lead[i]->kq_rec = static_cast<KqRec*>(ctx->kq_recs) + i;
+    return GL3_OK;
+}
+
 // src: full [rows_full x k_full] GGUF tensor on the host (Q8_0 / F16 / Q4_0 row-major blocks); keeps rows
 // [r0, r0+sub_rows), placed at row dst_row0 of m.  Only the kept rows are staged (tensor-parallel ranks upload 1/tp of
 // the bytes).
@@ -875,6 +997,7 @@ static int32_t upload_q8(gl3_ctx* ctx, Q8Mat& m, int dst_row0, int sub_rows, con
                          int k_full, long r0) {
     const int nb_full = k_full / 32;
     if (k_full != m.k) GL3_FAIL(GL3_E_ARG, "tensor inner dimension mismatch");
+    if (m.deferred) return upload_kq(ctx, m, dst_row0, sub_rows, host, bytes, rows_full, k_full, r0);
     const size_t row_bytes = (m.fmt == GL3_TYPE_Q8_0 || m.fmt == GL3_FMT_Q8V) ? (size_t)nb_full * 34 : m.fmt == GL3_TYPE_F16 ? (size_t)k_full * 2 : (size_t)nb_full * 18;
     if (bytes != (uint64_t)rows_full * row_bytes) GL3_FAIL(GL3_E_ARG, "tensor byte size does not match its shape");
     const uint8_t* h = (const uint8_t*)host + (size_t)r0 * row_bytes;
@@ -938,7 +1061,9 @@ int32_t gl3_upload_tensor(gl3_ctx* ctx, int32_t id, int32_t layer, const void* h
                           id == GL3_T_ATTN_K_NORM || id == GL3_T_BQ || id == GL3_T_BK || id == GL3_T_BV || id == GL3_T_FFN_GATE_INP ||
                           id == GL3_T_FFN_GATE_INP_SHEXP);
     if (id >= GL3_T_FFN_GATE_INP && d.arch != GL3_ARCH_QWEN2MOE) GL3_FAIL(GL3_E_ARG, "router / expert tensors belong to GL3_ARCH_QWEN2MOE");
-    if (is_mat && type != d.weight_type) GL3_FAIL(GL3_E_UNSUPPORTED, "matrix ggml type differs from gl3_model_desc.weight_type");
+    const bool kq_type = ctx->kq_native && (type == GL3_TYPE_Q4_K || type == GL3_TYPE_Q6_K);      // kept native (upload_kq)
+    if (is_mat && type != d.weight_type && !kq_type) GL3_FAIL(GL3_E_UNSUPPORTED, "matrix ggml type differs from gl3_model_desc.weight_type");
+    ctx->upload_type = type;
     if (id > GL3_T_OUTPUT && (layer < 0 || layer >= d.n_layers)) GL3_FAIL(GL3_E_ARG, "layer out of range");
     gl3_layer* L = id > GL3_T_OUTPUT ? &ctx->layers[layer] : nullptr;
     switch (id) {
@@ -964,6 +1089,11 @@ int32_t gl3_upload_tensor(gl3_ctx* ctx, int32_t id, int32_t layer, const void* h
     case GL3_T_W2: r = upload_q8(ctx, L->w2, 0, ctx->dim_l, host, bytes, d.dim, d.hidden, (long)rank * ctx->dim_l); break;
     case GL3_T_WQKV: {        // phi3: rows q | k | v of one tensor; each rank keeps its heads of all three parts
         const int full = ctx->q_dim + 2 * ctx->kv_dim;
+        if (ctx->kq_native) {      // one rank: the tensor is the matrix, one segment
+            r = upload_q8(ctx, L->wqkv, 0, full, host, bytes, full, d.dim, 0L);
+            if (r == GL3_OK) L->have |= (1u << GL3_T_WQ) | (1u << GL3_T_WK) | (1u << GL3_T_WV);
+            break;
+        }
         r = upload_q8(ctx, L->wqkv, 0, ctx->q_dim_l, host, bytes, full, d.dim, (long)rank * ctx->q_dim_l);
         if (r == GL3_OK) r = upload_q8(ctx, L->wqkv, ctx->q_dim_l, ctx->kv_dim_l, host, bytes, full, d.dim, (long)ctx->q_dim + (long)rank * ctx->kv_dim_l);
         if (r == GL3_OK) r = upload_q8(ctx, L->wqkv, ctx->q_dim_l + ctx->kv_dim_l, ctx->kv_dim_l, host, bytes, full, d.dim,
@@ -1036,6 +1166,7 @@ int32_t gl3_finalize(gl3_ctx* ctx) {
         GL3_FAIL(GL3_E_STATE, "tensor parallel plan without gl3_tp_p2p_attach / gl3_tp_init / gl3_tp_attach_local");
     { int32_t r = gl3_tp_local_resolve(ctx); if (r != GL3_OK) return r; }
     { int32_t r = tp_fold_setup(ctx); if (r != GL3_OK) return r; }
+    if (ctx->kq_native) { int32_t r = kq_finalize(ctx); if (r != GL3_OK) return r; }
     if (!(ctx->have_global & (1u << GL3_T_OUTPUT))) {   // tied: wcls = this rank's vocab rows of token_embd
         ctx->wcls = ctx->emb;
         ctx->wcls.rows = ctx->vocab_l;
@@ -1045,6 +1176,7 @@ int32_t gl3_finalize(gl3_ctx* ctx) {
         else ctx->wcls.w = ctx->emb.w + (size_t)(d.tp_rank * ctx->vocab_l / 64) * ctx->emb.rl_group_bytes();
         ctx->wcls_owned = false;
     }
+    if (ctx->kq_native) { int32_t r = kq_build_recs(ctx); if (r != GL3_OK) return r; }      // behind the tied wcls: it leads a launch of its own
     if (ctx->staging) { hipFree(ctx->staging); ctx->staging = nullptr; ctx->staging_bytes = 0; }
     ctx->finalized = true;
     if (!(d.flags & GL3_FLAG_NO_GRAPH) && !env_flag("GL3_NO_GRAPH", false) && !gl3_roctx_on()) {
@@ -2020,6 +2152,38 @@ int32_t gl3_reset_kv(gl3_ctx* ctx) {
     GL3_HIP(hipMemsetAsync(ctx->vcache, 0, kvn * 4, ctx->stream));
     GL3_HIP(hipStreamSynchronize(ctx->stream));
     return GL3_OK;
+}
+
+int32_t gl3_get_weight_bytes(gl3_ctx* ctx, uint64_t* bytes) {
+    if (!ctx || !bytes) return GL3_E_ARG;
+    uint64_t b = ctx->emb.bytes() + (ctx->wcls_owned ? ctx->wcls.bytes() : 0);
+    for (const gl3_layer& L : ctx->layers)
+        for (const Q8Mat* m : {&L.wqkv, &L.wo, &L.w1, &L.w3, &L.w2, &L.gate_exps, &L.up_exps, &L.down_exps}) b += m->rows ? m->bytes() : 0;
+    *bytes = b;
+    return GL3_OK;
+}
+
+int32_t gl3_debug_kquant_requant(int32_t device, int32_t type, const void* src, int32_t rows, int32_t k, void* dst) {
+    if (!src || !dst || rows < 1 || k < 256 || k % 256) return GL3_E_ARG;
+    if (type != GL3_TYPE_Q4_K && type != GL3_TYPE_Q6_K) return GL3_E_UNSUPPORTED;
+    if (hipSetDevice(device) != hipSuccess) return GL3_E_HIP;
+    const int nb = k / 32, ng = nb / 4, rows16 = (rows + 15) & ~15;
+    const size_t src_bytes = (size_t)rows * (k / 256) * (type == GL3_TYPE_Q4_K ? 144 : 210), tile_bytes = (size_t)(rows16 / 16) * ng * kq_tile_bytes(type);
+    const size_t dst_bytes = (size_t)rows * nb * 34;
+    uint8_t *dsrc = nullptr, *tiles = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc((void**)&dsrc, src_bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&tiles, tile_bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dout, dst_bytes);
+    if (e == hipSuccess) e = hipMemcpy(dsrc, src, src_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)(((long)rows16 * nb + 255) / 256));
+        if (type == GL3_TYPE_Q4_K) hipLaunchKernelGGL(repack_q4k_kernel, grid, dim3(256), 0, 0, dsrc, tiles, rows, nb, ng);
+        else hipLaunchKernelGGL(repack_q6k_kernel, grid, dim3(256), 0, 0, dsrc, tiles, rows, nb, ng);
+        hipLaunchKernelGGL(kq_requant_kernel, dim3((unsigned)(((long)rows * nb + 255) / 256)), dim3(256), 0, 0, tiles, type, rows, nb, ng, dout);
+        e = hipMemcpy(dst, dout, dst_bytes, hipMemcpyDeviceToHost);
+    }
+    hipFree(dsrc); hipFree(tiles); hipFree(dout);
+    return e == hipSuccess ? GL3_OK : e == hipErrorOutOfMemory ? GL3_E_OOM : GL3_E_HIP;
 }
 
 int32_t gl3_get_init_ms(gl3_ctx* ctx, double* plan_ms, double* copy_in_ms) {

@@ -152,6 +152,7 @@ struct MatvecArgs {
                              // down, logitScale on the logits — InferenceCore.forwardGranite :893-894, :911-912, :921; x * 1.0f is exact)
     const struct MoeSlots* moe;   // SEL instantiations only (Qwen2-MoE): what each blockIdx.y slot of the launch works on
     const TpRec* tp;         // tensor parallel, folded gathers: what this launch pushes to the peers / waits for (NULL: nothing)
+    const struct KqRec* kq;  // matvec_kq_kernel only (gl3_kquant_kernels.h): the row segments of w and the format of w2; w / w2 are unused there
 };
 
 // Qwen2-MoE launches of matvec_q8t_kernel<.., SEL = true> (InferenceCore.matmulExpert :430-432): blockIdx.y = slot.  Slots j < n_sel

@@ -18,6 +18,7 @@ ERR_NAMES = {0: "GL3_OK", -1: "GL3_E_ARG", -2: "GL3_E_UNSUPPORTED", -3: "GL3_E_O
              -6: "GL3_E_STATE"}
 FLAG_NO_GRAPH, FLAG_LAYER_TAPS, FLAG_FORCE_RCCL, FLAG_SCALAR_DOT, FLAG_F32_ACTIVATION = 1, 2, 4, 8, 16
 FLAG_VECTOR_512, FLAG_VECTOR_128 = 32, 64      # -Dllama.VectorBitSize (default 256): see include/gpullama3_hip.h
+FLAG_KQUANT_NATIVE = 128                       # Q4_K / Q6_K tensors stay native in HBM (single-token decode on one rank)
 CHAIN_MAX = 64                                 # GL3_CHAIN_MAX: the longest gl3_forward_decode_chain
 VL_GEMM_KERNELS = ["gemm_f16_mfma_kernel", "gemm_f16_mfma_v512_kernel", "gemm_vlq_kernel", "gemm_vlq_mfma_kernel"]      # gl3_debug_vl_gemm_plan's kernel ids
 GEMM3_KERNELS = ["pf_gemm3_kernel", "pf_gemm3t_kernel"]      # gl3_debug_gemm3_plan's kernel ids
@@ -125,6 +126,8 @@ _SIGS = {  # symbol -> (restype, argtypes): exactly the declarations of include/
     "gl3_profile_kernel": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "gl3_profile_prefill_kernel": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "gl3_probe_peaks": (C.c_int32, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gl3_get_weight_bytes": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "gl3_debug_kquant_requant": (C.c_int32, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gl3_get_init_ms": (C.c_int32, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gl3_destroy": (None, [C.c_void_p]),
     "gl3_last_error": (C.c_char_p, [C.c_void_p]),

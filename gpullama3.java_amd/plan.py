@@ -506,6 +506,12 @@ class HipMasterPlan:
     def reset_kv(self):
         hip.check(hip.lib().gl3_reset_kv(self._ctx), self._ctx)
 
+    def weight_bytes(self) -> int:
+        """HBM bytes of the repacked matrices (gl3_get_weight_bytes): what FLAG_KQUANT_NATIVE shrinks for a K-quant file."""
+        b = C.c_uint64()
+        hip.check(hip.lib().gl3_get_weight_bytes(self._ctx, C.byref(b)), self._ctx)
+        return b.value
+
     def profile_decode(self, token: int, position: int) -> dict:
         kt = hip.KernelTimes()
         hip.check(hip.lib().gl3_profile_decode(self._ctx, token, position, C.byref(kt)), self._ctx)

@@ -1,0 +1,120 @@
+"""tg128 of a Llama-3-8B-shaped random model in the Q4_K_M mix (Q4_K matrices; Q6_K for attn_v, every second ffn_down and output),
+once converted to Q8_0 at load (the default plan) and once with the K-quant tensors native in HBM (GL3_FLAG_KQUANT_NATIVE).
+
+bench.py's tg protocol (decode steps from an empty cache, logits to the host every step): 1 warm-up and --reps timed repetitions
+per plan, the two plans alternated inside one invocation, their logits compared for equality.  Also the per-class device times of
+instrumented steps and the algorithmic bytes per token of both plans, computed from the shapes.  Prints one JSON line.
+
+    python scripts/kquant_tg.py [--layers 32] [--reps 5]
+    rocprofv3 --kernel-trace --stats -- python scripts/kquant_tg.py --reps 1        # per-kernel times
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+Q8_0, Q4_K, Q6_K = 8, 12, 14
+BLOCK_BYTES = {Q4_K: 144, Q6_K: 210}            # per 256 elements
+
+
+def ggml_type(name):
+    layer = int(name.split(".")[1]) if name.startswith("blk.") else 0
+    return Q6_K if ("attn_v" in name or name == "output.weight" or ("ffn_down" in name and layer % 2 == 0)) else Q4_K
+
+
+class KqModel:
+    """Streams the tensors of the model in file order, generated from a seed; convert = as the default loader would upload them."""
+
+    def __init__(self, cfg, synth, lib, seed, convert):
+        self.cfg, self.wtype, self.rope = cfg, Q8_0, synth.model_rope(cfg)
+        self._synth, self._lib, self._seed, self._convert = synth, lib, seed, convert
+
+    def tensor_items(self):
+        rng = np.random.default_rng(self._seed)
+        for name, rows, cols, ty, kind in self._synth.tensor_specs(self.cfg, Q8_0):
+            if kind != "mat":
+                yield name, ((rng.standard_normal(rows * cols, dtype=np.float32) * np.float32(0.02) + np.float32(1)).view(np.uint8), ty, rows, cols)
+                continue
+            t, nb = ggml_type(name), rows * cols // 256
+            b = rng.integers(0, 256, (nb, BLOCK_BYTES[t]), dtype=np.uint8)
+            d = (np.abs(rng.standard_normal(nb)) * 2e-3 + 2e-4).astype(np.float16).view(np.uint8).reshape(nb, 2)
+            if t == Q6_K:
+                b[:, 208:210] = d
+            else:
+                b[:, 0:2] = d
+                b[:, 2:4] = (np.abs(rng.standard_normal(nb)) * 8e-3).astype(np.float16).view(np.uint8).reshape(nb, 2)
+            raw = b.reshape(-1)
+            if self._convert:
+                q8 = np.empty(rows * cols // 32 * 34, np.uint8)
+                assert self._lib.gl3_kquant_to_q8_0(t, raw.ctypes.data_as(C.c_void_p), rows * cols, q8.ctypes.data_as(C.c_void_p)) == 0
+                raw, t = q8, Q8_0
+            yield name, (raw, t, rows, cols)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--n-gen", type=int, default=128)
+    args = ap.parse_args()
+    import __graft_entry__ as ge
+    from importlib import import_module
+    pkg = ge.load_package()
+    synth = pkg.synth
+    plan_mod, hip = import_module(ge.PKG_NAME + ".plan"), import_module(ge.PKG_NAME + ".hip")
+    cfg = synth.CONFIGS["llama-3-8b"]
+    cfg = synth.ModelConfig(**{**cfg.__dict__, "ctx": args.n_gen + 8, "n_layers": args.layers})
+    t0 = time.time()
+    plans = {"converted": plan_mod.HipMasterPlan(KqModel(cfg, synth, hip.lib(), 42, True)),
+             "native": plan_mod.HipMasterPlan(KqModel(cfg, synth, hip.lib(), 42, False), flags=hip.FLAG_KQUANT_NATIVE)}
+    setup_s = time.time() - t0
+    toks = pkg.javarand.bench_tokens(cfg.vocab, args.n_gen)
+
+    def rep(plan):
+        t1 = time.perf_counter()
+        for i in range(args.n_gen):
+            logits = plan.forward_decode(toks[i], i, copy=False)
+        return time.perf_counter() - t1, logits.copy()
+
+    samples, equal = {k: [] for k in plans}, True
+    for r in range(args.reps + 1):                     # repetition 0 is the warm-up
+        last = {}
+        for k, plan in plans.items():
+            s, last[k] = rep(plan)
+            if r:
+                samples[k].append(args.n_gen / s)
+        equal = equal and bool(np.array_equal(last["converted"], last["native"]))
+    d, L = cfg.dim, cfg.n_layers
+    mats = [(n, r, c) for n, r, c, ty, kind in synth.tensor_specs(cfg, Q8_0) if kind == "mat" and n != "token_embd.weight"]
+    bpe = {Q4_K: 144 / 256, Q6_K: 210 / 256}
+    other = d * 34 / 32 + (2 * L + 1) * d * 4 + 2 * L * cfg.kv_dim * 4 * ((args.n_gen - 1) / 2.0 + 2) + cfg.vocab * 4
+    out = dict(metric="tg%d tokens/s" % args.n_gen, unit="tokens/s", n_gpus=1, data="synthetic", outputs_equal=equal, setup_s=round(setup_s, 1),
+               config=dict(workload="Llama-3-8B shape, Q4_K_M mix, %d layers, random weights" % L, reps=args.reps))
+    for k, plan in plans.items():
+        acc, n_prof = None, 8
+        for i in range(n_prof):
+            kt = plan.profile_decode(toks[64 + i], 64 + i)
+            if acc is None:
+                acc = kt
+            else:
+                for name in kt:
+                    for f in ("ms", "launches", "bytes"):
+                        acc[name][f] += kt[name][f]
+        weights = sum(r * c * (34 / 32 if k == "converted" else bpe[ggml_type(n)]) for n, r, c in mats)
+        s = samples[k] or [0.0]
+        out[k] = dict(tok_s=round(float(np.mean(s)), 2), samples_tok_s=[round(x, 2) for x in s], spread_tok_s=round(max(s) - min(s), 2),
+                      algorithmic_bytes_per_token=int(weights + other), weight_bytes_in_hbm=plan.weight_bytes(),
+                      kernel_classes={n: dict(us_per_token=round(v["ms"] / n_prof * 1e3, 1), launches_per_token=v["launches"] // n_prof,
+                                              gbs=round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None)
+                                      for n, v in acc.items() if v["launches"]})
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -613,13 +613,14 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     }
     if (d.weight_type != GL3_TYPE_Q8_0 && d.weight_type != GL3_TYPE_F16 && d.weight_type != GL3_TYPE_Q4_0)
         return bail(GL3_E_UNSUPPORTED, "matrix weight type must be Q8_0, F16 or Q4_0");
-    if (d.flags & GL3_FLAG_KQUANT_NATIVE) {      // single-token decode on one rank: the batched GEMMs read Q8T tiles only
+    if (d.flags & (GL3_FLAG_KQUANT_NATIVE | GL3_FLAG_KQUANT_NATIVE_BATCH)) {      // one rank; the batched entry points with GL3_FLAG_KQUANT_NATIVE_BATCH (gl3_kquant_gemm.h)
+        const std::string flag = (d.flags & GL3_FLAG_KQUANT_NATIVE_BATCH) ? "GL3_FLAG_KQUANT_NATIVE_BATCH" : "GL3_FLAG_KQUANT_NATIVE";
         if (d.weight_type != GL3_TYPE_Q8_0 || (d.flags & GL3_FLAG_F32_ACTIVATION))
-            return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: Q8_0 plans with the int8 activation only (K-quant tensors are rebuilt as Q8_0 blocks)");
-        if (moe) return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: qwen2moe experts have no native K-quant kernel");
-        if (d.tp_size > 1) return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: tensor parallelism is not built");
-        if (d.max_batch > 1 || d.n_seqs > 1)
-            return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: batched prefill and static-batched decode (max_batch > 1, n_seqs > 1) are not built");
+            return bail(GL3_E_UNSUPPORTED, flag + ": Q8_0 plans with the int8 activation only (K-quant tensors are rebuilt as Q8_0 blocks)");
+        if (moe) return bail(GL3_E_UNSUPPORTED, flag + ": qwen2moe experts have no native K-quant kernel");
+        if (d.tp_size > 1) return bail(GL3_E_UNSUPPORTED, flag + ": tensor parallelism is not built");
+        if (!(d.flags & GL3_FLAG_KQUANT_NATIVE_BATCH) && (d.max_batch > 1 || d.n_seqs > 1))
+            return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: batched prefill and static-batched decode (max_batch > 1, n_seqs > 1) need GL3_FLAG_KQUANT_NATIVE_BATCH");
         ctx->kq_native = true;
     }
     const bool q8v = d.weight_type == GL3_TYPE_Q8_0 && (d.flags & GL3_FLAG_F32_ACTIVATION);

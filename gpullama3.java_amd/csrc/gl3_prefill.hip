@@ -26,6 +26,7 @@
 using namespace gl3;
 #include "gl3_bd_gemm.h"      // GemmArgs, bdw_gemm_kernel (expects the gl3 names in scope)
 #include "gl3_moe_kernels.h"  // Qwen2-MoE: batched router, grouping, combine
+#include "gl3_kquant_gemm.h"  // GL3_FLAG_KQUANT_NATIVE_BATCH: kq_gemm_kernel, pf_embed_kq_kernel, kq_expand_q8t_kernel
 #include "gl3_prefill_gemm3.h"      // g3_scale_operands (the kernels of that header are instantiated in gl3_prefill_gemm3.hip only)
 // gl3_prefill_gemm3.hip (own translation unit, -fno-slp-vectorize): the > 64-token GEMM, every class (gl3_prefill_gemm3.h / gl3_prefill_gemm3t.h)
 void gl3_gemm3_launch(int epi, const GemmArgs& a, int rows, int ntok, hipStream_t s);
@@ -47,6 +48,8 @@ struct gl3_prefill_state {
     uint8_t* XPh = nullptr;             //   while other workgroups still read XQ / XP
     uint8_t* XQb = nullptr;             // second small-batch operand buffer: hb quantised by the gate/up kernel's own epilogue
     float* XSb = nullptr;               //   (its input still being read by other workgroups)
+    uint8_t* KQX = nullptr;             // GL3_FLAG_KQUANT_NATIVE_BATCH, max_batch > 64: Q8T scratch a native matrix' row slab is expanded into (launch_gemm_expanded)
+    size_t kqx_bytes = 0;               //   without the tail slack
     float* QKV = nullptr;               // [M][q_dim + 2 kv_dim]
     float* AO = nullptr;                // [M][q_dim] attention output (rank-chunked)
     float* HB = nullptr;                // [M][hidden] (rank-chunked)
@@ -328,6 +331,16 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     GL3_HIP(hipMemsetAsync(p->XQ, 0, xq_bytes, ctx->stream));
     GL3_HIP(hipMemsetAsync(p->XS, 0, xs_bytes, ctx->stream));
     GL3_HIP(gl3_gemm3_allow_lds());
+    if (ctx->kq_native && M > 64) {
+        // the Q8T form of the largest per-layer launch, the gate + up pair; a matrix with more (the logits) runs in row slabs.
+        // GL3_KQ_EXPAND_BYTES=<n> (diagnostic) shrinks it, down to one strip pair per matrix at the plan's largest K, so that a small model runs in slabs.
+        const size_t pair = (size_t)2 * (((ctx->hidden_l + 31) / 32) * 2) * ((d.dim + 127) / 128) * TILE_BYTES;
+        const size_t least = (size_t)2 * 2 * (p->maxk / 128) * TILE_BYTES;
+        p->kqx_bytes = std::max(pair, least);
+        const char* env = getenv("GL3_KQ_EXPAND_BYTES");
+        if (env && *env) p->kqx_bytes = std::min(p->kqx_bytes, std::max(least, (size_t)atoll(env)));
+        GL3_HIP(hipMalloc((void**)&p->KQX, p->kqx_bytes + GL3_TAIL_PAD));
+    }
     if (d.arch == GL3_ARCH_QWEN2MOE) {
         auto& m = p->moe;
         const size_t E = d.n_experts, K = d.n_experts_used, S = M * K;
@@ -365,7 +378,7 @@ void gl3_prefill_free(gl3_ctx* ctx) {
     if (!p) return;
     for (auto ge : p->step_graphs) if (ge) hipGraphExecDestroy(ge);
     auto f = [](void* q) { if (q) hipFree(q); };
-    f(p->tokens); f(p->XQ); f(p->XS); f(p->XP); f(p->XQh); f(p->XPh); f(p->XQb); f(p->XSb); f(p->QKV); f(p->ATT); f(p->TMX); f(p->SUMS); f(p->seqpos); f(p->tiles); f(p->deep); f(p->deep_rows); f(p->out_rows); f(p->XG); f(p->amax); f(p->amx_v); f(p->amx_i); f(p->XN); f(p->HB2);
+    f(p->tokens); f(p->XQ); f(p->XS); f(p->XP); f(p->XQh); f(p->XPh); f(p->XQb); f(p->XSb); f(p->KQX); f(p->QKV); f(p->ATT); f(p->TMX); f(p->SUMS); f(p->seqpos); f(p->tiles); f(p->deep); f(p->deep_rows); f(p->out_rows); f(p->XG); f(p->amax); f(p->amx_v); f(p->amx_i); f(p->XN); f(p->HB2);
     if (!p->in_arena) { f(p->X); f(p->AO); f(p->HB); f(p->LOGITS); }
     auto& m = p->moe;
     f(m.logits); f(m.w); f(m.sel); f(m.ticket); f(m.slot_tok); f(m.slot_dst); f(m.tab); f(m.HB); f(m.Y); f(m.XQx); f(m.XSx); f(m.XQh); f(m.XSh);
@@ -424,6 +437,60 @@ static void pf_quant(gl3_ctx* ctx, const float* src, int k, int cc, const float*
                        src, k, cc, norm_w, NORM ? ctx->d.rms_eps : 0.f, dst.XQ, dst.XS, dst.maxk, dst.tslots, (uint2*)dst.XP, dst.xp_tok);
 }
 
+// A matrix with native K-quant row segments (GL3_FLAG_KQUANT_NATIVE_BATCH; w2: either matrix of the pair may be the native one).
+// At most 64 tokens: kq_gemm_kernel, one workgroup per strip (kq_gemm_plan).  More: row slabs of the matrix expanded to Q8T tiles in
+// p->KQX, then the > 64-token launch on each slab as on a converted matrix.  A slab is an even number of strips (Q8Mat::bytes(): the
+// prefill GEMM reads 32-row groups), which every row unit of gl3_gemm3_launch's tilings starts on (a tile past the slab's rows is
+// clamped and not stored, as past a matrix' end), and the tiling of a slab may differ from the whole matrix': every tiling sums a
+// row's blocks in the same order.
+static KqRec kq_host_rec(const Q8Mat& w, const Q8Mat* w2) {      // as kq_build_recs (gl3_api.hip) writes it for the decode launch
+    KqRec r;
+    for (KqSeg& s : r.seg) s = {nullptr, INT32_MAX, GL3_TYPE_Q8_0};
+    if (!w.nseg) r.seg[0] = {w.w, 0, GL3_TYPE_Q8_0};
+    for (int i = 0; i < w.nseg; ++i) r.seg[i] = {w.seg[i].w, w.seg[i].row0 / 16, w.seg[i].fmt};
+    r.seg2 = {nullptr, 0, GL3_TYPE_Q8_0};
+    if (w2) r.seg2 = w2->nseg ? KqSeg{w2->seg[0].w, 0, w2->seg[0].fmt} : KqSeg{w2->w, 0, GL3_TYPE_Q8_0};
+    return r;
+}
+// strips [s0, s1) of m as Q8T tiles: in place for a Q8T matrix, else expanded segment by segment into dst
+static const uint8_t* kq_slab(gl3_ctx* ctx, const Q8Mat& m, int s0, int s1, uint8_t* dst) {
+    const size_t strip_bytes = (size_t)m.ng * TILE_BYTES;
+    if (!m.nseg) return m.w + (size_t)s0 * strip_bytes;
+    for (int i = 0; i < m.nseg; ++i) {
+        const Q8Mat::Seg& sg = m.seg[i];
+        const int f = sg.row0 / 16, lo = std::max(s0, f), hi = std::min(s1, f + (sg.rows + 15) / 16);
+        if (lo >= hi) continue;
+        const long ntiles = (long)(hi - lo) * m.ng;
+        hipLaunchKernelGGL(kq_expand_q8t_kernel, dim3((unsigned)((ntiles + 3) / 4)), dim3(256), 0, ctx->stream,
+                           sg.w + (size_t)(lo - f) * m.ng * kq_tile_bytes(sg.fmt), sg.fmt, ntiles, dst + (size_t)(lo - s0) * strip_bytes);
+    }
+    return dst;
+}
+template <int EPI>
+static void launch_gemm_native(gl3_ctx* ctx, GemmArgs a, const Q8Mat& w, const Q8Mat* w2, int ntok) {
+    gl3_prefill_state* p = ctx->pf;
+    if (!pf_chunk_major(ntok)) {
+        const KqGemmPlan pl = kq_gemm_plan(EPI, w.rows, w.k, ntok);
+        a.tslots = pl.tslots;
+        const KqRec kr = kq_host_rec(w, w2);
+        if (pl.tslots == BD_TS) hipLaunchKernelGGL((kq_gemm_kernel<EPI, BD_TS>), dim3(pl.grid), dim3(pl.threads), 0, ctx->stream, a, kr);
+        else hipLaunchKernelGGL((kq_gemm_kernel<EPI, BD_TS_MAX>), dim3(pl.grid), dim3(pl.threads), 0, ctx->stream, a, kr);
+        return;
+    }
+    const int nm = w2 ? 2 : 1, nstrips = (w.rows + 15) / 16;
+    const size_t strip_bytes = (size_t)w.ng * TILE_BYTES;
+    const int cap = (int)std::min<size_t>(p->kqx_bytes / nm / strip_bytes, (size_t)(nstrips + 1)) & ~1;      // strips of a slab per matrix, even
+    float* out = a.out;
+    for (int s0 = 0; s0 < nstrips; s0 += cap) {
+        const int s1 = std::min(nstrips, s0 + cap);
+        a.w = kq_slab(ctx, w, s0, s1, p->KQX);
+        if (w2) a.w2 = kq_slab(ctx, *w2, s0, s1, p->KQX + (size_t)cap * strip_bytes);
+        a.rows = std::min(w.rows, 16 * s1) - 16 * s0;
+        a.out = out + 16 * s0;
+        gl3_gemm3_launch(EPI, a, a.rows, ntok, ctx->stream);
+    }
+}
+
 template <int EPI>
 static void launch_gemm(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int ntok, float* out, int out_stride, float out_scale = 1.0f,
                         bool second_operand = false, bool quantised_out = false) {
@@ -434,9 +501,12 @@ static void launch_gemm(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, int ntok,
     a.maxk = p->maxk; a.ntok = ntok; a.out = out; a.out_stride = out_stride; a.out_scale = out_scale;
     a.XQo = p->XQb; a.XSo = p->XSb;
     a.XP = p->XP; a.xp_tok = p->xp_tok;
+    const bool native = w.nseg || (w2 && w2->nseg);      // native K-quant segments (gl3_kquant_gemm.h); never with a quantised output
+    if (native && !pf_chunk_major(ntok)) { launch_gemm_native<EPI>(ctx, a, w, w2, ntok); return; }
     if (pf_chunk_major(ntok)) {      // > 64 tokens: pf_gemm3_kernel / pf_gemm3t_kernel, tiling by matrix shape (gl3_prefill_gemm3.hip)
         if (quantised_out) { a.XQo = p->XQh; a.XPo = p->XPh; }          // gate + up: hb as the down projection's operand (tall tiling, one rank)
         if (second_operand) { a.XQ = p->XQh; a.XP = p->XPh; }            // down: reads it
+        if (native) { launch_gemm_native<EPI>(ctx, a, w, w2, ntok); return; }
         gl3_gemm3_launch(EPI, a, w.rows, ntok, ctx->stream);
         return;
     }
@@ -910,7 +980,9 @@ static int32_t pf_layers(gl3_ctx* ctx, const PfStep& st) {
     float* HBr = p->HB + (size_t)rank * n * hid;
     const PfOperand xq = pf_operand(p, n);
     int32_t r;
-    hipLaunchKernelGGL(pf_embed_kernel, dim3(n), dim3(256), 0, s, ctx->emb.w, ctx->emb.ng, d.dim, p->tokens, p->X, dml, ctx->emb_scale);
+    if (ctx->emb.nseg)
+        hipLaunchKernelGGL(pf_embed_kq_kernel, dim3(n), dim3(256), 0, s, ctx->emb.seg[0].w, ctx->emb.seg[0].fmt, ctx->emb.ng, d.dim, p->tokens, p->X, dml, ctx->emb_scale);
+    else hipLaunchKernelGGL(pf_embed_kernel, dim3(n), dim3(256), 0, s, ctx->emb.w, ctx->emb.ng, d.dim, p->tokens, p->X, dml, ctx->emb_scale);
     for (int l = 0; l < d.n_layers; ++l) {
         gl3_layer& L = ctx->layers[l];
         Gl3Range layer_range("layer", l);
@@ -935,7 +1007,9 @@ static int32_t pf_layers(gl3_ctx* ctx, const PfStep& st) {
         pf_quant<PQ_NORM>(ctx, p->X, d.dim, dml, L.ffn_norm, n, xq);
         // > 64 tokens on one rank: the tall gate + up tiling writes hb quantised (no f32 round trip, no quantise launch)
         const bool fuse_big = !fuse_off && pf_chunk_major(n) && d.tp_size == 1 && p->XQh && gl3_gemm3_swiglu_quantises(L.w1.rows, n);
-        if (fuse_q || fuse_big) {
+        // a gate / up pair with native K-quant segments writes hb as f32 (kq_gemm_kernel, the expanded slabs): the separate quantise launch
+        const bool native_pair = L.w1.nseg || L.w3.nseg;
+        if ((fuse_q || fuse_big) && !native_pair) {
             launch_gemm<EPI_SWIGLU>(ctx, L.w1, &L.w3, n, HBr, hid, 1.0f, false, true);
             launch_gemm<EPI_RESID>(ctx, L.w2, nullptr, n, Xr, dml, ctx->resid_scale, true);
         } else {

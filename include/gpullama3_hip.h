@@ -138,6 +138,15 @@ enum {
  * max_batch > 1, n_seqs > 1, GL3_ARCH_QWEN2MOE, GL3_FLAG_F32_ACTIVATION or a weight_type other than GL3_TYPE_Q8_0.  A plan with the flag
  * that receives no Q4_K / Q6_K tensor is the plan without it. */
 #define GL3_FLAG_KQUANT_NATIVE 0x80u
+/* GL3_FLAG_KQUANT_NATIVE_BATCH (opt-in): the storage of GL3_FLAG_KQUANT_NATIVE (it implies that flag; both bits = this one) with the
+ * batched entry points on it: gl3_create accepts every max_batch / n_seqs a plan without the flag accepts, and gl3_forward_batch_prefill,
+ * gl3_forward_decode_batch (_sample / _chain), gl3_forward_batch (_sample / _score / _verify / _verify_dist), gl3_kv_seq_copy and
+ * gl3_profile_* run on native storage, every logit, sampled id, score and K / V row bit-equal to the plan without the flag.  Steps of at
+ * most 64 tokens rebuild each Q8_0 block once per step in a fused GEMM (kq_gemm_kernel); larger steps expand row slabs of a native matrix
+ * to Q8_0 tiles in a scratch buffer no larger than the Q8_0 form of one layer's gate + up pair (allocated for max_batch > 64 only; not
+ * counted by gl3_get_weight_bytes) and run the Q8_0 GEMMs on it.  The single-token entry points are those of GL3_FLAG_KQUANT_NATIVE.
+ * Refused (GL3_E_UNSUPPORTED) with tp_size > 1, GL3_ARCH_QWEN2MOE, GL3_FLAG_F32_ACTIVATION or a weight_type other than GL3_TYPE_Q8_0. */
+#define GL3_FLAG_KQUANT_NATIVE_BATCH 0x100u
 
 /* Configuration (J/model/Configuration.java via LlamaModelLoader.java:47-63 / Qwen3ModelLoader.java:48-74)
  * plus the plan-selection knobs the reference reads from system properties

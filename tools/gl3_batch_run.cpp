@@ -55,7 +55,7 @@ static bool parse_id_list(const std::string& line, std::vector<int32_t>& out) {
 }
 
 static int usage(const char* why) {
-    fprintf(stderr, "gl3_batch_run: %s\nusage: gl3_batch_run -m model.gguf --prompts file -np SLOTS -b BATCH -n NEW [--stop id,id] [--share-prefix]\n", why);
+    fprintf(stderr, "gl3_batch_run: %s\nusage: gl3_batch_run -m model.gguf --prompts file -np SLOTS -b BATCH -n NEW [--stop id,id] [--share-prefix] [--kquant-native]\n", why);
     return 2;
 }
 
@@ -81,6 +81,7 @@ int main(int argc, char** argv) {
     int slots = 0, batch = 0, n_new = 0;
     std::vector<int32_t> stop;
     bool share_prefix = false;
+    bool kq_native = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() { return i + 1 < argc ? argv[++i] : (char*)""; };
@@ -91,6 +92,7 @@ int main(int argc, char** argv) {
         else if (a == "-n") n_new = atoi(val());
         else if (a == "--stop") { if (!parse_id_list(val(), stop)) return usage("--stop takes a comma-separated id list"); }
         else if (a == "--share-prefix") share_prefix = true;
+        else if (a == "--kquant-native") kq_native = true;      // Q4_K / Q6_K tensors stay native in HBM (GL3_FLAG_KQUANT_NATIVE_BATCH)
         else return usage(("unknown argument " + a).c_str());
     }
     if (path.empty() || prompts_path.empty()) return usage("-m model.gguf and --prompts file are required");
@@ -134,6 +136,7 @@ int main(int argc, char** argv) {
     opts.max_batch = batch;
     opts.tp_size = 1;
     opts.n_seqs = slots;
+    if (kq_native) opts.flags |= GL3_FLAG_KQUANT_NATIVE_BATCH;
     CK(gl3_load_gguf(path.c_str(), &opts, &ctx));
 
     const std::set<int32_t> stop_set(stop.begin(), stop.end());

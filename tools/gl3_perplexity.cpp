@@ -49,7 +49,7 @@ static bool parse_id_list(const std::string& text, std::vector<int32_t>& out) {
 }
 
 static int usage(const char* why) {
-    fprintf(stderr, "gl3_perplexity: %s\nusage: gl3_perplexity -m model.gguf --ids file -c CTX -b BATCH [-np SLOTS]\n", why);
+    fprintf(stderr, "gl3_perplexity: %s\nusage: gl3_perplexity -m model.gguf --ids file -c CTX -b BATCH [-np SLOTS] [--kquant-native]\n", why);
     return 2;
 }
 
@@ -67,6 +67,7 @@ struct Slot {
 int main(int argc, char** argv) {
     std::string path, ids_path;
     int n_ctx = 0, batch = 0, slots = 1;
+    bool kq_native = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() { return i + 1 < argc ? argv[++i] : (char*)""; };
@@ -75,6 +76,7 @@ int main(int argc, char** argv) {
         else if (a == "-c") n_ctx = atoi(val());
         else if (a == "-b") batch = atoi(val());
         else if (a == "-np") slots = atoi(val());
+        else if (a == "--kquant-native") kq_native = true;      // Q4_K / Q6_K tensors stay native in HBM (GL3_FLAG_KQUANT_NATIVE_BATCH)
         else return usage(("unknown argument " + a).c_str());
     }
     if (path.empty() || ids_path.empty()) return usage("-m model.gguf and --ids file are required");
@@ -108,6 +110,7 @@ int main(int argc, char** argv) {
     opts.max_batch = batch;
     opts.tp_size = 1;
     opts.n_seqs = slots;
+    if (kq_native) opts.flags |= GL3_FLAG_KQUANT_NATIVE_BATCH;
     CK(gl3_load_gguf(path.c_str(), &opts, &ctx));
 
     const int first = n_ctx / 2, last = n_ctx - 2;      // scored positions of a window

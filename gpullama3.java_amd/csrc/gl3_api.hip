@@ -57,7 +57,7 @@ static void launch_mv(gl3_ctx* ctx, MvKernel kernel, dim3 grid, int threads, siz
 
 // Every instantiation of matvec_q8t_kernel the library holds, named here and nowhere else (flags: gl3_decode_kernels.h).  launch_q8t
 // finds the entry with the flags its rule gives (a miss ends the process: no_kernel), and gl3_create walks the table for the large-LDS opt-in: what can be launched has it.
-// kq: the instantiations of matvec_kq_kernel (gl3_kquant_kernels.h: matrices with native Q4_K / Q6_K segments), found by launch_kq.
+// kq: the instantiations of matvec_kq_kernel (gl3_kquant_kernels.h: matrices with native Q4_K / Q5_K / Q6_K segments), found by launch_kq.
 struct MvVariant { int pro, epi, npw; bool sel, tpf, segs, kq; MvKernel kernel; };
 template <int PRO, int EPI, int NPW, bool SEL, bool TPF, bool SEGS>
 constexpr MvVariant mv_variant() { return {PRO, EPI, NPW, SEL, TPF, SEGS, false, matvec_q8t_kernel<PRO, EPI, NPW, SEL, TPF, SEGS>}; }
@@ -905,13 +905,13 @@ static int32_t stage(gl3_ctx* ctx, const void* host, size_t bytes) {
 
 static int32_t upload_q8(gl3_ctx* ctx, Q8Mat& m, int dst_row0, int sub_rows, const void* host, uint64_t bytes, int rows_full, int k_full, long r0);
 
-// GL3_FLAG_KQUANT_NATIVE plans: the tensor (ctx->upload_type: Q8_0, Q4_K or Q6_K) becomes a row segment of m in its own format and
+// GL3_FLAG_KQUANT_NATIVE plans: the tensor (ctx->upload_type: Q8_0, Q4_K, Q5_K or Q6_K) becomes a row segment of m in its own format and
 // allocation (Q8Mat::seg; layouts: gl3_kquant_kernels.h).  A whole Q8_0 matrix takes the plain Q8T allocation instead.
 static int32_t upload_kq(gl3_ctx* ctx, Q8Mat& m, int dst_row0, int sub_rows, const void* host, uint64_t bytes, int rows_full, int k_full, long r0) {
     const int type = ctx->upload_type, nb = k_full / 32;
     const bool native = type != GL3_TYPE_Q8_0;
     if (native && k_full % 256) GL3_FAIL(GL3_E_ARG, "a K-quant row is whole super-blocks of 256 elements");
-    const size_t row_bytes = type == GL3_TYPE_Q4_K ? (size_t)(k_full / 256) * 144 : type == GL3_TYPE_Q6_K ? (size_t)(k_full / 256) * 210 : (size_t)nb * 34;
+    const size_t row_bytes = native ? (size_t)(k_full / 256) * kq_superblock_bytes(type) : (size_t)nb * 34;
     if (bytes != (uint64_t)rows_full * row_bytes) GL3_FAIL(GL3_E_ARG, "tensor byte size does not match its shape");
     if (dst_row0 % 16) GL3_FAIL(GL3_E_UNSUPPORTED, "sub-matrix row offset must be a multiple of 16");
     if (!native && m.nseg == 0 && dst_row0 == 0 && sub_rows == m.rows) {
@@ -931,6 +931,7 @@ static int32_t upload_kq(gl3_ctx* ctx, Q8Mat& m, int dst_row0, int sub_rows, con
     const long total = (long)((sub_rows + 15) & ~15) * m.ng * 4;
     const dim3 grid((unsigned)((total + 255) / 256));
     if (type == GL3_TYPE_Q4_K) hipLaunchKernelGGL(repack_q4k_kernel, grid, dim3(256), 0, ctx->stream, ctx->staging, sg.w, sub_rows, nb, m.ng);
+    else if (type == GL3_TYPE_Q5_K) hipLaunchKernelGGL(repack_q5k_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, ctx->stream, ctx->staging, sg.w, sub_rows, nb, m.ng);
     else if (type == GL3_TYPE_Q6_K) hipLaunchKernelGGL(repack_q6k_kernel, grid, dim3(256), 0, ctx->stream, ctx->staging, sg.w, sub_rows, nb, m.ng);
     else hipLaunchKernelGGL(repack_q8t_kernel, grid, dim3(256), 0, ctx->stream, ctx->staging, sg.w, sub_rows, nb, m.ng, 0L, 0, nb);
     GL3_HIP(hipStreamSynchronize(ctx->stream));
@@ -1062,7 +1063,7 @@ int32_t gl3_upload_tensor(gl3_ctx* ctx, int32_t id, int32_t layer, const void* h
                           id == GL3_T_ATTN_K_NORM || id == GL3_T_BQ || id == GL3_T_BK || id == GL3_T_BV || id == GL3_T_FFN_GATE_INP ||
                           id == GL3_T_FFN_GATE_INP_SHEXP);
     if (id >= GL3_T_FFN_GATE_INP && d.arch != GL3_ARCH_QWEN2MOE) GL3_FAIL(GL3_E_ARG, "router / expert tensors belong to GL3_ARCH_QWEN2MOE");
-    const bool kq_type = ctx->kq_native && (type == GL3_TYPE_Q4_K || type == GL3_TYPE_Q6_K);      // kept native (upload_kq)
+    const bool kq_type = ctx->kq_native && (type == GL3_TYPE_Q4_K || type == GL3_TYPE_Q5_K || type == GL3_TYPE_Q6_K);      // kept native (upload_kq)
     if (is_mat && type != d.weight_type && !kq_type) GL3_FAIL(GL3_E_UNSUPPORTED, "matrix ggml type differs from gl3_model_desc.weight_type");
     ctx->upload_type = type;
     if (id > GL3_T_OUTPUT && (layer < 0 || layer >= d.n_layers)) GL3_FAIL(GL3_E_ARG, "layer out of range");
@@ -2166,10 +2167,10 @@ int32_t gl3_get_weight_bytes(gl3_ctx* ctx, uint64_t* bytes) {
 
 int32_t gl3_debug_kquant_requant(int32_t device, int32_t type, const void* src, int32_t rows, int32_t k, void* dst) {
     if (!src || !dst || rows < 1 || k < 256 || k % 256) return GL3_E_ARG;
-    if (type != GL3_TYPE_Q4_K && type != GL3_TYPE_Q6_K) return GL3_E_UNSUPPORTED;
+    if (type != GL3_TYPE_Q4_K && type != GL3_TYPE_Q5_K && type != GL3_TYPE_Q6_K) return GL3_E_UNSUPPORTED;
     if (hipSetDevice(device) != hipSuccess) return GL3_E_HIP;
     const int nb = k / 32, ng = nb / 4, rows16 = (rows + 15) & ~15;
-    const size_t src_bytes = (size_t)rows * (k / 256) * (type == GL3_TYPE_Q4_K ? 144 : 210), tile_bytes = (size_t)(rows16 / 16) * ng * kq_tile_bytes(type);
+    const size_t src_bytes = (size_t)rows * (k / 256) * kq_superblock_bytes(type), tile_bytes = (size_t)(rows16 / 16) * ng * kq_tile_bytes(type);
     const size_t dst_bytes = (size_t)rows * nb * 34;
     uint8_t *dsrc = nullptr, *tiles = nullptr, *dout = nullptr;
     hipError_t e = hipMalloc((void**)&dsrc, src_bytes);
@@ -2179,6 +2180,7 @@ int32_t gl3_debug_kquant_requant(int32_t device, int32_t type, const void* src, 
     if (e == hipSuccess) {
         const dim3 grid((unsigned)(((long)rows16 * nb + 255) / 256));
         if (type == GL3_TYPE_Q4_K) hipLaunchKernelGGL(repack_q4k_kernel, grid, dim3(256), 0, 0, dsrc, tiles, rows, nb, ng);
+        else if (type == GL3_TYPE_Q5_K) hipLaunchKernelGGL(repack_q5k_kernel, dim3((unsigned)(((long)rows16 * ng + 255) / 256)), dim3(256), 0, 0, dsrc, tiles, rows, nb, ng);
         else hipLaunchKernelGGL(repack_q6k_kernel, grid, dim3(256), 0, 0, dsrc, tiles, rows, nb, ng);
         hipLaunchKernelGGL(kq_requant_kernel, dim3((unsigned)(((long)rows * nb + 255) / 256)), dim3(256), 0, 0, tiles, type, rows, nb, ng, dout);
         e = hipMemcpy(dst, dout, dst_bytes, hipMemcpyDeviceToHost);

@@ -68,15 +68,15 @@ struct Q8Mat {               // one repacked matrix: Q8T tiles (gl3_decode_kerne
     bool vl = false;         // "VL" layout of the Vector-API-order kernels; false (F16 / Q4_0 only) = row-lane, scalar order
     size_t rl_group_bytes() const { return fmt == 1 ? (size_t)(k / 8) * 1024 : (size_t)(k / 32) * 1152; }
     size_t vl_group_bytes() const { return fmt == 1 ? (size_t)(k / 64) * 1024 : fmt == 2 ? (size_t)(k / 256) * 1152 : (size_t)(k / 128) * 1088; }
-    // GL3_FLAG_KQUANT_NATIVE plans (gl3_kquant_kernels.h): fmt stays 8 — the int8-activation path — and a matrix that holds a Q4_K or
-    // Q6_K tensor is a list of row segments, one per upload, each in its own format (8 = Q8T, 12 = Q4_K, 14 = Q6_K) and its own
+    // GL3_FLAG_KQUANT_NATIVE plans (gl3_kquant_kernels.h): fmt stays 8 — the int8-activation path — and a matrix that holds a Q4_K, Q5_K
+    // or Q6_K tensor is a list of row segments, one per upload, each in its own format (8 = Q8T, 12 = Q4_K, 13 = Q5_K, 14 = Q6_K) and its own
     // allocation; w is NULL then.  nseg = 0: one Q8T allocation as in every other plan.
     struct Seg { uint8_t* w; int row0, rows, fmt; };
     Seg seg[3] = {};
     int nseg = 0;
     bool deferred = false;          // not allocated yet: the first upload decides the format
     const void* kq_rec = nullptr;   // device KqRec of the decode launch this matrix leads (written by gl3_finalize); NULL: matvec_q8t_kernel
-    size_t seg_bytes(const Seg& s) const { return (size_t)((s.rows + 15) / 16) * ng * (s.fmt == 12 ? 1216 : s.fmt == 14 ? 1792 : 2176); }
+    size_t seg_bytes(const Seg& s) const { return (size_t)((s.rows + 15) / 16) * ng * (s.fmt == 12 ? 1216 : s.fmt == 13 ? 1488 : s.fmt == 14 ? 1792 : 2176); }
     size_t bytes() const {
         if (nseg) { size_t b = 0; for (int i = 0; i < nseg; ++i) b += seg_bytes(seg[i]); return b; }
         if (fmt != 8 && vl) return (size_t)((rows + 7) / 8) * vl_group_bytes();
@@ -84,7 +84,7 @@ struct Q8Mat {               // one repacked matrix: Q8T tiles (gl3_decode_kerne
         return (size_t)(nstrips + (nstrips & 1)) * ng * 2176;            // even #strips: the prefill GEMM reads 32-row groups
     }
     size_t algo_bytes() const {                                          // GGUF bytes (no padding)
-        if (nseg) { size_t b = 0; for (int i = 0; i < nseg; ++i) b += (size_t)seg[i].rows * (k / 256) * (seg[i].fmt == 12 ? 144 : seg[i].fmt == 14 ? 210 : 272); return b; }
+        if (nseg) { size_t b = 0; for (int i = 0; i < nseg; ++i) b += (size_t)seg[i].rows * (k / 256) * (seg[i].fmt == 12 ? 144 : seg[i].fmt == 13 ? 176 : seg[i].fmt == 14 ? 210 : 272); return b; }
         return (fmt == 8 || fmt == GL3_FMT_Q8V) ? (size_t)rows * (k / 32) * 34 : fmt == 1 ? (size_t)rows * k * 2 : (size_t)rows * (k / 32) * 18;
     }
 };
@@ -280,7 +280,7 @@ struct gl3_ctx {
     int last_sample_mode = -1;                    // SMP_* of the last gl3_forward_decode_sample or chained step (-1: none yet): what gl3_draft_probs_put may copy
     struct PinnedBuf { void* ptr; size_t bytes; bool registered; };      // registered: page-locked by this plan (hipHostRegister), which undoes it
     std::vector<PinnedBuf> pinned;                // caller buffers handed to gl3_pin_host_buffer (logits land there directly)
-    bool kq_native = false;                       // GL3_FLAG_KQUANT_NATIVE: Q4_K / Q6_K uploads stay native (Q8Mat::seg)
+    bool kq_native = false;                       // GL3_FLAG_KQUANT_NATIVE: Q4_K / Q5_K / Q6_K uploads stay native (Q8Mat::seg)
     int upload_type = 0;                          // ggml type of the tensor gl3_upload_tensor is placing
     void* kq_recs = nullptr;                      // KqRec per decode launch over a native matrix
     // upload staging

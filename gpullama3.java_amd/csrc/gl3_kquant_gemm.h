@@ -1,5 +1,5 @@
-// gl3_kquant_gemm.h — the batched GEMMs on native K-quant storage (GL3_FLAG_KQUANT_NATIVE_BATCH): matrices whose Q4_K / Q6_K row
-// segments stay at 19 / 28 bytes per block in HBM (gl3_kquant_kernels.h) under batched prefill, static-batched decode and mixed steps,
+// gl3_kquant_gemm.h — the batched GEMMs on native K-quant storage (GL3_FLAG_KQUANT_NATIVE_BATCH): matrices whose Q4_K / Q5_K / Q6_K row
+// segments stay at 19 / 23.25 / 28 bytes per block in HBM (gl3_kquant_kernels.h) under batched prefill, static-batched decode and mixed steps,
 // bit-equal to the Q8T kernels on the converted plan.  Every Q8_0 block is rebuilt by kq_load / kq_rebuild, the int8 dot is exact, and
 // the f32 steps are those of bdw_gemm_kernel: p = (float)isum * (wScale * aScale), acc += p, blocks ascending, then the epilogue.
 //
@@ -19,8 +19,8 @@
 //     which every wavefront reaches only after it has consumed stage s - 2.  The weight loads of stage s + 1 and the activation loads of
 //     stage s are issued before the rebuild of stage s, unconditionally; past the end of K the tile index is clamped (the duplicate tile
 //     is rebuilt into a slot nobody consumes), so nothing is read behind a strip and no load sits under a condition inside the loop.
-//   * The format of a strip is a wave-uniform value from the launch's KqRec: Q4_K | Q4_K | Q6_K segments of a fused qkv, a SwiGLU pair of
-//     two formats, Q8T segments beside native ones (Q5_K / Q8_0 tensors of the same file; kq_load reads them, the "rebuild" is a move).
+//   * The format of a strip is a wave-uniform value from the launch's KqRec: Q4_K | Q4_K | Q6_K or Q5_K | Q5_K | Q6_K segments of a fused qkv, a
+//     SwiGLU pair of two formats, Q8T segments beside native ones (Q8_0 tensors of the same file; kq_load reads them, the "rebuild" is a move).
 //   * Grid: one workgroup per strip.  bdw_grid's XCD rule co-locates the token tiles of a strip; here they are one workgroup.
 //   * Epilogues: EPI_STORE (out_scale; the logits), EPI_RESID, EPI_SWIGLU writing f32 (the layer code quantises hb with its own launch).
 //

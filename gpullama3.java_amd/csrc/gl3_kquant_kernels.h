@@ -1,18 +1,24 @@
-// gl3_kquant_kernels.h — Q4_K / Q6_K matrices kept in their own bit width in HBM (GL3_FLAG_KQUANT_NATIVE) and streamed by the
+// gl3_kquant_kernels.h — Q4_K / Q5_K / Q6_K matrices kept in their own bit width in HBM (GL3_FLAG_KQUANT_NATIVE) and streamed by the
 // decode matvec, bit-equal to the Q8_0 path on the load-time conversion.
 //
 // What the default path does with a K-quant tensor (gl3_kquant_to_q8_0 = ModelLoader.dequantizeToQ8_0TornadoTensor) is a pure
 // function of the 32 K-quant elements of a block: x_i = getFloat(i), max_abs = max |x_i|, scale = max_abs / 127,
 // q_i = clamp(Math.round(x_i * (1 / scale)), -128, 127), stored scale = f16(scale).  The producer lane that holds those 32 elements
-// rebuilds (q_i, f16 scale) in registers (kq_rebuild_q4k / kq_rebuild_q6k) and runs the int8 dot of matvec_q8t_kernel on them, so
-// every product p_b = isum * (wScale * aScale), the ordered block sum and the epilogues are those of the converted plan.
+// rebuilds (q_i, f16 scale) in registers (kq_rebuild_q4k / kq_rebuild_q5k / kq_rebuild_q6k) and runs the int8 dot of matvec_q8t_kernel
+// on them, so every product p_b = isum * (wScale * aScale), the ordered block sum and the epilogues are those of the converted plan.
 //
-// Layouts in HBM, built at upload by repack_q4k_kernel / repack_q6k_kernel.  As in Q8T a tile is 16 rows x 4 blocks of 32 elements,
-// lane l = (row l & 15, block 4g + (l >> 4)), and every field is one coalesced load of the wavefront:
+// Layouts in HBM, built at upload by repack_q4k_kernel / repack_q5k_kernel / repack_q6k_kernel.  As in Q8T a tile is 16 rows x 4 blocks
+// of 32 elements, lane l = (row l & 15, block 4g + (l >> 4)), and every field is one coalesced load of the wavefront:
 //   Q4_K tile, 1216 B (19 B per block; GGUF 18, Q8T 34):
 //     [16 x u32   f16 d | f16 dmin << 16 of row r: a tile lies inside one super-block of its rows]
 //     [64 x u16   scale | min << 6 | qarg << 12: the block's 6-bit pair, and the nibble value at which |getFloat| peaks]
 //     [64 x 16 B  nibbles: byte t of word j = element 8j + t (low nibble) | element 8j + 4 + t (high nibble)]
+//   Q5_K tile, 1488 B (23.25 B per block; GGUF 22):
+//     [16 x u32   f16 d | f16 dmin << 16 of row r, as Q4_K]
+//     [16 x u8    bit j = bit 4 of qarg of block 4g + j of row r: scale, min and a 5-bit qarg are 17 bits, one more than the u16 below]
+//     [64 x u16   scale | min << 6 | (qarg & 15) << 12]
+//     [64 x u32   fifth bits: bit 8t + f = element 4f + t, so that (word >> f) & 0x01010101 lines up with the masked nibble word]
+//     [64 x 16 B  low nibbles, packed as Q4_K's]
 //   Q6_K tile, 1792 B (28 B per block; GGUF 26.25):
 //     [64 x u32   int8 scale of elements 0..15 | int8 scale of 16..31 << 8 | f16 d << 16]
 //     [64 x 8 B   high two bits: bits 2f, 2f + 1 of byte t of word h = element 16h + 4f + t]
@@ -24,11 +30,18 @@
 // the order), so |x| over the nibbles present peaks at the smallest or the largest of them; which one is decided once at upload with
 // the same f32 arithmetic and kept as qarg.  The lane computes max_abs = |x(qarg)|, the 16 int8 codes of q = 0..15 (4 registers),
 // and turns nibbles into int8 lanes with two v_perm_b32 and a v_bfi_b32 per four elements.
+// Q5_K: x(q) is Q4_K's with q = 0..31, monotone by the same argument, so max_abs = |x(qarg)| comes from the header again.  32 levels
+// for 32 elements: a code table would cost what the elements cost and its lookup on top, so every element is computed where it
+// stands — four 5-bit values per word from (and, shift-and-or) of the nibble word and the fifth-bit word, then per element
+// v_cvt_f32_ubyteN, mul, sub, mul and the six steps of kq_round_clamp, once (Q6_K runs its elements twice), and two v_perm_b32 and an
+// or to pack four codes.  About 415 VALU instructions per block: some 40 for the header (two IEEE divisions), 4 per word for the 5-bit
+// values, 10 per element, 3 per word to pack.
 // Q6_K: 64 levels per 16-element sub-block and two sub-blocks per block: per element (v_cvt_f32_ubyteN, sub, mul), twice — once for
 // max_abs, once for the codes — rather than 32 live registers.
 //
-// The rebuild is a few hundred VALU instructions per 32 elements (Q4_K: 16 table entries of about ten steps, then nine per four elements;
-// Q6_K: about a dozen per element) where Q8T needs 8 v_dot4, so the kernel is sized for VALU throughput, not for bytes in flight:
+// The rebuild is a few hundred VALU instructions per 32 elements (Q4_K: 16 table entries of about ten steps, then nine per four elements,
+// about 270; Q5_K: about 415; Q6_K: about a dozen per element, twice, about 475) where Q8T needs 8 v_dot4, so the kernel is sized for VALU
+// throughput, not for bytes in flight:
 // KQ_NPW = 12 producer wavefronts in the one workgroup a CU holds (16 wavefronts of at most 128 registers) and only two tiles in flight
 // per wavefront (kq_ch): three producers per SIMD alternate between waiting and rebuilding.  (Two workgroups of 8 producers would need 80
 // registers; the prologue's register-held activation does not fit them.)  Measured, it stays VALU-bound well below the converted plan's
@@ -46,17 +59,22 @@ namespace gl3 {
 #define GL3_NO_PK_F32
 #endif
 
-constexpr int KQ_Q4K_TILE = 1216, KQ_Q6K_TILE = 1792;
+constexpr int KQ_Q4K_TILE = 1216, KQ_Q5K_TILE = 1488, KQ_Q6K_TILE = 1792;
 constexpr int KQ_NPW = 12;                    // producer wavefronts
 // tiles per matrix a producer has in flight (two tiles either way: a SwiGLU launch streams two matrices), and the tile groups the
 // producers finish as one batch = one chain segment: 24 groups (3072 elements), 12 (1536) for gate/up
 __host__ __device__ constexpr int kq_ch(int epi) { return epi == EPI_SWIGLU ? 1 : 2; }
 __host__ __device__ constexpr int kq_seg_groups(int epi) { return KQ_NPW * kq_ch(epi); }
 constexpr int KQ_THREADS = 64 * (KQ_NPW + MV_AUX);
-__host__ __device__ constexpr int kq_tile_bytes(int fmt) { return fmt == GL3_TYPE_Q4_K ? KQ_Q4K_TILE : fmt == GL3_TYPE_Q6_K ? KQ_Q6K_TILE : TILE_BYTES; }
+__host__ __device__ constexpr int kq_tile_bytes(int fmt) {
+    return fmt == GL3_TYPE_Q4_K ? KQ_Q4K_TILE : fmt == GL3_TYPE_Q5_K ? KQ_Q5K_TILE : fmt == GL3_TYPE_Q6_K ? KQ_Q6K_TILE : TILE_BYTES;
+}
+// GGUF bytes of one super-block (256 elements) of a native format
+__host__ __device__ constexpr int kq_superblock_bytes(int fmt) { return fmt == GL3_TYPE_Q4_K ? 144 : fmt == GL3_TYPE_Q5_K ? 176 : 210; }
 
 // Row segments of one launch's matrices: the fused qkv matrix is built from up to three uploads of different formats (Q4_K_M:
-// Q4_K, Q4_K, Q6_K).  seg[i] covers the strips from first_strip up to the next segment's; unused entries have first_strip = INT_MAX.
+// Q4_K, Q4_K, Q6_K; Q5_K_M: Q5_K, Q5_K, Q6_K).  seg[i] covers the strips from first_strip up to the next segment's; unused entries have
+// first_strip = INT_MAX.
 // seg2 = the second matrix of a SwiGLU pair (one segment; its format may differ from the first matrix's).
 struct KqSeg { const uint8_t* base; int first_strip; int fmt; };
 struct KqRec { KqSeg seg[3]; KqSeg seg2; };
@@ -64,7 +82,8 @@ struct KqRec { KqSeg seg[3]; KqSeg seg2; };
 // what a producer lane holds of one (row, block) slot, whatever the format, and the Q8_0 block rebuilt from it
 typedef int kq4i __attribute__((ext_vector_type(4)));
 typedef int kq2i __attribute__((ext_vector_type(2)));
-struct KqRaw { kq4i a, b; uint32_t h0, h1; };      // Q8T: a / b = quants 0..15 / 16..31; Q4_K: a = nibbles; Q6_K: a = low nibbles, b.xy = high bits
+// Q8T: a / b = quants 0..15 / 16..31; Q4_K: a = nibbles; Q5_K: a = nibbles, b.x = fifth bits; Q6_K: a = low nibbles, b.xy = high bits
+struct KqRaw { kq4i a, b; uint32_t h0, h1; };
 struct KqBlock { kq4i lo, hi; float ws; };        // int8 quants 0..15 / 16..31, f16 scale widened
 
 __device__ __forceinline__ const uint8_t* kq_uniform(const uint8_t* p) {      // a pointer every lane holds alike, into scalar registers
@@ -88,6 +107,12 @@ __device__ __forceinline__ KqRaw kq_load(int fmt, const uint8_t* p, int lane) {
         r.h1 = kq_ldnt<uint32_t>(p + 4 * (lane & 15));
         r.h0 = kq_ldnt<uint16_t>(p + 64 + 2 * lane);
         r.a = kq_ldnt<kq4i>(p + 192 + 16 * lane);
+    } else if (fmt == GL3_TYPE_Q5_K) {
+        r.h1 = kq_ldnt<uint32_t>(p + 4 * (lane & 15));
+        const uint32_t top = kq_ldnt<uint8_t>(p + 64 + (lane & 15));
+        r.h0 = kq_ldnt<uint16_t>(p + 80 + 2 * lane) | (((top >> (lane >> 4)) & 1) << 16);      // qarg whole again: bits 12..16
+        r.b.x = (int)kq_ldnt<uint32_t>(p + 208 + 4 * lane);
+        r.a = kq_ldnt<kq4i>(p + 464 + 16 * lane);
     } else if (fmt == GL3_TYPE_Q6_K) {
         r.h0 = kq_ldnt<uint32_t>(p + 4 * lane);
         const kq2i h = kq_ldnt<kq2i>(p + 256 + 8 * lane);
@@ -148,6 +173,31 @@ __device__ __forceinline__ KqBlock kq_rebuild_q4k(const kq4i qs, uint32_t hdr, u
     return r;
 }
 
+// Q5_KFloatTensor.getFloat: Q4_K's value with q = nibble + 16 * fifth bit.  No table: each of the 32 elements is computed once.
+__device__ __forceinline__ KqBlock kq_rebuild_q5k(const kq4i qs, uint32_t qh, uint32_t hdr, uint32_t ddm) {
+    const float d = h2f((uint16_t)(ddm & 0xFFFF)), dmin = h2f((uint16_t)(ddm >> 16));
+    const float a = d * (float)(hdr & 63), b = dmin * (float)((hdr >> 6) & 63);
+    const float max_abs = fabsf(kq_q4k_value(a, b, (hdr >> 12) & 31));
+    const float scale = max_abs / 127.0f;
+    const float inv = scale != 0.f ? 1.0f / scale : 0.f;
+    const uint32_t w[4] = {(uint32_t)qs.x, (uint32_t)qs.y, (uint32_t)qs.z, (uint32_t)qs.w};
+    uint32_t o[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t v = ((w[k >> 1] >> (4 * (k & 1))) & 0x0F0F0F0Fu) | (((qh >> k) & 0x01010101u) << 4);      // elements 4k .. 4k + 3
+        uint32_t c[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) c[i] = (uint32_t)kq_round_clamp(kq_q4k_value(a, b, (v >> (8 * i)) & 0xFF) * inv);
+        // the low bytes of the four clamped codes into one word: two v_perm_b32 (selector 0x0c = a zero byte) and an or
+        o[k] = __builtin_amdgcn_perm(c[1], c[0], 0x0c0c0400u) | __builtin_amdgcn_perm(c[3], c[2], 0x04000c0cu);
+    }
+    KqBlock r;
+    r.lo = (kq4i){(int)o[0], (int)o[1], (int)o[2], (int)o[3]};
+    r.hi = (kq4i){(int)o[4], (int)o[5], (int)o[6], (int)o[7]};
+    r.ws = (float)(_Float16)scale;
+    return r;
+}
+
 // Q6_KFloatTensor.getFloat: (d * sc) * (q - 32); v = four 6-bit values, one per byte
 __device__ __forceinline__ float kq_q6k_value(float a, uint32_t v, int i) { return a * ((float)((v >> (8 * i)) & 0xFF) - 32.0f); }
 
@@ -184,6 +234,7 @@ __device__ __forceinline__ KqBlock kq_rebuild_q6k(const kq4i ql, const kq4i qh, 
 // the one device function every consumer of a native matrix goes through: matvec producers, embedding gather, gl3_debug_kquant_requant
 __device__ __forceinline__ KqBlock kq_rebuild(int fmt, const KqRaw& r) {
     if (fmt == GL3_TYPE_Q4_K) return kq_rebuild_q4k(r.a, r.h0, r.h1);
+    if (fmt == GL3_TYPE_Q5_K) return kq_rebuild_q5k(r.a, (uint32_t)r.b.x, r.h0, r.h1);
     if (fmt == GL3_TYPE_Q6_K) return kq_rebuild_q6k(r.a, r.b, r.h0);
     KqBlock q;
     q.lo = r.a; q.hi = r.b; q.ws = h2f((uint16_t)r.h0);
@@ -201,8 +252,8 @@ __device__ __forceinline__ int kq_dot32(const kq4i a0, const kq4i a1, const int4
 // ---------------------------------------------------------------------------------------------------
 // Decode matvec over native row segments: the structure of matvec_q8t_kernel (producers | aux prologue | chain wavefront, same LDS
 // layout, same prologue and chain code, so the same sums in the same order) with KQ_NPW producers that rebuild every block before the
-// dot.  The format is a wave-uniform value per strip (KqRec), so a fused qkv matrix of Q4_K and Q6_K segments, a SwiGLU pair of two
-// formats and Q8T segments beside native ones (a Q5_K tensor converted at load) all run in this one launch.
+// dot.  The format is a wave-uniform value per strip (KqRec), so a fused qkv matrix of Q4_K / Q5_K and Q6_K segments, a SwiGLU pair of two
+// formats and Q8T segments beside native ones (a Q8_0 tensor of the same file) all run in this one launch.
 // SEGS: as in matvec_q8t_kernel, for strips of more than kq_seg_groups tile groups (K > 3072; gate/up: K > 1536).
 template <int PRO, int EPI, bool SEGS>
 __global__ GL3_NO_PK_F32 __launch_bounds__(KQ_THREADS, 4) void matvec_kq_kernel(const MatvecArgs a) {
@@ -471,6 +522,49 @@ static __global__ GL3_NO_PK_F32 void repack_q4k_kernel(const uint8_t* __restrict
     if ((pb & 3) == 0) *reinterpret_cast<uint32_t*>(tile + 4 * (row & 15)) = ddm;
     *reinterpret_cast<uint16_t*>(tile + 64 + 2 * l) = (uint16_t)hdr;
     *reinterpret_cast<uint4*>(tile + 192 + 16 * l) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// Q5_K super-block (176 B): f16 d | f16 dmin | 12 B scales / mins as Q4_K | 32 fifth-bit bytes | 128 nibble bytes; the fifth bit of
+// element e of sub-block j is bit j of byte e.  One thread per destination (row, tile) = the four slots that share the row's u8 of
+// qarg top bits.
+static __global__ GL3_NO_PK_F32 void repack_q5k_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int rows, int nb, int ng) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int rows16 = (rows + 15) & ~15;
+    if (idx >= (long)rows16 * ng) return;
+    const int row = (int)(idx / ng), g = (int)(idx % ng);
+    uint8_t* tile = dst + ((size_t)(row >> 4) * ng + g) * KQ_Q5K_TILE;
+    uint32_t ddm = 0, top = 0;
+    for (int c = 0; c < 4; ++c) {
+        const int pb = 4 * g + c, l = (row & 15) + 16 * c;
+        uint32_t hdr = 0, h = 0, w[4] = {0, 0, 0, 0};
+        if (row < rows) {
+            const uint8_t* sb = src + ((size_t)row * (nb >> 3) + (pb >> 3)) * 176;
+            const int j = pb & 7;
+            ddm = (uint32_t)sb[0] | ((uint32_t)sb[1] << 8) | ((uint32_t)sb[2] << 16) | ((uint32_t)sb[3] << 24);
+            const uint8_t* sc = sb + 4;
+            const int s = j < 4 ? (sc[j] & 63) : ((sc[j + 4] & 0xF) | ((sc[j - 4] >> 6) << 4));          // Q4_KFloatTensor.getScaleK4 / getMinK4
+            const int m = j < 4 ? (sc[j + 4] & 63) : ((sc[j + 4] >> 4) | ((sc[j] >> 6) << 4));
+            const uint8_t* qh = sb + 16;
+            const uint8_t* qs = sb + 48 + (j >> 1) * 32;
+            int qmin = 31, qmax = 0;
+            for (int e = 0; e < 32; ++e) {
+                const uint32_t lo = (j & 1) ? (qs[e] >> 4) : (qs[e] & 0xF), hi = (qh[e] >> j) & 1;
+                const int q = (int)(lo | (hi << 4));
+                qmin = min(qmin, q); qmax = max(qmax, q);
+                w[e >> 3] |= lo << (8 * (e & 3) + 4 * ((e >> 2) & 1));
+                h |= hi << (8 * (e & 3) + (e >> 2));
+            }
+            const float a = h2f((uint16_t)(ddm & 0xFFFF)) * (float)s, b = h2f((uint16_t)(ddm >> 16)) * (float)m;
+            const int qarg = fabsf(kq_q4k_value(a, b, qmax)) >= fabsf(kq_q4k_value(a, b, qmin)) ? qmax : qmin;
+            hdr = (uint32_t)s | ((uint32_t)m << 6) | ((uint32_t)(qarg & 15) << 12);
+            top |= (uint32_t)(qarg >> 4) << c;
+        }
+        *reinterpret_cast<uint16_t*>(tile + 80 + 2 * l) = (uint16_t)hdr;
+        *reinterpret_cast<uint32_t*>(tile + 208 + 4 * l) = h;
+        *reinterpret_cast<uint4*>(tile + 464 + 16 * l) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    *reinterpret_cast<uint32_t*>(tile + 4 * (row & 15)) = ddm;
+    tile[64 + (row & 15)] = (uint8_t)top;
 }
 
 // Q6_K super-block (210 B): 128 low-nibble bytes | 64 high-2-bit bytes | 16 int8 scales | f16 d.  Block j = 4 * half + grp: element e has

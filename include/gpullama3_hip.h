@@ -75,7 +75,7 @@ enum { GL3_ARCH_LLAMA = 0, GL3_ARCH_QWEN3 = 1, GL3_ARCH_QWEN2 = 2,
 /* ggml tensor types of the wire format (J/tensor/GGMLType.java:5-21) */
 enum { GL3_TYPE_F32 = 0, GL3_TYPE_F16 = 1, GL3_TYPE_Q4_0 = 2, GL3_TYPE_Q8_0 = 8,
        GL3_TYPE_Q4_K = 12, GL3_TYPE_Q5_K = 13, GL3_TYPE_Q6_K = 14 };   /* K-quants: converted to Q8_0 at load (gl3_kquant_to_q8_0);
-                                                                          Q4_K / Q6_K stay native under GL3_FLAG_KQUANT_NATIVE */
+                                                                          all three stay native under GL3_FLAG_KQUANT_NATIVE */
 
 /* weight set (J/inference/weights/tornado/TornadoWeights.java:20-48; GGUF names in
  * J/model/loader/LlamaModelLoader.java:83-98, Qwen3ModelLoader.java:96-118) */
@@ -129,14 +129,14 @@ enum {
  * GL3_FLAG_VECTOR_128 (4 accumulators; two fmas per block for Q8_0 / Q4_0): restated in the oracles, refused here (GL3_E_UNSUPPORTED). */
 #define GL3_FLAG_VECTOR_512 0x20u
 #define GL3_FLAG_VECTOR_128 0x40u
-/* GL3_FLAG_KQUANT_NATIVE (opt-in; Q8_0 plans with the int8 activation): gl3_upload_tensor also accepts GL3_TYPE_Q4_K / GL3_TYPE_Q6_K
- * for every matrix id and for token_embd / output, and keeps such a tensor in HBM at 19 / 28 bytes per 32 elements instead of the 34 of
- * its Q8_0 conversion; gl3_load_gguf passes Q4_K / Q6_K tensors through (Q5_K is still converted, Q8_0 tensors stay Q8_0: the format is
- * per tensor).  The decode matvec rebuilds each Q8_0 block of gl3_kquant_to_q8_0 in registers, so every logit is bit-equal to the plan
+/* GL3_FLAG_KQUANT_NATIVE (opt-in; Q8_0 plans with the int8 activation): gl3_upload_tensor also accepts GL3_TYPE_Q4_K / GL3_TYPE_Q5_K /
+ * GL3_TYPE_Q6_K for every matrix id and for token_embd / output, and keeps such a tensor in HBM at 19 / 23.25 / 28 bytes per 32 elements
+ * instead of the 34 of its Q8_0 conversion; gl3_load_gguf passes Q4_K / Q5_K / Q6_K tensors through (Q8_0 tensors stay Q8_0: the format
+ * is per tensor).  The decode matvec rebuilds each Q8_0 block of gl3_kquant_to_q8_0 in registers, so every logit is bit-equal to the plan
  * without the flag.  Single-token entry points only: gl3_forward_decode / _sample / _chain, gl3_forward_prefill (token by token),
  * gl3_profile_*, the gl3_get_* taps, with or without hipGraph.  gl3_create refuses the flag (GL3_E_UNSUPPORTED) with tp_size > 1,
  * max_batch > 1, n_seqs > 1, GL3_ARCH_QWEN2MOE, GL3_FLAG_F32_ACTIVATION or a weight_type other than GL3_TYPE_Q8_0.  A plan with the flag
- * that receives no Q4_K / Q6_K tensor is the plan without it. */
+ * that receives no K-quant tensor is the plan without it. */
 #define GL3_FLAG_KQUANT_NATIVE 0x80u
 /* GL3_FLAG_KQUANT_NATIVE_BATCH (opt-in): the storage of GL3_FLAG_KQUANT_NATIVE (it implies that flag; both bits = this one) with the
  * batched entry points on it: gl3_create accepts every max_batch / n_seqs a plan without the flag accepts, and gl3_forward_batch_prefill,
@@ -650,7 +650,8 @@ GL3_API int32_t gl3_probe_peaks(int32_t device, double* hbm_read_gbs, double* hb
  * layouts included, allocation slack not. */
 GL3_API int32_t gl3_get_weight_bytes(gl3_ctx* ctx, uint64_t* bytes);
 
-/* Test hook for GL3_FLAG_KQUANT_NATIVE (needs no plan): uploads rows x k elements of GL3_TYPE_Q4_K / GL3_TYPE_Q6_K super-blocks (row-major,
+/* Test hook for GL3_FLAG_KQUANT_NATIVE (needs no plan): uploads rows x k elements of GL3_TYPE_Q4_K / GL3_TYPE_Q5_K / GL3_TYPE_Q6_K
+ * super-blocks (row-major,
  * k a multiple of 256), repacks them with the kernel the upload path uses and runs the decode matvec's own device requantisation over
  * every 32-block; dst receives rows * k / 32 GGUF Q8_0 blocks (34 bytes each) — what gl3_kquant_to_q8_0 writes for the same input. */
 GL3_API int32_t gl3_debug_kquant_requant(int32_t device, int32_t type, const void* src, int32_t rows, int32_t k, void* dst);

@@ -1,11 +1,12 @@
-"""tg128 of a Llama-3-8B-shaped random model in the Q4_K_M mix (Q4_K matrices; Q6_K for attn_v, every second ffn_down and output),
+"""tg128 of a Llama-3-8B-shaped random model in the Q4_K_M mix (Q4_K matrices; Q6_K for attn_v, every second ffn_down and output)
+or, with --mix q5_k_m, the Q5_K_M mix (Q5_K in Q4_K's place),
 once converted to Q8_0 at load (the default plan) and once with the K-quant tensors native in HBM (GL3_FLAG_KQUANT_NATIVE).
 
 bench.py's tg protocol (decode steps from an empty cache, logits to the host every step): 1 warm-up and --reps timed repetitions
 per plan, the two plans alternated inside one invocation, their logits compared for equality.  Also the per-class device times of
 instrumented steps and the algorithmic bytes per token of both plans, computed from the shapes.  Prints one JSON line.
 
-    python scripts/kquant_tg.py [--layers 32] [--reps 5]
+    python scripts/kquant_tg.py [--layers 32] [--reps 5] [--mix q4_k_m|q5_k_m]
     rocprofv3 --kernel-trace --stats -- python scripts/kquant_tg.py --reps 1        # per-kernel times
 """
 import argparse
@@ -19,21 +20,22 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-Q8_0, Q4_K, Q6_K = 8, 12, 14
-BLOCK_BYTES = {Q4_K: 144, Q6_K: 210}            # per 256 elements
+Q8_0, Q4_K, Q5_K, Q6_K = 8, 12, 13, 14
+BLOCK_BYTES = {Q4_K: 144, Q5_K: 176, Q6_K: 210}            # per 256 elements
+MIXES = {"q4_k_m": Q4_K, "q5_k_m": Q5_K}        # the type of every matrix that is not Q6_K
 
 
-def ggml_type(name):
+def ggml_type(name, mix="q4_k_m"):
     layer = int(name.split(".")[1]) if name.startswith("blk.") else 0
-    return Q6_K if ("attn_v" in name or name == "output.weight" or ("ffn_down" in name and layer % 2 == 0)) else Q4_K
+    return Q6_K if ("attn_v" in name or name == "output.weight" or ("ffn_down" in name and layer % 2 == 0)) else MIXES[mix]
 
 
 class KqModel:
     """Streams the tensors of the model in file order, generated from a seed; convert = as the default loader would upload them."""
 
-    def __init__(self, cfg, synth, lib, seed, convert):
+    def __init__(self, cfg, synth, lib, seed, convert, mix="q4_k_m"):
         self.cfg, self.wtype, self.rope = cfg, Q8_0, synth.model_rope(cfg)
-        self._synth, self._lib, self._seed, self._convert = synth, lib, seed, convert
+        self._synth, self._lib, self._seed, self._convert, self._mix = synth, lib, seed, convert, mix
 
     def tensor_items(self):
         rng = np.random.default_rng(self._seed)
@@ -41,9 +43,10 @@ class KqModel:
             if kind != "mat":
                 yield name, ((rng.standard_normal(rows * cols, dtype=np.float32) * np.float32(0.02) + np.float32(1)).view(np.uint8), ty, rows, cols)
                 continue
-            t, nb = ggml_type(name), rows * cols // 256
+            t, nb = ggml_type(name, self._mix), rows * cols // 256
             b = rng.integers(0, 256, (nb, BLOCK_BYTES[t]), dtype=np.uint8)
-            d = (np.abs(rng.standard_normal(nb)) * 2e-3 + 2e-4).astype(np.float16).view(np.uint8).reshape(nb, 2)
+            step = 0.5 if t == Q5_K else 1.0           # 32 levels over the range Q4_K covers with 16: the fifth bit buys resolution
+            d = ((np.abs(rng.standard_normal(nb)) * 2e-3 + 2e-4) * step).astype(np.float16).view(np.uint8).reshape(nb, 2)
             if t == Q6_K:
                 b[:, 208:210] = d
             else:
@@ -62,6 +65,7 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--n-gen", type=int, default=128)
+    ap.add_argument("--mix", choices=sorted(MIXES), default="q4_k_m")
     args = ap.parse_args()
     import __graft_entry__ as ge
     from importlib import import_module
@@ -71,8 +75,8 @@ def main():
     cfg = synth.CONFIGS["llama-3-8b"]
     cfg = synth.ModelConfig(**{**cfg.__dict__, "ctx": args.n_gen + 8, "n_layers": args.layers})
     t0 = time.time()
-    plans = {"converted": plan_mod.HipMasterPlan(KqModel(cfg, synth, hip.lib(), 42, True)),
-             "native": plan_mod.HipMasterPlan(KqModel(cfg, synth, hip.lib(), 42, False), flags=hip.FLAG_KQUANT_NATIVE)}
+    plans = {"converted": plan_mod.HipMasterPlan(KqModel(cfg, synth, hip.lib(), 42, True, args.mix)),
+             "native": plan_mod.HipMasterPlan(KqModel(cfg, synth, hip.lib(), 42, False, args.mix), flags=hip.FLAG_KQUANT_NATIVE)}
     setup_s = time.time() - t0
     toks = pkg.javarand.bench_tokens(cfg.vocab, args.n_gen)
 
@@ -82,7 +86,7 @@ def main():
             logits = plan.forward_decode(toks[i], i, copy=False)
         return time.perf_counter() - t1, logits.copy()
 
-    samples, equal = {k: [] for k in plans}, True
+    samples, equal, finite = {k: [] for k in plans}, True, True
     for r in range(args.reps + 1):                     # repetition 0 is the warm-up
         last = {}
         for k, plan in plans.items():
@@ -90,12 +94,13 @@ def main():
             if r:
                 samples[k].append(args.n_gen / s)
         equal = equal and bool(np.array_equal(last["converted"], last["native"]))
+        finite = finite and bool(np.isfinite(last["converted"]).all())
     d, L = cfg.dim, cfg.n_layers
     mats = [(n, r, c) for n, r, c, ty, kind in synth.tensor_specs(cfg, Q8_0) if kind == "mat" and n != "token_embd.weight"]
-    bpe = {Q4_K: 144 / 256, Q6_K: 210 / 256}
+    bpe = {t: b / 256 for t, b in BLOCK_BYTES.items()}
     other = d * 34 / 32 + (2 * L + 1) * d * 4 + 2 * L * cfg.kv_dim * 4 * ((args.n_gen - 1) / 2.0 + 2) + cfg.vocab * 4
-    out = dict(metric="tg%d tokens/s" % args.n_gen, unit="tokens/s", n_gpus=1, data="synthetic", outputs_equal=equal, setup_s=round(setup_s, 1),
-               config=dict(workload="Llama-3-8B shape, Q4_K_M mix, %d layers, random weights" % L, reps=args.reps))
+    out = dict(metric="tg%d tokens/s" % args.n_gen, unit="tokens/s", n_gpus=1, data="synthetic", outputs_equal=equal, outputs_finite=finite, setup_s=round(setup_s, 1),
+               config=dict(workload="Llama-3-8B shape, %s mix, %d layers, random weights" % (args.mix.upper(), L), reps=args.reps))
     for k, plan in plans.items():
         acc, n_prof = None, 8
         for i in range(n_prof):
@@ -106,7 +111,7 @@ def main():
                 for name in kt:
                     for f in ("ms", "launches", "bytes"):
                         acc[name][f] += kt[name][f]
-        weights = sum(r * c * (34 / 32 if k == "converted" else bpe[ggml_type(n)]) for n, r, c in mats)
+        weights = sum(r * c * (34 / 32 if k == "converted" else bpe[ggml_type(n, args.mix)]) for n, r, c in mats)
         s = samples[k] or [0.0]
         out[k] = dict(tok_s=round(float(np.mean(s)), 2), samples_tok_s=[round(x, 2) for x in s], spread_tok_s=round(max(s) - min(s), 2),
                       algorithmic_bytes_per_token=int(weights + other), weight_bytes_in_hbm=plan.weight_bytes(),

@@ -61,8 +61,8 @@ static void launch_mv(gl3_ctx* ctx, MvKernel kernel, dim3 grid, int threads, siz
 struct MvVariant { int pro, epi, npw; bool sel, tpf, segs, kq; MvKernel kernel; };
 template <int PRO, int EPI, int NPW, bool SEL, bool TPF, bool SEGS>
 constexpr MvVariant mv_variant() { return {PRO, EPI, NPW, SEL, TPF, SEGS, false, matvec_q8t_kernel<PRO, EPI, NPW, SEL, TPF, SEGS>}; }
-template <int PRO, int EPI, bool SEGS>
-constexpr MvVariant mv_variant_kq() { return {PRO, EPI, KQ_NPW, false, false, SEGS, true, matvec_kq_kernel<PRO, EPI, SEGS>}; }
+template <int PRO, int EPI, bool SEGS, bool SEL = false>
+constexpr MvVariant mv_variant_kq() { return {PRO, EPI, KQ_NPW, SEL, false, SEGS, true, matvec_kq_kernel<PRO, EPI, SEGS, SEL>}; }
 constexpr MvVariant MV_VARIANTS[] = {
     //         prologue   epilogue  NPW   SEL    TPF    SEGS
     mv_variant<PRO_RMS,   EPI_STORE,  4, false, false, false>(),      // qkv, logits
@@ -83,13 +83,17 @@ constexpr MvVariant MV_VARIANTS[] = {
     mv_variant<PRO_QUANT, EPI_RESID,  8, false, true,  true>(),
     mv_variant<PRO_RMS,   EPI_SWIGLU, 4, true,  false, false>(),      // routed experts (launch_matvec_sel)
     mv_variant<PRO_QUANT, EPI_RESID,  4, true,  false, false>(),
-    //            prologue   epilogue    SEGS      native K-quant segments: KQ_NPW producers, one rank, no experts
+    //            prologue   epilogue    SEGS   SEL   native K-quant segments: KQ_NPW producers, one rank
     mv_variant_kq<PRO_RMS,   EPI_STORE,  false>(),                    // qkv, logits
     mv_variant_kq<PRO_RMS,   EPI_STORE,  true>(),
     mv_variant_kq<PRO_RMS,   EPI_SWIGLU, false>(),                    // gate/up
     mv_variant_kq<PRO_RMS,   EPI_SWIGLU, true>(),
     mv_variant_kq<PRO_QUANT, EPI_RESID,  false>(),                    // wo, down
     mv_variant_kq<PRO_QUANT, EPI_RESID,  true>(),
+    mv_variant_kq<PRO_RMS,   EPI_SWIGLU, false, true>(),              // routed experts on native stacks (launch_matvec_sel)
+    mv_variant_kq<PRO_RMS,   EPI_SWIGLU, true,  true>(),
+    mv_variant_kq<PRO_QUANT, EPI_RESID,  false, true>(),
+    mv_variant_kq<PRO_QUANT, EPI_RESID,  true,  true>(),
 };
 constexpr int mv_find(int pro, int epi, int npw, bool sel, bool tpf, bool segs, bool kq = false) {
     int i = 0;
@@ -117,10 +121,13 @@ static void launch_q8t(gl3_ctx* ctx, int pro, int epi, const MatvecArgs& a, int 
 
 // A matrix with native K-quant segments (a.kq): KQ_NPW producers at every shape, the chain in segments for strips of more than
 // kq_seg_groups tile groups, one workgroup per CU.  Same dynamic LDS as matvec_q8t_kernel (the layout is shared).
-static void launch_kq(gl3_ctx* ctx, int pro, int epi, const MatvecArgs& a) {
-    const int i = mv_find(pro, epi, KQ_NPW, false, false, a.ng > kq_seg_groups(epi), true);
+// slots > 0: the routed experts (SEL, a.kq = a KqSelRec), blockIdx.y = slot; the 256 workgroups are shared out among the slots, since every
+// workgroup runs the activation prologue before its first strip.
+static void launch_kq(gl3_ctx* ctx, int pro, int epi, const MatvecArgs& a, int slots = 0) {
+    const int i = mv_find(pro, epi, KQ_NPW, slots > 0, false, a.ng > kq_seg_groups(epi), true);
     if (i < 0) no_kernel("matvec_kq_kernel<prologue, epilogue>", pro, epi);
-    launch_mv(ctx, MV_VARIANTS[i].kernel, dim3(a.nstrips < 256 ? a.nstrips : 256), KQ_THREADS, matvec_smem(pro, epi, a.k), a);
+    const int wgs = slots > 0 ? std::max(1, 256 / slots) : 256;
+    launch_mv(ctx, MV_VARIANTS[i].kernel, dim3(a.nstrips < wgs ? a.nstrips : wgs, slots > 0 ? slots : 1), KQ_THREADS, matvec_smem(pro, epi, a.k), a);
 }
 
 // Run-time weight format (with the F16 accumulator species) and epilogue as compile-time constants for a generic lambda, the way
@@ -200,7 +207,8 @@ static void launch_matvec(gl3_ctx* ctx, int pro, int epi, const Q8Mat& w, const 
     launch_q8t(ctx, pro, epi, a);
 }
 
-// Routed experts of a Qwen2-MoE layer: one launch, blockIdx.y = slot of the top-k selection (matvec_q8t_kernel<.., SEL>).
+// Routed experts of a Qwen2-MoE layer: one launch, blockIdx.y = slot of the top-k selection (matvec_q8t_kernel<.., SEL>; a launch in which
+// some matrix has a native K-quant segment: matvec_kq_kernel<.., SEL> with the KqSelRec beside the slot record).
 // stack holds n_experts sub-matrices of `rows` rows each; x / out advance by x_slot / out_slot floats per slot.
 // which: record of this layer (0 = gate/up with the shared expert's chunks as extra slots, 1 = gate/up alone, 2 = down).
 static void launch_matvec_sel(gl3_ctx* ctx, int layer, int which, const Q8Mat& stack, const Q8Mat* stack2, int rows, const float* x,
@@ -211,14 +219,40 @@ static void launch_matvec_sel(gl3_ctx* ctx, int layer, int which, const Q8Mat& s
     a.x = x; a.norm_w = norm_w; a.eps = d.rms_eps; a.out = out; a.resid_in = nullptr; a.out_scale = 1.0f;
     a.moe = reinterpret_cast<const MoeSlots*>(ctx->moe_slots) + (size_t)layer * 3 + which;
     const int slots = d.n_experts_used + (which == 0 ? (shared_rows + rows - 1) / rows : 0);
+    const int pro = which != 2 ? PRO_RMS : PRO_QUANT, epi = which != 2 ? EPI_SWIGLU : EPI_RESID;
+    if (ctx->moe_kq_native[(size_t)layer * 3 + which]) {
+        a.kq = reinterpret_cast<const KqRec*>(static_cast<const KqSelRec*>(ctx->moe_kq_slots) + (size_t)layer * 3 + which);
+        launch_kq(ctx, pro, epi, a, slots);
+        return;
+    }
     if (which != 2) launch_q8t(ctx, PRO_RMS, EPI_SWIGLU, a, slots);
     else launch_q8t(ctx, PRO_QUANT, EPI_RESID, a, slots);
 }
 
-// The slot records of every layer's two routed-expert launches (MoeSlots, gl3_decode_kernels.h); pointers are final after gl3_create.
+// The slot records of every layer's two routed-expert launches (MoeSlots, gl3_decode_kernels.h); pointers are final after gl3_create —
+// on a native K-quant plan (GL3_FLAG_KQUANT_NATIVE_MOE) after the uploads, so gl3_finalize calls this there.  Such a plan also gets
+// the KqSelRec of every launch (gl3_kquant_kernels.h) and the note which launches meet a native segment (moe_kq_native).
 static int32_t moe_build_slots(gl3_ctx* ctx) {
     const gl3_model_desc& d = ctx->d;
     std::vector<MoeSlots> h((size_t)d.n_layers * 3);
+    ctx->moe_kq_native.assign(h.size(), 0);
+    if (ctx->kq_native) {
+        auto one = [](const Q8Mat& m) { return m.nseg ? KqSeg{m.seg[0].w, 0, m.seg[0].fmt} : KqSeg{m.w, 0, GL3_TYPE_Q8_0}; };
+        std::vector<KqSelRec> k(h.size());
+        for (int l = 0; l < d.n_layers; ++l) {
+            const gl3_layer& L = ctx->layers[l];
+            const KqSeg none{nullptr, 0, GL3_TYPE_Q8_0};
+            k[(size_t)l * 3 + 0] = {one(L.gate_exps), one(L.up_exps), one(L.w1), one(L.w3)};
+            k[(size_t)l * 3 + 1] = {one(L.gate_exps), one(L.up_exps), none, none};
+            k[(size_t)l * 3 + 2] = {one(L.down_exps), none, none, none};
+            const bool routed = L.gate_exps.nseg || L.up_exps.nseg;
+            ctx->moe_kq_native[(size_t)l * 3 + 0] = routed || L.w1.nseg || L.w3.nseg;
+            ctx->moe_kq_native[(size_t)l * 3 + 1] = routed;
+            ctx->moe_kq_native[(size_t)l * 3 + 2] = L.down_exps.nseg != 0;
+        }
+        if (!ctx->moe_kq_slots) GL3_HIP(hipMalloc(&ctx->moe_kq_slots, k.size() * sizeof(KqSelRec)));      // a gl3_finalize that failed behind this point may come again
+        GL3_HIP(hipMemcpy(ctx->moe_kq_slots, k.data(), k.size() * sizeof(KqSelRec), hipMemcpyHostToDevice));
+    }
     for (int l = 0; l < d.n_layers; ++l) {
         const gl3_layer& L = ctx->layers[l];
         MoeSlots gu{};
@@ -233,7 +267,7 @@ static int32_t moe_build_slots(gl3_ctx* ctx) {
         dn.x_slot_stride = d.moe_hidden; dn.out_slot_stride = d.dim; dn.n_sel = d.n_experts_used;
         h[(size_t)l * 3 + 2] = dn;
     }
-    GL3_HIP(hipMalloc(&ctx->moe_slots, h.size() * sizeof(MoeSlots)));
+    if (!ctx->moe_slots) GL3_HIP(hipMalloc(&ctx->moe_slots, h.size() * sizeof(MoeSlots)));
     GL3_HIP(hipMemcpy(ctx->moe_slots, h.data(), h.size() * sizeof(MoeSlots), hipMemcpyHostToDevice));
     return GL3_OK;
 }
@@ -582,6 +616,12 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
         d.arch != GL3_ARCH_QWEN2MOE)
         return bail(GL3_E_UNSUPPORTED, "unsupported architecture");
     const bool moe = d.arch == GL3_ARCH_QWEN2MOE;
+    constexpr uint32_t KQ_FLAGS = GL3_FLAG_KQUANT_NATIVE | GL3_FLAG_KQUANT_NATIVE_BATCH | GL3_FLAG_KQUANT_NATIVE_MOE;
+    if (moe && (d.flags & GL3_FLAG_KQUANT_NATIVE_MOE)) {      // what a qwen2moe plan refuses below, under this flag's name
+        if (d.tp_size > 1 || (d.flags & GL3_FLAG_FORCE_RCCL)) return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE_MOE: tensor parallelism is not built");
+        if (d.weight_type != GL3_TYPE_Q8_0 || (d.flags & GL3_FLAG_F32_ACTIVATION))
+            return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE_MOE: Q8_0 plans with the int8 activation only (K-quant tensors are rebuilt as Q8_0 blocks)");
+    }
     if (moe) {      // the reference's GPU plan for this family is Q8_0 (Qwen2MoEQ8_0PlanComponents); so is this one
         if (d.weight_type != GL3_TYPE_Q8_0 || (d.flags & GL3_FLAG_F32_ACTIVATION))
             return bail(GL3_E_UNSUPPORTED, "qwen2moe: Q8_0 matrices with the int8 activation only");
@@ -613,13 +653,15 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     }
     if (d.weight_type != GL3_TYPE_Q8_0 && d.weight_type != GL3_TYPE_F16 && d.weight_type != GL3_TYPE_Q4_0)
         return bail(GL3_E_UNSUPPORTED, "matrix weight type must be Q8_0, F16 or Q4_0");
-    if (d.flags & (GL3_FLAG_KQUANT_NATIVE | GL3_FLAG_KQUANT_NATIVE_BATCH)) {      // one rank; the batched entry points with GL3_FLAG_KQUANT_NATIVE_BATCH (gl3_kquant_gemm.h)
-        const std::string flag = (d.flags & GL3_FLAG_KQUANT_NATIVE_BATCH) ? "GL3_FLAG_KQUANT_NATIVE_BATCH" : "GL3_FLAG_KQUANT_NATIVE";
+    if (d.flags & KQ_FLAGS) {      // one rank; the batched entry points with GL3_FLAG_KQUANT_NATIVE_BATCH (gl3_kquant_gemm.h), qwen2moe with GL3_FLAG_KQUANT_NATIVE_MOE
+        const bool batch = d.flags & (GL3_FLAG_KQUANT_NATIVE_BATCH | GL3_FLAG_KQUANT_NATIVE_MOE);
+        const std::string flag = (d.flags & GL3_FLAG_KQUANT_NATIVE_MOE) ? "GL3_FLAG_KQUANT_NATIVE_MOE" : batch ? "GL3_FLAG_KQUANT_NATIVE_BATCH" : "GL3_FLAG_KQUANT_NATIVE";
         if (d.weight_type != GL3_TYPE_Q8_0 || (d.flags & GL3_FLAG_F32_ACTIVATION))
             return bail(GL3_E_UNSUPPORTED, flag + ": Q8_0 plans with the int8 activation only (K-quant tensors are rebuilt as Q8_0 blocks)");
-        if (moe) return bail(GL3_E_UNSUPPORTED, flag + ": qwen2moe experts have no native K-quant kernel");
+        if (moe && !(d.flags & GL3_FLAG_KQUANT_NATIVE_MOE))
+            return bail(GL3_E_UNSUPPORTED, flag + ": qwen2moe experts have no native K-quant kernel (GL3_FLAG_KQUANT_NATIVE_MOE has them)");
         if (d.tp_size > 1) return bail(GL3_E_UNSUPPORTED, flag + ": tensor parallelism is not built");
-        if (!(d.flags & GL3_FLAG_KQUANT_NATIVE_BATCH) && (d.max_batch > 1 || d.n_seqs > 1))
+        if (!batch && (d.max_batch > 1 || d.n_seqs > 1))
             return bail(GL3_E_UNSUPPORTED, "GL3_FLAG_KQUANT_NATIVE: batched prefill and static-batched decode (max_batch > 1, n_seqs > 1) need GL3_FLAG_KQUANT_NATIVE_BATCH");
         ctx->kq_native = true;
     }
@@ -773,7 +815,7 @@ int32_t gl3_create(const gl3_model_desc* desc, gl3_ctx** out) {
     TRYHIP(hipMemset(ctx->att_t, 0, attn_att_t_floats(ctx->kv_heads_l, d.n_heads / d.n_kv_heads, (d.ctx + 3) & ~3) * 4));
     TRY(dmalloc(ctx, &ctx->att_tmax, (size_t)ctx->heads_l * ctx->n_tsplit));
     TRY(dmalloc(ctx, &ctx->att_sums, (size_t)ctx->heads_l));
-    if (moe) TRY(moe_build_slots(ctx));          // after hb: the merged gate/up launch writes the shared expert's SwiGLU output there
+    if (moe && !ctx->kq_native) TRY(moe_build_slots(ctx));          // after hb: the merged gate/up launch writes the shared expert's SwiGLU output there
     for (const MvVariant& v : MV_VARIANTS) TRYHIP(hipFuncSetAttribute((const void*)v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GL3_LDS_MAX));
     hipError_t vq_attr = hipSuccess;
     for (int fmt : {GL3_TYPE_F16, GL3_TYPE_Q4_0})
@@ -875,9 +917,9 @@ void gl3_destroy(gl3_ctx* ctx) {
     for (auto& L : ctx->layers) {
         fm(L.wqkv); fm(L.wo); fm(L.w1); fm(L.w3); fm(L.w2);
         f(L.attn_norm); f(L.ffn_norm); f(L.qnorm); f(L.knorm); f(L.bq); f(L.bk); f(L.bv);
-        f(L.gate_exps.w); f(L.up_exps.w); f(L.down_exps.w); f(L.gate_inp); f(L.gate_inp_shexp);
+        fm(L.gate_exps); fm(L.up_exps); fm(L.down_exps); f(L.gate_inp); f(L.gate_inp_shexp);
     }
-    f(ctx->moe_logits); f(ctx->moe_w); f(ctx->moe_sel); f(ctx->moe_hb); f(ctx->moe_y); f(ctx->moe_slots); f(ctx->tp_recs);
+    f(ctx->moe_logits); f(ctx->moe_w); f(ctx->moe_sel); f(ctx->moe_hb); f(ctx->moe_y); f(ctx->moe_slots); f(ctx->moe_kq_slots); f(ctx->tp_recs);
     f(ctx->out_norm); f(ctx->rope_cr); f(ctx->rope_ci); f(ctx->kcache); f(ctx->vcache); f(ctx->kv_copy_dst); f(ctx->xn); f(ctx->qkv);
     if (!ctx->arena.base) { f(ctx->x); f(ctx->xb); f(ctx->hb); f(ctx->logits); }
     gl3_tp_arena_free(ctx);
@@ -944,7 +986,7 @@ static int32_t upload_kq(gl3_ctx* ctx, Q8Mat& m, int dst_row0, int sub_rows, con
 static int32_t kq_finalize(gl3_ctx* ctx) {
     std::vector<Q8Mat*> mats{&ctx->emb};
     if (ctx->wcls_owned) mats.push_back(&ctx->wcls);
-    for (auto& L : ctx->layers) for (Q8Mat* m : {&L.wqkv, &L.wo, &L.w1, &L.w3, &L.w2}) mats.push_back(m);
+    for (auto& L : ctx->layers) for (Q8Mat* m : {&L.wqkv, &L.wo, &L.w1, &L.w3, &L.w2, &L.gate_exps, &L.up_exps, &L.down_exps}) mats.push_back(m);
     for (Q8Mat* m : mats) {
         if (!m->nseg) continue;
         for (int i = 1; i < m->nseg; ++i) for (int j = i; j > 0 && m->seg[j].row0 < m->seg[j - 1].row0; --j) std::swap(m->seg[j], m->seg[j - 1]);
@@ -985,7 +1027,7 @@ static int32_t kq_build_recs(gl3_ctx* ctx) {
     for (auto& L : ctx->layers) { add(L.wqkv, nullptr); add(L.wo, nullptr); add(L.w1, &L.w3); add(L.w2, nullptr); }
     add(ctx->wcls, nullptr);
     if (h.empty()) return GL3_OK;
-    GL3_HIP(hipMalloc(&ctx->kq_recs, h.size() * sizeof(KqRec)));
+    if (!ctx->kq_recs) GL3_HIP(hipMalloc(&ctx->kq_recs, h.size() * sizeof(KqRec)));      // the count is fixed by the uploads, which end before the first gl3_finalize
     GL3_HIP(hipMemcpyAsync(ctx->kq_recs, h.data(), h.size() * sizeof(KqRec), hipMemcpyHostToDevice, ctx->stream));
     GL3_HIP(hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < lead.size(); ++i) lead[i]->kq_rec = static_cast<KqRec*>(ctx->kq_recs) + i;
@@ -1169,6 +1211,7 @@ int32_t gl3_finalize(gl3_ctx* ctx) {
     { int32_t r = gl3_tp_local_resolve(ctx); if (r != GL3_OK) return r; }
     { int32_t r = tp_fold_setup(ctx); if (r != GL3_OK) return r; }
     if (ctx->kq_native) { int32_t r = kq_finalize(ctx); if (r != GL3_OK) return r; }
+    if (ctx->kq_native && d.arch == GL3_ARCH_QWEN2MOE) { int32_t r = moe_build_slots(ctx); if (r != GL3_OK) return r; }
     if (!(ctx->have_global & (1u << GL3_T_OUTPUT))) {   // tied: wcls = this rank's vocab rows of token_embd
         ctx->wcls = ctx->emb;
         ctx->wcls.rows = ctx->vocab_l;

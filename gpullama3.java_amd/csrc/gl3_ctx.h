@@ -260,6 +260,8 @@ struct gl3_ctx {
     float *moe_logits = nullptr, *moe_w = nullptr, *moe_hb = nullptr, *moe_y = nullptr;
     int* moe_sel = nullptr;                       // [topk] expert ids, then the router kernel's arrival ticket
     void* moe_slots = nullptr;                    // MoeSlots[n_layers][3]: gate/up with the shared expert merged, gate/up alone, down
+    void* moe_kq_slots = nullptr;                 // GL3_FLAG_KQUANT_NATIVE_MOE: KqSelRec[n_layers][3] beside them, and which of the launches meet
+    std::vector<uint8_t> moe_kq_native;           //   a native segment (matvec_kq_kernel<.., SEL>); all 0 on every other plan
     int *dyn = nullptr, *argmax = nullptr;        // dyn[0] = token, dyn[1] = position, then the SmpRow of a single-row sampled step (GL3_DYN_ROW)
     int* h_dyn = nullptr;                         // pinned, same layout
     const int* dyn_cur = nullptr;                 // (token, position) pair the next launches read: dyn, or an entry of dyn_seq

@@ -497,8 +497,9 @@ int32_t gl3_load_gguf(const char* path, const gl3_model_desc* opts, gl3_ctx** ou
         if (it == g->by_name.end()) return required ? GL3_E_STATE : GL3_OK;
         const TensorInfo& t = g->tensors[it->second];
         const uint8_t* data = g->base + g->data_off + t.offset;
-        const bool matrix = id == GL3_T_TOKEN_EMBD || id == GL3_T_OUTPUT || (id >= GL3_T_WQ && id <= GL3_T_W3 && id != GL3_T_FFN_NORM) || id == GL3_T_WQKV || id == GL3_T_W13;
-        if ((d.flags & (GL3_FLAG_KQUANT_NATIVE | GL3_FLAG_KQUANT_NATIVE_BATCH)) && matrix && (t.type == GL3_TYPE_Q4_K || t.type == GL3_TYPE_Q5_K || t.type == GL3_TYPE_Q6_K))      // kept native in HBM
+        const bool matrix = id == GL3_T_TOKEN_EMBD || id == GL3_T_OUTPUT || (id >= GL3_T_WQ && id <= GL3_T_W3 && id != GL3_T_FFN_NORM) || id == GL3_T_WQKV || id == GL3_T_W13 ||
+                            (id >= GL3_T_FFN_GATE_EXPS && id <= GL3_T_FFN_DOWN_EXPS);
+        if ((d.flags & (GL3_FLAG_KQUANT_NATIVE | GL3_FLAG_KQUANT_NATIVE_BATCH | GL3_FLAG_KQUANT_NATIVE_MOE)) && matrix && (t.type == GL3_TYPE_Q4_K || t.type == GL3_TYPE_Q5_K || t.type == GL3_TYPE_Q6_K))      // kept native in HBM
             return gl3_upload_tensor(ctx, id, layer, data, t.bytes, t.type);
         if (t.type == GL3_TYPE_Q4_K || t.type == GL3_TYPE_Q5_K || t.type == GL3_TYPE_Q6_K) {     // K-quant -> Q8_0 at load
             uint64_t n = 1;

@@ -52,28 +52,18 @@ inline KqGemmPlan kq_gemm_plan(int epi, int rows, int k, int ntok) {
     return p;
 }
 
+// The K walk both kernels below run on one strip: this workgroup's four wavefronts rebuild the strip's tiles (matrix m: format fmt[m], first
+// tile at wbase[m]) stage by stage and, if `consumer`, this wavefront accumulates its 16 tokens (lane r: token slot tokslot) in acc.
+// TS: token slots of XQ2 / XS2 as a compile-time constant, or 0 for the run-time count ts (the grouped form).
 template <int EPI, int TS>
-__global__ GL3_NO_PK_F32 __launch_bounds__(KQG_THREADS) void kq_gemm_kernel(const GemmArgs a, const KqRec kr) {
+__device__ __forceinline__ void kq_gemm_strip(const GemmArgs& a, const int (&fmt)[EPI == EPI_SWIGLU ? 2 : 1], const uint8_t* const (&wbase)[EPI == EPI_SWIGLU ? 2 : 1],
+                                              bool consumer, uint32_t tokslot, int ts_rt, float (&acc)[EPI == EPI_SWIGLU ? 2 : 1][4]) {
     constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
     __shared__ __attribute__((aligned(16))) uint8_t codes[2][NM][KQG_STAGE][KQG_TILE_CODES];
     __shared__ __attribute__((aligned(16))) float wsc[2][NM][KQG_STAGE][64];       // [block][row] weight scales of a tile
     const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int strip = blockIdx.x, ng = a.ng;
-    const bool consumer = 16 * wave < a.ntok;                                      // wave-uniform
-    const uint32_t tokslot = 16 * min(wave, TS / 16 - 1) + r;                      // a wavefront without a token tile reads a valid slot
-    // the strip's segment and format per matrix (scalar)
-    const int first1 = __builtin_amdgcn_readfirstlane(kr.seg[1].first_strip), first2 = __builtin_amdgcn_readfirstlane(kr.seg[2].first_strip);
-    const int si = strip >= first2 ? 2 : strip >= first1 ? 1 : 0;
-    const uint8_t* sbase = si == 2 ? kr.seg[2].base : si == 1 ? kr.seg[1].base : kr.seg[0].base;
-    const int sfirst = si == 2 ? first2 : si == 1 ? first1 : 0;
-    int fmt[NM]; const uint8_t* wbase[NM];
-    fmt[0] = __builtin_amdgcn_readfirstlane(si == 2 ? kr.seg[2].fmt : si == 1 ? kr.seg[1].fmt : kr.seg[0].fmt);
-    wbase[0] = kq_uniform(sbase) + (size_t)(strip - sfirst) * ng * kq_tile_bytes(fmt[0]);
-    if (NM == 2) {
-        fmt[NM - 1] = __builtin_amdgcn_readfirstlane(kr.seg2.fmt);
-        wbase[NM - 1] = kq_uniform(kr.seg2.base) + (size_t)strip * ng * kq_tile_bytes(fmt[NM - 1]);
-    }
+    const int ng = a.ng, ts = TS ? TS : ts_rt;
     const uint8_t* xq = a.XQ + tokslot * 64 + 16 * g;
     const float* xs = a.XS + tokslot * 4;
     KqRaw raw[NM];
@@ -82,7 +72,6 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQG_THREADS) void kq_gemm_kernel(cons
 #pragma unroll
         for (int m = 0; m < NM; ++m) raw[m] = kq_load(fmt[m], wbase[m] + (size_t)tile * kq_tile_bytes(fmt[m]), lane);
     };
-    float acc[NM][4];
 #pragma unroll
     for (int m = 0; m < NM; ++m)
 #pragma unroll
@@ -101,8 +90,8 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQG_THREADS) void kq_gemm_kernel(cons
         for (int j = 0; j < KQG_STAGE; ++j) {
             const int tile = min(KQG_STAGE * s + j, ng - 1);
 #pragma unroll
-            for (int jj = 0; jj < 2; ++jj) B[j][jj] = *reinterpret_cast<const v2l_t*>(xq + ((size_t)tile * 2 + jj) * (TS * 64));
-            X[j] = *reinterpret_cast<const float4*>(xs + (size_t)tile * (TS * 4));
+            for (int jj = 0; jj < 2; ++jj) B[j][jj] = *reinterpret_cast<const v2l_t*>(xq + ((size_t)tile * 2 + jj) * ((size_t)ts * 64));
+            X[j] = *reinterpret_cast<const float4*>(xs + (size_t)tile * ((size_t)ts * 4));
         }
         // rebuild: lane (row r, block g) of tile `wave` -> its four k-chunks in operand order, and its scale
 #pragma unroll
@@ -138,11 +127,11 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQG_THREADS) void kq_gemm_kernel(cons
             }
         }
     }
-    // epilogue.  C layout: token = 16 wave + (lane & 15), weight rows 4g .. 4g + 3 of the strip
-    const int b = 16 * wave + r;
-    if (!consumer || b >= a.ntok) return;
-    const int rbase = strip * 16 + 4 * g;
-    float* o = a.out + (size_t)b * a.out_stride + rbase;
+}
+// o[i] = the epilogue of rows rbase .. rbase + 3 of one token (C layout: a lane holds weight rows 4g .. 4g + 3 of its token)
+template <int EPI>
+__device__ __forceinline__ void kq_gemm_store(const GemmArgs& a, float* o, int rbase, const float (&acc)[EPI == EPI_SWIGLU ? 2 : 1][4]) {
+    constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         if (rbase + i >= a.rows) continue;
@@ -153,6 +142,83 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQG_THREADS) void kq_gemm_kernel(cons
         } else if (EPI == EPI_STORE) o[i] = v0 * a.out_scale;
         else o[i] = o[i] + v0 * a.out_scale;
     }
+}
+
+template <int EPI, int TS>
+__global__ GL3_NO_PK_F32 __launch_bounds__(KQG_THREADS) void kq_gemm_kernel(const GemmArgs a, const KqRec kr) {
+    constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
+    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int strip = blockIdx.x, ng = a.ng;
+    const bool consumer = 16 * wave < a.ntok;                                      // wave-uniform
+    const uint32_t tokslot = 16 * min(wave, TS / 16 - 1) + r;                      // a wavefront without a token tile reads a valid slot
+    // the strip's segment and format per matrix (scalar)
+    const int first1 = __builtin_amdgcn_readfirstlane(kr.seg[1].first_strip), first2 = __builtin_amdgcn_readfirstlane(kr.seg[2].first_strip);
+    const int si = strip >= first2 ? 2 : strip >= first1 ? 1 : 0;
+    const uint8_t* sbase = si == 2 ? kr.seg[2].base : si == 1 ? kr.seg[1].base : kr.seg[0].base;
+    const int sfirst = si == 2 ? first2 : si == 1 ? first1 : 0;
+    int fmt[NM]; const uint8_t* wbase[NM];
+    fmt[0] = __builtin_amdgcn_readfirstlane(si == 2 ? kr.seg[2].fmt : si == 1 ? kr.seg[1].fmt : kr.seg[0].fmt);
+    wbase[0] = kq_uniform(sbase) + (size_t)(strip - sfirst) * ng * kq_tile_bytes(fmt[0]);
+    if (NM == 2) {
+        fmt[NM - 1] = __builtin_amdgcn_readfirstlane(kr.seg2.fmt);
+        wbase[NM - 1] = kq_uniform(kr.seg2.base) + (size_t)strip * ng * kq_tile_bytes(fmt[NM - 1]);
+    }
+    float acc[NM][4];
+    kq_gemm_strip<EPI, TS>(a, fmt, wbase, consumer, tokslot, 0, acc);
+    // epilogue.  C layout: token = 16 wave + (lane & 15), weight rows 4g .. 4g + 3 of the strip
+    const int b = 16 * wave + r;
+    if (!consumer || b >= a.ntok) return;
+    const int rbase = strip * 16 + 4 * g;
+    kq_gemm_store<EPI>(a, a.out + (size_t)b * a.out_stride + rbase, rbase, acc);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The routed experts of a Qwen2-MoE step on native stacked tensors (GL3_FLAG_KQUANT_NATIVE_MOE): kq_gemm_kernel over moe_group_kernel's tile
+// table.  bdw_gemm_kernel<.., GRP> is one wavefront per (table entry, strip) and would rebuild a strip once per entry; here a workgroup
+// owns (expert, strip, up to four consecutive entries of that expert = 64 sorted slots), rebuilds every stage once, and wavefront t
+// consumes entry t: token slots gathered through gtok, result rows scattered through gdst, as the GRP form does, the products and
+// their order those of bdw_gemm_kernel.  An expert with more than four entries takes further workgroups, each rebuilding again.
+//   * Grid: workgroup id = entry * gspe + strip over the bound moe_group_max_entries(), as the GRP form (the step stays one graph).
+//     Entry u leads a workgroup when its index within its expert is a multiple of four; that index is the number of entries in front
+//     of u with u's expert — the table lists an expert's entries consecutively — counted 64 per ballot.  Surplus workgroups and the
+//     other entries exit at once.
+//   * The token-slot count of XQ2 / XS2 is the run-time a.tslots (any chunk length), so one kernel serves every step size: nothing is
+//     expanded into the Q8T scratch.  The stacked tensor is one segment (s0; SwiGLU: s1 = up), expert e at strip e * gspe of it; a
+//     Q8T stack beside a native one is read through kq_load like any Q8T segment.
+template <int EPI>
+__global__ GL3_NO_PK_F32 __launch_bounds__(KQG_THREADS) void kq_gemm_grp_kernel(const GemmArgs a, const KqSeg s0, const KqSeg s1) {
+    constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
+    const int lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int u = blockIdx.x / a.gspe, strip = blockIdx.x % a.gspe, nent = a.gtab[0];
+    if (u >= nent) return;                                                          // the grid is sized for the bound on the table
+    const int e = a.gtab[4 + 4 * u];
+    int ahead = 0;                                                                  // entries of expert e in front of entry u
+    for (int u0 = u - 1;; u0 -= 64) {
+        const int v = u0 - lane;
+        const unsigned long long same = __builtin_amdgcn_ballot_w64(v >= 0 && a.gtab[4 + 4 * v] == e);
+        const int run = same == ~0ull ? 64 : __builtin_ctzll(~same);
+        ahead += run;
+        if (run < 64) break;
+    }
+    if (ahead & 3) return;
+    const int mine = u + wave;                                                      // wavefront t consumes entry u + t, if it is expert e's
+    const bool consumer = mine < nent && a.gtab[4 + 4 * mine] == e;                 // wave-uniform
+    const int4 en = *reinterpret_cast<const int4*>(a.gtab + 4 + 4 * (consumer ? mine : u));      // a wavefront without an entry reads valid slots
+    const int gcnt = en.z, gslot = en.y + min(r, gcnt - 1);                         // lanes past the ragged end: the last valid slot
+    const uint32_t tokslot = a.gtok ? a.gtok[gslot] : gslot;
+    int fmt[NM]; const uint8_t* wbase[NM];
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+        fmt[m] = __builtin_amdgcn_readfirstlane(m ? s1.fmt : s0.fmt);
+        wbase[m] = kq_uniform(m ? s1.base : s0.base) + ((size_t)e * a.gspe + strip) * a.ng * kq_tile_bytes(fmt[m]);
+    }
+    float acc[NM][4];
+    kq_gemm_strip<EPI, 0>(a, fmt, wbase, consumer, tokslot, a.tslots, acc);
+    if (!consumer || r >= gcnt) return;
+    const int rbase = strip * 16 + 4 * g;                                           // row of the expert's own output
+    kq_gemm_store<EPI>(a, a.out + (size_t)(a.gdst ? a.gdst[gslot] : gslot) * a.out_stride + rbase, rbase, acc);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -78,6 +78,11 @@ __host__ __device__ constexpr int kq_superblock_bytes(int fmt) { return fmt == G
 // seg2 = the second matrix of a SwiGLU pair (one segment; its format may differ from the first matrix's).
 struct KqSeg { const uint8_t* base; int first_strip; int fmt; };
 struct KqRec { KqSeg seg[3]; KqSeg seg2; };
+// The SEL form's record (Qwen2-MoE, GL3_FLAG_KQUANT_NATIVE_MOE; one per MoeSlots record, a.kq points at it): the stacked tensors of the
+// routed experts (exp / exp2 = gate / up, or down alone) and the shared expert's dense gate / up (sh / sh2), each ONE segment in its own
+// format — four formats may meet in one launch.  Unit u of a matrix (expert sel[slot], or chunk slot - n_sel of the shared expert) starts
+// u * (rows / 16) strips into its segment: byte offset u * (rows / 16) * ng * kq_tile_bytes(fmt).  first_strip is unused (0).
+struct KqSelRec { KqSeg exp, exp2, sh, sh2; };
 
 // what a producer lane holds of one (row, block) slot, whatever the format, and the Q8_0 block rebuilt from it
 typedef int kq4i __attribute__((ext_vector_type(4)));
@@ -255,8 +260,37 @@ __device__ __forceinline__ int kq_dot32(const kq4i a0, const kq4i a1, const int4
 // dot.  The format is a wave-uniform value per strip (KqRec), so a fused qkv matrix of Q4_K / Q5_K and Q6_K segments, a SwiGLU pair of two
 // formats and Q8T segments beside native ones (a Q8_0 tensor of the same file) all run in this one launch.
 // SEGS: as in matvec_q8t_kernel, for strips of more than kq_seg_groups tile groups (K > 3072; gate/up: K > 1536).
-template <int PRO, int EPI, bool SEGS>
-__global__ GL3_NO_PK_F32 __launch_bounds__(KQ_THREADS, 4) void matvec_kq_kernel(const MatvecArgs a) {
+// SEL: the routed experts of a Qwen2-MoE layer, blockIdx.y = slot, as matvec_q8t_kernel<.., SEL> (MoeSlots: x / out per slot, the shared
+// expert's chunks as slots >= n_sel with a ragged last chunk).  The slot's one segment per matrix comes from the launch's KqSelRec and,
+// for a routed slot, the expert id the router wrote: a scalar base and a scalar format per workgroup, so the producers below run the
+// loads and rebuilds they run for a dense matrix.
+template <int PRO, int EPI, bool SEGS, bool SEL = false>
+__global__ GL3_NO_PK_F32 __launch_bounds__(KQ_THREADS, 4) void matvec_kq_kernel(const MatvecArgs a_in) {
+    MatvecArgs a = a_in;
+    int sel_fmt[2] = {0, 0};
+    const uint8_t* sel_base[2] = {nullptr, nullptr};
+    if (SEL) {
+        const int slot = blockIdx.y;
+        const MoeSlots m = *a.moe;
+        const KqSelRec* ks = reinterpret_cast<const KqSelRec*>(a.kq);
+        const bool routed = slot < m.n_sel;
+        const int unit = __builtin_amdgcn_readfirstlane(routed ? m.sel[slot] : slot - m.n_sel);
+        const size_t tiles = (size_t)unit * (a.rows / 16) * a.ng;
+#pragma unroll
+        for (int i = 0; i < (EPI == EPI_SWIGLU ? 2 : 1); ++i) {
+            const KqSeg* sg = routed ? (i ? &ks->exp2 : &ks->exp) : (i ? &ks->sh2 : &ks->sh);
+            sel_fmt[i] = __builtin_amdgcn_readfirstlane(sg->fmt);
+            sel_base[i] = kq_uniform(sg->base) + tiles * kq_tile_bytes(sel_fmt[i]);
+        }
+        if (routed) {
+            a.x += (size_t)slot * m.x_slot_stride;
+            a.out += (size_t)slot * m.out_slot_stride;
+        } else {
+            a.out = m.sh_out + (size_t)unit * a.rows;
+            const int left = m.sh_rows - unit * a.rows;
+            if (left < a.rows) { a.rows = left; a.nstrips = (left + 15) / 16; }
+        }
+    }
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
     constexpr int CH = kq_ch(EPI), NPW = KQ_NPW, SEG = kq_seg_groups(EPI);
@@ -275,17 +309,18 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQ_THREADS, 4) void matvec_kq_kernel(
         // ------------------------------------------------------------------ producers
         // the row segments: read through the pointer and made scalar (the format decides wave-uniform branches)
         const KqRec* kr = a.kq;
-        const int first1 = __builtin_amdgcn_readfirstlane(kr->seg[1].first_strip), first2 = __builtin_amdgcn_readfirstlane(kr->seg[2].first_strip);
-        const int fmt1 = NM == 2 ? __builtin_amdgcn_readfirstlane(kr->seg2.fmt) : 0;
-        const uint8_t* base1 = NM == 2 ? kq_uniform(kr->seg2.base) : nullptr;
+        const int first1 = SEL ? INT32_MAX : __builtin_amdgcn_readfirstlane(kr->seg[1].first_strip);
+        const int first2 = SEL ? INT32_MAX : __builtin_amdgcn_readfirstlane(kr->seg[2].first_strip);
+        const int fmt1 = NM != 2 ? 0 : SEL ? sel_fmt[1] : __builtin_amdgcn_readfirstlane(kr->seg2.fmt);
+        const uint8_t* base1 = NM != 2 ? nullptr : SEL ? sel_base[1] : kq_uniform(kr->seg2.base);
         const int nt = (a.ng - wave + NPW - 1) / NPW;
         KqRaw raw[NM][CH];
         int fmt0 = 0;
         auto issue = [&](int strip, int i0) __attribute__((always_inline)) {
             const KqSeg* sg = kr->seg + (strip >= first2 ? 2 : strip >= first1 ? 1 : 0);
-            const uint8_t* sbase = kq_uniform(sg->base);
-            const int sfirst = __builtin_amdgcn_readfirstlane(sg->first_strip);
-            fmt0 = __builtin_amdgcn_readfirstlane(sg->fmt);
+            const uint8_t* sbase = SEL ? sel_base[0] : kq_uniform(sg->base);
+            const int sfirst = SEL ? 0 : __builtin_amdgcn_readfirstlane(sg->first_strip);
+            fmt0 = SEL ? sel_fmt[0] : __builtin_amdgcn_readfirstlane(sg->fmt);
 #pragma unroll
             for (int u = 0; u < CH; ++u) {
                 if (i0 + u < nt) {

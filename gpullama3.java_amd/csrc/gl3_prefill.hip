@@ -538,7 +538,8 @@ int32_t gl3_debug_bd_gemm_plan(int32_t epi, int32_t rows, int32_t k, int32_t nto
     return GL3_OK;
 }
 
-// The routed experts of a Qwen2-MoE step: one launch over (tile-table entry, strip of the entry's expert) — bdw_gemm_kernel<.., GRP>.
+// The routed experts of a Qwen2-MoE step: one launch over (tile-table entry, strip of the entry's expert) — bdw_gemm_kernel<.., GRP>, or
+// kq_gemm_grp_kernel when a stacked tensor is native (GL3_FLAG_KQUANT_NATIVE_MOE; at every step size: nothing is expanded).
 // w / w2 = the stacked expert tensors, rows = rows of one expert; XQ / XS = the operand in the XQ2 / XS2 layout with ts token slots;
 // gtok / gdst as in GemmArgs.  The grid covers the bound on the table's entries for n tokens; surplus workgroups exit.
 template <int EPI>
@@ -550,6 +551,11 @@ static void launch_gemm_grouped(gl3_ctx* ctx, const Q8Mat& w, const Q8Mat* w2, i
     a.XQ = XQ; a.XS = XS; a.tslots = ts; a.ntok = n; a.out = out; a.out_stride = out_stride; a.out_scale = 1.0f;
     a.gtab = p->moe.tab; a.gtok = gtok; a.gdst = gdst; a.gspe = rows / 16;
     const dim3 grid((unsigned)moe_group_max_entries(n, ctx->d.n_experts_used, ctx->d.n_experts) * a.gspe);
+    if (w.nseg || (w2 && w2->nseg)) {
+        auto stack = [](const Q8Mat* m) { return !m ? KqSeg{nullptr, 0, GL3_TYPE_Q8_0} : m->nseg ? KqSeg{m->seg[0].w, 0, m->seg[0].fmt} : KqSeg{m->w, 0, GL3_TYPE_Q8_0}; };
+        hipLaunchKernelGGL((kq_gemm_grp_kernel<EPI>), grid, dim3(KQG_THREADS), 0, ctx->stream, a, stack(&w), stack(w2));
+        return;
+    }
     if constexpr (EPI == EPI_SWIGLU) hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 4, 2, false, BD_TS, true>), grid, dim3(64), 0, ctx->stream, a);
     else hipLaunchKernelGGL((bdw_gemm_kernel<EPI, 8, 2, false, BD_TS, true>), grid, dim3(64), 0, ctx->stream, a);
 }
@@ -930,7 +936,8 @@ static void pf_moe_ffn(gl3_ctx* ctx, int l, int n) {
         const bool fuse_off = pf_fused_quant_off();
         const bool fuse_q = !fuse_off && bd_tslots(n) != 0 && (d.hidden % 32) == 0;
         const bool fuse_big = !fuse_off && pf_chunk_major(n) && p->XQh && gl3_gemm3_swiglu_quantises(L.w1.rows, n);
-        if (fuse_q || fuse_big) {
+        const bool native_pair = L.w1.nseg || L.w3.nseg;      // writes hb as f32, as in the dense feed-forward block (pf_layers)
+        if ((fuse_q || fuse_big) && !native_pair) {
             launch_gemm<EPI_SWIGLU>(ctx, L.w1, &L.w3, n, p->HB, d.hidden, 1.0f, false, true);
             launch_gemm<EPI_STORE>(ctx, L.w2, nullptr, n, ysh, ystride, 1.0f, true);
         } else {

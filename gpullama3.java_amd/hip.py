@@ -20,6 +20,7 @@ FLAG_NO_GRAPH, FLAG_LAYER_TAPS, FLAG_FORCE_RCCL, FLAG_SCALAR_DOT, FLAG_F32_ACTIV
 FLAG_VECTOR_512, FLAG_VECTOR_128 = 32, 64      # -Dllama.VectorBitSize (default 256): see include/gpullama3_hip.h
 FLAG_KQUANT_NATIVE = 128                       # Q4_K / Q5_K / Q6_K tensors stay native in HBM (single-token decode on one rank)
 FLAG_KQUANT_NATIVE_BATCH = 256                 # ... with batched prefill, static-batched decode and mixed steps on that storage
+FLAG_KQUANT_NATIVE_MOE = 512                   # ... and Qwen2-MoE plans: the stacked expert tensors stay native too
 CHAIN_MAX = 64                              # GL3_CHAIN_MAX: the longest gl3_forward_decode_chain
 VL_GEMM_KERNELS = ["gemm_f16_mfma_kernel", "gemm_f16_mfma_v512_kernel", "gemm_vlq_kernel", "gemm_vlq_mfma_kernel"]      # gl3_debug_vl_gemm_plan's kernel ids
 GEMM3_KERNELS = ["pf_gemm3_kernel", "pf_gemm3t_kernel"]      # gl3_debug_gemm3_plan's kernel ids

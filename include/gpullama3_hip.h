@@ -147,6 +147,18 @@ enum {
  * counted by gl3_get_weight_bytes) and run the Q8_0 GEMMs on it.  The single-token entry points are those of GL3_FLAG_KQUANT_NATIVE.
  * Refused (GL3_E_UNSUPPORTED) with tp_size > 1, GL3_ARCH_QWEN2MOE, GL3_FLAG_F32_ACTIVATION or a weight_type other than GL3_TYPE_Q8_0. */
 #define GL3_FLAG_KQUANT_NATIVE_BATCH 0x100u
+/* GL3_FLAG_KQUANT_NATIVE_MOE (opt-in): the storage of GL3_FLAG_KQUANT_NATIVE and the batched entry points of GL3_FLAG_KQUANT_NATIVE_BATCH
+ * (it implies both) for GL3_ARCH_QWEN2MOE, which those two flags alone still refuse.  gl3_create accepts a Qwen2-MoE plan under the
+ * conditions it has without K-quant flags (Q8_0 with the int8 activation, one rank, n_seqs > 1 only with max_batch > 1);
+ * GL3_T_FFN_GATE_EXPS / _UP_EXPS / _DOWN_EXPS accept GL3_TYPE_Q4_K / Q5_K / Q6_K and keep the stacked tensor as one native segment
+ * (expert e = strips [e * rows / 16, (e + 1) * rows / 16) of it; the format is per tensor, and a stacked tensor that arrives as Q8_0 stays
+ * Q8_0 tiles beside native ones — ffn_down_exps when moe_hidden is no multiple of 256); gl3_load_gguf passes them through and
+ * gl3_get_weight_bytes counts them at their native size.  The decode step's routed-expert launches rebuild the selected experts' blocks
+ * in registers (matvec_kq_kernel<.., SEL>), a batched step of any size rebuilds each (expert, strip) once per four tile-table entries
+ * (kq_gemm_grp_kernel; nothing is expanded into the scratch of GL3_FLAG_KQUANT_NATIVE_BATCH): every logit, id and K / V row is bit-equal
+ * to the plan without the flag.  Refused (GL3_E_UNSUPPORTED, the message names this flag) with tp_size > 1, GL3_FLAG_FORCE_RCCL,
+ * GL3_FLAG_F32_ACTIVATION or a weight_type other than GL3_TYPE_Q8_0.  On every other architecture the bit is GL3_FLAG_KQUANT_NATIVE_BATCH. */
+#define GL3_FLAG_KQUANT_NATIVE_MOE 0x200u
 
 /* Configuration (J/model/Configuration.java via LlamaModelLoader.java:47-63 / Qwen3ModelLoader.java:48-74)
  * plus the plan-selection knobs the reference reads from system properties

@@ -33,9 +33,10 @@ def ggml_type(name, mix="q4_k_m"):
 class KqModel:
     """Streams the tensors of the model in file order, generated from a seed; convert = as the default loader would upload them."""
 
-    def __init__(self, cfg, synth, lib, seed, convert, mix="q4_k_m"):
+    def __init__(self, cfg, synth, lib, seed, convert, mix="q4_k_m", types=None):
         self.cfg, self.wtype, self.rope = cfg, Q8_0, synth.model_rope(cfg)
-        self._synth, self._lib, self._seed, self._convert, self._mix = synth, lib, seed, convert, mix
+        self._synth, self._lib, self._seed, self._convert = synth, lib, seed, convert
+        self.types = types or (lambda name, cols: ggml_type(name, mix))      # types(name, cols) -> ggml type; Q8_0 where a row holds no super-block
 
     def tensor_items(self):
         rng = np.random.default_rng(self._seed)
@@ -43,7 +44,12 @@ class KqModel:
             if kind != "mat":
                 yield name, ((rng.standard_normal(rows * cols, dtype=np.float32) * np.float32(0.02) + np.float32(1)).view(np.uint8), ty, rows, cols)
                 continue
-            t, nb = ggml_type(name, self._mix), rows * cols // 256
+            t, nb = self.types(name, cols), rows * cols // 256
+            if t == Q8_0:                               # random int8 codes under small f16 scales, the same in both plans
+                b = rng.integers(0, 256, (rows * cols // 32, 34), dtype=np.uint8)
+                b[:, 0:2] = (np.abs(rng.standard_normal(len(b))) * 2e-4 + 2e-5).astype(np.float16).view(np.uint8).reshape(len(b), 2)
+                yield name, (b.reshape(-1), Q8_0, rows, cols)
+                continue
             b = rng.integers(0, 256, (nb, BLOCK_BYTES[t]), dtype=np.uint8)
             step = 0.5 if t == Q5_K else 1.0           # 32 levels over the range Q4_K covers with 16: the fifth bit buys resolution
             d = ((np.abs(rng.standard_normal(nb)) * 2e-3 + 2e-4) * step).astype(np.float16).view(np.uint8).reshape(nb, 2)
@@ -58,6 +64,55 @@ class KqModel:
                 assert self._lib.gl3_kquant_to_q8_0(t, raw.ctypes.data_as(C.c_void_p), rows * cols, q8.ctypes.data_as(C.c_void_p)) == 0
                 raw, t = q8, Q8_0
             yield name, (raw, t, rows, cols)
+
+
+def tg_compare(plans, toks, n_gen, reps):
+    """tg of the "converted" and the "native" plan alternated: 1 warm-up and `reps` timed repetitions each, the last logits of every repetition
+    compared; then 8 instrumented steps per plan.  -> ({plan: figures}, outputs equal, outputs finite)"""
+    def rep(plan):
+        t1 = time.perf_counter()
+        for i in range(n_gen):
+            logits = plan.forward_decode(toks[i], i, copy=False)
+        return time.perf_counter() - t1, logits.copy()
+
+    samples, equal, finite = {k: [] for k in plans}, True, True
+    for r in range(reps + 1):                          # repetition 0 is the warm-up
+        last = {}
+        for k, plan in plans.items():
+            s, last[k] = rep(plan)
+            if r:
+                samples[k].append(n_gen / s)
+        equal = equal and bool(np.array_equal(last["converted"], last["native"]))
+        finite = finite and bool(np.isfinite(last["converted"]).all())
+    out = {}
+    for k, plan in plans.items():
+        acc, n_prof = None, 8
+        for i in range(n_prof):
+            kt = plan.profile_decode(toks[64 + i], 64 + i)
+            if acc is None:
+                acc = kt
+            else:
+                for name in kt:
+                    for f in ("ms", "launches", "bytes"):
+                        acc[name][f] += kt[name][f]
+        s = samples[k] or [0.0]
+        out[k] = dict(tok_s=round(float(np.mean(s)), 2), samples_tok_s=[round(x, 2) for x in s], spread_tok_s=round(max(s) - min(s), 2),
+                      weight_bytes_in_hbm=plan.weight_bytes(),
+                      kernel_classes={n: dict(us_per_token=round(v["ms"] / n_prof * 1e3, 1), launches_per_token=v["launches"] // n_prof,
+                                              gbs=round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None)
+                                      for n, v in acc.items() if v["launches"]})
+    return out, equal, finite
+
+
+def moe_mix(name, cols):
+    """the K-quant mix of the Qwen2-MoE scripts: Q4_K everywhere, Q6_K for attn_v, ffn_down* and output, Q8_0 where K is no multiple of 256"""
+    return Q8_0 if cols % 256 else Q6_K if ("attn_v" in name or "ffn_down" in name or name == "output.weight") else Q4_K
+
+
+def moe_plans(cfg, synth, hip, plan_mod, **kw):
+    """the converted and the native plan (GL3_FLAG_KQUANT_NATIVE_MOE) of a Qwen2-MoE shape in that mix"""
+    return {"converted": plan_mod.HipMasterPlan(KqModel(cfg, synth, hip.lib(), 42, True, types=moe_mix), **kw),
+            "native": plan_mod.HipMasterPlan(KqModel(cfg, synth, hip.lib(), 42, False, types=moe_mix), flags=hip.FLAG_KQUANT_NATIVE_MOE, **kw)}
 
 
 def main():
@@ -79,45 +134,16 @@ def main():
              "native": plan_mod.HipMasterPlan(KqModel(cfg, synth, hip.lib(), 42, False, args.mix), flags=hip.FLAG_KQUANT_NATIVE)}
     setup_s = time.time() - t0
     toks = pkg.javarand.bench_tokens(cfg.vocab, args.n_gen)
-
-    def rep(plan):
-        t1 = time.perf_counter()
-        for i in range(args.n_gen):
-            logits = plan.forward_decode(toks[i], i, copy=False)
-        return time.perf_counter() - t1, logits.copy()
-
-    samples, equal, finite = {k: [] for k in plans}, True, True
-    for r in range(args.reps + 1):                     # repetition 0 is the warm-up
-        last = {}
-        for k, plan in plans.items():
-            s, last[k] = rep(plan)
-            if r:
-                samples[k].append(args.n_gen / s)
-        equal = equal and bool(np.array_equal(last["converted"], last["native"]))
-        finite = finite and bool(np.isfinite(last["converted"]).all())
+    measured, equal, finite = tg_compare(plans, toks, args.n_gen, args.reps)
     d, L = cfg.dim, cfg.n_layers
     mats = [(n, r, c) for n, r, c, ty, kind in synth.tensor_specs(cfg, Q8_0) if kind == "mat" and n != "token_embd.weight"]
     bpe = {t: b / 256 for t, b in BLOCK_BYTES.items()}
     other = d * 34 / 32 + (2 * L + 1) * d * 4 + 2 * L * cfg.kv_dim * 4 * ((args.n_gen - 1) / 2.0 + 2) + cfg.vocab * 4
     out = dict(metric="tg%d tokens/s" % args.n_gen, unit="tokens/s", n_gpus=1, data="synthetic", outputs_equal=equal, outputs_finite=finite, setup_s=round(setup_s, 1),
                config=dict(workload="Llama-3-8B shape, %s mix, %d layers, random weights" % (args.mix.upper(), L), reps=args.reps))
-    for k, plan in plans.items():
-        acc, n_prof = None, 8
-        for i in range(n_prof):
-            kt = plan.profile_decode(toks[64 + i], 64 + i)
-            if acc is None:
-                acc = kt
-            else:
-                for name in kt:
-                    for f in ("ms", "launches", "bytes"):
-                        acc[name][f] += kt[name][f]
+    for k in plans:
         weights = sum(r * c * (34 / 32 if k == "converted" else bpe[ggml_type(n, args.mix)]) for n, r, c in mats)
-        s = samples[k] or [0.0]
-        out[k] = dict(tok_s=round(float(np.mean(s)), 2), samples_tok_s=[round(x, 2) for x in s], spread_tok_s=round(max(s) - min(s), 2),
-                      algorithmic_bytes_per_token=int(weights + other), weight_bytes_in_hbm=plan.weight_bytes(),
-                      kernel_classes={n: dict(us_per_token=round(v["ms"] / n_prof * 1e3, 1), launches_per_token=v["launches"] // n_prof,
-                                              gbs=round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None)
-                                      for n, v in acc.items() if v["launches"]})
+        out[k] = dict(measured[k], algorithmic_bytes_per_token=int(weights + other))
     print(json.dumps(out))
 
 

@@ -5,6 +5,11 @@ device times of instrumented steps, and the algorithmic bytes one token streams:
 experts, the shared expert, norms, KV cache, the vocabulary projection.  Prints one JSON line.
 
     python scripts/moe_tg.py [--layers 24] [--steps 3]
+    python scripts/moe_tg.py --kquant-mix [--layers 24] [--steps 5]
+
+--kquant-mix: the same shape as a K-quant file (Q4_K; Q6_K for attn_v, ffn_down* and output; Q8_0 where K is no multiple of 256:
+ffn_down_exps), the plan converted to Q8_0 at load and the native plan (GL3_FLAG_KQUANT_NATIVE_MOE) alternated in one process as
+scripts/kquant_tg.py does: samples and spread, equal logits, gl3_get_weight_bytes and per-class times of both.
 """
 import argparse
 import json
@@ -21,6 +26,7 @@ def main():
     ap.add_argument("--layers", type=int, default=24)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--n-gen", type=int, default=128)
+    ap.add_argument("--kquant-mix", action="store_true")
     args = ap.parse_args()
     import torch
     import __graft_entry__ as ge
@@ -30,6 +36,16 @@ def main():
     plan_mod, hip = import_module(ge.PKG_NAME + ".plan"), import_module(ge.PKG_NAME + ".hip")
     cfg = synth.CONFIGS["qwen1.5-moe-a2.7b"]
     cfg = synth.ModelConfig(**{**cfg.__dict__, "ctx": args.n_gen + 8, "n_layers": args.layers})
+    if args.kquant_mix:
+        import kquant_tg
+        t0 = time.time()
+        plans = kquant_tg.moe_plans(cfg, synth, hip, plan_mod)
+        setup_s = time.time() - t0
+        measured, equal, finite = kquant_tg.tg_compare(plans, pkg.javarand.bench_tokens(cfg.vocab, args.n_gen), args.n_gen, args.steps)
+        print(json.dumps(dict(metric="tg%d tokens/s" % args.n_gen, unit="tokens/s", n_gpus=1, data="synthetic", outputs_equal=equal, outputs_finite=finite,
+                              config=dict(workload="Qwen1.5-MoE-A2.7B shape, K-quant mix, %d layers, 60 experts top-4, random weights" % cfg.n_layers,
+                                          reps=args.steps), setup_s=round(setup_s, 1), **measured)))
+        return
     t0 = time.time()
     mdl = synth.StreamModel(cfg, synth.GGML_Q8_0, synth.iter_torch(cfg, wtype=synth.GGML_Q8_0, seed=42, device="cuda"))
     plan = plan_mod.HipMasterPlan(mdl)

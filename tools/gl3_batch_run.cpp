@@ -92,7 +92,7 @@ int main(int argc, char** argv) {
         else if (a == "-n") n_new = atoi(val());
         else if (a == "--stop") { if (!parse_id_list(val(), stop)) return usage("--stop takes a comma-separated id list"); }
         else if (a == "--share-prefix") share_prefix = true;
-        else if (a == "--kquant-native") kq_native = true;      // Q4_K / Q6_K tensors stay native in HBM (GL3_FLAG_KQUANT_NATIVE_BATCH)
+        else if (a == "--kquant-native") kq_native = true;      // Q4_K / Q5_K / Q6_K tensors stay native in HBM (GL3_FLAG_KQUANT_NATIVE_BATCH; a Qwen2-MoE file: GL3_FLAG_KQUANT_NATIVE_MOE)
         else return usage(("unknown argument " + a).c_str());
     }
     if (path.empty() || prompts_path.empty()) return usage("-m model.gguf and --prompts file are required");
@@ -136,7 +136,7 @@ int main(int argc, char** argv) {
     opts.max_batch = batch;
     opts.tp_size = 1;
     opts.n_seqs = slots;
-    if (kq_native) opts.flags |= GL3_FLAG_KQUANT_NATIVE_BATCH;
+    if (kq_native) opts.flags |= d.arch == GL3_ARCH_QWEN2MOE ? GL3_FLAG_KQUANT_NATIVE_MOE : GL3_FLAG_KQUANT_NATIVE_BATCH;      // a Qwen2-MoE file: the expert stacks too
     CK(gl3_load_gguf(path.c_str(), &opts, &ctx));
 
     const std::set<int32_t> stop_set(stop.begin(), stop.end());

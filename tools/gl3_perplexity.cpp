@@ -76,7 +76,7 @@ int main(int argc, char** argv) {
         else if (a == "-c") n_ctx = atoi(val());
         else if (a == "-b") batch = atoi(val());
         else if (a == "-np") slots = atoi(val());
-        else if (a == "--kquant-native") kq_native = true;      // Q4_K / Q6_K tensors stay native in HBM (GL3_FLAG_KQUANT_NATIVE_BATCH)
+        else if (a == "--kquant-native") kq_native = true;      // Q4_K / Q5_K / Q6_K tensors stay native in HBM (GL3_FLAG_KQUANT_NATIVE_BATCH; a Qwen2-MoE file: GL3_FLAG_KQUANT_NATIVE_MOE)
         else return usage(("unknown argument " + a).c_str());
     }
     if (path.empty() || ids_path.empty()) return usage("-m model.gguf and --ids file are required");
@@ -110,7 +110,7 @@ int main(int argc, char** argv) {
     opts.max_batch = batch;
     opts.tp_size = 1;
     opts.n_seqs = slots;
-    if (kq_native) opts.flags |= GL3_FLAG_KQUANT_NATIVE_BATCH;
+    if (kq_native) opts.flags |= d.arch == GL3_ARCH_QWEN2MOE ? GL3_FLAG_KQUANT_NATIVE_MOE : GL3_FLAG_KQUANT_NATIVE_BATCH;      // a Qwen2-MoE file: the expert stacks too
     CK(gl3_load_gguf(path.c_str(), &opts, &ctx));
 
     const int first = n_ctx / 2, last = n_ctx - 2;      // scored positions of a window

@@ -1718,6 +1718,49 @@ int32_t gl3_forward_batch_verify_dist(gl3_ctx* ctx, const int32_t* tokens, const
     return forward_batch_verify(ctx, tokens, seq_ids, positions, n, temperature, coins, true, q_slots, results_out, n_runs_out);
 }
 
+// The draft-tree step (gl3_tree_run: the mixed step's GEMMs, the tree attention of gl3_tree_attn.h, every row an output row) + the greedy
+// walk (verify_tree_kernel) + the compaction of the accepted paths' K / V rows (kv_tree_compact_kernel) + ONE copy of 8 * n_trees + 4 * n bytes.
+// Every check comes before anything is staged or enqueued.
+int32_t gl3_forward_batch_verify_tree(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int32_t* parents, int32_t n,
+                                      gl3_verify_result* results_out, int32_t* path_out, int32_t* n_trees_out) {
+    if (!ctx) return GL3_E_ARG;
+    int32_t r = check_verify(ctx);
+    if (r != GL3_OK) return r;
+    if (!tokens || !seq_ids || !positions || !parents || n <= 0) GL3_FAIL(GL3_E_ARG, "bad batch arrays");
+    if (!results_out || !path_out || !n_trees_out) GL3_FAIL(GL3_E_ARG, "null results_out / path_out / n_trees_out");
+    if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
+    if (!ctx->pf) GL3_FAIL(GL3_E_UNSUPPORTED, "batched decode needs max_batch > 1 (and, for F16 / Q4_0 / f32-activation Q8_0, a Vector-API order: 256 bits, or 512 bits for F16 on one rank)");
+    if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
+    for (int i = 0; i < n; ++i)
+        if (tokens[i] < 0 || tokens[i] >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
+    TreePlan tp;
+    const char* why = tree_plan_build(tokens, seq_ids, positions, parents, n, ctx->n_seqs, ctx->d.ctx, tp);
+    if (why) GL3_FAIL(GL3_E_ARG, why);
+    if ((r = gl3_tree_run(ctx, tokens, seq_ids, positions, parents, n, tp)) != GL3_OK) return r;
+    const float* logits; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits, &greedy);
+    int32_t* tokens_dev; int32_t* positions_dev;
+    gl3_decode_batch_inputs(ctx, &tokens_dev, &positions_dev);
+    if ((r = gl3_verify_tree_enqueue(ctx, tokens_dev, greedy)) != GL3_OK) return r;
+    const gl3_tree_state& b = ctx->tree;
+    const int n_trees = b.ntrees;
+    KvTreeArgs a{};
+    a.kcache = ctx->kcache; a.vcache = ctx->vcache;
+    a.seq_stride4 = ctx->kv_seq_stride / 4; a.layer_stride4 = (size_t)ctx->d.ctx * ctx->kv_dim_l / 4;
+    a.row4 = ctx->kv_dim_l / 4; a.chunks = (a.row4 + KVT_THREADS - 1) / KVT_THREADS;
+    const size_t res_bytes = (size_t)n_trees * sizeof(gl3_verify_result), out_bytes = res_bytes + (size_t)n * sizeof(int32_t);
+    hipLaunchKernelGGL(kv_tree_compact_kernel, dim3((unsigned)(ctx->d.n_layers * a.chunks), (unsigned)n_trees), dim3(KVT_THREADS), 0, ctx->stream, a,
+                       tree_tab(b.tab, n, b.ntiles, n_trees).trees, reinterpret_cast<const int2*>(b.out), reinterpret_cast<const int32_t*>(b.out + res_bytes));
+    GL3_HIP(hipGetLastError());
+    GL3_HIP(hipMemcpyAsync(b.h_out, b.out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    GL3_HIP(hipStreamSynchronize(ctx->stream));
+    if ((r = gl3_tp_check(ctx)) != GL3_OK) return r;
+    memcpy(results_out, b.h_out, res_bytes);
+    memcpy(path_out, b.h_out + res_bytes, (size_t)n * sizeof(int32_t));
+    *n_trees_out = n_trees;
+    return GL3_OK;
+}
+
 static int32_t verify_rows(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs, const float* temperature,
                            const float* coins, bool dist, const int32_t* q_slots, gl3_verify_result* results_out) {
     if (!ctx) return GL3_E_ARG;

@@ -96,4 +96,57 @@ inline void batch_plan_split(const BatchPlan& bp, int fused_max_pos, BatchSplit&
                      [](const BatchSpan& a, const BatchSpan& b) { return a.pos0 + a.rows > b.pos0 + b.rows; });
 }
 
+// The plan of a draft-TREE verification step (gl3_forward_batch_verify_tree).  The n rows are a list of TREES, one per sequence id: a tree is
+// a maximal stretch of consecutive rows with the same sequence id; its first row (parent -1) is the sequence's last real token at position
+// p0, every other row names an earlier row of its tree as its parent (by step-row index) and sits at its parent's position + 1.  Row i of a
+// tree whose first row is row0 keeps its K / V row at SLOT p0 + (i - row0); mask bit s of a row = "the row at slot p0 + s is on my root
+// path, myself included".  Tiles are the attention kernel's unit of work {first row, rows <= BP_TILE_ROWS, sequence, slot of the first
+// row}: never across a tree, deepest last slot first.
+constexpr int TP_TREE_ROWS = 64;     // rows of a tree: one mask bit each
+struct TreePlan {
+    std::vector<BatchSpan> trees, tiles;      // trees: {first row, rows, sequence, p0}
+    std::vector<int32_t> slot, p0;            // by row
+    std::vector<uint64_t> mask;               // by row
+    int max_slot = 0;
+};
+// Returns nullptr and fills tp, or the reason the step is refused.  The caller has checked tokens against the vocabulary and n against the capacity.
+inline const char* tree_plan_build(const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int32_t* parents, int n, int n_seqs,
+                                   int ctx, TreePlan& tp) {
+    if (!tokens || !seq_ids || !positions || !parents || n <= 0) return "bad batch arrays";
+    tp = TreePlan{};
+    tp.slot.resize((size_t)n); tp.p0.resize((size_t)n); tp.mask.resize((size_t)n);
+    std::vector<char> seen((size_t)(n_seqs > 0 ? n_seqs : 0), 0);
+    for (int i = 0; i < n; ++i) {
+        if (seq_ids[i] < 0 || seq_ids[i] >= n_seqs) return "sequence id out of range";
+        if (positions[i] < 0 || positions[i] >= ctx) return "position outside the KV cache (context length)";
+        if (i == 0 || seq_ids[i] != seq_ids[i - 1]) {
+            if (seen[seq_ids[i]]) return "a sequence id belongs to at most one tree of a step";
+            seen[seq_ids[i]] = 1;
+            if (parents[i] != -1) return "the first row of a tree has no parent (-1)";
+            tp.trees.push_back({i, 1, seq_ids[i], positions[i]});
+            tp.mask[i] = 1;
+        } else {
+            BatchSpan& t = tp.trees.back();
+            const int par = parents[i];
+            if (par == -1) return "a row behind a tree's first needs a parent";
+            if (par < t.row0 || par >= i) return "a parent is an earlier row of the row's own tree";
+            if (positions[i] != positions[par] + 1) return "a row sits at its parent's position + 1";
+            if (++t.rows > TP_TREE_ROWS) return "a tree has at most 64 rows";
+            for (int j = t.row0 + 1; j < i; ++j)
+                if (parents[j] == par && tokens[j] == tokens[i]) return "siblings carry distinct tokens";
+            tp.mask[i] = tp.mask[par] | (1ull << (i - t.row0));
+        }
+        tp.p0[i] = tp.trees.back().pos0;
+        tp.slot[i] = tp.trees.back().pos0 + (i - tp.trees.back().row0);
+    }
+    for (const BatchSpan& t : tp.trees) {
+        if (t.pos0 + t.rows > ctx) return "a tree needs p0 + rows <= context length: its rows take the cache slots p0 .. p0 + rows - 1";
+        tp.max_slot = std::max(tp.max_slot, t.pos0 + t.rows - 1);
+        for (int o = 0; o < t.rows; o += BP_TILE_ROWS)
+            tp.tiles.push_back({t.row0 + o, std::min(BP_TILE_ROWS, t.rows - o), t.seq, t.pos0 + o});
+    }
+    std::stable_sort(tp.tiles.begin(), tp.tiles.end(), [](const BatchSpan& a, const BatchSpan& b) { return a.pos0 + a.rows > b.pos0 + b.rows; });
+    return nullptr;
+}
+
 }  // namespace gl3

@@ -194,6 +194,28 @@ struct gl3_verify_state {
     gl3_verify_result* h_out = nullptr;        // pinned
 };
 
+// Draft-tree verification (gl3_forward_batch_verify_tree).  tab = what a step stages, in one copy: its tiles and trees (int4 records of
+// gl3_batch_plan.h), then by row the masks, slots, p0 and parents (TreeTab below); out = what the decision writes and the compaction reads:
+// a gl3_verify_result per tree, then the n path entries.  Allocated by the first tree step for max_batch rows, freed with the verify buffers.
+struct gl3_tree_state {
+    int cap = 0;
+    uint8_t* tab = nullptr;
+    uint8_t* out = nullptr;
+    uint8_t* h_out = nullptr;                  // pinned
+    int n = 0, ntiles = 0, ntrees = 0;         // of the step in flight
+};
+constexpr size_t GL3_TREE_TAB_ROW_BYTES = 16 + 16 + 8 + 4 + 4 + 4;      // a step has at most n tiles and n trees
+struct TreeTab {
+    const int4* tiles; const int4* trees; const unsigned long long* mask; const int32_t* slot; const int32_t* p0; const int32_t* parents;
+};
+inline TreeTab tree_tab(const uint8_t* base, int n, int ntiles, int ntrees) {
+    TreeTab t;
+    t.tiles = reinterpret_cast<const int4*>(base); t.trees = t.tiles + ntiles;
+    t.mask = reinterpret_cast<const unsigned long long*>(t.trees + ntrees);
+    t.slot = reinterpret_cast<const int32_t*>(t.mask + n); t.p0 = t.slot + n; t.parents = t.p0 + n;
+    return t;
+}
+
 // Draft distributions of a TARGET plan (gl3_draft_probs_put, gl3_sample.hip): slot s = the f32[vocab] distribution one drafted token was
 // drawn from.  Allocated on the first put, freed with the sampler buffers.
 struct gl3_draft_state {
@@ -276,6 +298,7 @@ struct gl3_ctx {
     gl3_sample_state smp_rows{64, true};          // static-batched entries: grows with the batch, one hipGraph per (rows, any top-p row)
     gl3_score_state score;                        // gl3_forward_batch_score / gl3_score_rows
     gl3_verify_state verify;                      // gl3_forward_batch_verify / gl3_verify_rows and their _dist forms
+    gl3_tree_state tree;                          // gl3_forward_batch_verify_tree
     gl3_draft_state draft;                        // the draft distributions the _dist forms read
     gl3_chain_state chain;                        // gl3_forward_decode_chain
     gl3_batch_chain_state bchain;                 // gl3_forward_decode_batch_chain
@@ -379,7 +402,10 @@ int32_t gl3_verify_prepare(gl3_ctx* ctx, int32_t n, const int32_t* tokens, const
                            const int32_t* run_rows, const float* temperature, bool dist = false, const int32_t* q_slots = nullptr);
 int32_t gl3_verify_enqueue(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n_runs, bool dist = false);
 int32_t gl3_verify_collect(gl3_ctx* ctx, int32_t n_runs, gl3_verify_result* results_out);
-void gl3_verify_free(gl3_ctx* ctx);
+void gl3_verify_free(gl3_ctx* ctx);      // the tree buffers too
+void gl3_tree_free(gl3_ctx* ctx);
+// draft-tree decision: verify_tree_kernel over the step's greedy ids behind the step on the plan's stream -> ctx->tree.out
+int32_t gl3_verify_tree_enqueue(gl3_ctx* ctx, const int32_t* tokens_dev, const int32_t* greedy_dev);
 // draft distributions of a target plan (the argument checks are gl3_api.hip's): one slot from the draft plan's last sampled row, from
 // host memory, and back to the host
 int32_t gl3_draft_put(gl3_ctx* ctx, int32_t slot, gl3_ctx* draft);
@@ -425,6 +451,11 @@ namespace gl3 { struct BatchPlan; }      // gl3_batch_plan.h
 // one mixed step (gl3_forward_batch) whose plan the caller built and checked; outputs: the plan's out_rows, compact
 int32_t gl3_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, int32_t n, const gl3::BatchPlan& bp,
                       float* logits_out, int32_t* argmax_out, bool finish = true);
+namespace gl3 { struct TreePlan; }
+// one draft-tree step whose plan the caller built and checked: stages the plan (ctx->tree.tab), enqueues the layers, the logits of every row
+// and the greedy scan; nothing is waited for
+int32_t gl3_tree_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int32_t* parents, int32_t n,
+                     const gl3::TreePlan& tp);
 int32_t gl3_prefill_tap_x(gl3_ctx* ctx, int row, int n);
 int32_t gl3_prefill_attn_rows(gl3_ctx* ctx, int32_t out[4]);      // gl3_get_attn_rows
 void gl3_decode_batch_outputs(gl3_ctx* ctx, const float** logits, const int32_t** greedy);

@@ -102,4 +102,37 @@ static __global__ __launch_bounds__(KVC_THREADS) void kv_seq_copy_kernel(KvCopyA
     }
 }
 
+// kv_tree_compact_kernel — behind a draft-tree step (gl3_forward_batch_verify_tree): the accepted path's K / V rows, every layer, from the slots
+// the step wrote them at to the positions they belong at.  Tree k (first row row0, sequence seq, root at position p0) has its rows at slots
+// p0 + (row - row0); the decision left accepted = res[k].accepted and the path's step rows in path[row0 .. row0 + accepted].  Path entry j
+// belongs at position p0 + j and sits at slot p0 + (path[row0 + j] - row0) >= p0 + j (a child comes behind its parent, so the j-th node of a
+// path is at least the j-th row).  A thread owns one float4 column of K and of V for ALL path rows of its tree and moves them in ascending j:
+// every source slot is >= its destination and every earlier destination lies strictly below it, so the move is in place, needs no staging
+// and no thread touches another's columns.  Rows already in place (the root; a path along the first children) are not touched.
+// One launch: grid = (layers x column chunks of KVT_THREADS float4, trees).
+constexpr int KVT_THREADS = 256;
+struct KvTreeArgs {
+    float* kcache;
+    float* vcache;
+    size_t seq_stride4, layer_stride4;      // float4 per sequence / per layer
+    int row4;                                // float4 per K / V row (kv_dim_l / 4)
+    int chunks;                              // column chunks per row
+};
+static __global__ __launch_bounds__(KVT_THREADS) void kv_tree_compact_kernel(KvTreeArgs a, const int4* __restrict__ trees, const int2* __restrict__ res,
+                                                                             const int32_t* __restrict__ path) {
+    const int4 tr = trees[blockIdx.y];      // {first row, rows, sequence, p0}
+    const int accepted = res[blockIdx.y].x;
+    const int layer = blockIdx.x / a.chunks, col = (blockIdx.x % a.chunks) * KVT_THREADS + threadIdx.x;
+    if (col >= a.row4) return;
+    const size_t base = (size_t)tr.z * a.seq_stride4 + (size_t)layer * a.layer_stride4 + col;
+    kvc_v4f* k = reinterpret_cast<kvc_v4f*>(a.kcache) + base;
+    kvc_v4f* v = reinterpret_cast<kvc_v4f*>(a.vcache) + base;
+    for (int j = 1; j <= accepted; ++j) {
+        const int src = tr.w + (path[tr.x + j] - tr.x), dst = tr.w + j;
+        if (src == dst) continue;
+        k[(size_t)dst * a.row4] = k[(size_t)src * a.row4];
+        v[(size_t)dst * a.row4] = v[(size_t)src * a.row4];
+    }
+}
+
 }      // namespace gl3

@@ -13,6 +13,7 @@
 //   acc = acc + float(isum) * (wScale * aScale) on the VALU, blocks ascending — the reference's f32 order.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "gl3_ctx.h"
@@ -62,6 +63,7 @@ struct gl3_prefill_state {
     int4* tiles = nullptr;              // [M] BatchSpan records, deepest tile first (gl3_batch_plan.h); PfStep::ntab of them belong to the step
     int4* deep = nullptr;               // [M] the deep records of the step (batch_plan_split), deepest first; PfStep::ndeep of them
     int32_t* deep_rows = nullptr;       // [M] the step rows of the deep records, ascending; PfStep::deep_rows of them
+    int tree_max_slot = -1;             // last slot a tree may have on pf_attn_tree_kernel (pf_tree_max_slot); -1: the shape has no such kernel
     int tab_max_pos = 0;                // last position a tile may have in the one-launch table form (pf_tab_max_pos; INT_MAX: steps are not split)
     int32_t attn_rows[4] = {0, 0, 0, 0};      // rows of the last batched step by attention form (gl3_get_attn_rows), from the last layer's pf_attention
     bool attn_rows_set = false;
@@ -194,6 +196,7 @@ __global__ __launch_bounds__(256) void pf_norm_quant_kernel(const float* __restr
 }
 
 #include "gl3_prefill_attn.h"
+#include "gl3_tree_attn.h"
 
 // Greedy id per sequence: first index of the maximum of each logits row (FloatTensor.argmax :138-151).
 // logits: rank-chunked [tp][rows][n / tp] (cc = n / tp, a multiple of 4; tp = 1: plain rows).
@@ -244,6 +247,7 @@ __global__ __launch_bounds__(64) void pf_argmax_fold_kernel(const float* __restr
 static size_t nq_smem(int k) { return (size_t)(k + 32) * 4 + ss_scratch_bytes(k) + 64; }
 size_t gl3_prefill_norm_smem(int k) { return nq_smem(k); }
 static int pf_tab_max_pos(const gl3_ctx* ctx);      // next to pf_attention, whose conditions it shares
+static int32_t pf_tree_attributes(gl3_ctx* ctx);    // next to pf_attention_tree
 int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     const gl3_model_desc& d = ctx->d;
     gl3_prefill_state* p = new gl3_prefill_state();
@@ -282,6 +286,7 @@ int32_t gl3_prefill_alloc(gl3_ctx* ctx) {
     GL3_HIP(hipFuncSetAttribute((const void*)pf_norm_quant_kernel<PQ_NORM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
     GL3_HIP(hipFuncSetAttribute((const void*)pf_norm_quant_kernel<PQ_NORM_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
     p->tab_max_pos = pf_tab_max_pos(ctx);
+    { const int32_t tr = pf_tree_attributes(ctx); if (tr != GL3_OK) return tr; }
     if (p->vl) {       // f32-activation weight types: the GEMMs read f32 rows, no int8 operands
         // XN: normalised / un-chunked f32 operand of the next GEMM (K up to max(dim, q_dim, hidden)); HB2: this rank's up projection
         const size_t kmax = (size_t)(d.hidden > ctx->q_dim ? (d.hidden > d.dim ? d.hidden : d.dim) : (ctx->q_dim > d.dim ? ctx->q_dim : d.dim));
@@ -405,6 +410,7 @@ struct PfStep {
     int ndeep;          // records of the deep table in p->deep: rows past the one-launch table form's depth, on the long-context trio
     int deep_rows;      // step rows of the deep records (p->deep_rows)
     int tab_max_pos;    // last position of the deepest shallow tile (ndeep > 0 only: sizes the one-launch kernels' score rows)
+    int ntree = 0;      // a draft-tree step (gl3_tree_run): tiles of ctx->tree.tab; max_pos is then the step's last SLOT
     bool runs() const { return ntab + ndeep > 0; }      // a mixed step with a run of several rows
 };
 
@@ -415,7 +421,7 @@ struct PfStep {
 // later row of the same run would race with that write.
 static bool pf_fused_decode(const gl3_ctx* ctx, const PfStep& st) {
     static const bool bd_attn_off = env_flag("GL3_NO_FUSED_BD_ATTN", false);      // A/B switch: =1 the three-kernel attention of static-batched decode
-    return ctx->fused_attn_ok && st.max_pos < AF_MAXN && !bd_attn_off && !st.runs();
+    return ctx->fused_attn_ok && st.max_pos < AF_MAXN && !bd_attn_off && !st.runs() && !st.ntree;
 }
 
 
@@ -619,6 +625,61 @@ static int pf_tab_max_pos(const gl3_ctx* ctx) {
     return fm;
 }
 
+// Draft-tree steps (gl3_tree_attn.h).  pf_attn_tree_kernel<HS, kvMul> exists for the head sizes of the one-launch kernels and kvMul <= 4 (no
+// head groups); a step whose deepest slot leaves its score rows inside PF_ATTN_LDS_MAX takes it, every other step the masked per-row pair.
+// The limit is the plan's (read at gl3_create, so a test can lower it per plan): GL3_PF_TAB_MAXPOS=<p> lowers it to min(own, p) as it lowers
+// the run table's, GL3_PF_FUSED_ATTN=0 turns the one-launch kernel off.
+template <class F>
+static inline void pf_tree_dispatch(int hs, int kvmul, F&& f) {
+    pf_head_dispatch<32>(hs, [&](auto hc) {
+        constexpr int HS_ = decltype(hc)::value;
+        if (kvmul == 1) f(pf_attn_tree_kernel<HS_, 1>); else if (kvmul == 2) f(pf_attn_tree_kernel<HS_, 2>);
+        else if (kvmul == 3) f(pf_attn_tree_kernel<HS_, 3>); else f(pf_attn_tree_kernel<HS_, 4>); });
+}
+static int pf_tree_max_slot(const gl3_ctx* ctx) {
+    const char* env = getenv("GL3_PF_TAB_MAXPOS");
+    const int hs = ctx->d.head_size, kvmul = ctx->d.n_heads / ctx->d.n_kv_heads;
+    if (pf_sw_fused_off() || kvmul > 4 || !(hs == 32 || hs == 64 || hs == 128)) return -1;
+    int fm = -1;
+    for (int k = 1; 64 * (k - 1) < ctx->d.ctx && ta_smem_bytes(hs, kvmul, pf_fa_sstride(64 * k - 1)) <= PF_ATTN_LDS_MAX; ++k) fm = 64 * k - 1;
+    if (env && *env) fm = std::min(fm, atoi(env));
+    return fm;
+}
+static int32_t pf_tree_attributes(gl3_ctx* ctx) {
+    gl3_prefill_state* p = ctx->pf;
+    p->tree_max_slot = pf_tree_max_slot(ctx);
+    GL3_HIP(hipFuncSetAttribute((const void*)pf_attn_softmax_pv_tree_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    hipError_t e = hipSuccess;
+    if (p->tree_max_slot >= 0)
+        pf_tree_dispatch(ctx->d.head_size, ctx->d.n_heads / ctx->d.n_kv_heads, [&](auto kern) {
+            e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_ATTN_LDS_MAX); });
+    GL3_HIP(e);
+    return GL3_OK;
+}
+// The attention of a tree step behind its RoPE + KV launch; aa as pf_attention filled it.  Returns true when the one-launch kernel served the step.
+static bool pf_attention_tree(gl3_ctx* ctx, const PfStep& st, PfAttnArgs aa) {
+    gl3_prefill_state* p = ctx->pf;
+    const gl3_model_desc& d = ctx->d;
+    hipStream_t s = ctx->stream;
+    const int n = st.n, hs = d.head_size, kvmul = d.n_heads / d.n_kv_heads, H = ctx->heads_l, KVH = ctx->kv_heads_l;
+    const TreeTab tt = tree_tab(ctx->tree.tab, n, ctx->tree.ntiles, ctx->tree.ntrees);
+    if (st.max_pos <= p->tree_max_slot) {
+        const int sstride = pf_fa_sstride(st.max_pos);
+        pf_tree_dispatch(hs, kvmul, [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(KVH * st.ntree), dim3(256), ta_smem_bytes(hs, kvmul, sstride), s, aa.Q, aa.q_stride, aa.kcache, aa.vcache, aa.out,
+                               aa.out_stride, KVH, aa.kv_dim, aa.att_mul, sstride, tt.tiles, tt.p0, tt.mask, ctx->kv_seq_stride); });
+        return true;
+    }
+    // pf_attn_scores_kernel as it is over [0, slot] (a masked score is computed and ignored), then the masked softmax + weighted V sum
+    aa.pos = tt.slot;
+    const int nsplit = (st.max_pos + 1 + ATT_TT - 1) / ATT_TT;
+    const size_t sm1 = ((size_t)kvmul * hs + (size_t)ATT_TT * (hs + 1)) * 4;
+    hipLaunchKernelGGL(pf_attn_scores_kernel, dim3(nsplit, KVH, n), dim3(64 * kvmul), sm1, s, aa);
+    aa.win = ctx->attn_win;
+    hipLaunchKernelGGL(pf_attn_softmax_pv_tree_kernel, dim3(H * ((hs + 63) / 64), n), dim3(64), (size_t)ctx->attn_win * 4 + 16, s, aa, tt.p0, tt.mask);
+    return false;
+}
+
 // RoPE + KV write + attention of layer l for the n tokens whose raw q | k | v rows are in p->QKV -> AOr (this rank's chunk of the
 // attention output).  fuse_q: static-batched decode on one rank writes the output as the wo projection's int8 operand instead.
 // returns true when the attention output was written as the wo projection's int8 operand (no quantise launch needed)
@@ -680,7 +741,13 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
         note_rows(n, 0, 0, 0);
         return fuse_q;
     }
+    if (st.ntree) ra.slot = tree_tab(ctx->tree.tab, n, ctx->tree.ntiles, ctx->tree.ntrees).slot;      // roped with the position, written at the slot
     hipLaunchKernelGGL(pf_rope_kv_kernel, dim3(H + KVH, n), dim3(64), 0, s, ra);
+    if (st.ntree) {
+        const bool one = pf_attention_tree(ctx, st, aa);
+        note_rows(0, one ? n : 0, 0, one ? 0 : n);
+        return false;
+    }
     const bool rows_softmax = pf_rows_softmax(ctx);
     const bool tiled = (one_seq >= 0 || runs) && pf_tiled_shape(hs, kvmul, rows_softmax);
     const int group = pf_group_size(kvmul), NG = pf_head_groups(kvmul);      // head slots of a tiled workgroup, head groups per kv head (kvMul <= 4: kvMul, 1)
@@ -1298,6 +1365,41 @@ int32_t gl3_batch_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_id
     return gl3_tp_check(ctx);
 }
 
+// Draft-tree step (gl3_forward_batch_verify_tree): the mixed step with every row an output row, its attention in the tree form.  The
+// plan's tables go up in one copy before anything is enqueued; the decision and the compaction follow on the stream (gl3_api.hip).
+int32_t gl3_tree_run(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int32_t* parents, int32_t n,
+                     const TreePlan& tp) {
+    gl3_prefill_state* p = ctx->pf;
+    gl3_tree_state* b = &ctx->tree;
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    int32_t r = pf_grow_logits(ctx, n);
+    if (r != GL3_OK) return r;
+    if (!b->cap) {      // once, for the largest step the plan takes; all or none
+        const size_t cap = (size_t)p->max_batch;
+        hipError_t e = hipMalloc((void**)&b->tab, cap * GL3_TREE_TAB_ROW_BYTES);
+        if (e == hipSuccess) e = hipMalloc((void**)&b->out, cap * 12);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_out, cap * 12);
+        if (e != hipSuccess) { gl3_tree_free(ctx); GL3_HIP(e); }
+        b->cap = (int)cap;
+    }
+    const int ntiles = (int)tp.tiles.size(), ntrees = (int)tp.trees.size();
+    std::vector<uint8_t> host((size_t)(ntiles + ntrees) * 16 + (size_t)n * 20);
+    uint8_t* w = host.data();
+    auto put = [&w](const void* src, size_t bytes) { memcpy(w, src, bytes); w += bytes; };
+    put(tp.tiles.data(), (size_t)ntiles * 16); put(tp.trees.data(), (size_t)ntrees * 16); put(tp.mask.data(), (size_t)n * 8);
+    put(tp.slot.data(), (size_t)n * 4); put(tp.p0.data(), (size_t)n * 4); put(parents, (size_t)n * 4);
+    hipStream_t s = ctx->stream;
+    if ((r = pf_stage_tokens(ctx, tokens, seq_ids, positions, n)) != GL3_OK) return r;
+    GL3_HIP(hipMemcpyAsync(b->tab, host.data(), host.size(), hipMemcpyHostToDevice, s));      // pageable source: staged before the call returns
+    b->n = n; b->ntiles = ntiles; b->ntrees = ntrees;
+    PfStep st{n, tp.max_slot, -1, 0, 0, 0, 0};
+    st.ntree = ntiles;
+    if ((r = pf_layers(ctx, st)) != GL3_OK) return r;
+    hipLaunchKernelGGL(pf_unchunk_row_kernel, dim3(4), dim3(256), 0, s, p->X, n - 1, ctx->d.dim, ctx->dim_l, n, ctx->x);      // gl3_get_x: the last row, as after every mixed step
+    if ((r = pf_logits_tail(ctx, p->X, ctx->dim_l, n)) != GL3_OK) return r;
+    GL3_HIP(hipGetLastError());
+    return GL3_OK;
+}
 
 // Average device time of one batched-prefill GEMM class at n tokens: one HIP event pair around `iters` sweeps over every
 // layer's weights (GEMMs are 70-250 us, the ~1.5 us boundary is noise).  int8_ops = 2 * rows * K * n per launch (MFMA work

@@ -28,6 +28,7 @@ struct RopeArgs {
     const float* qnorm; const float* knorm; const float* bq; const float* bk; const float* bv;   // bias: qwen2 (else NULL)
     int n_heads, n_kv_heads, hs, q_dim, kv_dim, arch; float eps;
     const int32_t* seq; const int32_t* pos; size_t seq_stride;   // per-token sequence id / position; floats between sequences' caches
+    const int32_t* slot;                                         // cache row of every token's K / V; NULL: its position (a tree step: gl3_tree_attn.h)
 };
 
 __global__ __launch_bounds__(64) void pf_rope_kv_kernel(const RopeArgs a) {
@@ -51,9 +52,10 @@ __global__ __launch_bounds__(64) void pf_rope_kv_kernel(const RopeArgs a) {
         for (int i = t; i < hs; i += 64) src[i] = v[i];
     } else {
         const float* vsrc = a.QKV + (size_t)b * a.qkv_stride + a.q_dim + a.kv_dim + hk * hs;
+        const int row = a.slot ? a.slot[b] : pos;
         for (int i = t; i < hs; i += 64) {
-            a.kcache[soff + (size_t)pos * a.kv_dim + hk * hs + i] = v[i];
-            a.vcache[soff + (size_t)pos * a.kv_dim + hk * hs + i] = a.bv ? vsrc[i] + a.bv[hk * hs + i] : vsrc[i];
+            a.kcache[soff + (size_t)row * a.kv_dim + hk * hs + i] = v[i];
+            a.vcache[soff + (size_t)row * a.kv_dim + hk * hs + i] = a.bv ? vsrc[i] + a.bv[hk * hs + i] : vsrc[i];
         }
     }
 }

@@ -1061,6 +1061,14 @@ void gl3_verify_free(gl3_ctx* ctx) {
     if (b->h_params) hipHostFree(b->h_params);
     if (b->h_out) hipHostFree(b->h_out);
     *b = gl3_verify_state{};
+    gl3_tree_free(ctx);
+}
+void gl3_tree_free(gl3_ctx* ctx) {
+    gl3_tree_state* t = &ctx->tree;
+    if (t->tab) hipFree(t->tab);
+    if (t->out) hipFree(t->out);
+    if (t->h_out) hipHostFree(t->h_out);
+    *t = gl3_tree_state{};
 }
 
 // ---- draft distributions of a target plan: q[max_batch][vocab], the table and its event on the first put, all or none
@@ -1325,6 +1333,40 @@ int32_t gl3_verify_enqueue(gl3_ctx* ctx, const float* logits_dev, const int32_t*
     else hipLaunchKernelGGL(verify_runs_kernel<false>, dim3(n_runs), dim3(256), verify_smem(nchunks, false), s, logits_dev, v, runs, rows, greedy_dev, b->out, (const float*)nullptr);
     GL3_HIP(hipGetLastError());
     GL3_HIP(hipMemcpyAsync(b->h_out, b->out, (size_t)n_runs * sizeof(gl3_verify_result), hipMemcpyDeviceToHost, s));
+    return GL3_OK;
+}
+
+// gl3_forward_batch_verify_tree: the greedy walk of every tree of the step.  One launch whatever n and the number of trees: thread = tree
+// (a tree has at most 64 rows, a walk at most 64 * 64 compares).  From the root, at node a with the step's greedy id g = greedy[a] (the
+// first-max scan of the step), descend to the child of a whose token is g (siblings carry distinct tokens: at most one), else stop.
+// out = gl3_verify_result[n_trees] {depth reached, g of the last node}, then path[n]: for a tree with first row row0, path[row0 .. row0 +
+// accepted] = the step rows of the accepted nodes, root first, -1 behind them.  kv_tree_compact_kernel and the copy to the host read it there.
+__global__ __launch_bounds__(64) void verify_tree_kernel(const int4* __restrict__ trees, int n_trees, const int32_t* __restrict__ tokens,
+                                                         const int32_t* __restrict__ parents, const int32_t* __restrict__ greedy,
+                                                         gl3_verify_result* __restrict__ out, int32_t* __restrict__ path) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= n_trees) return;
+    const int row0 = trees[k].x, rows = trees[k].y;
+    int a = row0, depth = 0;
+    path[row0] = row0;
+    for (;;) {
+        const int g = greedy[a];
+        int child = -1;
+        for (int i = a + 1; i < row0 + rows; ++i)      // children come behind their parent
+            if (parents[i] == a && tokens[i] == g) { child = i; break; }
+        if (child < 0) { out[k] = gl3_verify_result{depth, g}; break; }
+        a = child;
+        path[row0 + ++depth] = a;
+    }
+    for (int j = depth + 1; j < rows; ++j) path[row0 + j] = -1;
+}
+
+int32_t gl3_verify_tree_enqueue(gl3_ctx* ctx, const int32_t* tokens_dev, const int32_t* greedy_dev) {
+    gl3_tree_state* b = &ctx->tree;
+    const TreeTab tt = tree_tab(b->tab, b->n, b->ntiles, b->ntrees);
+    hipLaunchKernelGGL(verify_tree_kernel, dim3((b->ntrees + 63) / 64), dim3(64), 0, ctx->stream, tt.trees, b->ntrees, tokens_dev, tt.parents, greedy_dev,
+                       reinterpret_cast<gl3_verify_result*>(b->out), reinterpret_cast<int32_t*>(b->out + (size_t)b->ntrees * sizeof(gl3_verify_result)));
+    GL3_HIP(hipGetLastError());
     return GL3_OK;
 }
 

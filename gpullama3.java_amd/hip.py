@@ -102,6 +102,8 @@ _SIGS = {  # symbol -> (restype, argtypes): exactly the declarations of include/
     "gl3_get_draft_probs": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
     "gl3_forward_batch_verify_dist": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.POINTER(C.c_int32)]),
+    "gl3_forward_batch_verify_tree": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(C.c_int32)]),
     "gl3_verify_rows_dist": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "gl3_debug_batch_plan": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,

@@ -333,6 +333,18 @@ class HipMasterPlan:
                                                      _p(co) if co is not None else None, _p(res), C.byref(got)), self._ctx)
         return res[:got.value].copy()
 
+    def forward_batch_verify_tree(self, tokens, seq_ids, positions, parents):
+        """One step over draft TREES, one per sequence id (gl3_forward_batch_verify_tree): parents[i] = -1 for a tree's first row (the
+        sequence's last real token), else the step row of the row's parent -> (results [n_trees] with fields accepted and token,
+        path int32[n]: per tree the step rows of the accepted nodes, root first, then -1)."""
+        t, s, p, par = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (tokens, seq_ids, positions, parents))
+        assert t.size == s.size == p.size == par.size
+        res = np.zeros(max(t.size, 1), VERIFY_DTYPE)
+        path = np.full(max(t.size, 1), -1, np.int32)
+        got = C.c_int32(0)
+        hip.check(hip.lib().gl3_forward_batch_verify_tree(self._ctx, _p(t), _p(s), _p(p), _p(par), t.size, _p(res), _p(path), C.byref(got)), self._ctx)
+        return res[:got.value].copy(), path[:t.size].copy()
+
     def verify_rows(self, logits, tokens, run_rows, temperature=None, coins=None) -> np.ndarray:
         """The verification kernel alone on host logits [n][vocab] (no forward pass); run_rows: the rows of every run, summing to n ->
         structured array [n_runs] with fields accepted and token."""

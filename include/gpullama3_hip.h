@@ -454,6 +454,30 @@ GL3_API int32_t gl3_forward_batch_verify_dist(gl3_ctx* ctx, const int32_t* token
 /* Parity tap: the same decision on caller-supplied logits (host f32[n][vocab]), as gl3_verify_rows; q_slots: int32[n]. */
 GL3_API int32_t gl3_verify_rows_dist(gl3_ctx* ctx, const float* logits, const int32_t* tokens, const int32_t* run_rows, int32_t n_runs,
                                      const float* temperature, const float* coins, const int32_t* q_slots, gl3_verify_result* results_out);
+/* Draft TREES: one step verifies, per sequence, a tree of drafted continuations instead of one run (greedy only).
+ * Rows: the n rows are a list of trees, one per sequence id; a tree is a maximal stretch of consecutive rows with the same seq_ids[i], at most
+ * 64 rows.  parents[i] == -1 marks a tree's first row, the sequence's last real token, at position p0 = positions[i]; every other row names an
+ * earlier row of its own tree as its parent by step-row index (parents[i] < i) and has positions[i] == positions[parents[i]] + 1.  Siblings
+ * carry distinct tokens.  Row i predicts the token after its own.  A chain (parents[i] == i - 1) is exactly a run of gl3_forward_batch_verify.
+ * Arithmetic: a row attends to the prefix [0, p0) and to its ancestors and itself, in root-path order, with the per-element arithmetic and
+ * order of every other step: its hidden state, logits and greedy id are bit for bit those of the linear run along its root path.
+ * Decision (on the device, one launch): from the root, at node a with greedy id g (the step's own first-max scan) descend to the child whose
+ * token is g, if there is one, else stop.  results_out[r] = {accepted = depth reached, token = g of the last node}, one per tree in row
+ * order, *n_trees_out of them; path_out: int32[n], for tree r with first row row0 path_out[row0 .. row0 + accepted] = the step-row indices of
+ * the accepted nodes, root first, the tree's remaining entries -1.  8 * n_trees + 4 * n bytes come back in one copy; no logits leave the device.
+ * K / V: during the step row i of a tree with first row row0 keeps its K / V row in the cache at SLOT p0 + (i - row0), roped with its true
+ * position; so a tree needs p0 + rows <= ctx.  After the decision one launch moves the accepted path's rows, every layer, to positions
+ * p0 .. p0 + accepted.  The caller continues with `token` at p0 + accepted + 1; rows above that are dead and are overwritten before anything
+ * reads them, as with gl3_forward_batch_verify.  Nothing is rolled back on the host.
+ * gl3_get_attn_rows afterwards: out[1] = n (pf_attn_tree_kernel, one launch per layer: head size 32 / 64 / 128, kvMul <= 4, score rows in
+ * LDS) or out[3] = n (the per-row pair with the masked softmax, every other shape and depth).
+ * GL3_E_ARG, before anything is staged or enqueued: what gl3_forward_batch refuses about (tokens, seq_ids, n); a null array; a first row with
+ * a parent or a later row without one; a parent outside the row's own tree or not earlier than the row; a position that is not its
+ * parent's + 1; duplicate sibling tokens; a tree of more than 64 rows; p0 + rows > ctx.  GL3_E_UNSUPPORTED: max_batch <= 1; tp_size > 1
+ * (one-rank, as gl3_forward_batch_verify).  Every plan gl3_forward_batch_verify accepts is accepted. */
+GL3_API int32_t gl3_forward_batch_verify_tree(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
+                                              const int32_t* parents, int32_t n, gl3_verify_result* results_out, int32_t* path_out,
+                                              int32_t* n_trees_out);
 /* Draft chain: k single-token steps of ONE plan behind one host wait, the id each step draws fed to the next step on the device.  What a
  * draft model is called for, and plain "generate k ids without a round trip per id".
  * Equivalence: the call computes, bit for bit, what k consecutive calls gl3_forward_decode_sample(ctx, t_j, position + j, temperature, 0.f,

@@ -3,7 +3,7 @@
 // weights and decides on the device how many drafts stand (8 bytes come back).  Greedy verification emits exactly the ids that decoding one
 // token per step emits, so the output is that of a plain greedy loop over the same (token, position) sequence.
 //
-//   gl3_spec_run -m model.gguf --ids 1,2,3 -n NEW [--draft K] [--ngram G] [-b BATCH] [--stop id,id]
+//   gl3_spec_run -m model.gguf --ids 1,2,3 -n NEW [--draft K] [--ngram G] [--branches B] [-b BATCH] [--stop id,id]
 //
 // Positions: prompt id k at position k, generated ids behind them, no begin-of-text of the tool's own.  All but the last prompt id are
 // prefilled with gl3_forward_batch (no output rows) in runs of up to -b rows (default 16).  A step is the run [last real token, drafts]:
@@ -12,6 +12,9 @@
 //              run passes the context, -b rows or -n: a step with k drafts emits at most k + 1 ids.
 //   result     {a, token}: the first a drafts and `token` are appended; the next run starts a + 1 positions on and overwrites the K / V
 //              rows of the rejected drafts before anything reads them.
+// --branches B (default 1: everything above, unchanged): for the longest g with a match, the continuations behind the B most recent earlier
+//              occurrences are merged into a trie under the last real token, most recent first, capped at K nodes; the step is ONE
+//              gl3_forward_batch_verify_tree call over the trie's rows (parents by row), and the accepted path's ids and `token` are appended.
 // --draft 0 is plain decoding through the same entry.  A stop id ends generation AT the stop id (it is printed), also when drafts behind
 // it were accepted.  stdout: "generated: id id ...".  stderr: the line "steps=… drafted=… accepted=… tokens=…", then a line "timing: …" with
 // the loop's host-clock times (prefill_ms, decode_ms, tok_s, step_us=rows:mean microseconds of a step by run length).
@@ -53,6 +56,34 @@ static std::vector<int32_t> draft(const std::vector<int32_t>& h, int ngram, int 
     return {};
 }
 
+// --branches: the trie of the continuations behind the `branches` most recent earlier occurrences of the longest matching suffix, at most k
+// nodes.  toks / parents / depth by row, row 0 = the last real token; a node is appended behind its parent, so parents[i] < i
+static void draft_tree(const std::vector<int32_t>& h, int ngram, int k, int branches, std::vector<int32_t>& toks, std::vector<int32_t>& parents,
+                       std::vector<int32_t>& depth) {
+    const int n = (int)h.size();
+    toks.assign(1, h.back()); parents.assign(1, -1); depth.assign(1, 0);
+    for (int g = ngram < n - 1 ? ngram : n - 1; g >= 1 && toks.size() == 1 && k > 0; --g) {
+        int found = 0;
+        for (int s = n - g - 1; s >= 0 && found < branches; --s) {
+            bool same = true;
+            for (int i = 0; i < g && same; ++i) same = h[s + i] == h[n - g + i];
+            if (!same) continue;
+            ++found;
+            int at = 0;
+            for (int j = s + g; j < n && j < s + g + k; ++j) {
+                int child = -1;
+                for (int c = at + 1; c < (int)toks.size() && child < 0; ++c) if (parents[c] == at && toks[c] == h[j]) child = c;
+                if (child < 0) {
+                    if ((int)toks.size() > k) break;      // the cap: K nodes behind the root
+                    child = (int)toks.size();
+                    toks.push_back(h[j]); parents.push_back(at); depth.push_back(depth[at] + 1);
+                }
+                at = child;
+            }
+        }
+    }
+}
+
 #define CK(call)                                                                                        \
     do {                                                                                                \
         const int32_t r_ = (call);                                                                      \
@@ -62,7 +93,7 @@ static std::vector<int32_t> draft(const std::vector<int32_t>& h, int ngram, int 
 int main(int argc, char** argv) {
     std::string path;
     std::vector<int32_t> prompt, stop;
-    int n_new = 0, K = 4, G = 3, batch = 16;
+    int n_new = 0, K = 4, G = 3, batch = 16, B = 1;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto val = [&]() { return i + 1 < argc ? argv[++i] : (char*)""; };
@@ -71,12 +102,14 @@ int main(int argc, char** argv) {
         else if (a == "-n") n_new = atoi(val());
         else if (a == "--draft") K = atoi(val());
         else if (a == "--ngram") G = atoi(val());
+        else if (a == "--branches") B = atoi(val());
         else if (a == "-b") batch = atoi(val());
         else if (a == "--stop") stop = parse_ids(val());
         else { fprintf(stderr, "gl3_spec_run: unknown argument %s (see the header of tools/gl3_spec_run.cpp)\n", a.c_str()); return 2; }
     }
     if (path.empty() || prompt.empty() || n_new <= 0) { fprintf(stderr, "gl3_spec_run: -m model.gguf, --ids a,b,c and -n NEW (> 0) are required\n"); return 2; }
     if (K < 0 || G < 1 || batch < 2) { fprintf(stderr, "gl3_spec_run: --draft >= 0, --ngram >= 1, -b >= 2\n"); return 2; }
+    if (B < 1) { fprintf(stderr, "gl3_spec_run: --branches >= 1\n"); return 2; }
 
     const int N = (int)prompt.size();
     gl3_gguf* g = nullptr;
@@ -119,6 +152,29 @@ int main(int argc, char** argv) {
         if (k > left - 1) k = left - 1;
         if (k > ctx_len - 1 - pos) k = ctx_len - 1 - pos;
         if (k > batch - 1) k = batch - 1;
+        if (B > 1) {      // a trie of drafts, verified as a tree
+            std::vector<int32_t> parents, depth, path;
+            draft_tree(history, G, k, B, toks, parents, depth);
+            const int m = (int)toks.size();
+            seqs.assign((size_t)m, 0);
+            poss.resize((size_t)m);
+            path.resize((size_t)m);
+            for (int i = 0; i < m; ++i) poss[i] = pos + depth[i];
+            gl3_verify_result res{};
+            int32_t n_trees = 0;
+            const double t0 = now_s();
+            CK(gl3_forward_batch_verify_tree(ctx, toks.data(), seqs.data(), poss.data(), parents.data(), m, &res, path.data(), &n_trees));
+            len_s[m] += now_s() - t0; ++len_n[m];
+            ++steps; drafted += m - 1; accepted += res.accepted;
+            for (int i = 1; i <= res.accepted + 1 && !stopped; ++i) {
+                const int32_t id = i <= res.accepted ? toks[path[i]] : res.token;
+                generated.push_back(id);
+                history.push_back(id);
+                stopped = stop_set.count(id) != 0;
+            }
+            pos += res.accepted + 1;
+            continue;
+        }
         const std::vector<int32_t> dr = draft(history, G, k);
         const int m = 1 + (int)dr.size();
         toks.assign(1, history.back());

@@ -38,9 +38,10 @@ static double now_ms() {
 // ------------------------------------------------------------------------------------------------ matvec launch
 static int q8_tile_groups(int k) { return ((k / 32) + 3) / 4; }      // 128-element tile groups of a Q8_0 row of k elements (Q8Mat.ng)
 // dynamic LDS of matvec_q8t_kernel for rows of k elements: int8 activation | block scales | f32 row (RMS prologue) | two product buffers | flags
-static size_t matvec_smem(int pro, int epi, int k) {
-    const int nm = epi == EPI_SWIGLU ? 2 : 1, ng = q8_tile_groups(k);
-    return (size_t)ng * 4 * 32 + (size_t)ng * 4 * 4 + (pro == PRO_RMS ? (size_t)(k + 32) * 4 : 0) + (size_t)2 * nm * ng * 64 * 4 + 128;
+// npw: the paired form (mv_paired) keeps the product buffers of two strips
+static size_t matvec_smem(int pro, int epi, int k, int npw = 4) {
+    const int nm = epi == EPI_SWIGLU ? 2 : 1, ng = q8_tile_groups(k), nh = mv_paired(pro, epi, npw) ? 2 : 1;
+    return (size_t)ng * 4 * 32 + (size_t)ng * 4 * 4 + (pro == PRO_RMS ? (size_t)(k + 32) * 4 : 0) + (size_t)2 * nh * nm * ng * 64 * 4 + 128;
 }
 // what every large-LDS kernel here may ask for (hipFuncAttributeMaxDynamicSharedMemorySize): the CU's 160 KB less the static part
 constexpr size_t GL3_LDS_MAX = 160 * 1024 - 256;
@@ -69,6 +70,7 @@ constexpr MvVariant MV_VARIANTS[] = {
     mv_variant<PRO_RMS,   EPI_STORE,  4, false, false, true>(),
     mv_variant<PRO_RMS,   EPI_STORE,  4, false, true,  false>(),
     mv_variant<PRO_RMS,   EPI_STORE,  4, false, true,  true>(),
+    mv_variant<PRO_RMS,   EPI_STORE,  8, false, false, false>(),      // qkv, paired: two one-segment strips per workgroup, one workgroup per CU
     mv_variant<PRO_RMS,   EPI_SWIGLU, 4, false, false, false>(),      // gate/up
     mv_variant<PRO_RMS,   EPI_SWIGLU, 4, false, false, true>(),
     mv_variant<PRO_RMS,   EPI_SWIGLU, 4, false, true,  false>(),
@@ -112,11 +114,14 @@ constexpr int mv_find(int pro, int epi, int npw, bool sel, bool tpf, bool segs, 
 static void launch_q8t(gl3_ctx* ctx, int pro, int epi, const MatvecArgs& a, int slots = 0) {
     static const int max_wgs = getenv("GL3_WGS") ? atoi(getenv("GL3_WGS")) : 512;   // 2 resident workgroups per CU
     const bool sel = slots > 0;
-    const int npw = !sel && pro == PRO_QUANT && epi == EPI_RESID && a.nstrips <= MV_WIDE_STRIPS ? 8 : 4;
-    const bool segs = !sel && a.ng > mv_seg_groups(npw, epi);     // more than one chain segment per strip: sum it under the weight stream
+    // paired (mv_paired): one prologue per CU instead of two that share it, where every pair of one-segment strips gets a workgroup of its own
+    const bool pair = !sel && !a.tp && pro == PRO_RMS && epi == EPI_STORE && a.ng <= mv_seg_groups(4, epi) && a.nstrips % 2 == 0 && a.nstrips / 2 <= MV_WIDE_STRIPS;
+    const int npw = pair || (!sel && pro == PRO_QUANT && epi == EPI_RESID && a.nstrips <= MV_WIDE_STRIPS) ? 8 : 4;
+    const bool segs = !sel && !pair && a.ng > mv_seg_groups(npw, epi);     // more than one chain segment per strip: sum it under the weight stream
     const int i = mv_find(pro, epi, npw, sel, a.tp != nullptr, segs);
     if (i < 0) no_kernel("matvec_q8t_kernel<prologue, epilogue>", pro, epi);
-    launch_mv(ctx, MV_VARIANTS[i].kernel, dim3(a.nstrips < max_wgs ? a.nstrips : max_wgs, sel ? slots : 1), mv_threads(npw), matvec_smem(pro, epi, a.k), a);
+    const int wgs = pair ? a.nstrips / 2 : a.nstrips < max_wgs ? a.nstrips : max_wgs;
+    launch_mv(ctx, MV_VARIANTS[i].kernel, dim3(wgs, sel ? slots : 1), mv_threads(npw), matvec_smem(pro, epi, a.k, npw), a);
 }
 
 // A matrix with native K-quant segments (a.kq): KQ_NPW producers at every shape, the chain in segments for strips of more than

@@ -47,6 +47,9 @@ enum { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2 };
 // one segment has nothing to overlap: the launch code picks SEGS = false for it, which is the one-pass chain.
 __host__ __device__ constexpr int mv_ch(int epi) { return epi == EPI_SWIGLU ? 4 : 8; }
 __host__ __device__ constexpr int mv_seg_groups(int npw, int epi) { return npw * mv_ch(epi); }
+// PRO_RMS / EPI_STORE with 8 producers is the paired form: a workgroup owns two adjacent strips at once, four producers and one chain
+// wavefront each, behind ONE prologue (matvec_q8t_kernel).
+__host__ __device__ constexpr bool mv_paired(int pro, int epi, int npw) { return pro == PRO_RMS && epi == EPI_STORE && npw == 8; }
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -58,16 +61,21 @@ __device__ long long gl3_mv_stamp[32];
 // Per-workgroup stamps of matvec_q8t_kernel on the chip-wide 100 MHz clock (clock64 is only comparable inside one workgroup): the LATEST
 // time any wavefront of workgroup blockIdx.x passed slot s.  Slots: 0 start, 1 products of the last strip done, 2 last chain (segment)
 // begin, 3 chain end, 4 result stored.  The host zeroes the array before a launch (scripts/probes/matvec_stamp_probe.hip).
+// Slots 5-7 are not times but the prologue phases of the workgroup's first aux wavefront in shader cycles (clock64 differences):
+// 5 activation to LDS, 6 sum of squares, 7 quantise to "producers released"; slot 5 carries __smid() + 1 in its upper half, so that
+// the host can tell workgroups that share a CU from those that have one to themselves.
 constexpr int MV_WG_STAMPS = 1024;
 __device__ unsigned long long gl3_mv_wg_stamp[MV_WG_STAMPS][8];
 // MV_WG_TIME reads the clock into a register; MV_WG_PUT files it later, so that no global access stands in front of a barrier.
 #define MV_WG_TIME(v) v = (unsigned long long)wall_clock64()
 #define MV_WG_PUT(s, v, cond) do { if (blockIdx.x < MV_WG_STAMPS && blockIdx.y == 0 && (cond)) atomicMax(&gl3_mv_wg_stamp[blockIdx.x][s], v); } while (0)
+#define MV_PH_TIME(v) v = clock64()
 #else
 #define PV_T(...)
 #define MV_STAMP(i, cond)
 #define MV_WG_TIME(v)
 #define MV_WG_PUT(s, v, cond)
+#define MV_PH_TIME(v)
 #define ATT_STAMP(i)
 #endif
 
@@ -329,8 +337,13 @@ __device__ __forceinline__ uint16_t ld2(const uint8_t* p) {
 // SEGS = false is the one-pass chain behind one __syncthreads() per strip: for strips of one segment (qkv, wo, logits at K = 4096,
 // every matrix of Llama-3.2-1B) the segment barrier form measured 0.05 us slower per launch and buys nothing.  Figures per class in
 // profiles/matvec_chain_overlap.md; one barrier round costs about 0.05 us, one group of the chain about 0.018 us.
+// Paired form (mv_paired: <PRO_RMS, EPI_STORE, NPW 8>, picked by the launch code for one-segment strips of a matrix whose strip pairs
+// fit one per CU): the prologue is the critical path of such a launch, and two workgroups that share a CU run two of them against each
+// other.  Here one workgroup runs ONE prologue for two adjacent strips: producers 0-3 stream strip 2p into pbuf half 0, producers 4-7
+// strip 2p + 1 into half 1 (each the whole strip in flight before the activation is ready, as in the NPW 4 form), and the first TWO aux
+// wavefronts become chain wavefronts, one per strip, side by side.  Every row is still summed in block order by one MFMA chain.
 // Register pressure is the maximum of the roles, not their sum (wave-uniform branches).
-//   LDS: xq[ng*128] | xs[ng*4] f32 | xf[k + 32] f32 (PRO_RMS) | pbuf[2][NM][ng*64] f32 | red[4] | sync[4]
+//   LDS: xq[ng*128] | xs[ng*4] f32 | xf[k + 32] f32 (PRO_RMS) | pbuf[2][NH][NM][ng*64] f32 (NH = 2 paired) | red[4] | sync[4]
 // TPF (tensor parallel, folded gathers): the aux wavefronts wait for the peers' slices of x before they read it (after the barrier
 // that releases the producers: the weight stream starts while the wait polls), and the chain wavefront stores every result into
 // the peers' arenas as well and publishes the gather (TpRec above).
@@ -357,6 +370,14 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
         }
     }
     constexpr int MV_PRODUCERS = NPW;
+    constexpr bool PAIR = mv_paired(PRO, EPI, NPW);
+    static_assert(!PAIR || (!SEL && !TPF && !SEGS), "the paired form is the one-pass chain of a single rank");
+    constexpr int NH = PAIR ? 2 : 1;                  // strips a workgroup works on at once
+    constexpr int PW = NPW / NH;                      // producer wavefronts per strip
+    // Behind the RMS prologue (6 us) the producers wait for the activation at a workgroup barrier: polling the flag keeps 4 or 8 wavefronts
+    // on the LDS pipe of the aux wavefronts for the whole of it.  Behind the short PRO_QUANT prologue the flag stays: the barrier form
+    // measured 0.2 us slower on wo (profiles/qkv_paired_prologue.md).
+    constexpr bool PBAR = PRO == PRO_RMS;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
     constexpr int CH = mv_ch(EPI);                    // tiles in flight per producer wave
@@ -368,8 +389,8 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
     float* xs = reinterpret_cast<float*>(smem + (size_t)nb4 * 32);
     float* xf = xs + nb4;
     float* pbuf = xf + (PRO == PRO_RMS ? a.k + 32 : 0);     // 32 zero floats pad xf for exact_sumsq_lds
-    float* red = pbuf + (size_t)2 * NM * a.ng * 64;         // [0] plain-chain result
-    int* sync_w = reinterpret_cast<int*>(red + 4);          // [0] aux sub-barrier counter, [1] activation-ready flag
+    float* red = pbuf + (size_t)2 * NH * NM * a.ng * 64;    // [0] plain-chain result
+    int* sync_w = reinterpret_cast<int*>(red + 4);          // [0] aux sub-barrier counter, [1] activation-ready flag (PRO_QUANT)
     const size_t strip_bytes = (size_t)a.ng * TILE_BYTES;
     MV_STAMP(0, t == 0);
     PV_T(unsigned long long wg_t0 = 0, wg_t1 = 0, wg_t2 = 0;)
@@ -378,14 +399,15 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
 
     if (wave < MV_PRODUCERS) {
         // ------------------------------------------------------------------ producers
-        const int nt = (a.ng - wave + MV_PRODUCERS - 1) / MV_PRODUCERS;      // tiles g = wave + 4*i of a strip
+        const int pw = PAIR ? wave % PW : wave, half = PAIR ? wave / PW : 0;      // paired: waves 0-3 strip 2p, waves 4-7 strip 2p + 1
+        const int nt = (a.ng - pw + PW - 1) / PW;                // tiles g = pw + PW*i of a strip
         uint16_t sc[NM][CH];
         int4 lo[NM][CH], hi[NM][CH];
         auto issue = [&](int strip, int i0) {
 #pragma unroll
             for (int u = 0; u < CH; ++u) {
                 if (i0 + u < nt) {
-                    const int g = wave + (i0 + u) * MV_PRODUCERS;
+                    const int g = pw + (i0 + u) * PW;
 #pragma unroll
                     for (int m = 0; m < NM; ++m) {
                         const uint8_t* p = (m == 0 ? a.w : a.w2) + (size_t)strip * strip_bytes + (size_t)g * TILE_BYTES;
@@ -400,7 +422,7 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
 #pragma unroll
             for (int u = 0; u < CH; ++u) {
                 if (i0 + u < nt) {
-                    const int g = wave + (i0 + u) * MV_PRODUCERS;
+                    const int g = pw + (i0 + u) * PW;
                     const int xb = 4 * g + (lane >> 4);
                     const int4 xlo = *reinterpret_cast<const int4*>(xq + 32 * xb);
                     const int4 xhi = *reinterpret_cast<const int4*>(xq + 32 * xb + 16);
@@ -413,17 +435,23 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
                 }
             }
         };
-        int strip = blockIdx.x;
+        int strip = blockIdx.x * NH + half;
         __syncthreads();                                         // the only prologue barrier the producers join
         if (strip < a.nstrips) issue(strip, 0);                  // HBM latency hides the activation prologue
-        while (__hip_atomic_load(&sync_w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(2);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if (PBAR) {
+            lds_barrier();                                       // xq / xs complete (no vmcnt(0): the loads above stay in flight)
+        } else {
+            while (__hip_atomic_load(&sync_w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(2);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
         MV_STAMP(3, t == 0);
         int it = 0;
-        for (; strip < a.nstrips; strip += gridDim.x, ++it) {
-            float* pb = pbuf + (size_t)(it & 1) * NM * a.ng * 64;
+        // paired: both halves of the workgroup run the same number of rounds (strip - half is the even strip of the pair), so that
+        // they meet at the same barriers also where the second strip of the last pair does not exist
+        for (; strip - half < a.nstrips; strip += gridDim.x * NH, ++it) {
+            float* pb = pbuf + (size_t)((it & 1) * NH + half) * NM * a.ng * 64;
             // batch i0 / CH = groups [i0 / CH * SEG, (i0 / CH + 1) * SEG) of the strip: one chain segment
-            for (int i0 = 0; i0 < nt; i0 += CH) {
+            for (int i0 = 0; i0 < (!PAIR || strip < a.nstrips ? nt : 0); i0 += CH) {
                 if (it != 0 || i0 != 0) issue(strip, i0);
                 compute(i0, pb);
                 if (SEGS) {
@@ -447,9 +475,11 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
     }
 
     // ---------------------------------------------------------------------- aux waves: prologue
-    // the prologue is the critical path of the kernel; the producers only issue their loads and poll
+    // the prologue is the critical path of the kernel; the producers only issue their loads and wait
     __builtin_amdgcn_s_setprio(3);
     const int ta = t - 64 * MV_PRODUCERS;                // 0..255
+    PV_T(long long ph0 = 0, ph1 = 0, ph2 = 0, ph3 = 0;)
+    MV_PH_TIME(ph0);
     const int nquads = a.k >> 2;
     float scale = 1.0f;
     constexpr int NXV = (PRO == PRO_RMS) ? 5 : 14;       // quads of the activation held in registers per aux thread
@@ -491,6 +521,7 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
         if (ta < 32) xf[a.k + ta] = 0.f;
         aux_sync();
         MV_STAMP(1, ta == 0);
+        MV_PH_TIME(ph1);
         // InferenceCore.rmsnorm :41 — the strict left-to-right sum of squares, evaluated exactly in parallel
         // (gl3_seqsum.h); pbuf is free during the prologue and serves as its scratch.
         float ss;
@@ -505,6 +536,7 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
             ss = red[0];
         }
         MV_STAMP(2, ta == 0);
+        MV_PH_TIME(ph2);
         ss /= (float)a.k;
         ss += a.eps;
         scale = (float)(1.0 / sqrt((double)ss));
@@ -532,14 +564,22 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
             quantize_quad(v, qd, xq, xs);
         }
     }
-    aux_sync();                                          // xq / xs complete
-    if (ta == 0) __hip_atomic_store(&sync_w[1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (wave != MV_PRODUCERS) return;                    // waves 5-7 retire; wave 4 becomes the chain wavefront
+    if (PBAR) {
+        lds_barrier();                                   // xq / xs complete: releases the producers
+    } else {
+        aux_sync();                                      // xq / xs complete
+        if (ta == 0) __hip_atomic_store(&sync_w[1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    MV_PH_TIME(ph3);
+    MV_WG_PUT(5, ((unsigned long long)(__smid() + 1) << 32) | (unsigned long long)(ph1 - ph0), ta == 0);
+    MV_WG_PUT(6, (unsigned long long)(ph2 - ph1), ta == 0); MV_WG_PUT(7, (unsigned long long)(ph3 - ph2), ta == 0);
+    const int half = wave - MV_PRODUCERS;                // the first aux wavefront becomes the chain wavefront (paired: the first two,
+    if (half >= NH) return;                              // one per strip of the pair); the others retire
 
     // ---------------------------------------------------------------------- chain wavefront
     int it = 0;
-    for (int strip = blockIdx.x; strip < a.nstrips; strip += gridDim.x, ++it) {
-        const float* pb = pbuf + (size_t)(it & 1) * NM * a.ng * 64;
+    for (int strip = blockIdx.x * NH + half; strip - half < a.nstrips; strip += gridDim.x * NH, ++it) {
+        const float* pb = pbuf + (size_t)((it & 1) * NH + half) * NM * a.ng * 64;
         v4f acc[NM];
 #pragma unroll
         for (int m = 0; m < NM; ++m) acc[m] = (v4f){0.f, 0.f, 0.f, 0.f};

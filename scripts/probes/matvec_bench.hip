@@ -66,8 +66,10 @@ int main(int argc, char** argv) {
             const int iters = 200;
             float us;
             const bool wide = getenv("MB_WIDE") != nullptr;     // 8 producer wavefronts, one workgroup per CU, for every shape
-            if (wide && sh.pro == PRO_RMS && sh.epi == EPI_STORE) us = run<PRO_RMS, EPI_STORE, 8>(a, std::min(g, 256), smem, iters, wb, w2b);
-            else if (wide && sh.pro == PRO_RMS) us = run<PRO_RMS, EPI_SWIGLU, 8>(a, std::min(g, 256), smem, iters, wb, w2b);
+            // <PRO_RMS, EPI_STORE, 8> is the paired form (two strips and twice the product buffers per workgroup): where launch_q8t picks it
+            const bool pair = sh.pro == PRO_RMS && sh.epi == EPI_STORE && a.ng <= mv_seg_groups(4, EPI_STORE) && a.nstrips % 2 == 0 && a.nstrips / 2 <= MV_WIDE_STRIPS;
+            if (wide && pair) us = run<PRO_RMS, EPI_STORE, 8>(a, a.nstrips / 2, smem + (size_t)2 * a.ng * 64 * 4, iters, wb, w2b);
+            else if (wide && sh.pro == PRO_RMS && sh.epi == EPI_SWIGLU) us = run<PRO_RMS, EPI_SWIGLU, 8>(a, std::min(g, 256), smem, iters, wb, w2b);
             else if (sh.pro == PRO_RMS && sh.epi == EPI_STORE) us = run<PRO_RMS, EPI_STORE>(a, g, smem, iters, wb, w2b);
             else if (sh.pro == PRO_QUANT && a.nstrips <= 256) us = run<PRO_QUANT, EPI_RESID, 8>(a, g, smem, iters, wb, w2b);
             else if (sh.pro == PRO_QUANT) us = run<PRO_QUANT, EPI_RESID>(a, g, smem, iters, wb, w2b);

@@ -20,11 +20,15 @@ static double median(std::vector<double> v) { std::sort(v.begin(), v.end()); ret
 template <int PRO, int EPI, int NPW>
 static void run(const Shape& sh, const MatvecArgs& a, int wgs, size_t smem, std::vector<uint8_t*>& wb, std::vector<uint8_t*>& w2b, const char* tag) {
     // as launch_matvec: the segmented chain for strips of more than one segment
-    auto kern = a.ng > mv_seg_groups(NPW, EPI) ? matvec_q8t_kernel<PRO, EPI, NPW, false, false, true> : matvec_q8t_kernel<PRO, EPI, NPW>;
+    void (*kern)(const MatvecArgs) = matvec_q8t_kernel<PRO, EPI, NPW>;
+    if constexpr (!mv_paired(PRO, EPI, NPW)) { if (a.ng > mv_seg_groups(NPW, EPI)) kern = matvec_q8t_kernel<PRO, EPI, NPW, false, false, true>; }
     CK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
     MatvecArgs b = a;
     const int reps = 24;
     std::vector<double> chip_tail, wg_tail, chain, span, last_begin;
+    // prologue phases (shader cycles) of workgroups that share their CU with another one of the launch, and of those alone on it
+    std::vector<double> ph_shared[3], ph_lone[3];
+    int n_shared = 0, n_lone = 0;
     std::vector<unsigned long long> st((size_t)MV_WG_STAMPS * 8);
     void* sym; CK(hipGetSymbolAddress(&sym, HIP_SYMBOL(gl3::gl3_mv_wg_stamp)));
     for (int i = 0; i < 4 + reps; ++i) {
@@ -38,6 +42,20 @@ static void run(const Shape& sh, const MatvecArgs& a, int wgs, size_t smem, std:
         const int n = std::min(wgs, MV_WG_STAMPS);
         unsigned long long t0 = ~0ull, p = 0, s = 0, cb = 0;
         std::vector<double> tails, chains;
+        if (PRO == PRO_RMS) {
+            // two workgroups share a CU if they report the same __smid() and their lifetimes (slot 0 .. slot 4) overlap
+            for (int w = 0; w < n; ++w) {
+                const unsigned long long* q = &st[(size_t)w * 8];
+                bool shared = false;
+                for (int v = 0; v < n && !shared; ++v) {
+                    const unsigned long long* r = &st[(size_t)v * 8];
+                    shared = v != w && (r[5] >> 32) == (q[5] >> 32) && r[0] < q[4] && q[0] < r[4];
+                }
+                const double ph[3] = {(double)(q[5] & 0xffffffffull), (double)q[6], (double)q[7]};
+                for (int j = 0; j < 3; ++j) (shared ? ph_shared : ph_lone)[j].push_back(ph[j]);
+                ++(shared ? n_shared : n_lone);
+            }
+        }
         for (int w = 0; w < n; ++w) {
             const unsigned long long* q = &st[(size_t)w * 8];
             t0 = std::min(t0, q[0]); p = std::max(p, q[1]); s = std::max(s, q[4]); cb = std::max(cb, q[2]);
@@ -56,6 +74,11 @@ static void run(const Shape& sh, const MatvecArgs& a, int wgs, size_t smem, std:
            "\"last_chain_ns_median\": %.0f, \"chip_last_chain_begin_to_store_ns_median\": %.0f, \"span_ns_median\": %.0f}\n",
            tag, sh.name, (int)(a.ng > mv_seg_groups(NPW, EPI)), sh.rows, sh.k, a.ng, wgs, NPW, reps, median(chip_tail), chip_tail.front(), chip_tail.back(), median(wg_tail),
            median(chain), median(last_begin), median(span));
+    if (PRO == PRO_RMS)
+        printf("{\"build\": \"%s\", \"class\": \"%s\", \"npw\": %d, \"wgs\": %d, \"prologue_cycles\": true, \"shared_cu_wgs_per_launch\": %.1f, \"lone_wgs_per_launch\": %.1f, "
+               "\"shared_x_to_lds\": %.0f, \"shared_sumsq\": %.0f, \"shared_quantise\": %.0f, \"lone_x_to_lds\": %.0f, \"lone_sumsq\": %.0f, \"lone_quantise\": %.0f}\n",
+               tag, sh.name, NPW, wgs, (double)n_shared / reps, (double)n_lone / reps, median(ph_shared[0]), median(ph_shared[1]), median(ph_shared[2]),
+               median(ph_lone[0]), median(ph_lone[1]), median(ph_lone[2]));
     fflush(stdout);
 }
 
@@ -93,6 +116,7 @@ int main(int argc, char** argv) {
         {"gate/up 8B", PRO_RMS, EPI_SWIGLU, 14336, 4096}, {"down 8B", PRO_QUANT, EPI_RESID, 4096, 14336},
         {"logits 8B", PRO_RMS, EPI_STORE, 128256, 4096},
         {"down 1B", PRO_QUANT, EPI_RESID, 2048, 8192}, {"down qwen3-4b", PRO_QUANT, EPI_RESID, 2560, 9728},
+        {"qkv 1B", PRO_RMS, EPI_STORE, 3072, 2048}, {"qkv qwen3-4b", PRO_RMS, EPI_STORE, 6144, 2560},
     };
     float *x, *nw, *out;
     CK(hipMalloc(&x, 16384 * 4)); CK(hipMalloc(&nw, 16384 * 4)); CK(hipMalloc(&out, 131072 * 4));
@@ -112,8 +136,12 @@ int main(int argc, char** argv) {
         std::vector<uint8_t*> wb, w2b;
         for (int i = 0; i < nbuf; ++i) { uint8_t* p; CK(hipMalloc(&p, bytes)); CK(hipMemset(p, 0x11 + i, bytes)); wb.push_back(p);
             if (nm == 2) { CK(hipMalloc(&p, bytes)); CK(hipMemset(p, 0x23 + i, bytes)); w2b.push_back(p); } }
-        const size_t smem = (size_t)a.ng * 4 * 32 + (size_t)a.ng * 4 * 4 + (sh.pro == PRO_RMS ? (size_t)(a.k + 32) * 4 : 0) + (size_t)2 * nm * a.ng * 64 * 4 + 128;
+        const size_t pbuf1 = (size_t)2 * nm * a.ng * 64 * 4;      // the paired form keeps two of them
+        const size_t smem = (size_t)a.ng * 4 * 32 + (size_t)a.ng * 4 * 4 + (sh.pro == PRO_RMS ? (size_t)(a.k + 32) * 4 : 0) + pbuf1 + 128;
         const int wgs = std::min(a.nstrips, 512);
+        // as launch_q8t: the paired form where every pair of one-segment strips gets a workgroup of its own; the four-producer form beside it
+        const bool pair = sh.pro == PRO_RMS && sh.epi == EPI_STORE && a.ng <= mv_seg_groups(4, EPI_STORE) && a.nstrips % 2 == 0 && a.nstrips / 2 <= MV_WIDE_STRIPS;
+        if (pair) run<PRO_RMS, EPI_STORE, 8>(sh, a, a.nstrips / 2, smem + pbuf1, wb, w2b, tag);
         if (sh.pro == PRO_RMS && sh.epi == EPI_STORE) run<PRO_RMS, EPI_STORE, 4>(sh, a, wgs, smem, wb, w2b, tag);
         else if (sh.pro == PRO_RMS) run<PRO_RMS, EPI_SWIGLU, 4>(sh, a, wgs, smem, wb, w2b, tag);
         else if (a.nstrips <= 256) run<PRO_QUANT, EPI_RESID, 8>(sh, a, wgs, smem, wb, w2b, tag);

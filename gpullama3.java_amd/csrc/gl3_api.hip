@@ -37,11 +37,10 @@ static double now_ms() {
 
 // ------------------------------------------------------------------------------------------------ matvec launch
 static int q8_tile_groups(int k) { return ((k / 32) + 3) / 4; }      // 128-element tile groups of a Q8_0 row of k elements (Q8Mat.ng)
-// dynamic LDS of matvec_q8t_kernel for rows of k elements: int8 activation | block scales | f32 row (RMS prologue) | two product buffers | flags
+// dynamic LDS of matvec_q8t_kernel and matvec_kq_kernel for rows of k elements: the layout mv_lds carves (gl3_decode_kernels.h; the K-quant kernel carves the same)
 // npw: the paired form (mv_paired) keeps the product buffers of two strips
 static size_t matvec_smem(int pro, int epi, int k, int npw = 4) {
-    const int nm = epi == EPI_SWIGLU ? 2 : 1, ng = q8_tile_groups(k), nh = mv_paired(pro, epi, npw) ? 2 : 1;
-    return (size_t)ng * 4 * 32 + (size_t)ng * 4 * 4 + (pro == PRO_RMS ? (size_t)(k + 32) * 4 : 0) + (size_t)2 * nh * nm * ng * 64 * 4 + 128;
+    return mv_lds_bytes(pro, epi == EPI_SWIGLU ? 2 : 1, mv_paired(pro, epi, npw) ? 2 : 1, k, q8_tile_groups(k));
 }
 // what every large-LDS kernel here may ask for (hipFuncAttributeMaxDynamicSharedMemorySize): the CU's 160 KB less the static part
 constexpr size_t GL3_LDS_MAX = 160 * 1024 - 256;

@@ -184,6 +184,13 @@ struct MoeSlots {
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct LdsBarrier { __device__ __forceinline__ void operator()() const { lds_barrier(); } };      // Sync functor of exact_seqsum_lds
+// __syncthreads() as the builtins it is made of: the library function is not always_inline, and what is not is never inlined into a
+// kernel with a target attribute of its own (matvec_kq_kernel, kq_gemm_kernel).  The same instructions in both contexts.
+__device__ __forceinline__ void wg_barrier() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
 
 __device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 
@@ -294,7 +301,9 @@ __device__ __forceinline__ size_t bdq_offset(int qd, int tok, int tslots) {
 }
 __device__ __forceinline__ size_t bds_offset(int blk, int tok, int tslots) { return ((size_t)(blk >> 2) * tslots + tok) * 4 + (blk & 3); }
 
-__device__ __forceinline__ int dot32(const int4& a0, const int4& a1, const int4& b0, const int4& b1) {
+// int8 dot of one 32-block: a = weight quants 0..15 / 16..31 (int4, or the ext-vector a K-quant block is rebuilt into), b = activation
+template <typename VA>
+__device__ __forceinline__ int dot32(const VA& a0, const VA& a1, const int4& b0, const int4& b1) {
     int s = 0;
     s = __builtin_amdgcn_sdot4(a0.x, b0.x, s, false); s = __builtin_amdgcn_sdot4(a0.y, b0.y, s, false);
     s = __builtin_amdgcn_sdot4(a0.z, b0.z, s, false); s = __builtin_amdgcn_sdot4(a0.w, b0.w, s, false);
@@ -319,165 +328,84 @@ __device__ __forceinline__ uint16_t ld2(const uint8_t* p) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Dequant-fused Q8_0 matvec, bit-exact to FloatTensor.matmul + dotQ8Activation.
-// Workgroup = 8 wavefronts with three roles:
-//   producers (waves 0-3): stream the weight tiles of the workgroup's 16-row strips (lane = one 32-block of one
-//       row: 3 coalesced non-temporal loads, 8 v_dot4, p = isum*(wScale*aScale)) into a double-buffered LDS
-//       array.  Their first loads are issued BEFORE the activation is ready, so HBM latency hides the prologue;
-//   aux (waves 4-7): the prologue — RMSNorm with the exact in-order sum of squares (gl3_seqsum.h) and the
-//       Q8_0 activation quantisation into LDS; waves 5-7 then retire;
-//   chain (wave 4): adds the p's of each row in block order with v_mfma_f32_16x16x4_f32 (B = 1.0) and applies
-//       the epilogue while the producers already stream the next strip.
-// SEGS = true (picked by the launch code for strips of more than one segment, mv_seg_groups): the chain runs in segments under the
-// weight stream.  What the producers finish as one batch (NPW wavefronts x CH tiles = SEG groups, contiguous in K) is handed over at a
-// workgroup barrier (lds_barrier: no vmcnt(0)), and the chain wavefront adds segment s while segment s + 1 streams; acc runs on across
-// the segments, so the adds and their order are those of one pass over the strip.  Every wavefront meets the barrier
-// ceil(ceil(ng / NPW) / CH) times per strip, also one whose tiles end a batch early.  Behind the last byte of a workgroup's last strip
-// only the last segment's adds and the epilogue remain (down at K = 14336: 48 of 112 groups, gate/up at K = 4096: 16 of 32).
-// SEGS = false is the one-pass chain behind one __syncthreads() per strip: for strips of one segment (qkv, wo, logits at K = 4096,
-// every matrix of Llama-3.2-1B) the segment barrier form measured 0.05 us slower per launch and buys nothing.  Figures per class in
-// profiles/matvec_chain_overlap.md; one barrier round costs about 0.05 us, one group of the chain about 0.018 us.
-// Paired form (mv_paired: <PRO_RMS, EPI_STORE, NPW 8>, picked by the launch code for one-segment strips of a matrix whose strip pairs
-// fit one per CU): the prologue is the critical path of such a launch, and two workgroups that share a CU run two of them against each
-// other.  Here one workgroup runs ONE prologue for two adjacent strips: producers 0-3 stream strip 2p into pbuf half 0, producers 4-7
-// strip 2p + 1 into half 1 (each the whole strip in flight before the activation is ready, as in the NPW 4 form), and the first TWO aux
-// wavefronts become chain wavefronts, one per strip, side by side.  Every row is still summed in block order by one MFMA chain.
-// Register pressure is the maximum of the roles, not their sum (wave-uniform branches).
-//   LDS: xq[ng*128] | xs[ng*4] f32 | xf[k + 32] f32 (PRO_RMS) | pbuf[2][NH][NM][ng*64] f32 (NH = 2 paired) | red[4] | sync[4]
-// TPF (tensor parallel, folded gathers): the aux wavefronts wait for the peers' slices of x before they read it (after the barrier
-// that releases the producers: the weight stream starts while the wait polls), and the chain wavefront stores every result into
-// the peers' arenas as well and publishes the gather (TpRec above).
-template <int PRO, int EPI, int NPW = 4, bool SEL = false, bool TPF = false, bool SEGS = false>
-__global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_kernel(const MatvecArgs a_in) {
-    MatvecArgs a = a_in;
-    if (SEL) {                                          // wave-uniform: one scalar load of the expert id
-        const int slot = blockIdx.y;
-        const MoeSlots m = *a.moe;
-        if (slot < m.n_sel) {
-            const size_t woff = (size_t)m.sel[slot] * m.sel_stride;
-            a.w += woff;
-            if (a.w2) a.w2 += woff;
-            a.x += (size_t)slot * m.x_slot_stride;
-            a.out += (size_t)slot * m.out_slot_stride;
-        } else {
-            const int c = slot - m.n_sel;
-            const size_t woff = (size_t)c * m.sel_stride;
-            a.w = m.sh_w + woff;
-            a.w2 = m.sh_w2 ? m.sh_w2 + woff : nullptr;
-            a.out = m.sh_out + (size_t)c * a.rows;
-            const int left = m.sh_rows - c * a.rows;
-            if (left < a.rows) { a.rows = left; a.nstrips = (left + 15) / 16; }
-        }
-    }
-    constexpr int MV_PRODUCERS = NPW;
-    constexpr bool PAIR = mv_paired(PRO, EPI, NPW);
-    static_assert(!PAIR || (!SEL && !TPF && !SEGS), "the paired form is the one-pass chain of a single rank");
-    constexpr int NH = PAIR ? 2 : 1;                  // strips a workgroup works on at once
-    constexpr int PW = NPW / NH;                      // producer wavefronts per strip
-    // Behind the RMS prologue (6 us) the producers wait for the activation at a workgroup barrier: polling the flag keeps 4 or 8 wavefronts
-    // on the LDS pipe of the aux wavefronts for the whole of it.  Behind the short PRO_QUANT prologue the flag stays: the barrier form
-    // measured 0.2 us slower on wo (profiles/qkv_paired_prologue.md).
-    constexpr bool PBAR = PRO == PRO_RMS;
+// The decode matvec, bit-exact to FloatTensor.matmul + dotQ8Activation: matvec_q8t_kernel (below) streams Q8T tiles, matvec_kq_kernel
+// (gl3_kquant_kernels.h) native Q4_K / Q5_K / Q6_K segments rebuilt into the same Q8_0 blocks.  A workgroup has three roles:
+//   producers (NPW wavefronts): stream the weight tiles of the workgroup's 16-row strips (lane = one 32-block of one row: coalesced
+//       non-temporal loads, 8 v_dot4, p = isum*(wScale*aScale)) into a double-buffered LDS array.  Their first loads are issued
+//       BEFORE the activation is ready, so HBM latency hides the prologue.  Each kernel has its own, with its own weight addressing;
+//   aux (MV_AUX wavefronts behind them): mv_aux_prologue; all but the first then retire;
+//   chain (the first aux wavefront): mv_chain, while the producers already stream the next strip.
+// Here the roles of matvec_q8t_kernel are functions of their own: the LDS layout (mv_lds, with the host's mv_lds_bytes), the SEL slot
+// bookkeeping, the prologue and the chain.  matvec_kq_kernel still carries its own text of the prologue and the chain, statement for
+// statement these; it shares wg_barrier, dot32 and the layout's byte count.  Calling the roles from it is correct (the suite passes) but
+// compiles its logits launch 3 % slower (profiles/matvec_shared_roles.md), so that step waits for a form that does not.
+//
+// The LDS of a launch, carved out of the dynamic allocation by every role that needs it (the same addresses: a pure function of the
+// template arguments, a.k and a.ng).  NM = matrices (2: SwiGLU), NH = strips a workgroup works on at once.
+//   xq[ng*128] | xs[ng*4] f32 | xf[k + 32] f32 (PRO_RMS) | pbuf[2][NH][NM][ng*64] f32 | red[4] | sync_w[4]
+struct MvLds {
+    uint8_t* xq; float* xs;    // the quantised activation: int8 quants and f16-rounded block scales
+    float* xf;                 // PRO_RMS: the f32 row, and 32 zero floats behind it that pad it for exact_sumsq_lds
+    float* pbuf;               // the producers' double-buffered products; free during the prologue, where it is the scratch of the sum
+    float* red;                // [0] plain-chain sum of squares
+    int* sync_w;               // [0] aux sub-barrier counter, [1] activation-ready flag (flag form of the release)
+};
+template <int PRO, int NM, int NH>
+__device__ __forceinline__ MvLds mv_lds(const MatvecArgs& a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
-    constexpr int CH = mv_ch(EPI);                    // tiles in flight per producer wave
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int nb4 = a.ng * 4;
-    constexpr int SEG = mv_seg_groups(NPW, EPI);       // groups per chain segment = what the producers finish as one batch (contiguous in K)
-    const int nbatch = SEGS ? ((a.ng + NPW - 1) / NPW + CH - 1) / CH : 1;      // barrier rounds per strip, the same for every wavefront
-    uint8_t* xq = smem;
-    float* xs = reinterpret_cast<float*>(smem + (size_t)nb4 * 32);
-    float* xf = xs + nb4;
-    float* pbuf = xf + (PRO == PRO_RMS ? a.k + 32 : 0);     // 32 zero floats pad xf for exact_sumsq_lds
-    float* red = pbuf + (size_t)2 * NH * NM * a.ng * 64;    // [0] plain-chain result
-    int* sync_w = reinterpret_cast<int*>(red + 4);          // [0] aux sub-barrier counter, [1] activation-ready flag (PRO_QUANT)
-    const size_t strip_bytes = (size_t)a.ng * TILE_BYTES;
-    MV_STAMP(0, t == 0);
-    PV_T(unsigned long long wg_t0 = 0, wg_t1 = 0, wg_t2 = 0;)
-    MV_WG_TIME(wg_t0);
-    if (t < 2) sync_w[t] = 0;
+    MvLds l;
+    l.xq = smem;
+    l.xs = reinterpret_cast<float*>(smem + (size_t)nb4 * 32);
+    l.xf = l.xs + nb4;
+    l.pbuf = l.xf + (PRO == PRO_RMS ? a.k + 32 : 0);
+    l.red = l.pbuf + (size_t)2 * NH * NM * a.ng * 64;
+    l.sync_w = reinterpret_cast<int*>(l.red + 4);
+    return l;
+}
+// its host twin: the bytes a launch asks for (matvec_smem, gl3_api.hip), term by term the carve-up above and 128 for red | sync_w
+__host__ __device__ constexpr size_t mv_lds_bytes(int pro, int nm, int nh, int k, int ng) {
+    return (size_t)ng * 4 * 32 + (size_t)ng * 4 * 4 + (pro == PRO_RMS ? (size_t)(k + 32) * 4 : 0) + (size_t)2 * nh * nm * ng * 64 * 4 + 128;
+}
 
-    if (wave < MV_PRODUCERS) {
-        // ------------------------------------------------------------------ producers
-        const int pw = PAIR ? wave % PW : wave, half = PAIR ? wave / PW : 0;      // paired: waves 0-3 strip 2p, waves 4-7 strip 2p + 1
-        const int nt = (a.ng - pw + PW - 1) / PW;                // tiles g = pw + PW*i of a strip
-        uint16_t sc[NM][CH];
-        int4 lo[NM][CH], hi[NM][CH];
-        auto issue = [&](int strip, int i0) {
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                if (i0 + u < nt) {
-                    const int g = pw + (i0 + u) * PW;
-#pragma unroll
-                    for (int m = 0; m < NM; ++m) {
-                        const uint8_t* p = (m == 0 ? a.w : a.w2) + (size_t)strip * strip_bytes + (size_t)g * TILE_BYTES;
-                        sc[m][u] = ld2<true>(p + 2 * lane);
-                        lo[m][u] = ld16<true>(p + 128 + 16 * lane);
-                        hi[m][u] = ld16<true>(p + 1152 + 16 * lane);
-                    }
-                }
-            }
-        };
-        auto compute = [&](int i0, float* pb) {
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                if (i0 + u < nt) {
-                    const int g = pw + (i0 + u) * PW;
-                    const int xb = 4 * g + (lane >> 4);
-                    const int4 xlo = *reinterpret_cast<const int4*>(xq + 32 * xb);
-                    const int4 xhi = *reinterpret_cast<const int4*>(xq + 32 * xb + 16);
-                    const float xsc = xs[xb];
-#pragma unroll
-                    for (int m = 0; m < NM; ++m) {
-                        const int isum = dot32(lo[m][u], hi[m][u], xlo, xhi);
-                        pb[(size_t)m * a.ng * 64 + g * 64 + lane] = (float)isum * (h2f(sc[m][u]) * xsc);
-                    }
-                }
-            }
-        };
-        int strip = blockIdx.x * NH + half;
-        __syncthreads();                                         // the only prologue barrier the producers join
-        if (strip < a.nstrips) issue(strip, 0);                  // HBM latency hides the activation prologue
-        if (PBAR) {
-            lds_barrier();                                       // xq / xs complete (no vmcnt(0): the loads above stay in flight)
-        } else {
-            while (__hip_atomic_load(&sync_w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(2);
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        }
-        MV_STAMP(3, t == 0);
-        int it = 0;
-        // paired: both halves of the workgroup run the same number of rounds (strip - half is the even strip of the pair), so that
-        // they meet at the same barriers also where the second strip of the last pair does not exist
-        for (; strip - half < a.nstrips; strip += gridDim.x * NH, ++it) {
-            float* pb = pbuf + (size_t)((it & 1) * NH + half) * NM * a.ng * 64;
-            // batch i0 / CH = groups [i0 / CH * SEG, (i0 / CH + 1) * SEG) of the strip: one chain segment
-            for (int i0 = 0; i0 < (!PAIR || strip < a.nstrips ? nt : 0); i0 += CH) {
-                if (it != 0 || i0 != 0) issue(strip, i0);
-                compute(i0, pb);
-                if (SEGS) {
-                    MV_STAMP(4 + 2 * it, t == 0 && it < 4 && i0 + CH >= nt);
-                    MV_WG_TIME(wg_t1);
-                    lds_barrier();                               // hands the segment to the chain wavefront; no vmcnt(0) as __syncthreads() has
-                }
-            }
-            if (SEGS) {
-                // a wavefront whose tiles end a batch early (ng % NPW != 0) still meets the others once per batch
-                for (int b = (nt + CH - 1) / CH; b < nbatch; ++b) lds_barrier();
-            } else {
-                MV_STAMP(4 + 2 * it, t == 0 && it < 4);
-                MV_WG_TIME(wg_t1);
-                __syncthreads();
-            }
-            MV_STAMP(5 + 2 * it, t == 0 && it < 4);
-        }
-        MV_WG_PUT(0, wg_t0, t == 0); MV_WG_PUT(1, wg_t1, lane == 0);
-        return;
+// SEL: what a slot changes whatever the weight format — x / out of a routed slot (slot < n_sel), and out, rows and nstrips of chunk
+// c = slot - n_sel of the shared expert (the last one may be ragged).  Called from the branch in which the kernel does the slot's weight
+// addressing, which is its own.
+__device__ __forceinline__ void mv_sel_routed(MatvecArgs& a, const MoeSlots& m, int slot) {
+    a.x += (size_t)slot * m.x_slot_stride;
+    a.out += (size_t)slot * m.out_slot_stride;
+}
+__device__ __forceinline__ void mv_sel_shared(MatvecArgs& a, const MoeSlots& m, int c) {
+    a.out = m.sh_out + (size_t)c * a.rows;
+    const int left = m.sh_rows - c * a.rows;
+    if (left < a.rows) { a.rows = left; a.nstrips = (left + 15) / 16; }
+}
+
+// The producers' side of the release at the end of mv_aux_prologue<.., PBAR>: xq / xs are complete when it returns.  PBAR: a workgroup
+// barrier without vmcnt(0), so the loads issued in front of it stay in flight; else the producers poll the flag.
+template <bool PBAR>
+__device__ __forceinline__ void mv_await_activation(const MvLds& l) {
+    if (PBAR) {
+        lds_barrier();
+    } else {
+        while (__hip_atomic_load(&l.sync_w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(2);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     }
+}
 
-    // ---------------------------------------------------------------------- aux waves: prologue
-    // the prologue is the critical path of the kernel; the producers only issue their loads and wait
+// The prologue, run by the MV_AUX wavefronts behind the NPW producers (t = threadIdx.x): the activation a.x — under PRO_RMS
+// RMS-normalised with the exact in-order sum of squares (gl3_seqsum.h) — quantised to Q8_0 blocks in xq / xs, then the producers are
+// released.  It is the critical path of the kernel; the producers only issue their loads and wait.  It joins ONE workgroup barrier, which
+// the producers meet before their first loads, and under PBAR the releasing one (mv_await_activation<PBAR> on their side).
+// The release form is this one template argument: the barrier under PRO_RMS, the flag under PRO_QUANT.
+template <int PRO, bool TPF, bool PBAR, int NPW, int NM, int NH>
+__device__ __forceinline__ void mv_aux_prologue(const MatvecArgs& a, const int t) {
+    const MvLds l = mv_lds<PRO, NM, NH>(a);
+    uint8_t* const xq = l.xq;
+    float *const xs = l.xs, *const xf = l.xf;
+    const int lane = t & 63, wave = t >> 6, nb4 = a.ng * 4;
     __builtin_amdgcn_s_setprio(3);
-    const int ta = t - 64 * MV_PRODUCERS;                // 0..255
+    const int ta = t - 64 * NPW;                         // 0..255
     PV_T(long long ph0 = 0, ph1 = 0, ph2 = 0, ph3 = 0;)
     MV_PH_TIME(ph0);
     const int nquads = a.k >> 2;
@@ -497,13 +425,13 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
 #pragma unroll
         for (int i = 0; i < 5; ++i) nwv[i] = *reinterpret_cast<const float4*>(a.norm_w + 4 * min(ta + 256 * i, nquads - 1));
     }
-    __syncthreads();                                     // activation loads are queued ahead of the weight stream
+    wg_barrier();                                        // activation loads are queued ahead of the weight stream
     if (TPF) {
         if (a.tp->w.flags) tp_wait(a.tp->w);
 #pragma unroll
         for (int i = 0; i < NXV; ++i) xv[i] = *reinterpret_cast<const float4*>(a.x + 4 * min(ta + 256 * i, nquads - 1));
     }
-    SubBarrier aux_sync{&sync_w[0], MV_AUX, 0};
+    SubBarrier aux_sync{&l.sync_w[0], MV_AUX, 0};
     for (int b = (a.k >> 5) + ta; b < nb4; b += 256) {   // zero-padded blocks: nothing of them waits for the sum
         xs[b] = 0.f;
         const int4 z = {0, 0, 0, 0};
@@ -523,17 +451,18 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
         MV_STAMP(1, ta == 0);
         MV_PH_TIME(ph1);
         // InferenceCore.rmsnorm :41 — the strict left-to-right sum of squares, evaluated exactly in parallel
-        // (gl3_seqsum.h); pbuf is free during the prologue and serves as its scratch.
+        // (gl3_seqsum.h); pbuf is free during the prologue and serves as its scratch.  The size asked of it is ONE strip's double buffer
+        // (2 * NM, not 2 * NH * NM): the paired form's second half is left out on purpose, so that pairing does not change the branch taken.
         float ss;
         if ((size_t)2 * NM * a.ng * 64 * 4 >= ss_scratch_bytes(a.k) && a.k >= 1024 && a.k <= 5120) {
-            ss = exact_sumsq_lds(xf, a.k, reinterpret_cast<uint8_t*>(pbuf), ta, aux_sync);
+            ss = exact_sumsq_lds(xf, a.k, reinterpret_cast<uint8_t*>(l.pbuf), ta, aux_sync);
         } else {
-            if (wave == MV_PRODUCERS) {
+            if (wave == NPW) {                           // the first aux wavefront
                 const float s1 = seq_sum_lds<true>(xf, a.k);
-                if (lane == 0) red[0] = s1;
+                if (lane == 0) l.red[0] = s1;
             }
             aux_sync();
-            ss = red[0];
+            ss = l.red[0];
         }
         MV_STAMP(2, ta == 0);
         MV_PH_TIME(ph2);
@@ -568,25 +497,32 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
         lds_barrier();                                   // xq / xs complete: releases the producers
     } else {
         aux_sync();                                      // xq / xs complete
-        if (ta == 0) __hip_atomic_store(&sync_w[1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (ta == 0) __hip_atomic_store(&l.sync_w[1], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     MV_PH_TIME(ph3);
     MV_WG_PUT(5, ((unsigned long long)(__smid() + 1) << 32) | (unsigned long long)(ph1 - ph0), ta == 0);
     MV_WG_PUT(6, (unsigned long long)(ph2 - ph1), ta == 0); MV_WG_PUT(7, (unsigned long long)(ph3 - ph2), ta == 0);
-    const int half = wave - MV_PRODUCERS;                // the first aux wavefront becomes the chain wavefront (paired: the first two,
-    if (half >= NH) return;                              // one per strip of the pair); the others retire
+}
 
-    // ---------------------------------------------------------------------- chain wavefront
+// The chain wavefront of strip `half` of the NH a workgroup works on at once: for each of its strips it adds the products of every row in
+// block order with v_mfma_f32_16x16x4_f32 (B = 1.0) and applies the epilogue.  SEGS: in nbatch segments of SEG tile groups, each behind
+// one lds_barrier that every producer meets too (SEG = what they finish as one batch: mv_seg_groups / kq_seg_groups); else one pass
+// behind one wg_barrier per strip.  The producers' loop runs the same strips and the same barrier rounds.
+template <int PRO, int EPI, bool SEGS, bool TPF, int NH, int SEG>
+__device__ __forceinline__ void mv_chain(const MatvecArgs& a, const int half, const int nbatch, const int lane) {
+    constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
+    const MvLds l = mv_lds<PRO, NM, NH>(a);
+    PV_T(unsigned long long wg_t1 = 0, wg_t2 = 0, wg_t3 = 0;)      // segment begin, chain end, result stored
     int it = 0;
     for (int strip = blockIdx.x * NH + half; strip - half < a.nstrips; strip += gridDim.x * NH, ++it) {
-        const float* pb = pbuf + (size_t)((it & 1) * NH + half) * NM * a.ng * 64;
+        const float* pb = l.pbuf + (size_t)((it & 1) * NH + half) * NM * a.ng * 64;
         v4f acc[NM];
 #pragma unroll
         for (int m = 0; m < NM; ++m) acc[m] = (v4f){0.f, 0.f, 0.f, 0.f};
         // One segment per producer batch: segment s is summed while the producers stream segment s + 1 (or the next strip), acc runs
         // on across the segments, so the order of the adds is the one of a single pass over the strip.
         for (int b = 0; b < nbatch; ++b) {
-            if (SEGS) lds_barrier(); else __syncthreads();      // segment b of this strip (SEGS = false: the whole strip) is in pbuf
+            if (SEGS) lds_barrier(); else wg_barrier();         // segment b of this strip (SEGS = false: the whole strip) is in pbuf
             MV_STAMP(16 + 2 * it, lane == 0 && it < 4 && b == nbatch - 1);
             MV_WG_TIME(wg_t1);
             int g = b * SEG;
@@ -629,10 +565,148 @@ __global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_
             }
         }
         PV_T(asm volatile("s_waitcnt vmcnt(0)" ::: "memory");)
-        MV_WG_TIME(wg_t0);
-        MV_WG_PUT(2, wg_t1, lane == 0); MV_WG_PUT(3, wg_t2, lane == 0); MV_WG_PUT(4, wg_t0, lane == 0);
+        MV_WG_TIME(wg_t3);
+        MV_WG_PUT(2, wg_t1, lane == 0); MV_WG_PUT(3, wg_t2, lane == 0); MV_WG_PUT(4, wg_t3, lane == 0);
     }
     if (TPF && a.tp->p.npeers) tp_publish(a.tp->p, gridDim.x);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Dequant-fused Q8_0 matvec over Q8T tiles: NPW producers (waves 0 .. NPW-1: 3 loads per tile), MV_AUX aux wavefronts behind them.
+// SEGS = true (picked by the launch code for strips of more than one segment, mv_seg_groups): the chain runs in segments under the
+// weight stream.  What the producers finish as one batch (NPW wavefronts x CH tiles = SEG groups, contiguous in K) is handed over at a
+// workgroup barrier (lds_barrier: no vmcnt(0)), and the chain wavefront adds segment s while segment s + 1 streams; acc runs on across
+// the segments, so the adds and their order are those of one pass over the strip.  Every wavefront meets the barrier
+// ceil(ceil(ng / NPW) / CH) times per strip, also one whose tiles end a batch early.  Behind the last byte of a workgroup's last strip
+// only the last segment's adds and the epilogue remain (down at K = 14336: 48 of 112 groups, gate/up at K = 4096: 16 of 32).
+// SEGS = false is the one-pass chain behind one wg_barrier() per strip: for strips of one segment (qkv, wo, logits at K = 4096,
+// every matrix of Llama-3.2-1B) the segment barrier form measured 0.05 us slower per launch and buys nothing.  Figures per class in
+// profiles/matvec_chain_overlap.md; one barrier round costs about 0.05 us, one group of the chain about 0.018 us.
+// Paired form (mv_paired: <PRO_RMS, EPI_STORE, NPW 8>, picked by the launch code for one-segment strips of a matrix whose strip pairs
+// fit one per CU): the prologue is the critical path of such a launch, and two workgroups that share a CU run two of them against each
+// other.  Here one workgroup runs ONE prologue for two adjacent strips: producers 0-3 stream strip 2p into pbuf half 0, producers 4-7
+// strip 2p + 1 into half 1 (each the whole strip in flight before the activation is ready, as in the NPW 4 form), and the first TWO aux
+// wavefronts become chain wavefronts, one per strip, side by side.  Every row is still summed in block order by one MFMA chain.
+// Register pressure is the maximum of the roles, not their sum (wave-uniform branches).
+// TPF (tensor parallel, folded gathers): the aux wavefronts wait for the peers' slices of x before they read it (after the barrier
+// that releases the producers: the weight stream starts while the wait polls), and the chain wavefront stores every result into
+// the peers' arenas as well and publishes the gather (TpRec above).
+template <int PRO, int EPI, int NPW = 4, bool SEL = false, bool TPF = false, bool SEGS = false>
+__global__ __launch_bounds__(mv_threads(NPW), NPW == 4 ? 4 : 2) void matvec_q8t_kernel(const MatvecArgs a_in) {
+    MatvecArgs a = a_in;
+    if (SEL) {                                          // wave-uniform: one scalar load of the expert id
+        const int slot = blockIdx.y;
+        const MoeSlots m = *a.moe;
+        if (slot < m.n_sel) {
+            const size_t woff = (size_t)m.sel[slot] * m.sel_stride;
+            a.w += woff;
+            if (a.w2) a.w2 += woff;
+            mv_sel_routed(a, m, slot);
+        } else {
+            const int c = slot - m.n_sel;
+            const size_t woff = (size_t)c * m.sel_stride;
+            a.w = m.sh_w + woff;
+            a.w2 = m.sh_w2 ? m.sh_w2 + woff : nullptr;
+            mv_sel_shared(a, m, c);
+        }
+    }
+    constexpr bool PAIR = mv_paired(PRO, EPI, NPW);
+    static_assert(!PAIR || (!SEL && !TPF && !SEGS), "the paired form is the one-pass chain of a single rank");
+    constexpr int NH = PAIR ? 2 : 1;                  // strips a workgroup works on at once
+    constexpr int PW = NPW / NH;                      // producer wavefronts per strip
+    // Behind the RMS prologue (6 us) the producers wait for the activation at a workgroup barrier: polling the flag keeps 4 or 8 wavefronts
+    // on the LDS pipe of the aux wavefronts for the whole of it.  Behind the short PRO_QUANT prologue the flag stays: the barrier form
+    // measured 0.2 us slower on wo (profiles/qkv_paired_prologue.md).
+    constexpr bool PBAR = PRO == PRO_RMS;
+    constexpr int NM = (EPI == EPI_SWIGLU) ? 2 : 1;
+    constexpr int CH = mv_ch(EPI);                    // tiles in flight per producer wave
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    constexpr int SEG = mv_seg_groups(NPW, EPI);       // groups per chain segment = what the producers finish as one batch (contiguous in K)
+    const int nbatch = SEGS ? ((a.ng + NPW - 1) / NPW + CH - 1) / CH : 1;      // barrier rounds per strip, the same for every wavefront
+    const MvLds l = mv_lds<PRO, NM, NH>(a);
+    const size_t strip_bytes = (size_t)a.ng * TILE_BYTES;
+    MV_STAMP(0, t == 0);
+    PV_T(unsigned long long wg_t0 = 0, wg_t1 = 0;)
+    MV_WG_TIME(wg_t0);
+    if (t < 2) l.sync_w[t] = 0;
+
+    if (wave < NPW) {
+        // ------------------------------------------------------------------ producers
+        const int pw = PAIR ? wave % PW : wave, half = PAIR ? wave / PW : 0;      // paired: waves 0-3 strip 2p, waves 4-7 strip 2p + 1
+        const int nt = (a.ng - pw + PW - 1) / PW;                // tiles g = pw + PW*i of a strip
+        uint16_t sc[NM][CH];
+        int4 lo[NM][CH], hi[NM][CH];
+        auto issue = [&](int strip, int i0) {
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                if (i0 + u < nt) {
+                    const int g = pw + (i0 + u) * PW;
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) {
+                        const uint8_t* p = (m == 0 ? a.w : a.w2) + (size_t)strip * strip_bytes + (size_t)g * TILE_BYTES;
+                        sc[m][u] = ld2<true>(p + 2 * lane);
+                        lo[m][u] = ld16<true>(p + 128 + 16 * lane);
+                        hi[m][u] = ld16<true>(p + 1152 + 16 * lane);
+                    }
+                }
+            }
+        };
+        auto compute = [&](int i0, float* pb) {
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+                if (i0 + u < nt) {
+                    const int g = pw + (i0 + u) * PW;
+                    const int xb = 4 * g + (lane >> 4);
+                    const int4 xlo = *reinterpret_cast<const int4*>(l.xq + 32 * xb);
+                    const int4 xhi = *reinterpret_cast<const int4*>(l.xq + 32 * xb + 16);
+                    const float xsc = l.xs[xb];
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) {
+                        const int isum = dot32(lo[m][u], hi[m][u], xlo, xhi);
+                        pb[(size_t)m * a.ng * 64 + g * 64 + lane] = (float)isum * (h2f(sc[m][u]) * xsc);
+                    }
+                }
+            }
+        };
+        int strip = blockIdx.x * NH + half;
+        wg_barrier();                                            // the only prologue barrier the producers join
+        if (strip < a.nstrips) issue(strip, 0);                  // HBM latency hides the activation prologue
+        mv_await_activation<PBAR>(l);
+        MV_STAMP(3, t == 0);
+        int it = 0;
+        // paired: both halves of the workgroup run the same number of rounds (strip - half is the even strip of the pair), so that
+        // they meet at the same barriers also where the second strip of the last pair does not exist
+        for (; strip - half < a.nstrips; strip += gridDim.x * NH, ++it) {
+            float* pb = l.pbuf + (size_t)((it & 1) * NH + half) * NM * a.ng * 64;
+            // batch i0 / CH = groups [i0 / CH * SEG, (i0 / CH + 1) * SEG) of the strip: one chain segment
+            for (int i0 = 0; i0 < (!PAIR || strip < a.nstrips ? nt : 0); i0 += CH) {
+                if (it != 0 || i0 != 0) issue(strip, i0);
+                compute(i0, pb);
+                if (SEGS) {
+                    MV_STAMP(4 + 2 * it, t == 0 && it < 4 && i0 + CH >= nt);
+                    MV_WG_TIME(wg_t1);
+                    lds_barrier();                               // hands the segment to the chain wavefront; no vmcnt(0) as wg_barrier() has
+                }
+            }
+            if (SEGS) {
+                // a wavefront whose tiles end a batch early (ng % NPW != 0) still meets the others once per batch
+                for (int b = (nt + CH - 1) / CH; b < nbatch; ++b) lds_barrier();
+            } else {
+                MV_STAMP(4 + 2 * it, t == 0 && it < 4);
+                MV_WG_TIME(wg_t1);
+                wg_barrier();
+            }
+            MV_STAMP(5 + 2 * it, t == 0 && it < 4);
+        }
+        MV_WG_PUT(0, wg_t0, t == 0); MV_WG_PUT(1, wg_t1, lane == 0);
+        return;
+    }
+
+    // ---------------------------------------------------------------------- aux wavefronts
+    mv_aux_prologue<PRO, TPF, PBAR, NPW, NM, NH>(a, t);
+    const int half = wave - NPW;                         // the first aux wavefront becomes the chain wavefront (paired: the first two,
+    if (half >= NH) return;                              // one per strip of the pair); the others retire
+    mv_chain<PRO, EPI, SEGS, TPF, NH, SEG>(a, half, nbatch, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------

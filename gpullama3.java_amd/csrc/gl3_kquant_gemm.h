@@ -104,7 +104,7 @@ __device__ __forceinline__ void kq_gemm_strip(const GemmArgs& a, const int (&fmt
             *reinterpret_cast<kq2i*>(c + ((4 * g + 3) * 16 + r) * 8) = (kq2i){q.hi.z, q.hi.w};      // k 24-31
             wsc[slot][m][wave][lane] = q.ws;                                        // lane = 16 block + row
         }
-        kq_syncthreads();
+        wg_barrier();
         if (consumer) {
 #pragma unroll
             for (int j = 0; j < KQG_STAGE; ++j) {

@@ -96,12 +96,6 @@ __device__ __forceinline__ const uint8_t* kq_uniform(const uint8_t* p) {      //
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
     return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
 }
-// __syncthreads(), spelled out: the library function is not inlined into a kernel with its own target attribute
-__device__ __forceinline__ void kq_syncthreads() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 template <typename T>
 __device__ __forceinline__ T kq_ldnt(const uint8_t* p) { return __builtin_nontemporal_load(reinterpret_cast<const T*>(p)); }
 
@@ -245,14 +239,6 @@ __device__ __forceinline__ KqBlock kq_rebuild(int fmt, const KqRaw& r) {
     q.lo = r.a; q.hi = r.b; q.ws = h2f((uint16_t)r.h0);
     return q;
 }
-__device__ __forceinline__ int kq_dot32(const kq4i a0, const kq4i a1, const int4& b0, const int4& b1) {      // dot32 of gl3_decode_kernels.h
-    int s = 0;
-    s = __builtin_amdgcn_sdot4(a0.x, b0.x, s, false); s = __builtin_amdgcn_sdot4(a0.y, b0.y, s, false);
-    s = __builtin_amdgcn_sdot4(a0.z, b0.z, s, false); s = __builtin_amdgcn_sdot4(a0.w, b0.w, s, false);
-    s = __builtin_amdgcn_sdot4(a1.x, b1.x, s, false); s = __builtin_amdgcn_sdot4(a1.y, b1.y, s, false);
-    s = __builtin_amdgcn_sdot4(a1.z, b1.z, s, false); s = __builtin_amdgcn_sdot4(a1.w, b1.w, s, false);
-    return s;
-}
 
 // ---------------------------------------------------------------------------------------------------
 // Decode matvec over native row segments: the structure of matvec_q8t_kernel (producers | aux prologue | chain wavefront, same LDS
@@ -346,14 +332,14 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQ_THREADS, 4) void matvec_kq_kernel(
 #pragma unroll
                     for (int m = 0; m < NM; ++m) {
                         const KqBlock q = kq_rebuild(m == 0 ? fmt0 : fmt1, raw[m][u]);
-                        const int isum = kq_dot32(q.lo, q.hi, xlo, xhi);
+                        const int isum = dot32(q.lo, q.hi, xlo, xhi);
                         pb[(size_t)m * a.ng * 64 + g * 64 + lane] = (float)isum * (q.ws * xsc);
                     }
                 }
             }
         };
         int strip = blockIdx.x;
-        kq_syncthreads();
+        wg_barrier();
         if (strip < a.nstrips) issue(strip, 0);                  // HBM latency hides the activation prologue
         while (__hip_atomic_load(&sync_w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(2);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -368,7 +354,7 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQ_THREADS, 4) void matvec_kq_kernel(
             if (SEGS) {
                 for (int b = (nt + CH - 1) / CH; b < nbatch; ++b) lds_barrier();
             } else {
-                kq_syncthreads();
+                wg_barrier();
             }
         }
         return;
@@ -387,7 +373,7 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQ_THREADS, 4) void matvec_kq_kernel(
 #pragma unroll
         for (int i = 0; i < 5; ++i) nwv[i] = *reinterpret_cast<const float4*>(a.norm_w + 4 * min(ta + 256 * i, nquads - 1));
     }
-    kq_syncthreads();
+    wg_barrier();
     SubBarrier aux_sync{&sync_w[0], MV_AUX, 0};
     for (int b = (a.k >> 5) + ta; b < nb4; b += 256) {
         xs[b] = 0.f;
@@ -406,7 +392,7 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQ_THREADS, 4) void matvec_kq_kernel(
         if (ta < 32) xf[a.k + ta] = 0.f;
         aux_sync();
         float ss;
-        static_assert(ss_scratch_bytes(1000) == 128 + 3000, "the line below spells ss_scratch_bytes out (not inlined here, see kq_syncthreads)");
+        static_assert(ss_scratch_bytes(1000) == 128 + 3000, "the line below spells ss_scratch_bytes out (a call from here is not inlined, see wg_barrier; through an always_inline copy the listing changes)");
         if ((size_t)2 * NM * a.ng * 64 * 4 >= 128 + (size_t)3 * a.k && a.k >= 1024 && a.k <= 5120) {
             ss = exact_sumsq_lds(xf, a.k, reinterpret_cast<uint8_t*>(pbuf), ta, aux_sync);
         } else {
@@ -456,7 +442,7 @@ __global__ GL3_NO_PK_F32 __launch_bounds__(KQ_THREADS, 4) void matvec_kq_kernel(
 #pragma unroll
         for (int m = 0; m < NM; ++m) acc[m] = (v4f){0.f, 0.f, 0.f, 0.f};
         for (int b = 0; b < nbatch; ++b) {
-            if (SEGS) lds_barrier(); else kq_syncthreads();
+            if (SEGS) lds_barrier(); else wg_barrier();
             int g = b * SEG;
             const int ge = SEGS ? min(g + SEG, a.ng) : a.ng;
             for (; g + 8 <= ge; g += 8) {

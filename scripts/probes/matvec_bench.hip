@@ -59,7 +59,7 @@ int main(int argc, char** argv) {
         std::vector<uint8_t*> wb, w2b;
         for (int i = 0; i < nbuf; ++i) { uint8_t* p; CK(hipMalloc(&p, bytes)); CK(hipMemset(p, 0x11 + i, bytes)); wb.push_back(p);
             if (nm == 2) { CK(hipMalloc(&p, bytes)); CK(hipMemset(p, 0x23 + i, bytes)); w2b.push_back(p); } }
-        const size_t smem = (size_t)a.ng * 4 * 32 + (size_t)a.ng * 4 * 4 + (sh.pro == PRO_RMS ? (size_t)(a.k + 32) * 4 : 0) + (size_t)2 * nm * a.ng * 64 * 4 + 128;
+        const size_t smem = mv_lds_bytes(sh.pro, nm, 1, a.k, a.ng);
         const double algo = (double)sh.rows * (sh.k / 32) * 34 * nm + sh.k * 4 + sh.rows * 4;
         for (int wgs : wg_list) {
             const int g = std::min(wgs, a.nstrips);
@@ -68,7 +68,7 @@ int main(int argc, char** argv) {
             const bool wide = getenv("MB_WIDE") != nullptr;     // 8 producer wavefronts, one workgroup per CU, for every shape
             // <PRO_RMS, EPI_STORE, 8> is the paired form (two strips and twice the product buffers per workgroup): where launch_q8t picks it
             const bool pair = sh.pro == PRO_RMS && sh.epi == EPI_STORE && a.ng <= mv_seg_groups(4, EPI_STORE) && a.nstrips % 2 == 0 && a.nstrips / 2 <= MV_WIDE_STRIPS;
-            if (wide && pair) us = run<PRO_RMS, EPI_STORE, 8>(a, a.nstrips / 2, smem + (size_t)2 * a.ng * 64 * 4, iters, wb, w2b);
+            if (wide && pair) us = run<PRO_RMS, EPI_STORE, 8>(a, a.nstrips / 2, mv_lds_bytes(PRO_RMS, 1, 2, a.k, a.ng), iters, wb, w2b);
             else if (wide && sh.pro == PRO_RMS && sh.epi == EPI_SWIGLU) us = run<PRO_RMS, EPI_SWIGLU, 8>(a, std::min(g, 256), smem, iters, wb, w2b);
             else if (sh.pro == PRO_RMS && sh.epi == EPI_STORE) us = run<PRO_RMS, EPI_STORE>(a, g, smem, iters, wb, w2b);
             else if (sh.pro == PRO_QUANT && a.nstrips <= 256) us = run<PRO_QUANT, EPI_RESID, 8>(a, g, smem, iters, wb, w2b);

@@ -136,12 +136,11 @@ int main(int argc, char** argv) {
         std::vector<uint8_t*> wb, w2b;
         for (int i = 0; i < nbuf; ++i) { uint8_t* p; CK(hipMalloc(&p, bytes)); CK(hipMemset(p, 0x11 + i, bytes)); wb.push_back(p);
             if (nm == 2) { CK(hipMalloc(&p, bytes)); CK(hipMemset(p, 0x23 + i, bytes)); w2b.push_back(p); } }
-        const size_t pbuf1 = (size_t)2 * nm * a.ng * 64 * 4;      // the paired form keeps two of them
-        const size_t smem = (size_t)a.ng * 4 * 32 + (size_t)a.ng * 4 * 4 + (sh.pro == PRO_RMS ? (size_t)(a.k + 32) * 4 : 0) + pbuf1 + 128;
+        const size_t smem = mv_lds_bytes(sh.pro, nm, 1, a.k, a.ng);
         const int wgs = std::min(a.nstrips, 512);
         // as launch_q8t: the paired form where every pair of one-segment strips gets a workgroup of its own; the four-producer form beside it
         const bool pair = sh.pro == PRO_RMS && sh.epi == EPI_STORE && a.ng <= mv_seg_groups(4, EPI_STORE) && a.nstrips % 2 == 0 && a.nstrips / 2 <= MV_WIDE_STRIPS;
-        if (pair) run<PRO_RMS, EPI_STORE, 8>(sh, a, a.nstrips / 2, smem + pbuf1, wb, w2b, tag);
+        if (pair) run<PRO_RMS, EPI_STORE, 8>(sh, a, a.nstrips / 2, mv_lds_bytes(PRO_RMS, 1, 2, a.k, a.ng), wb, w2b, tag);
         if (sh.pro == PRO_RMS && sh.epi == EPI_STORE) run<PRO_RMS, EPI_STORE, 4>(sh, a, wgs, smem, wb, w2b, tag);
         else if (sh.pro == PRO_RMS) run<PRO_RMS, EPI_SWIGLU, 4>(sh, a, wgs, smem, wb, w2b, tag);
         else if (a.nstrips <= 256) run<PRO_QUANT, EPI_RESID, 8>(sh, a, wgs, smem, wb, w2b, tag);

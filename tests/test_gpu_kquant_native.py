@@ -3,8 +3,10 @@ NumPy-converted Q8_0 tensors — the check tests/test_gpu_kquant.py makes of the
 
 Shapes sit on each side of the boundaries of matvec_kq_kernel's plan (12 producers; one chain segment = 24 tile groups, 12 for
 gate/up): K = 256 (one super-block), 768 (6 groups: fewer than the producers), 1536 | 1792 (gate/up: one | two segments) and
-3072 | 3328 (qkv, logits, wo, down: one | two segments; 26 and 14 groups are no multiple of 12).  gl3_create accepts vocabularies
-that are multiples of 16 only, so 528 (33 strips) stands in for a ragged vocabulary."""
+3072 | 3328 (qkv, logits, wo, down: one | two segments; 26 and 14 groups are no multiple of 12).  Of the kernel's RMS prologue
+these reach the single-wavefront sum of squares (K = 256, 768) and the exact parallel one with the row in registers (1536 to 3328);
+dim 5376, the first multiple of 256 above 5120, reaches the third form: the row re-read in a loop and the single-wavefront sum again.
+gl3_create accepts vocabularies that are multiples of 16 only, so 528 (33 strips) stands in for a ragged vocabulary."""
 import ctypes as C
 from importlib import import_module
 
@@ -36,6 +38,7 @@ CASES = [("q4_k_m",      0, 256,  768,  2,     8,    2, 32,  False, q4_k_m,     
          ("q4_k-tied",   0, 1536, 3072, 1,     12,   2, 128, True,  lambda n: Q4_K,       0),
          ("q6_k",        0, 1792, 3328, 1,     14,   2, 128, False, lambda n: Q6_K,       0),
          ("mixed",       0, 3328, 512,  1,     26,   2, 128, False, mixed,                0),
+         ("q4_k_m-5376", 0, 5376, 256,  1,     42,   6, 128, False, q4_k_m,               0),
          ("phi3",        4, 256,  512,  2,     8,    8, 32,  False, phi3,                 0)]
 
 

@@ -64,6 +64,7 @@ struct gl3_prefill_state {
     int4* deep = nullptr;               // [M] the deep records of the step (batch_plan_split), deepest first; PfStep::ndeep of them
     int32_t* deep_rows = nullptr;       // [M] the step rows of the deep records, ascending; PfStep::deep_rows of them
     int tree_max_slot = -1;             // last slot a tree may have on pf_attn_tree_kernel (pf_tree_max_slot); -1: the shape has no such kernel
+    int tree_tiled_min_slot = 0, tree_tiled_min_rows = 0;      // floors of the tiled tree form: the step's last slot, its rows (pf_tree_attributes)
     int tab_max_pos = 0;                // last position a tile may have in the one-launch table form (pf_tab_max_pos; INT_MAX: steps are not split)
     int32_t attn_rows[4] = {0, 0, 0, 0};      // rows of the last batched step by attention form (gl3_get_attn_rows), from the last layer's pf_attention
     bool attn_rows_set = false;
@@ -625,10 +626,54 @@ static int pf_tab_max_pos(const gl3_ctx* ctx) {
     return fm;
 }
 
-// Draft-tree steps (gl3_tree_attn.h).  pf_attn_tree_kernel<HS, kvMul> exists for the head sizes of the one-launch kernels and kvMul <= 4 (no
-// head groups); a step whose deepest slot leaves its score rows inside PF_ATTN_LDS_MAX takes it, every other step the masked per-row pair.
-// The limit is the plan's (read at gl3_create, so a test can lower it per plan): GL3_PF_TAB_MAXPOS=<p> lowers it to min(own, p) as it lowers
-// the run table's, GL3_PF_FUSED_ATTN=0 turns the one-launch kernel off.
+// Which scores kernel the long-context trio launches (pf_attention, pf_scores_table); group = head slots of a workgroup.  GL3_PF_SCORES_MFMA=0:
+// no pf_scores_mfma_kernel; GL3_PF_SCORES_PK=0: no pf_scores_pk_kernel; GL3_SCM_SPLIT: workgroups that share a (kv head, token tile)'s K tiles.
+static int pf_sw_scm_split() { static const int v = getenv("GL3_SCM_SPLIT") ? atoi(getenv("GL3_SCM_SPLIT")) : SCM_SPLIT; return v; }
+static bool pf_scores_on_mfma(int hs, int group) {
+    static const bool off = getenv("GL3_PF_SCORES_MFMA") && atoi(getenv("GL3_PF_SCORES_MFMA")) == 0;
+    return !off && group == 4 && (hs == 128 || hs == 64);
+}
+static bool pf_scores_on_pk(int hs, int group) {
+    static const bool off = getenv("GL3_PF_SCORES_PK") && atoi(getenv("GL3_PF_SCORES_PK")) == 0;
+    return !off && scores_pk_smem_bytes(hs, group) <= PF_ATTN_LDS_MAX && (group == 4 || group == 2 || group == 1);
+}
+// The trio's scores launch in its table form: `ntab` records {first row, rows <= 16, sequence, position of the first row} — the deep records of
+// a mixed step, or the tiles of a tree step (position = SLOT) — of a step of n rows whose deepest record ends at max_pos.  Row b of a record
+// gets its scores over [0, its position] in ATT and their per-tile maxima in TMX.
+static void pf_scores_table(gl3_ctx* ctx, const PfAttnArgs& aa, const int4* tab, int ntab, int max_pos, int n) {
+    gl3_prefill_state* p = ctx->pf;
+    hipStream_t s = ctx->stream;
+    const int hs = ctx->d.head_size, kvmul = ctx->d.n_heads / ctx->d.n_kv_heads, KVH = ctx->kv_heads_l;
+    const int group = pf_group_size(kvmul), NG = pf_head_groups(kvmul), nsplit = (max_pos + 1 + ATT_TT - 1) / ATT_TT;
+    const size_t sst = ctx->kv_seq_stride;
+    const dim3 g1(nsplit, KVH * NG, ntab), b1(64 * group);
+    if (pf_scores_on_mfma(hs, group))
+        pf_head_dispatch<64>(hs, [&](auto hc) {
+            hipLaunchKernelGGL((pf_scores_mfma_kernel<decltype(hc)::value, true>), dim3(std::min(nsplit, pf_sw_scm_split()), KVH * NG, ntab), dim3(512), scores_mfma_smem_bytes(hs), s,
+                               aa.Q, aa.q_stride, aa.kcache, aa.att, aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, tab, sst); });
+    else if (pf_scores_on_pk(hs, group))
+        pf_head_dispatch<32, true>(hs, [&](auto hc) { pf_kvmul_dispatch(group, [&](auto mc) {
+            hipLaunchKernelGGL((pf_scores_pk_kernel<decltype(hc)::value, decltype(mc)::value, true>), g1, b1, scores_pk_smem_bytes(hs, group), s, aa.Q, aa.q_stride, aa.kcache, aa.att,
+                               aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, tab, sst); }); });
+    else
+        pf_head_dispatch<32, true>(hs, [&](auto hc) {
+            hipLaunchKernelGGL((pf_scores_tiled_kernel<decltype(hc)::value, true>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, aa.kcache, aa.att,
+                               aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, tab, sst); });
+}
+
+// Draft-tree steps (gl3_tree_attn.h), three forms:
+//   one launch   pf_attn_tree_kernel<HS, kvMul> exists for the head sizes of the one-launch kernels and kvMul <= 4 (no head groups); a step whose
+//                deepest slot leaves its score rows inside PF_ATTN_LDS_MAX takes it.  The limit is the plan's (read at gl3_create, so a test can
+//                lower it per plan): GL3_PF_TAB_MAXPOS=<p> lowers it to min(own, p) as it lowers the run table's, GL3_PF_FUSED_ATTN=0 turns the
+//                kernel off.
+//   tiled        past that limit, on every shape the tiled kernels exist for (pf_tiled_shape: kvMul up to 16, head size 96) in a plan with
+//                pf_softmax_rows_kernel's row layout, a step at or past both floors — last slot and rows — takes the trio with its score rows
+//                in HBM: pf_scores_table over the tree tiles, pf_softmax_rows_tree_kernel, pf_pv_tree_kernel.  The floors are where the trio's
+//                three launches and their fixed cost overtake the pair (profiles/spec_tree.md); GL3_PF_TREE_TILED_MIN=<slot>,<rows>, read at
+//                gl3_create, replaces both (0,1: whenever the shape allows; a slot past any context: never).
+//   pair         every other step: pf_attn_scores_kernel + the masked pf_attn_softmax_pv_tree_kernel, per row.
+constexpr int TREE_TILED_MIN_SLOT = 1024, TREE_TILED_MIN_ROWS = 32;
+enum { TREE_ONE_LAUNCH = 0, TREE_TILED = 1, TREE_PAIR = 2 };
 template <class F>
 static inline void pf_tree_dispatch(int hs, int kvmul, F&& f) {
     pf_head_dispatch<32>(hs, [&](auto hc) {
@@ -654,10 +699,17 @@ static int32_t pf_tree_attributes(gl3_ctx* ctx) {
         pf_tree_dispatch(ctx->d.head_size, ctx->d.n_heads / ctx->d.n_kv_heads, [&](auto kern) {
             e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_ATTN_LDS_MAX); });
     GL3_HIP(e);
+    pf_head_dispatch<32, true>(ctx->d.head_size, [&](auto hc) {
+        e = hipFuncSetAttribute((const void*)pf_pv_tree_kernel<decltype(hc)::value>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pv_tree_smem_bytes(ctx->d.head_size)); });
+    GL3_HIP(e);
+    p->tree_tiled_min_slot = TREE_TILED_MIN_SLOT; p->tree_tiled_min_rows = TREE_TILED_MIN_ROWS;
+    const char* env = getenv("GL3_PF_TREE_TILED_MIN");
+    if (env && *env && (sscanf(env, "%d,%d", &p->tree_tiled_min_slot, &p->tree_tiled_min_rows) != 2 || p->tree_tiled_min_slot < 0 || p->tree_tiled_min_rows < 1))
+        GL3_FAIL(GL3_E_ARG, "GL3_PF_TREE_TILED_MIN must be <slot>,<rows> with slot >= 0 and rows >= 1");
     return GL3_OK;
 }
-// The attention of a tree step behind its RoPE + KV launch; aa as pf_attention filled it.  Returns true when the one-launch kernel served the step.
-static bool pf_attention_tree(gl3_ctx* ctx, const PfStep& st, PfAttnArgs aa) {
+// The attention of a tree step behind its RoPE + KV launch; aa as pf_attention filled it.  Returns the form that served the step (TREE_*).
+static int pf_attention_tree(gl3_ctx* ctx, const PfStep& st, PfAttnArgs aa) {
     gl3_prefill_state* p = ctx->pf;
     const gl3_model_desc& d = ctx->d;
     hipStream_t s = ctx->stream;
@@ -668,16 +720,26 @@ static bool pf_attention_tree(gl3_ctx* ctx, const PfStep& st, PfAttnArgs aa) {
         pf_tree_dispatch(hs, kvmul, [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(KVH * st.ntree), dim3(256), ta_smem_bytes(hs, kvmul, sstride), s, aa.Q, aa.q_stride, aa.kcache, aa.vcache, aa.out,
                                aa.out_stride, KVH, aa.kv_dim, aa.att_mul, sstride, tt.tiles, tt.p0, tt.mask, ctx->kv_seq_stride); });
-        return true;
+        return TREE_ONE_LAUNCH;
     }
-    // pf_attn_scores_kernel as it is over [0, slot] (a masked score is computed and ignored), then the masked softmax + weighted V sum
-    aa.pos = tt.slot;
+    aa.pos = tt.slot;      // a row's scores run over [0, slot] in both forms below (a masked score is computed and ignored)
+    if (pf_rows_softmax(ctx) && pf_tiled_shape(hs, kvmul, true) && st.max_pos >= p->tree_tiled_min_slot && n >= p->tree_tiled_min_rows) {
+        pf_scores_table(ctx, aa, tt.tiles, st.ntree, st.max_pos, n);
+        const int rows = n * H;      // R rows per workgroup as pf_attention picks it for the linear trio
+        if (rows >= 64 * 256) hipLaunchKernelGGL((pf_softmax_rows_tree_kernel<64>), dim3((rows + 63) / 64), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, tt.p0, tt.mask);
+        else if (rows >= 32 * 256) hipLaunchKernelGGL((pf_softmax_rows_tree_kernel<32>), dim3((rows + 31) / 32), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, tt.p0, tt.mask);
+        else hipLaunchKernelGGL((pf_softmax_rows_tree_kernel<16>), dim3((rows + 15) / 16), dim3(576), 0, s, aa, rows, p->TMX, p->tmx_tiles, p->SUMS, tt.p0, tt.mask);
+        pf_head_dispatch<32, true>(hs, [&](auto hc) {
+            hipLaunchKernelGGL((pf_pv_tree_kernel<decltype(hc)::value>), dim3(H, PVT_PER_TREE * ctx->tree.ntrees), dim3(64 * PVT_NW), pv_tree_smem_bytes(hs), s, aa, p->SUMS, tt.trees, tt.mask); });
+        return TREE_TILED;
+    }
+    // pf_attn_scores_kernel as it is, then the masked softmax + weighted V sum
     const int nsplit = (st.max_pos + 1 + ATT_TT - 1) / ATT_TT;
     const size_t sm1 = ((size_t)kvmul * hs + (size_t)ATT_TT * (hs + 1)) * 4;
     hipLaunchKernelGGL(pf_attn_scores_kernel, dim3(nsplit, KVH, n), dim3(64 * kvmul), sm1, s, aa);
     aa.win = ctx->attn_win;
     hipLaunchKernelGGL(pf_attn_softmax_pv_tree_kernel, dim3(H * ((hs + 63) / 64), n), dim3(64), (size_t)ctx->attn_win * 4 + 16, s, aa, tt.p0, tt.mask);
-    return false;
+    return TREE_PAIR;
 }
 
 // RoPE + KV write + attention of layer l for the n tokens whose raw q | k | v rows are in p->QKV -> AOr (this rank's chunk of the
@@ -697,9 +759,6 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     static const bool v1_only = pf_sw_v1_only();      // (GL3_PF_FUSED_ATTN, GL3_PF_FUSED_V1: above, shared with pf_tab_max_pos, which reads GL3_PF_TAB_MAXPOS)
     static const bool qao_off = getenv("GL3_PF_ATTN_QOUT") && atoi(getenv("GL3_PF_ATTN_QOUT")) == 0;
     static const bool mfma_off = getenv("GL3_PF_FUSED_MFMA") && atoi(getenv("GL3_PF_FUSED_MFMA")) == 0;
-    static const bool pk_off = getenv("GL3_PF_SCORES_PK") && atoi(getenv("GL3_PF_SCORES_PK")) == 0;
-    static const bool scm_off = getenv("GL3_PF_SCORES_MFMA") && atoi(getenv("GL3_PF_SCORES_MFMA")) == 0;
-    static const int scm_split = getenv("GL3_SCM_SPLIT") ? atoi(getenv("GL3_SCM_SPLIT")) : SCM_SPLIT;      // workgroups that share a (kv head, token tile)'s K tiles
     static const bool pvm_off = getenv("GL3_PF_PV_MFMA") && atoi(getenv("GL3_PF_PV_MFMA")) == 0;
     const int n = st.n, max_pos = st.max_pos, one_seq = st.one_seq, ntab = st.ntab, ndeep = st.ndeep;
     const bool runs = st.runs();                          // the run-table forms
@@ -744,8 +803,8 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     if (st.ntree) ra.slot = tree_tab(ctx->tree.tab, n, ctx->tree.ntiles, ctx->tree.ntrees).slot;      // roped with the position, written at the slot
     hipLaunchKernelGGL(pf_rope_kv_kernel, dim3(H + KVH, n), dim3(64), 0, s, ra);
     if (st.ntree) {
-        const bool one = pf_attention_tree(ctx, st, aa);
-        note_rows(0, one ? n : 0, 0, one ? 0 : n);
+        const int form = pf_attention_tree(ctx, st, aa);
+        note_rows(0, form == TREE_ONE_LAUNCH ? n : 0, form == TREE_TILED ? n : 0, form == TREE_PAIR ? n : 0);
         return false;
     }
     const bool rows_softmax = pf_rows_softmax(ctx);
@@ -805,29 +864,20 @@ static bool pf_attention(gl3_ctx* ctx, int l, const PfStep& st, float* AOr, bool
     const int4* dtab = p->deep;
     const int ntt = ndeep ? ndeep : (n + PA_TB - 1) / PA_TB;
     const dim3 g1(nsplit, KVH * NG, ntt), b1(64 * group);
-    const bool pk = !pk_off && scores_pk_smem_bytes(hs, group) <= PF_ATTN_LDS_MAX && (group == 4 || group == 2 || group == 1);
-    if (!scm_off && mfma_shape) {      // r6: products on the matrix pipe, query rows resident, K tiles prefetched
-        const dim3 g(nsplit < scm_split ? nsplit : scm_split, KVH * NG, ndeep ? ndeep : (n + SCM_TB - 1) / SCM_TB);
+    if (ndeep) pf_scores_table(ctx, aa, dtab, ndeep, max_pos, n);
+    else if (pf_scores_on_mfma(hs, group))      // r6: products on the matrix pipe, query rows resident, K tiles prefetched
         pf_head_dispatch<64>(hs, [&](auto hc) {
-            constexpr int HS_ = decltype(hc)::value;
-            if (ndeep) hipLaunchKernelGGL((pf_scores_mfma_kernel<HS_, true>), g, dim3(512), scores_mfma_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att, aa.n_heads,
-                                          kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, dtab, sst);
-            else hipLaunchKernelGGL((pf_scores_mfma_kernel<HS_>), g, dim3(512), scores_mfma_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att, aa.n_heads,
-                                    kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); });
-    } else if (pk)
+            const dim3 g(std::min(nsplit, pf_sw_scm_split()), KVH * NG, (n + SCM_TB - 1) / SCM_TB);
+            hipLaunchKernelGGL((pf_scores_mfma_kernel<decltype(hc)::value>), g, dim3(512), scores_mfma_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att, aa.n_heads,
+                               kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); });
+    else if (pf_scores_on_pk(hs, group))
         pf_head_dispatch<32, true>(hs, [&](auto hc) { pf_kvmul_dispatch(group, [&](auto mc) {
-            constexpr int HS_ = decltype(hc)::value, KVM_ = decltype(mc)::value;
-            if (ndeep) hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_, true>), g1, b1, scores_pk_smem_bytes(hs, group), s, aa.Q, aa.q_stride, kc1, aa.att,
-                                          aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, dtab, sst);
-            else hipLaunchKernelGGL((pf_scores_pk_kernel<HS_, KVM_>), g1, b1, scores_pk_smem_bytes(hs, group), s, aa.Q, aa.q_stride, kc1, aa.att,
-                                    aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); }); });
+            hipLaunchKernelGGL((pf_scores_pk_kernel<decltype(hc)::value, decltype(mc)::value>), g1, b1, scores_pk_smem_bytes(hs, group), s, aa.Q, aa.q_stride, kc1, aa.att,
+                               aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); }); });
     else
         pf_head_dispatch<32, true>(hs, [&](auto hc) {
-            constexpr int HS_ = decltype(hc)::value;
-            if (ndeep) hipLaunchKernelGGL((pf_scores_tiled_kernel<HS_, true>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att,
-                                          aa.n_heads, kvmul, aa.kv_dim, aa.ctx, 0, n, aa.att_mul, p->TMX, p->tmx_tiles, dtab, sst);
-            else hipLaunchKernelGGL((pf_scores_tiled_kernel<HS_>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att,
-                                    aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); });
+            hipLaunchKernelGGL((pf_scores_tiled_kernel<decltype(hc)::value>), g1, b1, scores_tiled_smem_bytes(hs), s, aa.Q, aa.q_stride, kc1, aa.att,
+                               aa.n_heads, kvmul, aa.kv_dim, aa.ctx, pos0, n, aa.att_mul, p->TMX, p->tmx_tiles); });
     // r6: R rows per workgroup, the sums as R chains of one wavefront; at least one workgroup per CU when the chunk has the rows.
     // A split step: the deep rows only (a shallow row's ATT / TMX were not written in this step)
     const int rows = (ndeep ? st.deep_rows : n) * H;

@@ -469,8 +469,13 @@ GL3_API int32_t gl3_verify_rows_dist(gl3_ctx* ctx, const float* logits, const in
  * position; so a tree needs p0 + rows <= ctx.  After the decision one launch moves the accepted path's rows, every layer, to positions
  * p0 .. p0 + accepted.  The caller continues with `token` at p0 + accepted + 1; rows above that are dead and are overwritten before anything
  * reads them, as with gl3_forward_batch_verify.  Nothing is rolled back on the host.
- * gl3_get_attn_rows afterwards: out[1] = n (pf_attn_tree_kernel, one launch per layer: head size 32 / 64 / 128, kvMul <= 4, score rows in
- * LDS) or out[3] = n (the per-row pair with the masked softmax, every other shape and depth).
+ * Attention, one of three forms per step (gl3_get_attn_rows afterwards): out[1] = n — pf_attn_tree_kernel, one launch per layer: head size
+ * 32 / 64 / 128, kvMul <= 4, while the score rows of the step's last slot fit LDS (slot 511 at head size 128, kvMul 4).  out[2] = n — past that,
+ * and on kvMul up to 16 and head size 96, the tiled trio with its score rows in HBM (table scores kernel, pf_softmax_rows_tree_kernel,
+ * pf_pv_tree_kernel: K and V are read once per tile of rows, not once per row) for a step of at least 32 rows whose last slot is at least
+ * 1024, in a plan with ctx % 4 == 0 and ctx >= 64; GL3_PF_TREE_TILED_MIN=<slot>,<rows>, read in gl3_create (malformed: GL3_E_ARG), replaces
+ * the two floors: 0,1 = whenever the shape allows, a slot past any context = never.  out[3] = n — every other step: the per-row pair with
+ * the masked softmax.  The three forms give the same bits.
  * GL3_E_ARG, before anything is staged or enqueued: what gl3_forward_batch refuses about (tokens, seq_ids, n); a null array; a first row with
  * a parent or a later row without one; a parent outside the row's own tree or not earlier than the row; a position that is not its
  * parent's + 1; duplicate sibling tokens; a tree of more than 64 rows; p0 + rows > ctx.  GL3_E_UNSUPPORTED: max_batch <= 1; tp_size > 1
@@ -631,7 +636,8 @@ GL3_API int32_t gl3_kv_seq_copy(gl3_ctx* ctx, int32_t src_seq, const int32_t* ds
 /* Dispatch tap: the rows of the last batched step (gl3_forward_prefill_seq, gl3_forward_decode_batch, gl3_forward_batch and their sampled
  * forms) by the attention form that served them in the last layer — out[0] attn_head_kernel (RoPE + attention in one launch per row),
  * out[1] the one-launch tiled kernels, out[2] the long-context trio (scores, softmax rows, weighted V sum), out[3] the per-row pair.  The
- * four sum to the step's n.  Host bookkeeping only.  GL3_E_STATE before any batched step, GL3_E_UNSUPPORTED without max_batch > 1. */
+ * four sum to the step's n.  A tree step (gl3_forward_batch_verify_tree) has all its n rows in one slot: out[1] pf_attn_tree_kernel, out[2]
+ * its tiled form (pf_softmax_rows_tree_kernel, pf_pv_tree_kernel), out[3] the masked per-row pair.  Host bookkeeping only.  GL3_E_STATE before any batched step, GL3_E_UNSUPPORTED without max_batch > 1. */
 GL3_API int32_t gl3_get_attn_rows(gl3_ctx* ctx, int32_t out[4]);
 
 /* Parity tap: the probabilities (f32[vocab]) row `row` of the last batched sampled step (or gl3_sample_rows call) was drawn from

@@ -1,11 +1,13 @@
 """What a draft-tree step costs (profiles/spec_tree.md).
 
     python scripts/spec_tree_bench.py step [--root TREE] [--modes tree,linear] [--layers 8] [--reps 7] [--inner 5] [--only M,DEPTH]
+                                           [--depths 0,4096] [--ms 8,16,64]
     python scripts/spec_tree_bench.py tool [--n-gen 128] [--reps 7] [--draft 7]
 
-step: a Llama-3-8B-shaped random-weight Q8_0 model cut to --layers layers, context 4224, one sequence.  Per prefix depth (0, 4096) and
-m in (8, 16, 64): `tree` = one gl3_forward_batch_verify_tree over one binary tree of m rows (parents[i] = (i - 1) / 2), `linear` = one
-gl3_forward_batch_verify over a chain of the same m tokens.  The modes alternate in one process after a warm-up call of each; a sample is
+step: a Llama-3-8B-shaped random-weight Q8_0 model cut to --layers layers, context 4224, one sequence.  Per prefix depth (--depths) and
+m in --ms: `tree` = one gl3_forward_batch_verify_tree over one binary tree of m rows (parents[i] = (i - 1) / 2), `linear` = one
+gl3_forward_batch_verify over a chain of the same m tokens; `tree_tiled` / `tree_pair` = the tree step on a plan of its own created under
+GL3_PF_TREE_TILED_MIN=0,1 / =1000000000,1 (the tiled form wherever the shape allows / never).  The modes alternate in one process after a warm-up call of each; a sample is
 --inner calls in a row (host clock; every call ends in the library's stream synchronise).  --root names the checkout whose package and
 library are loaded: a checkout of the parent commit with `--modes linear` is the yardstick, run in turn with this tree.  --only M,DEPTH with
 --reps 1 --inner 1 runs one case alone behind its warm-up: the target of a rocprofv3 --kernel-trace --stats run.
@@ -37,18 +39,27 @@ def step(args):
     import torch
     pkg, plan_mod = load(args.root)
     synth = pkg.synth
-    depths, ms = (0, 4096), (8, 16, 64)
+    depths, ms = tuple(int(x) for x in args.depths.split(",")), tuple(int(x) for x in args.ms.split(","))
     cfg = synth.ModelConfig(**{**synth.CONFIGS["llama-3-8b"].__dict__, "n_layers": args.layers, "ctx": 4096 + 128})
     toks = pkg.javarand.bench_tokens(cfg.vocab, cfg.ctx)
-    plan = plan_mod.HipMasterPlan(synth.StreamModel(cfg, synth.GGML_Q8_0, synth.iter_torch(cfg, wtype=synth.GGML_Q8_0, seed=42, device="cuda")),
-                                  prefill_batch_size=64)
     modes = args.modes.split(",")
+    # a plan per GL3_PF_TREE_TILED_MIN setting (read when the plan is created): `tree` and `linear` share the plan of the defaults
+    setting = {"tree": None, "linear": None, "tree_tiled": "0,1", "tree_pair": "1000000000,1"}
+    plans = {}
+    for k in modes:
+        if setting[k] not in plans:
+            os.environ.pop("GL3_PF_TREE_TILED_MIN", None)
+            if setting[k]:
+                os.environ["GL3_PF_TREE_TILED_MIN"] = setting[k]
+            plans[setting[k]] = plan_mod.HipMasterPlan(
+                synth.StreamModel(cfg, synth.GGML_Q8_0, synth.iter_torch(cfg, wtype=synth.GGML_Q8_0, seed=42, device="cuda")), prefill_batch_size=64)
     only = tuple(int(x) for x in args.only.split(",")) if args.only else None
     out = {"root": os.path.abspath(args.root), "layers": args.layers, "cases": {}}
     done = 0
-    for depth in depths:
+    for depth in sorted(depths):
         if done < depth:
-            plan.prefill_seq(0, toks[done:depth], done)
+            for plan in plans.values():
+                plan.prefill_seq(0, toks[done:depth], done)
             done = depth
         for m in ms:
             if only and only != (m, depth):
@@ -56,13 +67,18 @@ def step(args):
             row = [toks[depth]] + [1000 + i for i in range(1, m)]        # siblings carry distinct tokens
             parents = [-1] + [(i - 1) // 2 for i in range(1, m)]
             tree_pos = [depth + (i + 1).bit_length() - 1 for i in range(m)]
-            calls = {"tree": lambda: plan.forward_batch_verify_tree(row, [0] * m, tree_pos, parents),
-                     "linear": lambda: plan.forward_batch_verify(row, [0] * m, list(range(depth, depth + m)))}
-            calls = {k: calls[k] for k in modes}
-            rows = None
+
+            def call(k):
+                plan = plans[setting[k]]
+                if k == "linear":
+                    return lambda: plan.forward_batch_verify(row, [0] * m, list(range(depth, depth + m)))
+                return lambda: plan.forward_batch_verify_tree(row, [0] * m, tree_pos, parents)
+            calls = {k: call(k) for k in modes}
+            rows = {}
             for k, f in calls.items():
                 f()
-                rows = [int(x) for x in plan.attn_rows()] if k == "tree" else rows      # the attention form that served the tree step
+                if k != "linear":
+                    rows[k] = [int(x) for x in plans[setting[k]].attn_rows()]      # the attention form that served the tree step
             samples = {k: [] for k in calls}
             for _ in range(args.reps):
                 for k, f in calls.items():
@@ -74,7 +90,8 @@ def step(args):
             out["cases"]["m%d depth%d" % (m, depth)] = {k: dict(median_ms=statistics.median(v), samples_ms=v) for k, v in samples.items()}
             if rows:
                 out["cases"]["m%d depth%d" % (m, depth)]["attn_rows"] = rows
-    plan.freeTornadoExecutionPlan()
+    for plan in plans.values():
+        plan.freeTornadoExecutionPlan()
     print(json.dumps(out))
 
 
@@ -116,6 +133,8 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--inner", type=int, default=5)
     ap.add_argument("--only", default=None)
+    ap.add_argument("--depths", default="0,4096")
+    ap.add_argument("--ms", default="8,16,64")
     ap.add_argument("--n-gen", type=int, default=128)
     ap.add_argument("--draft", type=int, default=7)
     a = ap.parse_args()

@@ -1909,6 +1909,89 @@ int32_t gl3_get_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out) {
     return gl3_sample_probs_row(ctx, row, out);
 }
 
+// ---- top-k / min-p / top-p sampler (gl3_topk_sample.h): the three entries and the tap.  Every check before anything is staged.
+static int32_t check_topk(gl3_ctx* ctx) {
+    if (ctx->d.tp_size > 1) GL3_FAIL(GL3_E_UNSUPPORTED, "the top-k sampler is built for one rank (tp_size == 1)");
+    return GL3_OK;
+}
+
+int32_t gl3_sample_rows_topk(gl3_ctx* ctx, const float* logits, int32_t n, const int32_t* top_k, const float* temperature, const float* topp,
+                             const float* minp, const float* coins, int32_t* tokens_out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!logits || !top_k || !temperature || !topp || !minp || !coins || n <= 0) GL3_FAIL(GL3_E_ARG, "bad logits / top_k / temperature / topp / minp / coins arrays");
+    if (!tokens_out) GL3_FAIL(GL3_E_ARG, "null tokens_out");
+    int32_t r = check_batch_sampler(ctx);
+    if (r != GL3_OK) return r;
+    if ((r = check_topk(ctx)) != GL3_OK) return r;
+    if (n > ctx->d.max_batch) GL3_FAIL(GL3_E_ARG, "batch larger than max_batch");
+    bool all_greedy = false;
+    if ((r = gl3_topk_prepare(ctx, n, top_k, temperature, topp, minp, coins, &all_greedy)) != GL3_OK) return r;
+    ctx->smp_rows.last_n = 0;                                     // no full distribution of this step exists for gl3_draft_probs_put_row
+    if ((r = gl3_decode_batch_load_logits(ctx, logits, n)) != GL3_OK) return r;
+    const float* logits_dev; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits_dev, &greedy);
+    if (all_greedy) {
+        GL3_HIP(hipMemcpyAsync(tokens_out, greedy, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        GL3_HIP(hipStreamSynchronize(ctx->stream));
+        return GL3_OK;
+    }
+    return gl3_topk_finish(ctx, logits_dev, greedy, n, tokens_out);
+}
+
+int32_t gl3_forward_batch_sample_topk(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions, const int8_t* want_logits,
+                                      int32_t n, const int32_t* top_k, const float* temperature, const float* topp, const float* minp, const float* coins,
+                                      int32_t* tokens_out) {
+    if (!ctx) return GL3_E_ARG;
+    BatchPlan bp;
+    int32_t r = check_mixed(ctx, tokens, seq_ids, positions, want_logits, n, bp);
+    if (r != GL3_OK) return r;
+    if ((r = check_topk(ctx)) != GL3_OK) return r;
+    const int n_out = (int)bp.out_rows.size();
+    if (n_out == 0) return gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, nullptr);      // nothing to sample: a pure prefill
+    if (!top_k || !temperature || !topp || !minp || !coins) GL3_FAIL(GL3_E_ARG, "null top_k / temperature / topp / minp / coins");
+    if (!tokens_out) GL3_FAIL(GL3_E_ARG, "null tokens_out");
+    bool all_greedy = false;
+    if ((r = gl3_topk_prepare(ctx, n_out, top_k, temperature, topp, minp, coins, &all_greedy)) != GL3_OK) return r;
+    ctx->smp_rows.last_n = 0;                                     // as gl3_sample_rows_topk
+    if (all_greedy) return gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, tokens_out);
+    if ((r = gl3_batch_run(ctx, tokens, seq_ids, positions, n, bp, nullptr, nullptr, false)) != GL3_OK) return r;
+    const float* logits; const int32_t* greedy;
+    gl3_decode_batch_outputs(ctx, &logits, &greedy);
+    return gl3_topk_finish(ctx, logits, greedy, n_out, tokens_out);
+}
+
+int32_t gl3_forward_decode_sample_topk(gl3_ctx* ctx, int32_t token, int32_t pos, int32_t top_k, float temperature, float topp, float minp, float coin,
+                                       int32_t* token_out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!token_out) GL3_FAIL(GL3_E_ARG, "null token_out");
+    int32_t r = check_topk(ctx);
+    if (r != GL3_OK) return r;
+    if (!(temperature >= 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be >= 0");
+    if (temperature == 0.f) {                                     // greedy: the step's first-max id, as gl3_forward_decode_sample
+        ctx->last_sample_mode = SMP_GREEDY;
+        ctx->topk.last_n = 0;
+        return gl3_forward_decode(ctx, token, pos, nullptr, token_out);
+    }
+    if (!ctx->finalized) GL3_FAIL(GL3_E_STATE, "forward before gl3_finalize");
+    if (token < 0 || token >= ctx->d.vocab) GL3_FAIL(GL3_E_ARG, "token id out of range");
+    if (pos < 0 || pos >= ctx->d.ctx) GL3_FAIL(GL3_E_ARG, "position outside the KV cache (context length)");
+    bool all_greedy = false;
+    if ((r = gl3_topk_prepare(ctx, 1, &top_k, &temperature, &topp, &minp, &coin, &all_greedy)) != GL3_OK) return r;
+    if ((r = set_dyn(ctx, token, pos)) != GL3_OK) return r;
+    const int amode = attn_mode(ctx, pos);
+    if (ctx->graph_exec[ATT_LONG]) GL3_HIP(hipGraphLaunch(step_graph(ctx, amode), ctx->stream));
+    else if ((r = enqueue_decode(ctx, true, nullptr, amode)) != GL3_OK) return r;
+    ctx->last_sample_mode = -1;                                   // no full distribution of this step exists for gl3_draft_probs_put
+    return gl3_topk_finish(ctx, ctx->logits, nullptr, 1, token_out);      // ends with the stream synchronisation and gl3_tp_check
+}
+
+int32_t gl3_get_topk_row(gl3_ctx* ctx, int32_t row, int32_t* ids_out, float* probs_out, int32_t* n_out) {
+    if (!ctx) return GL3_E_ARG;
+    if (!ids_out || !probs_out || !n_out) GL3_FAIL(GL3_E_ARG, "null ids_out / probs_out / n_out");
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    return gl3_topk_get_row(ctx, row, ids_out, probs_out, n_out);
+}
+
 int32_t gl3_profile_decode(gl3_ctx* ctx, int32_t token, int32_t pos, gl3_kernel_times* out) {
     if (!ctx || !out) return GL3_E_ARG;
     memset(out, 0, sizeof(*out));

@@ -169,6 +169,20 @@ struct gl3_sample_state {
     gl3_sample_state(int blocks_, bool graph_) : blocks(blocks_), graph(graph_) {}
 };
 
+// Top-k / min-p / top-p sampler (topk_sample_kernel, gl3_topk_sample.h): everything it keeps on the device, for the single-row and the
+// row-batched entries alike (one launch either way; the tap answers for the last step of either).  Grows with the row count, all or none.
+namespace gl3 { struct TopkRow; }
+struct gl3_topk_state {
+    int rows = 0;                              // capacity of every buffer below
+    gl3::TopkRow* params = nullptr;            // [rows]
+    gl3::TopkRow* h_params = nullptr;          // pinned
+    int* res = nullptr;                        // [rows][2] {token, n_keep}
+    int* h_res = nullptr;                      // pinned
+    int* ids = nullptr;                        // [rows][1024] survivor ids, descending
+    float* probs = nullptr;                    // [rows][1024] their p_j
+    int last_n = 0;                            // rows of the last step (settings: h_params, results: h_res); 0 = none yet
+};
+
 // Token scores (score_rows_kernel, gl3_sample.hip): a row's settings as the kernel reads them, and everything scoring keeps on the device
 struct ScoreRow { int target; float temperature; };
 struct gl3_score_state {
@@ -296,6 +310,7 @@ struct gl3_ctx {
     // samplers (gl3_sample.hip): one set of kernels, one state per entry, so each entry's parity tap answers for its own last step
     gl3_sample_state smp_one{256, false};         // gl3_forward_decode_sample: one row, eager launches
     gl3_sample_state smp_rows{64, true};          // static-batched entries: grows with the batch, one hipGraph per (rows, any top-p row)
+    gl3_topk_state topk;                          // gl3_sample_rows_topk / gl3_forward_batch_sample_topk / gl3_forward_decode_sample_topk
     gl3_score_state score;                        // gl3_forward_batch_score / gl3_score_rows
     gl3_verify_state verify;                      // gl3_forward_batch_verify / gl3_verify_rows and their _dist forms
     gl3_tree_state tree;                          // gl3_forward_batch_verify_tree
@@ -389,6 +404,12 @@ void gl3_sample_free(gl3_ctx* ctx);
 int32_t gl3_sample_batch_prepare(gl3_ctx* ctx, int32_t n, const float* temperature, const float* topp, const float* coins, bool* all_greedy);
 int32_t gl3_sample_batch_finish(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n, int32_t* tokens_out);
 int32_t gl3_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);
+// top-k / min-p / top-p sampler: prepare = every check on the rows' settings + stage them (before the step is enqueued); finish = the one
+// launch behind the step on the plan's stream over plain [n][vocab] logits, 8 * n bytes back; get_row = the parity tap
+int32_t gl3_topk_prepare(gl3_ctx* ctx, int32_t n, const int32_t* top_k, const float* temperature, const float* topp, const float* minp, const float* coins,
+                         bool* all_greedy);
+int32_t gl3_topk_finish(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n, int32_t* tokens_out);
+int32_t gl3_topk_get_row(gl3_ctx* ctx, int32_t row, int32_t* ids_out, float* probs_out, int32_t* n_out);
 // token scores: prepare = every check + stage (target, temperature) of the n rows (temperature NULL: 1), before the step is enqueued;
 // finish = score_rows_kernel behind the step on the plan's stream, 16 * n bytes back
 int32_t gl3_score_prepare(gl3_ctx* ctx, int32_t n, const int32_t* targets, const float* temperature);

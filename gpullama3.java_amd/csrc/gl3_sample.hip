@@ -70,6 +70,7 @@
 #include "gl3_ctx.h"
 #include "gl3_chunked.h"      // chunked(), RowLayout: the logits of a tensor-parallel batched step are rank-chunked
 #include "gl3_decode_kernels.h"
+#include "gl3_topk_sample.h"  // topk_sample_kernel: the top-k / min-p / top-p sampler, one launch of its own (host side at the end of this file)
 
 using namespace gl3;
 
@@ -823,7 +824,19 @@ static void batch_chain_free(gl3_ctx* ctx) {
     *b = gl3_batch_chain_state{};
 }
 
+static void topk_free(gl3_ctx* ctx) {
+    gl3_topk_state* b = &ctx->topk;
+    if (b->params) hipFree(b->params);
+    if (b->res) hipFree(b->res);
+    if (b->ids) hipFree(b->ids);
+    if (b->probs) hipFree(b->probs);
+    if (b->h_params) hipHostFree(b->h_params);
+    if (b->h_res) hipHostFree(b->h_res);
+    *b = gl3_topk_state{};
+}
+
 void gl3_sample_free(gl3_ctx* ctx) {
+    topk_free(ctx);
     sample_free_buffers(&ctx->smp_one);
     sample_free_buffers(&ctx->smp_rows);
     draft_free(ctx);
@@ -1375,5 +1388,73 @@ int32_t gl3_verify_collect(gl3_ctx* ctx, int32_t n_runs, gl3_verify_result* resu
     const int32_t r = gl3_tp_check(ctx);
     if (r != GL3_OK) return r;
     memcpy(results_out, ctx->verify.h_out, (size_t)n_runs * sizeof(gl3_verify_result));
+    return GL3_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ top-k / min-p / top-p sampler
+// Host side of topk_sample_kernel (gl3_topk_sample.h; the argument checks on the plan are gl3_api.hip's): prepare = the checks on the rows'
+// settings, the buffers (all or none, as sample_alloc) and the settings up in one copy; finish = the one launch and 8 * n bytes back.
+int32_t gl3_topk_prepare(gl3_ctx* ctx, int32_t n, const int32_t* top_k, const float* temperature, const float* topp, const float* minp, const float* coins,
+                         bool* all_greedy) {
+    gl3_topk_state* b = &ctx->topk;
+    bool any = false;
+    for (int i = 0; i < n; ++i) {
+        if (!(temperature[i] >= 0.f)) GL3_FAIL(GL3_E_ARG, "temperature must be >= 0");
+        if (temperature[i] == 0.f) continue;                          // greedy: the row's other settings are not looked at
+        if (top_k[i] < 1 || top_k[i] > TK_MAX) GL3_FAIL(GL3_E_ARG, "top_k must be in [1, 1024]");
+        if (!(coins[i] >= 0.f && coins[i] < 1.f)) GL3_FAIL(GL3_E_ARG, "coin must be in [0, 1)");
+        any = true;
+    }
+    *all_greedy = !any;
+    b->last_n = 0;
+    if (!any) return GL3_OK;
+    GL3_HIP(hipSetDevice(ctx->d.device));
+    if (b->rows < n) {
+        if (b->rows) GL3_HIP(hipStreamSynchronize(ctx->stream));
+        topk_free(ctx);
+        hipError_t e = hipMalloc((void**)&b->params, (size_t)n * sizeof(TopkRow));
+        if (e == hipSuccess) e = hipMalloc((void**)&b->res, (size_t)n * 2 * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&b->ids, (size_t)n * TK_MAX * sizeof(int));
+        if (e == hipSuccess) e = hipMalloc((void**)&b->probs, (size_t)n * TK_MAX * sizeof(float));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_params, (size_t)n * sizeof(TopkRow));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_res, (size_t)n * 2 * sizeof(int));
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)topk_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TK_SMEM);
+        if (e != hipSuccess) { topk_free(ctx); GL3_HIP(e); }
+        b->rows = n;
+    }
+    for (int i = 0; i < n; ++i) {
+        const bool greedy = temperature[i] == 0.f;
+        b->h_params[i] = TopkRow{greedy ? 1 : top_k[i], temperature[i], greedy ? 0.f : topp[i], greedy ? 0.f : minp[i], greedy ? 0.f : coins[i]};
+    }
+    GL3_HIP(hipMemcpyAsync(b->params, b->h_params, (size_t)n * sizeof(TopkRow), hipMemcpyHostToDevice, ctx->stream));
+    return GL3_OK;
+}
+
+int32_t gl3_topk_finish(gl3_ctx* ctx, const float* logits_dev, const int32_t* greedy_dev, int32_t n, int32_t* tokens_out) {
+    gl3_topk_state* b = &ctx->topk;
+    hipStream_t s = ctx->stream;
+    hipLaunchKernelGGL(topk_sample_kernel, dim3(n), dim3(TK_THREADS), TK_SMEM, s, logits_dev, ctx->d.vocab, RowLayout{ctx->d.vocab, n}, b->params, greedy_dev, b->res,
+                       b->ids, b->probs);
+    GL3_HIP(hipGetLastError());
+    GL3_HIP(hipMemcpyAsync(b->h_res, b->res, (size_t)n * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    GL3_HIP(hipStreamSynchronize(s));
+    const int32_t r = gl3_tp_check(ctx);
+    if (r != GL3_OK) return r;
+    b->last_n = n;
+    for (int i = 0; i < n; ++i) tokens_out[i] = b->h_res[2 * i];
+    return GL3_OK;
+}
+
+int32_t gl3_topk_get_row(gl3_ctx* ctx, int32_t row, int32_t* ids_out, float* probs_out, int32_t* n_out) {
+    const gl3_topk_state* b = &ctx->topk;
+    if (!b->last_n) GL3_FAIL(GL3_E_STATE, "no top-k sampled step yet");
+    if (row < 0 || row >= b->last_n) GL3_FAIL(GL3_E_ARG, "row outside the last top-k sampled step");
+    if (b->h_params[row].temperature == 0.f) GL3_FAIL(GL3_E_STATE, "the row was greedy: it has no survivors");
+    const int kk = std::min(b->h_params[row].top_k, ctx->d.vocab);
+    memset(ids_out, 0, TK_MAX * sizeof(int32_t));
+    memset(probs_out, 0, TK_MAX * sizeof(float));
+    GL3_HIP(hipMemcpy(ids_out, b->ids + (size_t)row * TK_MAX, (size_t)kk * sizeof(int), hipMemcpyDeviceToHost));
+    GL3_HIP(hipMemcpy(probs_out, b->probs + (size_t)row * TK_MAX, (size_t)kk * sizeof(float), hipMemcpyDeviceToHost));
+    n_out[0] = kk; n_out[1] = b->h_res[2 * row + 1];
     return GL3_OK;
 }

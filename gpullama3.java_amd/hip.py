@@ -21,6 +21,7 @@ FLAG_VECTOR_512, FLAG_VECTOR_128 = 32, 64      # -Dllama.VectorBitSize (default 
 FLAG_KQUANT_NATIVE = 128                       # Q4_K / Q5_K / Q6_K tensors stay native in HBM (single-token decode on one rank)
 FLAG_KQUANT_NATIVE_BATCH = 256                 # ... with batched prefill, static-batched decode and mixed steps on that storage
 FLAG_KQUANT_NATIVE_MOE = 512                   # ... and Qwen2-MoE plans: the stacked expert tensors stay native too
+TOPK_MAX = 1024                             # the largest top_k of the top-k / min-p / top-p sampler
 CHAIN_MAX = 64                              # GL3_CHAIN_MAX: the longest gl3_forward_decode_chain
 VL_GEMM_KERNELS = ["gemm_f16_mfma_kernel", "gemm_f16_mfma_v512_kernel", "gemm_vlq_kernel", "gemm_vlq_mfma_kernel"]      # gl3_debug_vl_gemm_plan's kernel ids
 GEMM3_KERNELS = ["pf_gemm3_kernel", "pf_gemm3t_kernel"]      # gl3_debug_gemm3_plan's kernel ids
@@ -119,6 +120,12 @@ _SIGS = {  # symbol -> (restype, argtypes): exactly the declarations of include/
     "gl3_get_attn_rows": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "gl3_get_sample_probs_row": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),
     "gl3_sample_rows": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gl3_sample_rows_topk": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gl3_forward_batch_sample_topk": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gl3_forward_decode_sample_topk": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                   C.POINTER(C.c_int32)]),
+    "gl3_get_topk_row": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gl3_get_kv_seq": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gl3_get_x": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "gl3_get_layer_x": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -284,6 +284,43 @@ class HipMasterPlan:
         hip.check(hip.lib().gl3_sample_rows(self._ctx, _p(lg), n, _p(te), _p(tp), _p(co), _p(ids)), self._ctx)
         return ids
 
+    def _topk_rows(self, top_k, temperature, topp, minp, coins, n):
+        return (np.ascontiguousarray(np.broadcast_to(np.asarray(top_k, np.int32), (n,))), self._per_row(temperature, n), self._per_row(topp, n),
+                self._per_row(minp, n), self._per_row(coins, n))
+
+    def sample_rows_topk(self, logits, top_k, temperature, topp, minp, coins) -> np.ndarray:
+        """The top-k / min-p / top-p sampler alone on host logits [n][vocab] (gl3_sample_rows_topk) -> sampled ids [n].  Per-row settings,
+        scalars broadcast; temperature 0 = greedy."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        assert lg.ndim == 2 and lg.shape[1] == self.cfg.vocab
+        n = lg.shape[0]
+        k, te, tp, mp, co = self._topk_rows(top_k, temperature, topp, minp, coins, n)
+        ids = np.empty(n, np.int32)
+        hip.check(hip.lib().gl3_sample_rows_topk(self._ctx, _p(lg), n, _p(k), _p(te), _p(tp), _p(mp), _p(co), _p(ids)), self._ctx)
+        return ids
+
+    def forward_batch_sample_topk(self, tokens, seq_ids, positions, top_k, temperature, topp, minp, coins, want_logits=None) -> np.ndarray:
+        """Mixed batched step + the top-k / min-p / top-p sampler for every OUTPUT row (gl3_forward_batch_sample_topk) -> ids [n_out]."""
+        t, s, p, w, n_out = self._mixed_args(tokens, seq_ids, positions, want_logits)
+        k, te, tp, mp, co = self._topk_rows(top_k, temperature, topp, minp, coins, n_out)
+        ids = np.empty(n_out, np.int32)
+        hip.check(hip.lib().gl3_forward_batch_sample_topk(self._ctx, _p(t), _p(s), _p(p), _p(w) if w is not None else None, t.size,
+                                                          _p(k), _p(te), _p(tp), _p(mp), _p(co), _p(ids)), self._ctx)
+        return ids
+
+    def forward_decode_sample_topk(self, token: int, position: int, top_k: int, temperature: float, topp: float, minp: float, coin: float) -> int:
+        """One decode step + the top-k / min-p / top-p sampler (gl3_forward_decode_sample_topk); `coin` in [0, 1) is the caller's."""
+        out = C.c_int32()
+        hip.check(hip.lib().gl3_forward_decode_sample_topk(self._ctx, token, position, top_k, temperature, topp, minp, coin, C.byref(out)), self._ctx)
+        return int(out.value)
+
+    def topk_row(self, row: int = 0):
+        """Parity tap (gl3_get_topk_row) -> (survivor ids [kk] in sorted order, their probabilities [kk], n_keep) of row `row` of the last
+        step of the three entries above."""
+        ids, probs, n = np.empty(hip.TOPK_MAX, np.int32), np.empty(hip.TOPK_MAX, np.float32), np.zeros(2, np.int32)
+        hip.check(hip.lib().gl3_get_topk_row(self._ctx, row, _p(ids), _p(probs), _p(n)), self._ctx)
+        return ids[:n[0]].copy(), probs[:n[0]].copy(), int(n[1])
+
     def _score_args(self, targets, temperature, n):
         """targets int32[n] (None: NULL, which the library refuses), temperature f32[n] or None for 1 everywhere, the result array"""
         tg = np.ascontiguousarray(targets, np.int32) if targets is not None else None

@@ -649,6 +649,40 @@ GL3_API int32_t gl3_get_sample_probs_row(gl3_ctx* ctx, int32_t row, float* out);
 GL3_API int32_t gl3_sample_rows(gl3_ctx* ctx, const float* logits, int32_t n, const float* temperature, const float* topp,
                                 const float* coins, int32_t* tokens_out);
 
+/* Top-k / min-p / top-p sampling: the sampler other GGUF hosts default to.  The reference has none, so the arithmetic is this library's
+ * own, fixed to the last f32 operation (csrc/gl3_topk_sample.h), and the ids are reproducible bit for bit.  Per row: top_k, temperature,
+ * topp, minp and the caller's coin in [0, 1).
+ *   greedy     temperature == 0: the step's greedy first-max id; the row's other settings are not looked at.
+ *   survivors  kk = min(top_k, vocab); logits compared as floats after l + 0.0f (-0.0 equals +0.0); the first kk entries of the order
+ *              (logit descending, index ascending) = np.argsort(-l, kind="stable")[:kk].  Logits finite or -inf; NaN is unspecified.
+ *   softmax    over the survivors j = 0 .. kk-1 in that order, in f32: v_j = l_j / temperature, e_j = (float) exp((double) (v_j - v_0)),
+ *              s = ((0f + e_0) + e_1) + ... strictly sequential, p_j = e_j / s.
+ *   min-p      0 < minp <= 1: keep the prefix of j with p_j >= minp * p_0 (at least one entry); otherwise off.
+ *   top-p      0 < topp < 1: inside that prefix, with the sequential cdf c_n = ((0f + p_0) + ...) + p_{n-1}, n_keep = the smallest n with
+ *              c_n > topp, the whole prefix if there is none; otherwise off (n_keep = the prefix).
+ *   draw       r = coin * c_{n_keep}; the survivor at the first j < n_keep with r < c_{j+1}, survivor n_keep - 1 if there is none.
+ * One launch per step whatever the row count, on the device end to end: a radix select of the kk-th largest key, no sort of the vocabulary,
+ * no [rows][vocab] intermediate, no host fallback.  GL3_E_ARG, before anything is staged: a row at a temperature > 0 whose top_k is outside
+ * [1, 1024] or whose coin is outside [0, 1); a temperature that is not >= 0.  Out of scope: tp_size > 1 returns GL3_E_UNSUPPORTED; the draft
+ * chains and gl3_forward_batch_verify_dist keep taking full distributions only, and after a step of these entries gl3_draft_probs_put /
+ * gl3_draft_probs_put_row answer GL3_E_STATE, so a truncated distribution is never filed as q.
+ *
+ * gl3_sample_rows_topk: the sampler alone on caller-supplied logits (host f32[n][vocab]), the twin of gl3_sample_rows: a plan with
+ * max_batch > 1 (GL3_E_UNSUPPORTED otherwise), n <= max_batch, per-row arrays of n entries, tokens_out int32[n]. */
+GL3_API int32_t gl3_sample_rows_topk(gl3_ctx* ctx, const float* logits, int32_t n, const int32_t* top_k, const float* temperature,
+                                     const float* topp, const float* minp, const float* coins, int32_t* tokens_out);
+/* The step of gl3_forward_batch + that sampler over its output rows: gl3_forward_batch_sample with two more arrays, one entry per OUTPUT
+ * row each.  A step of single-row runs is a static-batched decode step. */
+GL3_API int32_t gl3_forward_batch_sample_topk(gl3_ctx* ctx, const int32_t* tokens, const int32_t* seq_ids, const int32_t* positions,
+                                              const int8_t* want_logits, int32_t n, const int32_t* top_k, const float* temperature,
+                                              const float* topp, const float* minp, const float* coins, int32_t* tokens_out);
+/* One decode step + that sampler: gl3_forward_decode_sample's twin on the single-row plan. */
+GL3_API int32_t gl3_forward_decode_sample_topk(gl3_ctx* ctx, int32_t token, int32_t position, int32_t top_k, float temperature, float topp,
+                                               float minp, float coin, int32_t* token_out);
+/* Parity tap: row `row` of the last step of any of the three entries: the kk survivor ids in sorted order and their p_j (zeros behind
+ * them), n_out = {kk, n_keep}.  GL3_E_STATE for a greedy row or before any such step. */
+GL3_API int32_t gl3_get_topk_row(gl3_ctx* ctx, int32_t row, int32_t ids_out[1024], float probs_out[1024], int32_t n_out[2]);
+
 /* Parity taps. */
 GL3_API int32_t gl3_get_x(gl3_ctx* ctx, float* out /* f32[dim] */);
 GL3_API int32_t gl3_get_layer_x(gl3_ctx* ctx, int32_t layer, float* out /* f32[dim], needs GL3_FLAG_LAYER_TAPS */);

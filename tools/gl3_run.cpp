@@ -20,9 +20,11 @@
 // Sampling: temperature 0 = greedy (Sampler.TENSOR_ARGMAX, first index of the maximum); else gl3_forward_decode_sample with the
 // caller-side coin rng.nextFloat(1f) — RandomGeneratorFactory.getDefault().create(seed) = L32X64MixRandom in the reference
 // (J/inference/sampler/Sampler.java:76-123); --rng lcg selects java.util.Random instead.  One coin per sampled token.
+// --top-k N (with --min-p P, --top-p, --temperature) selects the top-k / min-p / top-p sampler instead (gl3_forward_decode_sample_topk;
+// not a sampler of the reference: its arithmetic is fixed in include/gpullama3_hip.h), on the same coins.
 //
 //   gl3_run -m model.gguf --ids 1,2,3 [--protocol llama|qwen3] [--bos ID] [-n maxTokens] [-b prefillBatch] [--start-pos P]
-//           [--temperature T] [--top-p P] [--seed S] [--rng l32x64|lcg] [--stop id,id] [--scalar-dot] [--f32-activation]
+//           [--temperature T] [--top-p P] [--top-k N] [--min-p P] [--seed S] [--rng l32x64|lcg] [--stop id,id] [--scalar-dot] [--f32-activation]
 //           [--vector-bits 256|512]
 // prints "generated: id id ..." (stdout) and the reference's metric lines (stderr).
 #include <chrono>
@@ -95,7 +97,8 @@ int main(int argc, char** argv) {
     std::string path, protocol, rng_kind = "l32x64";
     std::vector<int32_t> prompt, stop;
     int max_tokens = 0, batch = 1, start_pos = 0, bos = -1;
-    float temperature = 0.f, topp = 0.95f;
+    float temperature = 0.f, topp = 0.95f, minp = 0.f;
+    int top_k = 0;                                         // > 0: the top-k / min-p / top-p sampler
     uint64_t seed = 1234;                                  // the reference's default (Options.java)
     uint32_t flags = 0;
     for (int i = 1; i < argc; ++i) {
@@ -110,6 +113,8 @@ int main(int argc, char** argv) {
         else if (a == "--start-pos") start_pos = atoi(val());
         else if (a == "--temperature") temperature = (float)atof(val());
         else if (a == "--top-p") topp = (float)atof(val());
+        else if (a == "--top-k") top_k = atoi(val());
+        else if (a == "--min-p") minp = (float)atof(val());
         else if (a == "--seed") seed = strtoull(val(), nullptr, 10);
         else if (a == "--rng") rng_kind = val();
         else if (a == "--stop") stop = parse_ids(val());
@@ -158,6 +163,7 @@ int main(int argc, char** argv) {
     auto sample = [&](int32_t token, int pos, int32_t* out) -> int32_t {      // forward + Sampler.sampleToken
         if (temperature == 0.f) return gl3_forward_decode(ctx, token, pos, nullptr, out);
         const float coin = rng_kind == "lcg" ? lcg.nextFloat() : mix.nextFloat();
+        if (top_k > 0) return gl3_forward_decode_sample_topk(ctx, token, pos, top_k, temperature, topp, minp, coin, out);
         return gl3_forward_decode_sample(ctx, token, pos, temperature, topp, coin, out);
     };
 
